@@ -9,10 +9,12 @@ bonded forces, Langevin thermostat, and the reaction scan every `interval` steps
 reference's integratorLoop (start_simulation.py:779-781): wall time inside run() only, inputs
 already resident in HBM.  Prints ONE JSON line (see DESIGN.md "Measurement").
 
-Sequence (all set-up outside the timer):
+Sequence of a plain run (all set-up outside the timer):
   1. lattice start, `--equil` steps WITHOUT reactions: the melt the metric is named after
      (the reference attaches the reaction extension at step `start_ar`, start_simulation.py:735-741);
-  2. reactions enabled, W warm-up steps, then EXACTLY K timed steps;
+  2. reactions enabled, W warm-up steps, then EXACTLY K timed steps (no HIP-event sampling inside them);
+  2b. `--dump-outputs DIR`: the state the timed steps left behind, written as DIR/<name>.npy (dump_outputs).
+With `--full`, the timed region of 2. is sampled with HIP events for the per-kernel rooflines (`roofline`), and after it:
   3. if no reaction step fell into the timed region (K < interval), the next reaction step is timed
      on its own afterwards and reported as `reaction_step_ms` (it is never folded into `value`);
   3b. `late_stage`: 10 more reaction steps (untimed), then max(K, 400) timed steps of the gelled system;
@@ -45,16 +47,24 @@ def parse():
     p.add_argument("--interval", type=int, default=500)
     p.add_argument("--equil", type=int, default=2000, help="untimed melting steps before reactions are enabled")
     p.add_argument("--precision", type=int, default=32)
-    p.add_argument("--f64-steps", type=int, default=-1, help="timed steps of the fp64 leg (-1: min(K, 400); 0 = skip)")
-    p.add_argument("--cpu-steps", type=int, default=-1, help="oracle steps per cpu_baseline leg (-1: automatic, 0 = skip)")
+    p.add_argument("--f64-steps", type=int, default=-1, help="--full: timed steps of the fp64 leg (-1: min(K, 400); 0 = skip)")
+    p.add_argument("--cpu-steps", type=int, default=-1, help="--full: oracle steps per cpu_baseline leg (-1: automatic, 0 = skip)")
     p.add_argument("--tpp", type=int, default=0)
     p.add_argument("--opt", action="append", default=[], help="name=value engine option (tuning)")
     p.add_argument("--no-roofline", action="store_true")
-    p.add_argument("--late-stage", type=int, default=10, help="reaction steps to advance (untimed) before the late-stage leg (0 = skip)")
+    p.add_argument("--late-stage", type=int, default=10, help="--full: reaction steps to advance (untimed) before the late-stage leg (0 = skip)")
     p.add_argument("--verbose", action="store_true", help="timers to stderr")
     p.add_argument("--rendezvous-only", action="store_true",
                    help="N > 1: start the ranks, run the gloo rendezvous (barrier + max over ranks) and stop before any GPU work")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also the rooflines (HIP-event sampling of the timed region), the separate reaction step, the late-stage and "
+                        "fp64 legs and the CPU baseline; a plain run sets up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the state after the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    a = p.parse_args()
+    if not a.full:
+        a.no_roofline = True      # (multigpu.bench_main reads the same flag)
+    return a
 
 
 WORKLOAD = ("C5 reactive LJ melt (chain_growth_catalytic shape): %d particles, rho*=%.4g, rc=2.5, skin=%.3g, dt=0.005, "
@@ -169,22 +179,23 @@ def run_leg(a, spec, precision, local_rank, equil_state=None, steps=None, warmup
     steps = a.steps if steps is None else steps
     warmup = a.warmup if warmup is None else warmup
     eng = Engine(device=local_rank, precision=precision)
-    W.apply(spec if equil_state is None else equil_state, eng)
+    handles = W.apply(spec if equil_state is None else equil_state, eng)
     if a.tpp:
         eng.set_option("tpp", a.tpp)
     for kv in a.opt:
         k, v = kv.split("=")
         eng.set_option(k, float(v))
-    info = {}
+    info = dict(handles=handles)
     if equil_state is None:
         eng.reactions_enable(False)
         x0 = np.asarray(spec["pos"], dtype=np.float64)
         eng.run(a.equil)
         eng.sync()
-        if a.equil > 0:
-            d = eng.get_state("POS_UNFOLDED") - x0
-            info["msd_after_melting"] = float((d * d).sum(1).mean())   # lattice spacing^2 = 1.16: > that means the lattice is gone
-        info["melted"] = melted_spec(spec, eng)
+        if a.full:      # the melt check and the start of the fp64 / CPU legs
+            if a.equil > 0:
+                d = eng.get_state("POS_UNFOLDED") - x0
+                info["msd_after_melting"] = float((d * d).sum(1).mean())   # lattice spacing^2 = 1.16: > that means the lattice is gone
+            info["melted"] = melted_spec(spec, eng)
         eng.reactions_enable(True)
     eng.run(warmup)
     eng.sync()
@@ -229,6 +240,45 @@ def time_reaction_step(eng, interval, ms_per_step):
     tm1 = eng.timers()
     return dict(reaction_step_ms=1e3 * (tm1["reaction_wall_s"] - tm0["reaction_wall_s"]), reaction_step_call_ms=max(0.0, 1e3 * dt - ms_per_step),
                 reaction_events=len(eng.get_events()) - ev0, at_step=int(eng.step))
+
+
+DUMP_PARTICLE_BYTES = 52_000_000   # per-particle arrays of dump_outputs, all together
+DUMP_BOND_BYTES = 10_000_000       # the reaction-bond list (with the .npy headers: < 64 MB in all)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outdir, eng, handles, precision, particle_bytes=DUMP_PARTICLE_BYTES, bond_bytes=DUMP_BOND_BYTES):
+    """What a caller of the timed path reads back after its last step, as outdir/<name>.npy:
+      ids           particle ids (float64), the row order of every per-particle array below;
+      pos_unfolded  unfolded positions, vel, force (n x 3, float32 for --precision 32, float64 for 64);
+      type, state   particle type and chemical state (float32, small integers);
+      bonds         the reaction-bond list, (lower id, higher id) rows in ascending order (float64).
+    Where the per-particle arrays exceed `particle_bytes`, a fixed, seeded sample of particles (its size depends on n and
+    the precision only) is written; the bonds then are those whose lower id is in the sample, cut to `bond_bytes`."""
+    os.makedirs(outdir, exist_ok=True)
+    fdt = np.float32 if precision == 32 else np.float64
+    ids = eng.get_state("ID")
+    n = ids.shape[0]
+    per_particle = 8 + 3 * 3 * np.dtype(fdt).itemsize + 2 * 4
+    rows = None
+    if n * per_particle > particle_bytes:
+        m = particle_bytes // per_particle
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    pick = (lambda x: x) if rows is None else (lambda x: x[rows])
+    out = dict(ids=pick(ids).astype(np.float64))
+    for name, what in (("pos_unfolded", "POS_UNFOLDED"), ("vel", "VEL"), ("force", "FORCE")):
+        out[name] = pick(eng.get_state(what)).astype(fdt)
+    out["type"] = pick(eng.get_state("TYPE")).astype(np.float32)
+    out["state"] = pick(eng.get_state("STATE")).astype(np.float32)
+    if "reaction_bonds" in handles:
+        b = np.sort(eng.get_list(handles["reaction_bonds"]), axis=1)
+        b = b[np.lexsort((b[:, 1], b[:, 0]))]
+        if rows is not None:
+            b = b[np.isin(b[:, 0], out["ids"].astype(np.int64))]
+        out["bonds"] = b[: bond_bytes // 16].astype(np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr))
+    return sorted(out)
 
 
 def spawn_ranks(nranks):
@@ -299,6 +349,8 @@ def main():
         return 0
     spec = W.reactive_melt(n=a.n, rho=a.rho, interval=a.interval, seed=2, skin=a.skin)
     if world > 1 or os.environ.get("CHEM_FORCE_DD"):   # CHEM_FORCE_DD: exercise the RCCL slab path with one rank
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: single-domain runs only (one GPU, no CHEM_FORCE_DD)")
         from chemlab_amd import multigpu
         return multigpu.bench_main(a, spec, rank, local_rank, world)
 
@@ -306,6 +358,8 @@ def main():
     wall, tm = info["wall"], info["tm"]
     steps_per_s = a.steps / wall
     ms_per_step = 1e3 * wall / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, eng, info["handles"], a.precision)
 
     out = dict(metric="MD steps/sec, 1M-particle reactive LJ melt", value=steps_per_s, unit="steps/s",
                n_gpus=1, steps=a.steps, warmup=a.warmup, ms_per_step=ms_per_step,
@@ -313,13 +367,14 @@ def main():
                dtype="f32" if a.precision == 32 else "f64", data="synthetic",
                config=dict(workload=WORKLOAD % (a.n, a.rho, a.skin, a.interval, a.equil),
                            particles=a.n, reaction_interval=a.interval, equilibration_steps=a.equil,
-                           msd_after_melting=info.get("msd_after_melting"),
                            reaction_steps_timed=int(info["reaction_steps_timed"]), reaction_events=int(info["events"]),
                            list_rebuilds_timed=int(info["rebuilds_timed"]), list_builds_timed=int(info["list_builds_timed"]),
                            tau_per_day=steps_per_s * spec["dt"] * 86400, parallelism="1 GPU, single domain"))
+    if "msd_after_melting" in info:
+        out["config"]["msd_after_melting"] = info["msd_after_melting"]
     if info["reaction_steps_timed"] > 0:
         out["config"]["reaction_step_ms"] = 1e3 * info["reaction_wall_s"] / info["reaction_steps_timed"]
-    else:
+    elif a.full:
         # K < interval: the reaction step the metric's name promises is measured on its own, right after the
         # timed region, and reported beside `value` (never folded into it)
         r = time_reaction_step(eng, a.interval, ms_per_step)
@@ -352,8 +407,11 @@ def main():
         out["late_stage"] = late_stage_leg(eng, a, a.late_stage)
     if a.verbose:
         print("timers:", json.dumps(tm), file=sys.stderr)
-    melted = info["melted"]
     eng.close()
+    if not a.full:
+        print(json.dumps(out))
+        return 0
+    melted = info["melted"]
 
     f64_steps = a.f64_steps if a.f64_steps >= 0 else min(a.steps, 400)
     if f64_steps > 0 and a.precision == 32:

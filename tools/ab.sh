@@ -5,7 +5,7 @@ mkdir -p "$out"
 for spec in "$@"; do
   label=${spec%%:*}; rest=${spec#*:}; lib=${rest%%:*}; args=${rest#*:}
   [ "$lib" = "-" ] && unset CHEM_MI355_LIB || export CHEM_MI355_LIB=$PWD/$lib
-  timeout -k 10 240 python3 bench.py --steps ${STEPS:-1000} --cpu-steps 0 --f64-steps 0 $args > "$out/$label.json" 2> "$out/$label.err" || { echo "$label FAILED"; tail -3 "$out/$label.err"; exit 1; }
+  timeout -k 10 240 python3 bench.py --full --steps ${STEPS:-1000} --cpu-steps 0 --f64-steps 0 $args > "$out/$label.json" 2> "$out/$label.err" || { echo "$label FAILED"; tail -3 "$out/$label.err"; exit 1; }
   python3 - "$out/$label.json" "$label" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -1,10 +1,11 @@
 #!/bin/bash
 # A/B of library variants on the C5 bench: tools/ab_bench.sh OUT_PREFIX "extra bench args" name1 name2 ...   (name "main" = the product library)
 out=$1; shift; extra=$1; shift
+dir=${BENCH_OUT:-bench_out}; mkdir -p "$dir"     # output files: $dir/OUT_PREFIX_<name>.json / .err
 for v in "$@"; do
   if [ "$v" = main ]; then unset CHEM_MI355_LIB; else export CHEM_MI355_LIB=$PWD/chemlab_amd/csrc/variants/libchem_$v.so; fi
-  python bench.py --f64-steps 0 --cpu-steps 0 $extra > gpurun_out/${out}_$v.json 2> gpurun_out/${out}_$v.err || { echo "$v FAILED"; tail -5 gpurun_out/${out}_$v.err; continue; }
-  python - "$v" gpurun_out/${out}_$v.json <<'PY'
+  python bench.py --full --f64-steps 0 --cpu-steps 0 $extra > $dir/${out}_$v.json 2> $dir/${out}_$v.err || { echo "$v FAILED"; tail -5 $dir/${out}_$v.err; continue; }
+  python - "$v" $dir/${out}_$v.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 r = d["roofline"]; ks = {k["kernel"].split(" ")[0]: k for k in r["kernels"]}

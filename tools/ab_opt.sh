@@ -1,10 +1,11 @@
 #!/bin/bash
 # A/B of engine options on the C5 bench (same library): tools/ab_opt.sh OUT_PREFIX "bench args" "name1:--opt a=b" "name2:" ...
 out=$1; shift; extra=$1; shift
+dir=${BENCH_OUT:-bench_out}; mkdir -p "$dir"     # output files: $dir/OUT_PREFIX_<name>.json / .err
 for spec in "$@"; do
   name=${spec%%:*}; opts=${spec#*:}
-  python bench.py --f64-steps 0 --cpu-steps 0 $extra $opts > gpurun_out/${out}_$name.json 2> gpurun_out/${out}_$name.err || { echo "$name FAILED"; tail -5 gpurun_out/${out}_$name.err; continue; }
-  python - "$name" gpurun_out/${out}_$name.json <<'PY'
+  python bench.py --full --f64-steps 0 --cpu-steps 0 $extra $opts > $dir/${out}_$name.json 2> $dir/${out}_$name.err || { echo "$name FAILED"; tail -5 $dir/${out}_$name.err; continue; }
+  python - "$name" $dir/${out}_$name.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 r = d["roofline"]; dv = r["device_us_per_step"]

@@ -1,9 +1,10 @@
 #!/bin/bash
 # internal-skin / tile-shape study on the C5 bench (user-level skin stands in for the internal one: same forces)
 run() { # name lib skin extra
+  local dir=${BENCH_OUT:-bench_out}; mkdir -p "$dir"
   if [ "$2" = main ]; then unset CHEM_MI355_LIB; else export CHEM_MI355_LIB=$PWD/chemlab_amd/csrc/variants/libchem_$2.so; fi
-  python bench.py --f64-steps 0 --cpu-steps 0 --late-stage 0 --steps 1000 --skin $3 $4 > gpurun_out/skin_$1.json 2> gpurun_out/skin_$1.err || { echo "$1 FAILED"; tail -3 gpurun_out/skin_$1.err; return; }
-  python - "$1" gpurun_out/skin_$1.json <<'PY'
+  python bench.py --full --f64-steps 0 --cpu-steps 0 --late-stage 0 --steps 1000 --skin $3 $4 > $dir/skin_$1.json 2> $dir/skin_$1.err || { echo "$1 FAILED"; tail -3 $dir/skin_$1.err; return; }
+  python - "$1" $dir/skin_$1.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 r = d["roofline"]; ks = {k["kernel"].split(" ")[0]: k for k in r["kernels"]}
