@@ -2175,6 +2175,9 @@ template <typename R> struct CtxT : Ctx {
     int idx = 0;
     HIPCHK(hipMemcpyAsync(&idx, rtag.p + t, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
+    // a slab rank holds only its home particles and ghosts (rtag = -1 for every other tag): nothing to write there; a ghost
+    // copy that does exist takes the new type / mass from its owner at the forced rebuild (resort)
+    if ((what == CHEM_STATE_TYPE || what == CHEM_STATE_MASS) && idx < 0) return;
     if (what == CHEM_STATE_TYPE) { R w = (R)value; HIPCHK(hipMemcpyAsync(&x4.p[idx].w, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_MASS) { R w = (R)value; HIPCHK(hipMemcpyAsync(&v4.p[idx].w, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_STATE) { int w = (int)value; HIPCHK(hipMemcpyAsync(state.p + t, &w, sizeof(int), hipMemcpyHostToDevice, stream)); }
@@ -2575,6 +2578,15 @@ int chem_reaction_set_rate(chem_ctx* ctx, int r, double rate) {
 int chem_run(chem_ctx* ctx, int64_t nsteps) {
   API_BEGIN_NOJOIN   // a pending label merge keeps running beside the MD steps; react_step joins it
   REQUIRE(nsteps >= 0, CHEM_EINVAL, "nsteps");
+  // a pair cutoff beyond the list cutoff (max_cutoff) would make the forces depend on the list's own radius (list_skin): the
+  // reference builds its Verlet list at the largest pair cutoff (start_simulation.py:80,193-197), so it never asks for this.
+  // (Without a cutoff the system is incomplete: CTX.run reports that, as orc_run does.)
+  if (CTX.rc > 0) for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = a; b < CHEM_MAX_TYPES; ++b) {
+    const HostPairPot& p = CTX.pp[a][b];
+    if (p.kind && p.rc > CTX.rc * (1.0 + 1e-12))
+      throw ChemError(CHEM_EINVAL, "run: cutoff " + std::to_string(p.rc) + " of type pair (" + std::to_string(a) + "," + std::to_string(b) +
+                                   ") exceeds the list cutoff max_cutoff = " + std::to_string(CTX.rc));
+  }
   CTX.run(nsteps);
   return 0;
   API_END(ctx)

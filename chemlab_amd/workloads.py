@@ -227,8 +227,8 @@ def apply(spec, eng, thermostat=True, reactions=True):
     eng.set_dt(spec["dt"])
     eng.set_particles(spec["ids"], spec["types"], spec["pos"], spec["mass"], vel=spec.get("vel"),
                       state=spec.get("state"), res_id=spec.get("res_id"))
-    for (t1, t2, eps, sig, rc) in spec.get("lj", []):
-        eng.nb_lj(t1, t2, eps, sig, rc, True)
+    for lj in spec.get("lj", []):               # (t1, t2, eps, sigma, rc[, shift_auto]): shift_auto defaults to on
+        eng.nb_lj(*lj[:5], lj[5] if len(lj) > 5 else True)
     for (t1, t2, r0, dr, e, f, rc) in spec.get("tables", []):
         eng.nb_table(t1, t2, r0, dr, e, f, rc)
     handles = {}

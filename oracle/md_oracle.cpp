@@ -1023,6 +1023,13 @@ int orc_reaction_set_rate(void* c, int r, double rate) { Orc& o = O(c); if (r < 
 int orc_run(void* c, int64_t nsteps) {
   Orc& o = O(c);
   if (o.n == 0 || !(o.L[0] > 0) || !(o.rc > 0) || !(o.dt > 0)) FAIL(CHEM_ESTATE, "run: system incomplete");
+  // the Verlet list is built at rc + skin (build_pairs): a pair cutoff beyond rc would lose pairs between rebuilds
+  for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = a; b < CHEM_MAX_TYPES; ++b) {
+    const PairPot& p = o.pp[a][b];
+    if (p.kind && p.rc > o.rc * (1.0 + 1e-12))
+      FAIL(CHEM_EINVAL, "run: cutoff " + std::to_string(p.rc) + " of type pair (" + std::to_string(a) + "," + std::to_string(b) +
+                        ") exceeds the list cutoff max_cutoff = " + std::to_string(o.rc));
+  }
   run(o, nsteps); return 0;
 }
 

@@ -58,13 +58,13 @@ def force_error_without_cutoff_flips(spec, f_test, f_ref, tol, shell=2e-6, max_f
     force -- then IS the maximum error, whatever the arithmetic precision.  This helper finds, for every particle whose
     error exceeds `tol`, the neighbours within `shell` of their pair cutoff, removes the contribution of exactly those
     pairs from the difference, and returns (corrected relative error, number of flipped pairs).  The flipped pairs are
-    verified to be boundary pairs (|r - rc| < shell); nothing else is forgiven."""
+    verified to be boundary pairs (|r - rc| < shell); nothing else is forgiven.  Every type pair is taken at its own cutoff
+    and with its own potential (per-pair LJ, tables: pair_params)."""
     pos = np.asarray(spec["pos"], dtype=np.float64)
     L = np.asarray(spec["box"], dtype=np.float64)
     types = np.asarray(spec["types"])
-    lj = {}
-    for (t1, t2, eps, sig, rc) in spec.get("lj", []):
-        lj[(t1, t2)] = lj[(t2, t1)] = (eps, sig, rc)
+    prm = pair_params(spec)
+    rcs = sorted({pair_cutoff(v) for v in prm.values()})
     df = np.asarray(f_test, dtype=np.float64) - np.asarray(f_ref, dtype=np.float64)
     fmax = np.abs(f_ref).max()
     bad = np.nonzero(np.abs(df).max(1) > tol * fmax)[0]
@@ -75,19 +75,17 @@ def force_error_without_cutoff_flips(spec, f_test, f_ref, tol, shell=2e-6, max_f
         d = pos - pos[i]
         d -= L * np.rint(d / L)
         r = np.sqrt((d * d).sum(1))
-        rcs = sorted({v[2] for v in lj.values()})
         near = np.zeros(len(r), dtype=bool)
         for rc_ in rcs:
             near |= np.abs(r - rc_) < shell
         for j in np.nonzero(near)[0]:
-            prm = lj.get((int(types[i]), int(types[j])))
-            if prm is None or j == i:
+            p = prm.get((int(types[i]), int(types[j])))
+            if p is None or j == i:
                 continue
-            eps, sig, rc = prm
-            if abs(r[j] - rc) >= shell:
+            if abs(r[j] - pair_cutoff(p)) >= shell:
                 continue
-            s6 = (sig / r[j]) ** 6
-            fpair = 24.0 * eps * (2.0 * s6 * s6 - s6) / (r[j] * r[j]) * (-d[j])     # force on i from j (d = x_j - x_i)
+            ff, _ = pair_eval(p, r[j] * r[j], cut=False)
+            fpair = ff * (-d[j])                                           # force on i from j (d = x_j - x_i)
             # the test side either dropped this pair or kept it against the reference: take whichever sign explains the error
             for sgn in (+1.0, -1.0):
                 if np.abs(df[i] + sgn * fpair).max() < np.abs(df[i]).max():
@@ -95,3 +93,234 @@ def force_error_without_cutoff_flips(spec, f_test, f_ref, tol, shell=2e-6, max_f
                     flips.add((min(int(i), int(j)), max(int(i), int(j))))
                     break
     return np.abs(df).max() / fmax, len(flips)
+
+
+# ---- heterogeneous pair-potential matrices (tests/test_*_pair_matrix.py) ------------------------------------------------
+
+def pair_params(spec):
+    """{(t1, t2): params} of the spec's non-bonded matrix, both orders, in W.apply's order (tables after LJ: a later entry
+    replaces an earlier one).  LJ: ("lj", eps, sigma, rc, shift) with the shift nb_lj's shift_auto gives; table:
+    ("tab", r0, dr, e, f, rc)."""
+    out = {}
+    for lj in spec.get("lj", []):
+        t1, t2, eps, sig, rc = lj[:5]
+        if not (sig > 0 and rc > 0):
+            continue
+        shift = 0.0
+        if len(lj) < 6 or lj[5]:
+            s6 = (sig * sig / (rc * rc)) ** 3
+            shift = -4.0 * eps * (s6 * s6 - s6)
+        out[(t1, t2)] = out[(t2, t1)] = ("lj", eps, sig, rc, shift)
+    for (t1, t2, r0, dr, e, f, rc) in spec.get("tables", []):
+        out[(t1, t2)] = out[(t2, t1)] = ("tab", r0, dr, np.asarray(e, np.float64), np.asarray(f, np.float64), rc)
+    return out
+
+
+def pair_cutoff(prm):
+    return prm[3] if prm[0] == "lj" else prm[5]
+
+
+def pair_eval(prm, r2, cut=True):
+    """(ff, e) of one pair at squared distance r2 (arrays): F_i = ff * (x_i - x_j); zero beyond the pair cutoff (cut=False:
+    the potential continued past it).  LJ truncated
+    and energy-shifted; tables interpolated linearly in r, below r0 row 0, beyond the last row the last row (the oracle's
+    documented clamps, md_oracle.cpp pair_eval)."""
+    r2 = np.asarray(r2, dtype=np.float64)
+    inside = (r2 <= pair_cutoff(prm) ** 2) | (not cut)
+    if prm[0] == "lj":
+        _, eps, sig, rc, shift = prm
+        frac2 = 1.0 / r2
+        s2 = sig * sig * frac2
+        s6 = s2 * s2 * s2
+        ff = 24.0 * eps * (2.0 * s6 * s6 - s6) * frac2
+        e = 4.0 * eps * (s6 * s6 - s6) + shift
+    else:
+        _, r0, dr, te, tf, rc = prm
+        r = np.sqrt(r2)
+        t = (r - r0) / dr
+        nrow = len(te)
+        k = np.clip(np.floor(t), 0, nrow - 2).astype(np.int64)
+        w = t - k
+        fv = tf[k] + w * (tf[k + 1] - tf[k])
+        ev = te[k] + w * (te[k + 1] - te[k])
+        lo, hi = t <= 0, t >= nrow - 1
+        fv = np.where(lo, tf[0], np.where(hi, tf[-1], fv))
+        ev = np.where(lo, te[0], np.where(hi, te[-1], ev))
+        ff, e = fv / r, ev
+    return np.where(inside, ff, 0.0), np.where(inside, e, 0.0)
+
+
+def pair_reference(spec):
+    """Independent fp64 all-pairs evaluation of the non-bonded matrix with minimum image (no list, no exclusions): forces
+    by particle (spec order), epot_lj, epot_tab, virial_nb = sum over pairs of ff * r^2."""
+    pos = np.asarray(spec["pos"], dtype=np.float64)
+    L = np.asarray(spec["box"], dtype=np.float64)
+    types = np.asarray(spec["types"])
+    n = len(pos)
+    f = np.zeros((n, 3))
+    elj = etab = vir = 0.0
+    prm = pair_params(spec)
+    for i in range(n - 1):
+        d = pos[i] - pos[i + 1:]
+        d -= L * np.rint(d / L)
+        r2 = (d * d).sum(1)
+        tj = types[i + 1:]
+        for t in np.unique(tj):
+            p = prm.get((int(types[i]), int(t)))
+            if p is None:
+                continue
+            m = np.nonzero(tj == t)[0]
+            ff, e = pair_eval(p, r2[m])
+            fij = ff[:, None] * d[m]
+            f[i] += fij.sum(0)
+            np.subtract.at(f, i + 1 + m, fij)
+            if p[0] == "lj":
+                elj += e.sum()
+            else:
+                etab += e.sum()
+            vir += (ff * r2[m]).sum()
+    return f, elj, etab, vir
+
+
+def energy_scales(spec, shell=2e-6):
+    """{epot_lj, epot_tab, virial_nb: (sum of |term| over the pairs within their cutoff, what the pairs within `shell` of
+    their cutoff contribute)}.  The first scales the rounding of an fp32 sum whose terms cancel; the second is what a pair
+    the fp32 build decides the other way at its cutoff can move it by (force_error_without_cutoff_flips)."""
+    from scipy.spatial import cKDTree
+    L = np.asarray(spec["box"], dtype=np.float64)
+    pos = np.mod(np.asarray(spec["pos"], dtype=np.float64), L)
+    pos = np.where(pos >= L, 0.0, pos)
+    types = np.asarray(spec["types"])
+    prm = pair_params(spec)
+    out = dict(epot_lj=[0.0, 0.0], epot_tab=[0.0, 0.0], virial_nb=[0.0, 0.0])
+    if not prm:
+        return out
+    rmax = max(pair_cutoff(p) for p in prm.values()) + shell
+    ij = cKDTree(pos, boxsize=L).query_pairs(rmax, output_type="ndarray")
+    d = pos[ij[:, 0]] - pos[ij[:, 1]]
+    d -= L * np.rint(d / L)
+    r2 = (d * d).sum(1)
+    ta, tb = types[ij[:, 0]], types[ij[:, 1]]
+    for (a, b), p in prm.items():
+        if a > b:
+            continue
+        m = ((ta == a) & (tb == b)) | ((ta == b) & (tb == a))
+        ff, e = pair_eval(p, r2[m], cut=False)
+        inside = r2[m] <= pair_cutoff(p) ** 2
+        edge = np.abs(np.sqrt(r2[m]) - pair_cutoff(p)) < shell
+        k = "epot_lj" if p[0] == "lj" else "epot_tab"
+        out[k][0] += np.abs(e[inside]).sum()
+        out[k][1] += np.abs(e[edge]).sum()
+        out["virial_nb"][0] += np.abs(ff * r2[m])[inside].sum()
+        out["virial_nb"][1] += np.abs(ff * r2[m])[edge].sum()
+    return out
+
+
+def smooth_table(rng, r0, dr, nrow, rz):
+    """Rows (r0 + k dr) of a soft Morse-like pair potential times (1 - (r/rz)^2)^2: e and f = -dU/dr go smoothly to zero
+    at rz and stay zero beyond (rz = inf: no switch, the table is cut wherever it ends)."""
+    r = r0 + dr * np.arange(nrow)
+    eps, sig, a = rng.uniform(0.3, 2.0), rng.uniform(0.8, 1.1), rng.uniform(2.0, 3.5)
+    x = r / sig - 1.0
+    u = eps * (np.exp(-2.0 * a * x) - 2.0 * np.exp(-a * x))
+    du = eps * (a / sig) * (-2.0 * np.exp(-2.0 * a * x) + 2.0 * np.exp(-a * x))
+    if np.isfinite(rz):
+        q = np.clip(1.0 - (r / rz) ** 2, 0.0, None)
+        sw, dsw = q * q, -4.0 * r / rz ** 2 * q
+        u, du = u * sw, du * sw + u * dsw
+    return u, -du
+
+
+def pair_matrix(rng, type_ids, rc, fixed=False, kind=None):
+    """Random non-bonded matrix over `type_ids` (spec "lj" / "tables" lists).  kind: None (draw one), "mixed" (LJ pairs
+    with their own eps / sigma / rc / shift, inactive pairs, several tables), "all_active" (the same with every pair
+    carrying a potential), "lj_only" (no tables), "uniform_shift" (every active LJ pair shares eps / sigma / rc, the shifts
+    differ: MODE 2 forces, per-pair energies), "uniform_table" (that LJ set plus one table: MODE 0).
+    fixed: a frozen-configuration draw (tables may end or be cut anywhere, values at the clamps and the cutoff non-zero)."""
+    type_ids = sorted(int(t) for t in type_ids)
+    if kind is None:
+        kind = str(rng.choice(["mixed", "mixed", "all_active", "lj_only", "uniform_shift", "uniform_table"]))
+    pairs = [(a, b) for i, a in enumerate(type_ids) for b in type_ids[i:]]
+    lj, tables = [], []
+    if kind.startswith("uniform"):
+        eps, sig, prc = rng.uniform(0.3, 2.0), rng.uniform(0.85, 1.1), rng.uniform(1.5, rc)
+        off = rng.random(len(pairs)) < 0.25
+        off[0] = False
+        for (a, b), o in zip(pairs, off):
+            if not o:
+                lj.append((a, b, eps, sig, prc, bool(rng.random() < 0.5)))
+        if kind == "uniform_table":
+            a, b = pairs[int(rng.integers(len(pairs)))]
+            tables.append(_draw_table(rng, a, b, rc, fixed))
+        return lj, tables
+    p_off = 0.0 if kind == "all_active" else rng.uniform(0.1, 0.4)
+    p_tab = 0.0 if kind == "lj_only" else rng.uniform(0.15, 0.5)
+    ntab = int(rng.integers(1, 5))
+    protos = [_draw_table(rng, 0, 0, rc, fixed) for _ in range(ntab)]
+    for (a, b) in pairs:
+        u = rng.random()
+        if u < p_off:
+            continue
+        if u < p_off + p_tab:
+            tables.append((a, b) + protos[int(rng.integers(ntab))][2:])
+        else:
+            lj.append((a, b, rng.uniform(0.3, 2.0), rng.uniform(0.85, 1.1), rng.uniform(1.5, rc), bool(rng.random() < 0.5)))
+    if not lj and not tables:
+        lj.append((type_ids[0], type_ids[0], 1.0, 1.0, rc, True))
+    return lj, tables
+
+
+def _draw_table(rng, a, b, rc, fixed):
+    """One table on (a, b): rows start at dr as the converter writes them (r0 = dr) unless a frozen draw moves r0 out to test
+    the row-0 clamp; nrow = 2 sometimes; some tables end before the pair cutoff (the last row is clamped)."""
+    prc = rng.uniform(1.5, rc)
+    u = rng.random()
+    if u < 0.15:                              # two rows: a linear force ramp, clamped to the last row beyond it
+        dr = rng.uniform(0.4, 0.7) if not fixed else rng.uniform(0.3, 0.8)
+        nrow = 2
+    else:
+        dr = float(rng.choice([0.002, 0.005, 0.01, 0.02, 0.05]))
+        nrow = int(np.ceil(prc / dr)) + int(rng.integers(-int(0.3 * prc / dr), 4))
+        nrow = max(nrow, 3)
+    r0 = dr
+    if fixed and rng.random() < 0.4:
+        r0 = rng.uniform(0.7, 0.95)
+    rend = r0 + (nrow - 1) * dr
+    if fixed:
+        rz = np.inf if rng.random() < 0.5 else rng.uniform(0.8 * prc, 1.5 * prc)
+    else:
+        rz = min(prc, rend)                   # zero at the pair cutoff, or at the table's end when that comes first
+    e, f = smooth_table(rng, r0, dr, nrow, rz)
+    if not fixed and nrow == 2:
+        e, f = np.array([e[0] if e[0] > 0 else 1.0, 0.0]), np.array([abs(f[0]) + 1.0, 0.0])   # a soft repulsive ramp to zero at 2 dr
+    return (a, b, float(r0), float(dr), e, f, float(prc))
+
+
+def pair_matrix_spec(case, n=None, fixed=False, kind=None, kT=1.0, gamma=2.0, dt=0.004):
+    """A seeded system under a random pair matrix: K = 2..16 types (type id 15 in every third draw, ids 0..K-1 all active
+    in every eighth), positions from the
+    lattice generator with jitter, types drawn at random.  n: particle count (default 2k .. 60k, or a few hundred when
+    fixed).  Returns a plain spec that W.apply accepts (Langevin thermostat at kT, gamma)."""
+    from chemlab_amd import workloads as W
+    rng = np.random.default_rng(31000 + case)
+    K = int(rng.integers(2, 17))
+    ids = rng.choice(16, size=K, replace=False)
+    if case % 3 == 0 and 15 not in ids:
+        ids[0] = 15
+    type_ids = sorted(int(t) for t in ids)
+    if case % 8 == 4:           # type ids 0..K-1, every pair active: the engine's all_active list path (type filter on)
+        type_ids = list(range(K))
+        kind = kind or "all_active"
+    rc = float(rng.uniform(2.0, 2.8))
+    skin = float(rng.uniform(0.2, 0.45))
+    if n is None:
+        n = int(rng.choice([4 * k ** 3 for k in range(8, 25, 2)] + [k ** 3 for k in range(13, 40, 3)] if not fixed else [256, 343, 500]))
+    rho = float(rng.uniform(0.55, 0.85))
+    pos, L, _ = W._lattice(n, rho)
+    pos = pos + rng.uniform(-0.06, 0.06, pos.shape) * (L / round(n ** (1 / 3)))
+    types = rng.choice(type_ids, size=n).astype(np.int32)
+    lj, tables = pair_matrix(rng, type_ids, rc, fixed=fixed, kind=kind)
+    mass = rng.uniform(0.8, 1.5, n) if rng.random() < 0.5 else np.ones(n)
+    return dict(name="pair_matrix", n=n, box=[L] * 3, rc=rc, skin=skin, dt=dt, ids=np.arange(1, n + 1), types=types, pos=pos,
+                vel=W._maxwell(rng, n, kT, mass), mass=mass, state=np.zeros(n, np.int32), res_id=np.arange(1, n + 1, dtype=np.int32),
+                lj=lj, tables=tables, kT=kT, gamma=gamma, seed=case + 1, type_ids=type_ids)
