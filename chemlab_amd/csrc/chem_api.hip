@@ -145,6 +145,8 @@ struct Ctx {
   int opt_dd_merge = 1;     // decomposed path: displacement fold in the integrate kernel, decision in the force kernel (no one-block launches)
   bool opt_dd_fastx = true;  // decomposed path: excluded partners located as slots by the standalone list kernel (ghost copies through gtag)
   int opt_ablate_list = 0;  // diagnostics (with debug_stamps): parts of the list build left out, see tools/rebuild_stamps.py
+                            // (1 tables + staging only, 3 no peel, 5 exclusions ignored, 4 home particles behind the first pass of 512 skipped: the lists are incomplete)
+  int opt_coop_overflow = 1; // list build: the home particles behind a tile's last full pass of 512 are swept by nine lanes each (dev_nlist_tile_f32)
   int opt_tiles = 1;        // LDS-tiled list/force kernels when the cell grid allows
   int opt_fused = 1;        // rebuild chain as one persistent launch with grid barriers (single domain, tiles)
   int pair_guard = 0;       // 256 while the force kernels are launched speculatively (decomposed path)
@@ -533,7 +535,7 @@ template <typename R> struct CtxT : Ctx {
   void launch_rebuild_fused() {
     FusedArgs<R> a{};
     a.n = n; a.ncell = box.ncell; a.ntiles = ntiles; a.CAP = tile_cap; a.S = S; a.has_excl = has_excl; a.criterion = opt_criterion;
-    a.par = fused_par; a.seg_shift = seg_shift; a.tseg_shift = tseg_shift; a.nblk = cdiv(n, kIntPerBlock); a.want32 = want32 ? 1 : 0; a.ntypes = ntypes; a.ablate = dbg_on ? opt_ablate_list : 0;
+    a.par = fused_par; a.seg_shift = seg_shift; a.tseg_shift = tseg_shift; a.nblk = cdiv(n, kIntPerBlock); a.want32 = want32 ? 1 : 0; a.ntypes = ntypes; a.ablate = dbg_on ? opt_ablate_list : 0; a.coop = opt_coop_overflow;
     a.half_skin = 0.5 * skin_eff(); a.rl2 = (R)((rc + skin_eff()) * (rc + skin_eff()));
     a.half_skin_ref = 0.5 * skin; a.rl2_rows = (R)((rc + skin) * (rc + skin));
     a.istep = step;
@@ -955,7 +957,7 @@ template <typename R> struct CtxT : Ctx {
       }
       hipLaunchKernelGGL((k_nlist_tiles<R, 512>), dim3(ntiles), dim3(512), list_lds_need(want32), stream, ntiles, tile_cap, x4.p, tag.p, tdesc.p, rl2,
                          excl_start.p, excl_list.p, list_excl, act, ntypes, nl16.p, S, nnh.p, want32 ? nlist.p : (int*)nullptr, S, nn.p, c, rl2_rows, bs,
-                         bxp, (const int*)rtag.p, (const int*)gtag.p, G, G + n);
+                         bxp, (const int*)rtag.p, (const int*)gtag.p, G, G + n, opt_coop_overflow);
     } else if (box.nc[0] > 0)
       hipLaunchKernelGGL((k_nlist_cells<R, 1536>), dim3(std::min(box.ncell, 2560)), dim3(256), 0, stream, n, x4.p, tag.p, cell_start.p, box, rl2,
                          excl_start.p, excl_list.p, has_excl, nlist.p, nn.p, S, c);
@@ -2662,6 +2664,7 @@ int chem_set_option(chem_ctx* ctx, const char* name, double value) {
   else if (k == "dd_merge") CTX.opt_dd_merge = value != 0;
   else if (k == "dd_fold") CTX.opt_dd_fold = value != 0;
   else if (k == "dd_fastx") { CTX.opt_dd_fastx = value != 0; CTX.resort = true; }
+  else if (k == "coop_overflow") { CTX.opt_coop_overflow = value != 0 ? 1 : 0; CTX.resort = true; }
   else if (k == "lpt_tiles") { CTX.opt_lpt = value != 0; CTX.resort = true; }
   else if (k == "tiles") { CTX.opt_tiles = value != 0; CTX.geom_dirty = true; }
   else if (k == "fused_rebuild") { CTX.opt_fused = value != 0; CTX.geom_dirty = true; }

@@ -1600,12 +1600,15 @@ __device__ __forceinline__ void dev_nlist_tile(const TileLDS<R>& T, Vec4<R>* con
 // leaves its result in the sign bit of rl^2 + delta - r^2, which one v_alignbit per candidate
 // shifts into the segment's miss mask.  Hits surviving the type mask (and, located as slots, the self pair and up to
 // four excluded partners) are peeled off and appended to the lane's 16-byte chunk register.
+// The home particles behind the last full pass of BS (nhome % BS of them) are swept by nine lanes each, one per stencil
+// row (`coop_on`, option coop_overflow): see the cooperative rounds at the end.
 template <typename RS, int BS>
 __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigned char* lds, const ListLDS& L, const int* tag, const float rl2,
                                                    const int* excl_start, const int* excl_list, const int has_excl,
                                                    unsigned short* nl16, const int S16, int* nnh, int* nlist, const int S, int* nn, DevCtl* ctl,
                                                    const Box<RS>* bx, const int* rtag, const Vec4<RS>* x4, const int ablate = 0, const float rl2_rows_ = -1.f,
-                                                   uint4* bslots = nullptr, const int* gtag = nullptr, const int real0 = 0, const int real1 = 0x7fffffff) {
+                                                   uint4* bslots = nullptr, const int* gtag = nullptr, const int real0 = 0, const int real1 = 0x7fffffff,
+                                                   const int coop_on = 0) {
   // (gtag, real0, real1: slab decomposition -- index of a tag's GHOST copy on this rank, range of the real particles)
   const float rl2_rows = rl2_rows_ > 0.f ? rl2_rows_ : rl2;   // int32 Verlet rows: the workload's rc+skin (the 16-bit force list may use a wider list skin)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1618,7 +1621,17 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
   const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4], hbase = T.geom[5];
   const bool nowin = T.geom[7] != 0;
   unsigned short* reg16 = nl16 + (size_t)hbase * S16;
-  for (int q = threadIdx.x; q < nhome; q += BS) {
+  const float clen0 = (float)T.clen[0], clen1 = (float)T.clen[1], clen2 = (float)T.clen[2], subinv = (float)T.subinv;
+  const float weps = clen0 * 2e-4f;
+
+  // What a sweep needs to know about its home particle q (one lane per home, or the nine lanes of the cooperative pass).
+  struct Home {
+    int p, ly, lz, sself, e0, e1, xs0, xs1, xs2, xs3, fmin, fmax;
+    float xix, xiy, xiz, cq, dylo, dyhi, dzlo, dzhi, sxi;
+    const CHEM_LDS unsigned int* tmrow;
+    bool fastx;
+  };
+  auto home_setup = [&](const int q, Home& h) __attribute__((always_inline)) {
     int sgi = 0;
 #pragma unroll
     for (int k = 1; k < NHSEG; ++k) sgi += (q >= T.hoff[k]) ? 1 : 0;
@@ -1632,14 +1645,13 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     const int sself = T.rowoff[hr] + eh;
     const CHEM_LDS float* self = img + (sself >> 2) * kGrpF + (sself & 3);
     const float xix = self[0], xiy = self[4], xiz = self[8];             // relative to the stencil's lower corner
-    const float cq = rl2 + kListDelta - self[12];
-    const f32x2 ax = {2.f * xix, 2.f * xix}, ay = {2.f * xiy, 2.f * xiy}, az = {2.f * xiz, 2.f * xiz}, cc = {cq, cq};
+    h.p = p; h.ly = ly; h.lz = lz; h.sself = sself; h.xix = xix; h.xiy = xiy; h.xiz = xiz;
+    h.cq = rl2 + kListDelta - self[12];
     const int ti = (int)x4[p].w & 15;                 // home cells carry no periodic shift: x4[p] is the staged particle
-    const CHEM_LDS unsigned int* tmrow = tmask + ti * L.nwords;
+    h.tmrow = tmask + ti * L.nwords;
     int e0 = 0, e1 = 0;
     if (has_excl && ablate != 5) { const int tg = tag[p]; e0 = excl_start[tg]; e1 = excl_start[tg + 1]; }      // (ablate 5, diagnostic: exclusions ignored)
-    int cnt = 0, cnt16 = 0;
-    int* row32 = nlist ? nlist + (size_t)p * S : nullptr;
+    h.e0 = e0; h.e1 = e1;
     // Exclusions without leaving the plain path: the few excluded partners of a particle are located
     // in the staged tile ONCE (tag -> index -> position -> cell -> slot, the binning arithmetic repeated on the same
     // bits) and their bits are cleared from the hit masks, like the self pair.  More than 4 exclusions: generic path.
@@ -1648,7 +1660,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     // The copy that counts is the one in a cell layer next to the home particle's (a partner is closer than one cell edge).
     int xs0 = -1, xs1 = -1, xs2 = -1, xs3 = -1;
     bool fastx = false;
-    if (bx && e1 > e0 && e1 - e0 <= 4 && !row32) {
+    if (bx && e1 > e0 && e1 - e0 <= 4 && !nlist) {
       fastx = true;
       const int org = T.geom[6];
       const int nx = bx->nc[0], ny = bx->nc[1], nz = bx->nc[2];
@@ -1685,26 +1697,111 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
         if (k == 0) xs0 = slot; else if (k == 1) xs1 = slot; else if (k == 2) xs2 = slot; else xs3 = slot;
       }
     }
-    // Inline bonds (force kernel epilogue).  The host enables this only where the exclusion set IS the bond set and all bonds
-    // share one harmonic parameter set (chain-growth systems: every reaction bond is excluded, nothing else is): the LDS slots
-    // of the excluded partners are the bonded partners -- recorded as they are (eight 32-bit words per home particle, ~0 = none),
-    // no bonded table is consulted.  Located partners (<= 4 exclusions) are written here; on the generic path (5..8 exclusions,
-    // or int32 rows wanted) every excluded hit is recorded as it is met in the sweep below.  More than kBondSlots exclusions:
-    // the particle's bonds stay with the work list.
+    h.xs0 = xs0; h.xs1 = xs1; h.xs2 = xs2; h.xs3 = xs3; h.fastx = fastx;
+    // x-window of a stencil row: a candidate in row (dy, dz) is at least (ddy, ddz) away in y and z (distance of the
+    // home particle from that row's slab), so only x within sqrt(rl^2 - ddy^2 - ddz^2) can be a neighbour -- 46 % of the
+    // 3-cell run on average.  `weps` absorbs every rounding difference between the binning arithmetic and this one (the
+    // slices only prune, the distance test decides membership).
+    const float ylo = ((float)(ly + 1) - kRefCells) * clen1, zlo = ((float)(lz + 1) - kRefCells) * clen2;   // (image coordinates are relative to T.org)
+    h.dylo = fmaxf(xiy - ylo - weps, 0.f); h.dyhi = fmaxf(ylo + clen1 - xiy - weps, 0.f);
+    h.dzlo = fmaxf(xiz - zlo - weps, 0.f); h.dzhi = fmaxf(zlo + clen2 - xiz - weps, 0.f);
+    h.sxi = (xix + kRefCells * clen0) * subinv;
+    h.fmin = lx * NSUB; h.fmax = (lx + 3) * NSUB - 1;
+  };
+  // Inline bonds (force kernel epilogue).  The host enables this only where the exclusion set IS the bond set and all bonds
+  // share one harmonic parameter set (chain-growth systems: every reaction bond is excluded, nothing else is): the LDS slots
+  // of the excluded partners are the bonded partners -- recorded as they are (eight 32-bit words per home particle, ~0 = none),
+  // no bonded table is consulted.  Located partners (<= 4 exclusions) are written here; on the generic path (5..8 exclusions,
+  // or int32 rows wanted) every excluded hit is recorded as it is met in the sweep below.  More than kBondSlots exclusions:
+  // the particle's bonds stay with the work list.
+  auto bonds_located = [&](const Home& h, unsigned int* const bsw) __attribute__((always_inline)) {
+    uint4 bw = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (h.fastx) {
+      if (h.xs0 >= 0) bw.x = (unsigned int)h.xs0; else if (h.e0 + 0 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs1 >= 0) bw.y = (unsigned int)h.xs1; else if (h.e0 + 1 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs2 >= 0) bw.z = (unsigned int)h.xs2; else if (h.e0 + 2 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs3 >= 0) bw.w = (unsigned int)h.xs3; else if (h.e0 + 3 < h.e1) ctl->bond_slot_miss = 1;
+    }
+    *reinterpret_cast<uint4*>(bsw) = bw;
+    if (bw.w != ~0u) *reinterpret_cast<uint4*>(bsw + 4) = make_uint4(~0u, ~0u, ~0u, ~0u);   // (the second quad is only read behind a full first one)
+  };
+  auto window = [&](const Home& h, const int dzy, int& a, int& b) __attribute__((always_inline)) {
+    const int dz = dzy / 3, dy = dzy - 3 * dz;
+    const int r = (h.lz + dz) * SY + (h.ly + dy);
+    const float ddy = dy == 0 ? h.dylo : (dy == 2 ? h.dyhi : 0.f), ddz = dz == 0 ? h.dzlo : (dz == 2 ? h.dzhi : 0.f);
+    const float w2 = rl2 - ddy * ddy - ddz * ddz;
+    int f_lo = h.fmin, f_hi = h.fmax;
+    if (!nowin) {
+      const float ws = (__builtin_amdgcn_sqrtf(fmaxf(w2, 0.f)) + weps) * subinv;
+      const int g_lo = (int)(h.sxi - ws), g_hi = (int)(h.sxi + ws);     // truncation == floor where it matters (clamped at >= fmin)
+      f_lo = g_lo > h.fmin ? g_lo : h.fmin; f_lo = f_lo < h.fmax ? f_lo : h.fmax; f_hi = g_hi < h.fmax ? g_hi : h.fmax; f_hi = f_hi > h.fmin ? f_hi : h.fmin;
+    }
+    const int ro = T.rowoff[r];
+    a = ro + (int)((const volatile CHEM_LDS unsigned short*)bnd)[r * NBND + f_lo];
+    b = ro + (int)((const volatile CHEM_LDS unsigned short*)bnd)[r * NBND + f_hi + 1];
+    b = b < total ? b : total;
+    if (w2 < 0.f) b = a;                                            // the whole row is out of reach
+  };
+  // The 32 slots from s0 of the window [a, b): candidates within the list radius, the self pair taken out (candidate u ->
+  // bit 31-u); tm = type-pair filter of the same slots.
+  auto segment = [&](const Home& h, const int s0, const int a, const int b, unsigned int& tm) __attribute__((always_inline)) -> unsigned int {
+    const f32x2 ax = {2.f * h.xix, 2.f * h.xix}, ay = {2.f * h.xiy, 2.f * h.xiy}, az = {2.f * h.xiz, 2.f * h.xiz}, cc = {h.cq, h.cq};
+    const int len = (b - s0) < 32 ? (b - s0) : 32;
+    const int ng = (len + 3) >> 2;
+    lds_f32x4* gp = (lds_f32x4*)(l3) + (kGrpF / 4) * (s0 >> 2);
+    const unsigned int w0 = h.tmrow[s0 >> 5], w1 = h.tmrow[(s0 >> 5) + 1];
+    // two groups per trip, ping-pong registers: the reads of the group after next are in flight while one is tested
+    f32x4 X0 = gp[0], Y0 = gp[1], Z0 = gp[2], Q0 = gp[3];
+    unsigned int miss = 0;
+    auto test4 = [&](const f32x4& X, const f32x4& Y, const f32x4& Z, const f32x4& Q) {
+      f32x2 lo = cc - Q.xy, hi = cc - Q.zw;                       // sign bit set at the end: outside
+      lo = __builtin_elementwise_fma(az, Z.xy, lo); hi = __builtin_elementwise_fma(az, Z.zw, hi);
+      lo = __builtin_elementwise_fma(ay, Y.xy, lo); hi = __builtin_elementwise_fma(ay, Y.zw, hi);
+      lo = __builtin_elementwise_fma(ax, X.xy, lo); hi = __builtin_elementwise_fma(ax, X.zw, hi);
+      miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(lo.x), 31);
+      miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(lo.y), 31);
+      miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(hi.x), 31);
+      miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(hi.y), 31);
+    };
+    const int ng2 = (ng + 1) & ~1;                                // (the odd group's bits fall behind `len` and are masked)
+    for (int g = 0; g < ng2; g += 2) {
+      const f32x4 X1 = gp[kGrpF / 4], Y1 = gp[kGrpF / 4 + 1], Z1 = gp[kGrpF / 4 + 2], Q1 = gp[kGrpF / 4 + 3];
+      test4(X0, Y0, Z0, Q0);
+      gp += 2 * (kGrpF / 4);
+      X0 = gp[0]; Y0 = gp[1]; Z0 = gp[2]; Q0 = gp[3];             // (up to two groups past the run: allocated, never used)
+      test4(X1, Y1, Z1, Q1);
+    }
+    unsigned int m = ng2 < 8 ? ~miss << (32 - 4 * ng2) : ~miss;  // candidate u -> bit 31-u
+    m &= ~(len < 32 ? (0xffffffffu >> len) : 0u);                 // slots behind the run
+    m &= 0xffffffffu >> (a > s0 ? a - s0 : 0);                    // slots in front of a run that starts inside a group
+    const int sh = s0 & 31;
+    tm = sh ? __builtin_amdgcn_alignbit(w0, w1, 32 - sh) : w0;    // type-pair filter of these 32 slots
+    const unsigned int ks = (unsigned int)(h.sself - s0);
+    if (ks < 32u) m &= ~(0x80000000u >> ks);
+    return m;
+  };
+  // the located exclusions of a plain home taken out of a segment's hits (like the self pair)
+  auto clear_located = [&](const Home& h, const int s0, unsigned int m) __attribute__((always_inline)) -> unsigned int {
+    const unsigned int k0 = (unsigned int)(h.xs0 - s0), k1 = (unsigned int)(h.xs1 - s0), k2 = (unsigned int)(h.xs2 - s0), k3 = (unsigned int)(h.xs3 - s0);
+    if (k0 < 32u) m &= ~(0x80000000u >> k0);
+    if (k1 < 32u) m &= ~(0x80000000u >> k1);
+    if (k2 < 32u) m &= ~(0x80000000u >> k2);
+    if (k3 < 32u) m &= ~(0x80000000u >> k3);
+    return m;
+  };
+
+  // one lane sweeps the nine rows of home particle q
+  auto sweep = [&](const int q) __attribute__((always_inline)) {
+    Home h;
+    home_setup(q, h);
+    const int p = h.p, e0 = h.e0, e1 = h.e1;
+    const bool fastx = h.fastx;
+    int cnt = 0, cnt16 = 0;
+    int* row32 = nlist ? nlist + (size_t)p * S : nullptr;
     unsigned int* const bsw = bslots ? reinterpret_cast<unsigned int*>(bslots) + (size_t)p * kBondSlots : nullptr;      // (indexed by the particle's place in the sorted arrays)
     int nbw = 0;
     const bool bond_rec = bsw && !fastx && e1 > e0 && e1 - e0 <= kBondSlots;      // generic path records while sweeping
-    if (bsw && (fastx || e1 == e0)) {
-      uint4 bw = make_uint4(~0u, ~0u, ~0u, ~0u);
-      if (fastx) {
-        if (xs0 >= 0) bw.x = (unsigned int)xs0; else if (e0 + 0 < e1) ctl->bond_slot_miss = 1;
-        if (xs1 >= 0) bw.y = (unsigned int)xs1; else if (e0 + 1 < e1) ctl->bond_slot_miss = 1;
-        if (xs2 >= 0) bw.z = (unsigned int)xs2; else if (e0 + 2 < e1) ctl->bond_slot_miss = 1;
-        if (xs3 >= 0) bw.w = (unsigned int)xs3; else if (e0 + 3 < e1) ctl->bond_slot_miss = 1;
-      }
-      *reinterpret_cast<uint4*>(bsw) = bw;
-      if (bw.w != ~0u) *reinterpret_cast<uint4*>(bsw + 4) = make_uint4(~0u, ~0u, ~0u, ~0u);   // (the second quad is only read behind a full first one)
-    }
+    if (bsw && (fastx || e1 == e0)) bonds_located(h, bsw);
     const bool plain = (e1 == e0 || fastx) && !row32;
     uint4* regq = reinterpret_cast<uint4*>(reg16) + q;   // chunk c of this particle: regq[c * nhome]
     // accepted slots are shifted into a 128-bit register; every 8th append stores one whole 16-byte chunk (one
@@ -1718,85 +1815,21 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
       if ((cnt16 & 7) == 7 && cnt16 < S16 && ablate != 2) regq[(size_t)(cnt16 >> 3) * nhome] = acc;
       ++cnt16;
     };
-    // x-window of stencil row dzy: a candidate in row (dy, dz) is at least (ddy, ddz) away in y and z (distance of the
-    // home particle from that row's slab), so only x within sqrt(rl^2 - ddy^2 - ddz^2) can be a neighbour -- 46 % of the
-    // 3-cell run on average.  `weps` absorbs every rounding difference between the binning arithmetic and this one (the
-    // slices only prune, the distance test decides membership).
-    const float clen0 = (float)T.clen[0], clen1 = (float)T.clen[1], clen2 = (float)T.clen[2], subinv = (float)T.subinv;
-    const float weps = clen0 * 2e-4f;
-    const float ylo = ((float)(ly + 1) - kRefCells) * clen1, zlo = ((float)(lz + 1) - kRefCells) * clen2;   // (image coordinates are relative to T.org)
-    const float dylo = fmaxf(xiy - ylo - weps, 0.f), dyhi = fmaxf(ylo + clen1 - xiy - weps, 0.f);
-    const float dzlo = fmaxf(xiz - zlo - weps, 0.f), dzhi = fmaxf(zlo + clen2 - xiz - weps, 0.f);
-    const float sxi = (xix + kRefCells * clen0) * subinv;
-    const int fmin = lx * NSUB, fmax = (lx + 3) * NSUB - 1;
-    auto window = [&](int dzy, int& a, int& b) {
-      const int dz = dzy / 3, dy = dzy - 3 * dz;
-      const int r = (lz + dz) * SY + (ly + dy);
-      const float ddy = dy == 0 ? dylo : (dy == 2 ? dyhi : 0.f), ddz = dz == 0 ? dzlo : (dz == 2 ? dzhi : 0.f);
-      const float w2 = rl2 - ddy * ddy - ddz * ddz;
-      int f_lo = fmin, f_hi = fmax;
-      if (!nowin) {
-        const float ws = (__builtin_amdgcn_sqrtf(fmaxf(w2, 0.f)) + weps) * subinv;
-        const int g_lo = (int)(sxi - ws), g_hi = (int)(sxi + ws);     // truncation == floor where it matters (clamped at >= fmin)
-        f_lo = g_lo > fmin ? g_lo : fmin; f_lo = f_lo < fmax ? f_lo : fmax; f_hi = g_hi < fmax ? g_hi : fmax; f_hi = f_hi > fmin ? f_hi : fmin;
-      }
-      const int ro = T.rowoff[r];
-      a = ro + (int)((const volatile CHEM_LDS unsigned short*)bnd)[r * NBND + f_lo];
-      b = ro + (int)((const volatile CHEM_LDS unsigned short*)bnd)[r * NBND + f_hi + 1];
-      b = b < total ? b : total;
-      if (w2 < 0.f) b = a;                                            // the whole row is out of reach
-    };
     int a_n, b_n;
-    window(0, a_n, b_n);
+    window(h, 0, a_n, b_n);
 #pragma unroll 1
     for (int dzy = 0; dzy < 9; ++dzy) {
       const int a = a_n, b = b_n;
-      if (dzy < 8) window(dzy + 1, a_n, b_n);
-      const int r = (lz + dzy / 3) * SY + (ly + dzy % 3);
+      if (dzy < 8) window(h, dzy + 1, a_n, b_n);
+      const int r = (h.lz + dzy / 3) * SY + (h.ly + dzy % 3);
       for (int s0 = a & ~3; s0 < b; s0 += 32) {
-        const int len = (b - s0) < 32 ? (b - s0) : 32;
-        const int ng = (len + 3) >> 2;
-        lds_f32x4* gp = (lds_f32x4*)(l3) + (kGrpF / 4) * (s0 >> 2);
-        const unsigned int w0 = tmrow[s0 >> 5], w1 = tmrow[(s0 >> 5) + 1];
-        // two groups per trip, ping-pong registers: the reads of the group after next are in flight while one is tested
-        f32x4 X0 = gp[0], Y0 = gp[1], Z0 = gp[2], Q0 = gp[3];
-        unsigned int miss = 0;
-        auto test4 = [&](const f32x4& X, const f32x4& Y, const f32x4& Z, const f32x4& Q) {
-          f32x2 lo = cc - Q.xy, hi = cc - Q.zw;                       // sign bit set at the end: outside
-          lo = __builtin_elementwise_fma(az, Z.xy, lo); hi = __builtin_elementwise_fma(az, Z.zw, hi);
-          lo = __builtin_elementwise_fma(ay, Y.xy, lo); hi = __builtin_elementwise_fma(ay, Y.zw, hi);
-          lo = __builtin_elementwise_fma(ax, X.xy, lo); hi = __builtin_elementwise_fma(ax, X.zw, hi);
-          miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(lo.x), 31);
-          miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(lo.y), 31);
-          miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(hi.x), 31);
-          miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(hi.y), 31);
-        };
-        const int ng2 = (ng + 1) & ~1;                                // (the odd group's bits fall behind `len` and are masked)
-        for (int g = 0; g < ng2; g += 2) {
-          const f32x4 X1 = gp[kGrpF / 4], Y1 = gp[kGrpF / 4 + 1], Z1 = gp[kGrpF / 4 + 2], Q1 = gp[kGrpF / 4 + 3];
-          test4(X0, Y0, Z0, Q0);
-          gp += 2 * (kGrpF / 4);
-          X0 = gp[0]; Y0 = gp[1]; Z0 = gp[2]; Q0 = gp[3];             // (up to two groups past the run: allocated, never used)
-          test4(X1, Y1, Z1, Q1);
-        }
-        unsigned int m = ng2 < 8 ? ~miss << (32 - 4 * ng2) : ~miss;  // candidate u -> bit 31-u
-        m &= ~(len < 32 ? (0xffffffffu >> len) : 0u);                 // slots behind the run
-        m &= 0xffffffffu >> (a > s0 ? a - s0 : 0);                    // slots in front of a run that starts inside a group
-        const int sh = s0 & 31;
-        const unsigned int tm = sh ? __builtin_amdgcn_alignbit(w0, w1, 32 - sh) : w0;   // type-pair filter of these 32 slots
-        const unsigned int ks = (unsigned int)(sself - s0);
-        if (ks < 32u) m &= ~(0x80000000u >> ks);
+        unsigned int tm;
+        unsigned int m = segment(h, s0, a, b, tm);
         if (ablate == 3) { cnt16 += __popc(m & tm); continue; }
         if (plain) {
           // no exclusions (or located as slots) and no int32 row: a hit needs nothing from memory
           m &= tm;
-          if (fastx) {
-            const unsigned int k0 = (unsigned int)(xs0 - s0), k1 = (unsigned int)(xs1 - s0), k2 = (unsigned int)(xs2 - s0), k3 = (unsigned int)(xs3 - s0);
-            if (k0 < 32u) m &= ~(0x80000000u >> k0);
-            if (k1 < 32u) m &= ~(0x80000000u >> k1);
-            if (k2 < 32u) m &= ~(0x80000000u >> k2);
-            if (k3 < 32u) m &= ~(0x80000000u >> k3);
-          }
+          if (fastx) m = clear_located(h, s0, m);
           while (m) {
             const int k = __clz((int)m);
             m &= ~(0x80000000u >> k);
@@ -1815,7 +1848,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
             for (int qq = 1; qq < SX; ++qq) kc += (e >= T.celloff[r][qq]) ? 1 : 0;
             const int j = T.cellg[r][kc] + (e - T.celloff[r][kc]);
             const CHEM_LDS float* cj = img + (sl >> 2) * kGrpF + (sl & 3);
-            const float ddx = xix - cj[0], ddy = xiy - cj[4], ddz = xiz - cj[8];
+            const float ddx = h.xix - cj[0], ddy = h.xiy - cj[4], ddz = h.xiz - cj[8];
             const bool exact = ddx * ddx + ddy * ddy + ddz * ddz <= rl2_rows;  // difference form: the mask is a superset by the delta shell
             bool ok = true;
             if (e1 > e0) {
@@ -1846,6 +1879,94 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
       nn[p] = c32;
       if (cnt > S) atomicMax(&ctl->nl_overflow, cnt);
     }
+  };
+
+  // Full passes of BS home particles, one lane each.  A tile of the flagship holds 578: the 66 behind the first pass would
+  // cost the workgroup a second nine-row sweep on two waves while six wait, so they go to the cooperative rounds below --
+  // unless those would be no shorter than two ordinary passes (more than 2 BS / 9 left over: crowded tiles).
+  // Cooperative round: nine adjacent lanes per home particle (seven homes per wave, lane 63 idle), lane `row` owns stencil
+  // row `row`.  Every lane tests its row's window and keeps the final hit masks (up to four segments = 128 slots) in
+  // registers; an exclusive prefix of the hit counts over the nine lanes places each lane's hits in the home's chunks, so
+  // the entries come out in the order of the one-lane sweep: rows 0..8, ascending slots inside a row.  A home this form
+  // does not cover (generic exclusion path, a window beyond the kept masks) is handed to one lane of the wave, which
+  // sweeps it in the next trip of the loop: one loop, so that the sweep exists once in the kernel (a second inlined copy
+  // costs the kernel 100 bytes of scratch per lane).
+  const int nrem = nhome % BS, nfull = nhome - nrem;
+  const bool coop = coop_on && ablate == 0 && !nlist && nrem > 0 && 9 * nrem <= 2 * BS;
+  const int npass = coop ? nfull / BS : (nhome + BS - 1) / BS;
+  const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+  const int hl = ln / 9, row = ln - 9 * hl;
+  constexpr int kRound = 7 * (BS / 64);      // homes per cooperative round of the workgroup
+  const int ncr = (coop && nrem > 7 * wv) ? (nrem - 7 * wv + kRound - 1) / kRound : 0;      // rounds of this wave
+  int qf = -1;      // home this lane sweeps alone in the next trip (fallback of a cooperative round)
+  for (int it = 0; it < npass + (ncr > 0 ? ncr + 1 : 0); ++it) {      // (wave-uniform)
+    int q = qf;
+    if (it < npass) {
+      q = it * BS + (int)threadIdx.x;
+      if (q >= nhome) q = -1;
+      if (ablate == 4 && q >= BS) { nnh[hbase + q] = 0; q = -1; }      // (diagnostic: what the sweeps behind the first pass cost)
+    } else if (it - npass < ncr) {
+      qf = -1;
+      const int q0 = nfull + 7 * wv + kRound * (it - npass), qc = q0 + hl;
+      const bool live = ln < 63 && qc < nhome;
+      unsigned int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+      int s00 = 0;
+      bool fb = false;      // this home falls back to the one-lane sweep
+      if (live) {
+        Home h;
+        home_setup(qc, h);      // (redundantly in the nine lanes: the same loads from the same addresses)
+        if (!(h.e1 == h.e0 || h.fastx)) fb = true;
+        else {
+          int a, b;
+          window(h, row, a, b);
+          s00 = a & ~3;
+          if (b - s00 > 128) fb = true;
+          else {
+            if (row == 0 && bslots) bonds_located(h, reinterpret_cast<unsigned int*>(bslots) + (size_t)h.p * kBondSlots);
+            int k = 0;
+            for (int s0 = s00; s0 < b; s0 += 32, ++k) {
+              unsigned int tm;
+              unsigned int m = segment(h, s0, a, b, tm) & tm;
+              if (h.fastx) m = clear_located(h, s0, m);
+              if (k == 0) m0 = m; else if (k == 1) m1 = m; else if (k == 2) m2 = m; else m3 = m;
+            }
+          }
+        }
+      }
+      // a home falls back as a whole: the verdicts of its nine lanes are collected from the wave's ballot
+      const bool hfb = live && ((__ballot(fb) >> (9 * hl)) & 0x1ffull) != 0ull;
+      if (hfb) { m0 = 0; m1 = 0; m2 = 0; m3 = 0; }
+      const int c = __popc(m0) + __popc(m1) + __popc(m2) + __popc(m3);
+      int incl = c;      // inclusive prefix over the home's nine lanes
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1) { const int v = __shfl_up(incl, d); if (row >= d) incl += v; }
+      if (live && !hfb) {
+        int e = incl - c;
+        unsigned short* const regq = reg16 + (size_t)qc * 8;      // entry e of this particle: regq[(e >> 3) * nhome * 8 + (e & 7)]
+        auto peel = [&](unsigned int m, const int s0) {
+          while (m) {
+            const int k = __clz((int)m);
+            m &= ~(0x80000000u >> k);
+            if (e < S16) regq[(size_t)(e >> 3) * nhome * 8 + (e & 7)] = (unsigned short)(s0 + k);
+            ++e;
+          }
+        };
+        peel(m0, s00); peel(m1, s00 + 32); peel(m2, s00 + 64); peel(m3, s00 + 96);
+        if (row == 8) {      // e = the home's row count: pad the last chunk with the far-away dummy slot, as the one-lane sweep does
+          const int real16 = e;
+          if (real16 <= S16) for (; e & 7; ++e) regq[(size_t)(e >> 3) * nhome * 8 + (e & 7)] = (unsigned short)total;
+          nnh[hbase + qc] = real16 < S16 ? real16 : S16;
+          if (real16 > S16) atomicMax(&ctl->nl_overflow, real16);
+        }
+      }
+      // fallback homes of this round: lane j takes the j-th of them (bit 9 hl of the ballot: home hl)
+      unsigned long long hm = __ballot(hfb && row == 0);
+      if (ln < __popcll(hm)) {
+        for (int j = 0; j < ln; ++j) hm &= hm - 1;
+        qf = q0 + (__ffsll((long long)hm) - 1) / 9;
+      }
+    }
+    if (q >= 0) sweep(q);
   }
 }
 
@@ -1855,7 +1976,7 @@ __global__ __launch_bounds__(BS, 4) void k_nlist_tiles(int ntiles, int CAP, cons
                                                     const int* __restrict__ excl_start, const int* __restrict__ excl_list, int has_excl,
                                                     ActMask act, int ntypes, unsigned short* __restrict__ nl16, int S16, int* __restrict__ nnh,
                                                     int* __restrict__ nlist, int S, int* __restrict__ nn, DevCtl* ctl, R rl2_rows, uint4* __restrict__ bslots,
-                                                    const Box<R>* __restrict__ boxp, const int* __restrict__ rtag, const int* __restrict__ gtag, int real0, int real1) {
+                                                    const Box<R>* __restrict__ boxp, const int* __restrict__ rtag, const int* __restrict__ gtag, int real0, int real1, int coop) {
   // (rl2: the radius the 16-bit force list is built for, rc + list skin; rl2_rows: the int32 Verlet rows', rc + skin;
   //  boxp/rtag/gtag/real0/real1: located-partner path of the exclusions on a slab, boxp == nullptr: generic path)
   if (!ctl->need_rebuild) return;
@@ -1875,7 +1996,7 @@ __global__ __launch_bounds__(BS, 4) void k_nlist_tiles(int ntiles, int CAP, cons
       list_stage_f32<R, BS>(T, chem_dyn_lds, L, CAP, x4, act, ntypes);
       __syncthreads();
       dev_nlist_tile_f32<R, BS>(T, chem_dyn_lds, L, tag, (float)rl2, excl_start, excl_list, has_excl, nl16, S16, nnh, nlist, S, nn, ctl,
-                                boxp ? (const Box<R>*)&sbox : (const Box<R>*)nullptr, rtag, x4, 0, (float)rl2_rows, bslots, gtag, real0, real1);      // (bslots: inline bonds, see dev_nlist_tile_f32)
+                                boxp ? (const Box<R>*)&sbox : (const Box<R>*)nullptr, rtag, x4, 0, (float)rl2_rows, bslots, gtag, real0, real1, coop);      // (bslots: inline bonds, see dev_nlist_tile_f32)
     } else {
       tile_fill<R, BS, true>(T, sx, CAP, x4, 1);
       __syncthreads();
@@ -2623,7 +2744,7 @@ __device__ __forceinline__ bool grid_barrier(GridBar* gb, DevCtl* ctl) {
 }
 
 template <typename R> struct FusedArgs {
-  int n, ncell, ntiles, CAP, S, has_excl, criterion, par, seg_shift, tseg_shift, nblk, want32, ntypes, ablate;
+  int n, ncell, ntiles, CAP, S, has_excl, criterion, par, seg_shift, tseg_shift, nblk, want32, ntypes, ablate, coop;      // (coop: option coop_overflow, see dev_nlist_tile_f32)
   double half_skin; R rl2;
   long long istep;                     // step this launch belongs to (recorded in ctl->halt_step when the launch has to stop the run)
   double half_skin_ref; R rl2_rows;    // the workload's skin: reference rebuild count, radius of the int32 Verlet rows (rl2 / half_skin: list skin)
@@ -2854,7 +2975,7 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
         else
         dev_nlist_tile_f32<R, BS>(T, chem_dyn_lds, L, a.tago, (float)a.rl2, a.excl_start, a.excl_list, a.bond_pass ? 0 : a.has_excl, a.nl16, a.S, a.nnh,
                                (DIAG && a.want32) ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, ablate, (float)a.rl2_rows,
-                               a.bond_pass ? (uint4*)nullptr : a.bslots);
+                               a.bond_pass ? (uint4*)nullptr : a.bslots, nullptr, 0, 0x7fffffff, a.coop);
       } else {
         tile_fill<R, BS, true>(T, sx, a.CAP, a.x4o, 1);
         __syncthreads();
