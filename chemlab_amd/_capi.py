@@ -48,6 +48,20 @@ class ReactionDesc(C.Structure):
     ]
 
 
+class DissociationDesc(C.Structure):
+    _fields_ = [
+        ("type_1", C.c_int32), ("type_2", C.c_int32),
+        ("delta_1", C.c_int32), ("delta_2", C.c_int32),
+        ("min_state_1", C.c_int32), ("max_state_1", C.c_int32),
+        ("min_state_2", C.c_int32), ("max_state_2", C.c_int32),
+        ("diss_rate", C.c_double), ("cutoff", C.c_double),
+        ("bond_list", C.c_int32), ("unexclude", C.c_int32), ("active", C.c_int32),
+        ("new_type_1", C.c_int32), ("new_type_2", C.c_int32), ("pad", C.c_int32),
+        ("new_mass_1", C.c_double), ("new_mass_2", C.c_double),
+        ("new_q_1", C.c_double), ("new_q_2", C.c_double),
+    ]
+
+
 class NbChange(C.Structure):
     _fields_ = [("reaction", C.c_int32), ("invoke_on", C.c_int32), ("old_type", C.c_int32), ("nb_level", C.c_int32),
                 ("new_type", C.c_int32), ("set_state", C.c_int32), ("new_state", C.c_int32), ("pad", C.c_int32),
@@ -149,6 +163,7 @@ PRODUCT_ONLY = {
     "comm_init": (_i, [_P, _i, _i, C.POINTER(C.c_int), C.c_char_p]),
     "comm_init_local": (_i, [_P, _i, _i, _i]),
     "comm_init_ipc": (_i, [_P, _i, _i, C.c_char_p]),
+    "dissociation_add": (_i, [_P, C.POINTER(DissociationDesc)]),   # (the CPU oracle has no bond removal)
 }
 
 

@@ -93,6 +93,12 @@ struct Ctx {
   bool react_init = false, react_on = false;
   int interval = 0, nearest = 1, max_per_interval = 0; uint64_t react_seed = 0;
   std::vector<chem_reaction_desc> reactions;
+  // Dissociation reactions (chem_dissociation_add) live beside the association table -- they occupy no row of ReactSet or of
+  // the role words -- but share its public index space: pub_map[public] = row of `reactions` (>= 0) or ~row of `dissociations`.
+  std::vector<chem_dissociation_desc> dissociations;
+  std::vector<int> pub_map, assoc_pub, diss_pub;
+  int assoc_row(int pub) const { return pub >= 0 && pub < (int)pub_map.size() && pub_map[pub] >= 0 ? pub_map[pub] : -1; }
+  int public_index(int arena_r) const { return arena_r >= 0 ? assoc_pub[arena_r] : diss_pub[~arena_r]; }
   std::vector<chem_nb_change> nb_rules;   // PostProcessChangeNeighboursProperty (chem_reaction_neighbour_change)
   // RestrictReaction.define_connection (chem_reaction_restrict): (tag lo, tag hi) -> reaction bits; CSR rebuilt when it changed
   std::map<std::pair<int32_t, int32_t>, uint32_t> restrict_map; uint32_t restricted_mask = 0; bool restrict_dirty = false;
@@ -125,6 +131,7 @@ struct Ctx {
   }
   void sync_type_mirrors() {
     for (size_t k = arena.mirror_pos; k < arena.size(); ++k) {
+      if (arena.r[k] < 0) continue;      // (a dissociation event: diss_step brought the mirrors up to date itself)
       const chem_reaction_desc& d = reactions[arena.r[k]];
       const int32_t ea = arena.a[k], eb = arena.b[k];
       if (d.new_type_1 >= 0 && d.new_type_1 != top.type[ea]) { top.type[ea] = d.new_type_1; top.mass[ea] = d.new_mass_1; top.q[ea] = d.new_q_1; }
@@ -683,6 +690,7 @@ template <typename R> struct CtxT : Ctx {
     for (int t : top.type) nt = std::max(nt, t + 1);
     for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = 0; b < CHEM_MAX_TYPES; ++b) if (pp[a][b].kind) nt = std::max(nt, std::max(a, b) + 1);
     for (auto& r : reactions) { nt = std::max(nt, std::max(r.new_type_1, r.new_type_2) + 1); }
+    for (auto& r : dissociations) { nt = std::max(nt, std::max(r.new_type_1, r.new_type_2) + 1); }
     for (auto& r : nb_rules) nt = std::max(nt, r.new_type + 1);
     for (auto& c : atrp_centers) nt = std::max(nt, std::max(c.type, c.new_type) + 1);
     ntypes = nt;
@@ -1502,6 +1510,7 @@ template <typename R> struct CtxT : Ctx {
         ++step;
         if (resc_kind == 1 || resc_kind == 3 || (resc_kind == 2 && step % (int64_t)resc_param == 0)) rescale_velocities();
         if ((react_due || atrp_due || last) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
+        if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
         if (react_due) react_step();
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
         need_int1 = true;
@@ -1911,6 +1920,87 @@ template <typename R> struct CtxT : Ctx {
       if (any_typed) upload_bonded(false);     // same tuples, slots re-resolved against the new types
     }
     trc.lap("end");
+    tm.reaction_wall_s += now_s() - t0;
+  }
+
+  // ---- dissociation reactions: every `interval` steps, in front of the association scan (rule set: include/chem_mi355.h) ----
+  // Device: k_diss_scan over the flat tuple arrays -> records of the broken bonds.  Host: canonical order, property changes
+  // (accumulated: one particle may lose several bonds), removal from every table (HostTopology::remove_bonds), then the
+  // synchronous full path of a set-up change: both CSR tables from scratch, labels, forced rebuild.  O(all bonds) per step
+  // that breaks something; a step that breaks nothing costs the scan and one read-back.
+  DBuf<Candidate> diss_rec; DBuf<int> diss_count;
+  void diss_step() {
+    bool any = false;
+    for (auto& d : dissociations) any |= d.active != 0;
+    if (!any) return;
+    HIPCHK(hipStreamSynchronize(stream));
+    const double t0 = now_s();
+    join_thread();      // lists, graph, labels and exclusion rows of the previous reaction step are complete
+    if (fent_n == 0) return;
+    Trace trc("diss");
+    DissSet ds{};
+    ds.n = (int)dissociations.size(); ds.seed = react_seed; ds.step = (unsigned long long)step;
+    for (int q = 0; q < ds.n; ++q) {
+      const chem_dissociation_desc& d = dissociations[q];
+      DissDev& r = ds.r[q];
+      r.type_1 = d.type_1; r.type_2 = d.type_2; r.min1 = d.min_state_1; r.max1 = d.max_state_1; r.min2 = d.min_state_2; r.max2 = d.max_state_2;
+      r.list = d.bond_list; r.active = d.active; r.pub = diss_pub[q]; r.pad = 0;
+      r.cut2 = d.cutoff > 0 ? d.cutoff * d.cutoff : 0.0; r.prob = d.diss_rate * dt * (double)interval;
+    }
+    if (diss_rec.n < fent_n) diss_rec.alloc(fent_n + fent_n / 2 + 1024);
+    if (!diss_count.p) diss_count.alloc(1);
+    HIPCHK(hipMemsetAsync(diss_count.p, 0, sizeof(int), stream));
+    hipLaunchKernelGGL(k_diss_scan<R>, dim3(cdiv((long long)fent_n, 256)), dim3(256), 0, stream, (int)fent_n, fent.p, flist.p, x4.p, rtag.p, nglob,
+                       state.p, boxd, ds, diss_rec.p, (int)diss_rec.n, diss_count.p);
+    int nrec = 0;
+    HIPCHK(hipMemcpyAsync(&nrec, diss_count.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    trc.lap("scan");
+    if (nrec <= 0) { tm.reaction_wall_s += now_s() - t0; return; }
+    std::vector<Candidate> rec;
+    diss_rec.download(rec, (size_t)nrec, stream);
+    std::sort(rec.begin(), rec.end(), [&](const Candidate& p, const Candidate& q) {
+      const int lp = dissociations[p.r].bond_list, lq = dissociations[q.r].bond_list;
+      return lp != lq ? lp < lq : p.h < q.h;
+    });
+    // property changes on the mirrors, in canonical order; states as they are on the device
+    if (state_mirror_stale) { std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false; }
+    sync_type_mirrors();
+    std::vector<int32_t> changed;
+    std::vector<HostTopology::BrokenBond> broken;
+    broken.reserve(rec.size());
+    for (Candidate& e : rec) {
+      const chem_dissociation_desc& d = dissociations[e.r];
+      top.state[e.a] += d.delta_1; top.state[e.b] += d.delta_2;
+      if (d.new_type_1 >= 0) { top.type[e.a] = d.new_type_1; top.mass[e.a] = d.new_mass_1; top.q[e.a] = d.new_q_1; }
+      if (d.new_type_2 >= 0) { top.type[e.b] = d.new_type_2; top.mass[e.b] = d.new_mass_2; top.q[e.b] = d.new_q_2; }
+      changed.push_back(e.a); changed.push_back(e.b);
+      broken.push_back(HostTopology::BrokenBond{e.a, e.b, d.bond_list, d.unexclude});
+      e.r = ~e.r;      // the arena tells the two kinds of event apart by the sign
+    }
+    std::sort(changed.begin(), changed.end());
+    changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
+    std::vector<PropChangeDev> chg;
+    chg.reserve(changed.size());
+    for (int32_t t : changed) chg.push_back(PropChangeDev{t, top.type[t], 1, top.state[t], top.mass[t], top.q[t]});
+    DBuf<PropChangeDev> dchg; dchg.alloc(chg.size());
+    HIPCHK(hipMemcpyAsync(dchg.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), dchg.p, state.p, rtag.p, x4.p, v4.p);
+    append_events(rec.data(), rec.size(), step, std::vector<int8_t>());
+    arena.mirror_pos = arena.size();
+    std::vector<int32_t> touched;
+    top.remove_bonds(broken, touched);
+    excl_deg.clear();      // (the exclusion log shrank: degrees are counted afresh)
+    HIPCHK(hipStreamSynchronize(stream));
+    if (g_trace) fprintf(stderr, "[chem trace] broken bonds %zu\n", rec.size());
+    trc.lap("host removal");
+    upload_excl(true);
+    upload_bonded(true);      // (re-proves bonds_excluded: a break that keeps its exclusion ends the inline-bond mode; typed slots against the new types)
+    mol_id.upload(top.mol_id, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    resort = true;
+    set_ctl_field(&DevCtl::force_rebuild, 1);
+    trc.lap("table rebuild");
     tm.reaction_wall_s += now_s() - t0;
   }
 
@@ -2480,7 +2570,27 @@ int chem_reaction_add(chem_ctx* ctx, const chem_reaction_desc* d) {
   if (d->new_type_1 >= 0) REQUIRE(d->new_mass_1 > 0, CHEM_EINVAL, "new_mass_1");
   if (d->new_type_2 >= 0) REQUIRE(d->new_mass_2 > 0, CHEM_EINVAL, "new_mass_2");
   c.reactions.push_back(*d); c.pair_dirty = true;
-  return (int)c.reactions.size() - 1;
+  c.pub_map.push_back((int)c.reactions.size() - 1); c.assoc_pub.push_back((int)c.pub_map.size() - 1);
+  return (int)c.pub_map.size() - 1;
+  API_END(ctx)
+}
+
+int chem_dissociation_add(chem_ctx* ctx, const chem_dissociation_desc* d) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(c.react_init, CHEM_ESTATE, "chem_reaction_init first");
+  REQUIRE(d, CHEM_EINVAL, "null descriptor");
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "dissociation reactions are not available on the decomposed path (chem_comm_init*)");
+  REQUIRE((int)c.dissociations.size() < CHEM_MAX_REACTIONS && c.pub_map.size() < 256, CHEM_ENOSPC, "too many reactions");
+  REQUIRE(d->type_1 >= 0 && d->type_1 < CHEM_MAX_TYPES && d->type_2 >= 0 && d->type_2 < CHEM_MAX_TYPES, CHEM_EINVAL, "dissociation types");
+  REQUIRE(d->new_type_1 < CHEM_MAX_TYPES && d->new_type_2 < CHEM_MAX_TYPES, CHEM_EINVAL, "dissociation new types");
+  REQUIRE(d->diss_rate >= 0, CHEM_EINVAL, "diss_rate must not be negative");
+  REQUIRE(d->bond_list >= 0 && d->bond_list < (int)c.top.lists.size() && c.top.lists[d->bond_list].arity == 2, CHEM_EINVAL, "dissociation bond_list must be an arity-2 list");
+  if (d->new_type_1 >= 0) REQUIRE(d->new_mass_1 > 0, CHEM_EINVAL, "new_mass_1");
+  if (d->new_type_2 >= 0) REQUIRE(d->new_mass_2 > 0, CHEM_EINVAL, "new_mass_2");
+  c.dissociations.push_back(*d); c.pair_dirty = true;
+  c.pub_map.push_back(~((int)c.dissociations.size() - 1)); c.diss_pub.push_back((int)c.pub_map.size() - 1);
+  return (int)c.pub_map.size() - 1;
   API_END(ctx)
 }
 
@@ -2488,11 +2598,11 @@ int chem_reaction_neighbour_change(chem_ctx* ctx, const chem_nb_change* r) {
   API_BEGIN
   Ctx& c = CTX;
   REQUIRE(r, CHEM_EINVAL, "null rule");
-  REQUIRE(r->reaction >= 0 && r->reaction < (int)c.reactions.size(), CHEM_EINVAL, "neighbour_change: reaction index");
+  REQUIRE(c.assoc_row(r->reaction) >= 0, CHEM_EINVAL, "neighbour_change: reaction index");
   REQUIRE(r->invoke_on >= 1 && r->invoke_on <= 3 && r->nb_level >= 1, CHEM_EINVAL, "neighbour_change: invoke_on must be 1, 2 or 3 and nb_level >= 1");
   REQUIRE(r->old_type >= 0 && r->old_type < CHEM_MAX_TYPES && r->new_type >= 0 && r->new_type < CHEM_MAX_TYPES, CHEM_EINVAL, "neighbour_change: types");
   REQUIRE(r->new_mass > 0, CHEM_EINVAL, "neighbour_change: new_mass");
-  c.nb_rules.push_back(*r); c.pair_dirty = true;
+  c.nb_rules.push_back(*r); c.nb_rules.back().reaction = c.assoc_row(r->reaction); c.pair_dirty = true;
   return 0;
   API_END(ctx)
 }
@@ -2500,6 +2610,7 @@ int chem_reaction_neighbour_change(chem_ctx* ctx, const chem_nb_change* r) {
 int chem_reaction_constraint(chem_ctx* ctx, int reaction, int role, int nb_type, int min_state, int max_state) {
   API_BEGIN
   Ctx& c = CTX;
+  reaction = c.assoc_row(reaction);
   REQUIRE(reaction >= 0 && reaction < (int)c.reactions.size() && reaction < 32, CHEM_EINVAL, "reaction_constraint: reaction index");
   REQUIRE((role == 1 || role == 2) && nb_type >= 0 && nb_type < CHEM_MAX_TYPES, CHEM_EINVAL, "reaction_constraint: role must be 1 or 2, nb_type a type id");
   if (c.constraints.size() < c.reactions.size()) c.constraints.resize(c.reactions.size());
@@ -2511,6 +2622,7 @@ int chem_reaction_constraint(chem_ctx* ctx, int reaction, int role, int nb_type,
 int chem_reaction_restrict(chem_ctx* ctx, int reaction, int64_t n, const int64_t* p) {
   API_BEGIN
   Ctx& c = CTX;
+  reaction = c.assoc_row(reaction);
   REQUIRE(reaction >= 0 && reaction < (int)c.reactions.size() && reaction < 32, CHEM_EINVAL, "reaction_restrict: reaction index");
   REQUIRE(n >= 0 && (n == 0 || p), CHEM_EINVAL, "reaction_restrict: pairs");
   for (int64_t k = 0; k < n; ++k) {
@@ -2571,8 +2683,10 @@ int chem_reactions_enable(chem_ctx* ctx, int on) { API_BEGIN CTX.react_on = on !
 
 int chem_reaction_set_rate(chem_ctx* ctx, int r, double rate) {
   API_BEGIN
-  REQUIRE(r >= 0 && r < (int)CTX.reactions.size(), CHEM_EINVAL, "reaction index");
-  CTX.reactions[r].rate = rate;
+  REQUIRE(r >= 0 && r < (int)CTX.pub_map.size(), CHEM_EINVAL, "reaction index");
+  const int row = CTX.pub_map[r];
+  if (row >= 0) CTX.reactions[row].rate = rate;
+  else { REQUIRE(rate >= 0, CHEM_EINVAL, "diss_rate must not be negative"); CTX.dissociations[~row].diss_rate = rate; }
   return 0;
   API_END(ctx)
 }
@@ -2615,7 +2729,7 @@ int64_t chem_get_events(chem_ctx* ctx, chem_event* out, int64_t cap) {
   for (size_t bi = A.expanded_blocks; bi < A.blocks.size(); ++bi) {
     const size_t k0 = A.blocks[bi].second, k1 = bi + 1 < A.blocks.size() ? A.blocks[bi + 1].second : A.size(), first = c.events.size();
     for (size_t k = k0; k < k1; ++k)
-      c.events.push_back(chem_event{A.blocks[bi].first, c.top.id[A.a[k]], c.top.id[A.b[k]], A.r[k], A.intra.size() > k ? (int32_t)A.intra[k] : 0, A.d2[k]});
+      c.events.push_back(chem_event{A.blocks[bi].first, c.top.id[A.a[k]], c.top.id[A.b[k]], c.public_index(A.r[k]), A.intra.size() > k ? (int32_t)A.intra[k] : 0, A.d2[k]});
     std::sort(c.events.begin() + first, c.events.end(), [](const chem_event& p, const chem_event& q) {
       return std::make_pair(std::min(p.id_a, p.id_b), std::max(p.id_a, p.id_b)) < std::make_pair(std::min(q.id_a, q.id_b), std::max(q.id_a, q.id_b));
     });
@@ -2719,6 +2833,7 @@ int chem_comm_init(chem_ctx* ctx, int nranks, int rank, const int node_grid[3], 
   API_BEGIN
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init: rank/nranks");
+  REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on, CHEM_ESTATE, "comm_init: already initialised");
   if (nranks == 1 && !uid) return 0;   // single domain, nothing to do
   REQUIRE(node_grid && node_grid[0] == 1 && node_grid[1] == 1 && node_grid[2] == nranks, CHEM_ENOTIMPL,
@@ -2784,6 +2899,7 @@ int chem_comm_init_ipc(chem_ctx* ctx, int nranks, int rank, const char* shm_name
   API_BEGIN
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks && shm_name, CHEM_EINVAL, "comm_init_ipc: rank/nranks/name");
+  REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_ipc must precede the first run");
   HIPCHK(hipSetDevice(c.device));
   c.tr.reset(new IpcTransport(nranks, rank, shm_name));
@@ -2796,6 +2912,7 @@ int chem_comm_init_local(chem_ctx* ctx, int nranks, int rank, int hub_id) {
   API_BEGIN
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init_local: rank/nranks");
+  REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_local must precede the first run");
   c.tr.reset(new LocalTransport(nranks, rank, hub_id));
   c.dd_on = true; c.P = nranks; c.rk = rank; c.geom_dirty = true;

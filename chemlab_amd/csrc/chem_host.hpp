@@ -71,6 +71,29 @@ struct TupleSet {
     while (!empty_key(slot[i])) { if (slot[i] == k) return false; i = (i + 1) & m; }
     slot[i] = k; ++used; return true;
   }
+  bool contains(const TupleKey& k) const {
+    if (slot.empty()) return false;
+    size_t m = slot.size() - 1, i = TupleKeyHash()(k) & m;
+    while (!empty_key(slot[i])) { if (slot[i] == k) return true; i = (i + 1) & m; }
+    return false;
+  }
+  // removal (dissociation reactions): backward-shift deletion, so the probe sequences stay free of tombstones and a
+  // removed key can be inserted again
+  bool erase(const TupleKey& k) {
+    if (slot.empty()) return false;
+    const size_t m = slot.size() - 1;
+    size_t i = TupleKeyHash()(k) & m;
+    while (!empty_key(slot[i]) && !(slot[i] == k)) i = (i + 1) & m;
+    if (empty_key(slot[i])) return false;
+    for (size_t j = (i + 1) & m; !empty_key(slot[j]); j = (j + 1) & m) {
+      const size_t h = TupleKeyHash()(slot[j]) & m;
+      // slot[j] may move into the hole at i unless its home lies cyclically in (i, j]
+      const bool stays = i <= j ? (h > i && h <= j) : (h > i || h <= j);
+      if (!stays) { slot[i] = slot[j]; i = j; }
+    }
+    slot[i] = TupleKey{~0ull, ~0ull}; --used;
+    return true;
+  }
 };
 
 // sorted small set of tags with inline storage for the common case (<= 6 partners): the bond
@@ -93,6 +116,14 @@ struct TagRow {
     if (!big) { big = new std::vector<int32_t>(inl, inl + n); }
     big->insert(big->begin() + (it - b), x); ++n; return true;
   }
+  bool erase(int32_t x) {
+    int32_t* b = big ? big->data() : inl;
+    int32_t* it = std::lower_bound(b, b + n, x);
+    if (it == b + n || *it != x) return false;
+    if (big) big->erase(big->begin() + (it - b)); else std::copy(it + 1, b + n, it);
+    --n; return true;
+  }
+  bool contains(int32_t x) const { return std::binary_search(begin(), end(), x); }
 };
 
 struct HostList {
@@ -247,6 +278,79 @@ struct HostTopology {
         }
         for (int32_t m : graph[b]) if (m != a)
           for (int32_t m2 : graph[m]) if (m2 != b && m2 != a) { int32_t t[4] = {a, b, m, m2}; spawn_tuple(4, t); }
+      }
+    }
+  }
+
+  // ---- bond removal (dissociation reactions, chem_dissociation_add) ---------------------------------------------
+  // One batch = the bonds one reaction step broke.  Every table that knows about a bond gives it up: the pair list
+  // (order of the survivors kept) and its de-duplication set, the bond graph (unless another arity-2 list still holds
+  // the pair), the 1-2 exclusion if `unexclude` (rows, pair count and the append-only log the device table is built
+  // from), and every triple / quadruple that has the pair as consecutive members.  The 1-3 / 1-4 exclusions those
+  // tuples once caused stay.  mol_id of every cluster that lost an edge becomes the lowest tag of what is still
+  // connected (nothing changes where the two ends still reach each other); res_id stays -- a merge cannot be undone.
+  struct BrokenBond { int32_t a, b; int32_t list; int32_t unexclude; };
+  static TupleKey pair_key(int32_t a, int32_t b) { const int32_t t[2] = {a, b}; return tuple_key(t, 2); }
+  void remove_bonds(const std::vector<BrokenBond>& bb, std::vector<int32_t>& touched) {
+    if (bb.empty()) return;
+    // pair lists
+    std::vector<TupleSet> gone(lists.size());
+    for (auto& e : bb) gone[e.list].insert(pair_key(e.a, e.b));
+    for (size_t li = 0; li < lists.size(); ++li) {
+      HostList& l = lists[li];
+      if (l.arity != 2 || !gone[li].used) continue;
+      size_t w = 0;
+      for (size_t e = 0; e + 2 <= l.ent.size(); e += 2) {
+        const TupleKey k = tuple_key(&l.ent[e], 2);
+        if (gone[li].contains(k)) { l.seen.erase(k); continue; }
+        l.ent[w] = l.ent[e]; l.ent[w + 1] = l.ent[e + 1]; w += 2;
+      }
+      l.ent.resize(w);
+    }
+    // bond graph, exclusions
+    TupleSet cut, unex;
+    for (auto& e : bb) {
+      if (e.unexclude && excl[e.a].erase(e.b)) { excl[e.b].erase(e.a); --n_excl_pairs; unex.insert(pair_key(e.a, e.b)); }
+      bool held = false;
+      for (auto& l : lists) held |= l.arity == 2 && l.seen.contains(pair_key(e.a, e.b));
+      if (held) continue;
+      if (graph[e.a].erase(e.b)) { graph[e.b].erase(e.a); cut.insert(pair_key(e.a, e.b)); }
+    }
+    if (unex.used) {
+      size_t w = 0;
+      for (size_t k = 0; k < excl_log.size(); ++k) if (!unex.contains(pair_key(excl_log[k].first, excl_log[k].second))) excl_log[w++] = excl_log[k];
+      excl_log.resize(w);
+    }
+    if (!cut.used) return;
+    // dependent triples and quadruples
+    for (auto& l : lists) {
+      if (l.arity < 3) continue;
+      size_t w = 0;
+      for (size_t e = 0; e + l.arity <= l.ent.size(); e += l.arity) {
+        bool hit = false;
+        for (int k = 0; k + 1 < l.arity; ++k) hit |= cut.contains(pair_key(l.ent[e + k], l.ent[e + k + 1]));
+        if (hit) { l.seen.erase(tuple_key(&l.ent[e], l.arity)); continue; }
+        for (int k = 0; k < l.arity; ++k) l.ent[w + k] = l.ent[e + k];
+        w += l.arity;
+      }
+      l.ent.resize(w);
+    }
+    // fragment labels: every component that lost an edge is flooded once (one epoch for the whole batch)
+    if (visit_stamp.size() != (size_t)n) { visit_stamp.assign((size_t)n, 0); visit_epoch = 0; }
+    if (++visit_epoch == 0) { std::fill(visit_stamp.begin(), visit_stamp.end(), 0); visit_epoch = 1; }
+    std::vector<int32_t> comp;
+    for (auto& e : bb) {
+      if (!cut.contains(pair_key(e.a, e.b))) continue;
+      for (int32_t root : {e.a, e.b}) {
+        if (visit_stamp[root] == visit_epoch) continue;
+        comp.clear(); flood_stack.clear(); flood_stack.push_back(root); visit_stamp[root] = visit_epoch;
+        int32_t lo = root;
+        while (!flood_stack.empty()) {
+          const int32_t p = flood_stack.back(); flood_stack.pop_back();
+          comp.push_back(p); lo = std::min(lo, p);
+          for (int32_t nb : graph[p]) if (visit_stamp[nb] != visit_epoch) { visit_stamp[nb] = visit_epoch; flood_stack.push_back(nb); }
+        }
+        for (int32_t p : comp) if (mol_id[p] != lo) { mol_id[p] = lo; touched.push_back(p); }
       }
     }
   }

@@ -3569,6 +3569,67 @@ __global__ void k_apply_props(int nchg, const PropChangeDev* __restrict__ chg, i
   if (i >= 0) { x4[i].w = (R)c.type; v4[i].w = (R)c.mass; }
 }
 
+// ---- dissociation reactions (chem_dissociation_add; rule set in include/chem_mi355.h) ----------------------------
+// One lane per flat tuple entry (the arrays the bonded CSR is built from).  Entries of a scanned pair list go
+// tags -> rtag -> positions (decoded exactly in the fp32 build), state by tag, type from x4.w; the fp64 distance is the
+// association scan's (minimgD + dist2_unfused).  Broken bonds are compacted with a wave ballot and one atomic per wave;
+// the order the atomics give is arbitrary, the host sorts the records by (list, flat index) = list order.  A record is a
+// Candidate: a / b the role-1 / role-2 tags, r the dissociation's own index, h the flat index, d2 = r^2.  The buffer
+// holds one record per flat entry, so it cannot overflow.
+struct DissDev { int type_1, type_2, min1, max1, min2, max2, list, active, pub, pad; double cut2, prob; };
+struct DissSet { int n, pad; unsigned long long seed, step; DissDev r[CHEM_MAX_REACTIONS]; };
+template <typename R>
+__global__ __launch_bounds__(256) void k_diss_scan(int ne, const int4* __restrict__ fent, const int* __restrict__ flist,
+                                                   const Vec4<R>* __restrict__ x4, const int* __restrict__ rtag, int npart,
+                                                   const int* __restrict__ state, BoxD box, DissSet ds,
+                                                   Candidate* __restrict__ rec, int rec_cap, int* __restrict__ rec_count) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  bool hit = false;
+  Candidate c{0, 0, 0, 0u, 0.0};
+  if (e < ne) {
+    const int li = flist[e];
+    bool scanned = false;
+    for (int q = 0; q < ds.n; ++q) scanned |= ds.r[q].active && ds.r[q].list == li;
+    const int4 tt = fent[e];
+    const int ta = tt.x, tb = tt.y;
+    if (scanned && ta >= 0 && tb >= 0 && ta < npart && tb < npart) {
+      const int ia = rtag[ta], ib = rtag[tb];
+      if (ia >= 0 && ib >= 0) {
+        const Vec4<R> xa = x4[ia], xb = x4[ib];
+        const int tya = (int)xa.w, tyb = (int)xb.w, sa = state[ta], sb = state[tb];
+        const int lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
+        const D3 d = lo == ta ? minimgD(box, posD<R>(xa, box) - posD<R>(xb, box)) : minimgD(box, posD<R>(xb, box) - posD<R>(xa, box));
+        const double d2 = dist2_unfused(d);
+        for (int q = 0; q < ds.n && !hit; ++q) {
+          const DissDev& D = ds.r[q];
+          if (!D.active || D.list != li) continue;
+          const bool fwd = tya == D.type_1 && tyb == D.type_2, rev = tyb == D.type_1 && tya == D.type_2;
+          if (!fwd && !rev) continue;
+          const bool a_first = fwd && rev ? ta < tb : fwd;     // equal types: the lower tag takes role 1
+          const int s1 = a_first ? sa : sb, s2 = a_first ? sb : sa;
+          if (!(s1 >= D.min1 && s1 < D.max1 && s2 >= D.min2 && s2 < D.max2)) continue;
+          bool brk = D.cut2 > 0.0 && d2 >= D.cut2;
+          if (!brk && D.prob > 0.0) {
+            uint32_t rr[4];
+            chem_philox::dissociation_draw(ds.seed, ds.step, (uint32_t)lo, (uint32_t)hi, (uint32_t)D.pub, rr);
+            brk = chem_philox::u01(rr[0]) < D.prob;
+          }
+          if (brk) { hit = true; c = Candidate{a_first ? ta : tb, a_first ? tb : ta, q, (unsigned int)e, d2}; }
+        }
+      }
+    }
+  }
+  const unsigned long long m = __ballot(hit);
+  if (!m) return;
+  const int leader = __ffsll((long long)m) - 1;
+  int base = 0;
+  if (lane_id() == leader) base = atomicAdd(rec_count, __popcll(m));
+  base = __shfl(base, leader);
+  if (!hit) return;
+  const int pos = base + __popcll(m & lanemask_lt());
+  if (pos < rec_cap) rec[pos] = c;
+}
+
 // =======================================================================================
 // Per-tag CSR tables (bonded entries, exclusions) built ON THE DEVICE from flat, append-only arrays.
 // A bond-forming reaction step used to rebuild both tables on the host (a pass over all 10^6 rows, ~14 MB of

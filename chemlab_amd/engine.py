@@ -165,6 +165,17 @@ class Engine:
                                bond_list, new_type_1, new_type_2, new_mass_1, new_mass_2, new_q_1, new_q_2)
         return self._ck(self.api.reaction_add(self.ctx, C.byref(d)))
 
+    def dissociation_add(self, type_1, type_2, delta_1, delta_2, min_state_1, max_state_1, min_state_2, max_state_2,
+                         diss_rate, cutoff, bond_list, unexclude=True, active=True, new_type_1=-1, new_type_2=-1,
+                         new_mass_1=0.0, new_mass_2=0.0, new_q_1=0.0, new_q_2=0.0):
+        """Dissociation reaction on the pair list `bond_list`: a bond breaks when it is longer than `cutoff` (> 0) or with
+        probability diss_rate * dt * interval (rule set: include/chem_mi355.h).  Returns the reaction index, which shares
+        the index space of reaction_add."""
+        d = _capi.DissociationDesc(type_1, type_2, delta_1, delta_2, min_state_1, max_state_1, min_state_2, max_state_2,
+                                   float(diss_rate), float(cutoff), int(bond_list), int(bool(unexclude)), int(bool(active)),
+                                   new_type_1, new_type_2, 0, new_mass_1, new_mass_2, new_q_1, new_q_2)
+        return self._ck(self.api.dissociation_add(self.ctx, C.byref(d)))
+
     def reaction_neighbour_change(self, reaction, invoke_on, old_type, nb_level, new_type, new_mass, new_q=0.0, new_state=None,
                                   incr_state=None, state_window=None):
         """PostProcessChangeNeighboursProperty rule for the events of `reaction` (index from reaction_add):

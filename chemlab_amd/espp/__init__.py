@@ -877,6 +877,29 @@ class _RestrictReaction(_Reaction):
             self._system.engine.reaction_restrict(self._index, [(int(b1), int(b2))])
 
 
+class _DissociationReaction(_Reaction):
+    """integrator.DissociationReaction(type_1, type_2, delta_1, delta_2, min_state_1, max_state_1, min_state_2, max_state_2,
+    rate, fpl, cutoff) + .diss_rate (reaction_setup.py:257-356): breaks bonds of `fpl` that are longer than `cutoff` or,
+    with probability diss_rate * dt * interval, any of them (chem_dissociation_add; rule set in include/chem_mi355.h).
+    `unexclude` (this shim's own attribute, default True): a broken pair interacts through the pair potential again.
+    The delayed type change of BasicDynamicResolution is not modelled: a PostProcessChangeProperty acts at once."""
+
+    def __init__(self, *a, **kw):
+        _Reaction.__init__(self, *a, **kw)
+        object.__setattr__(self, "diss_rate", 0.0)
+        object.__setattr__(self, "unexclude", True)
+
+    def add_postprocess(self, pp, which="type_1"):
+        if not isinstance(pp, _PostProcessChangeProperty):
+            raise NotImplementedError("post-process %s of a DissociationReaction is outside the hot-path scope" % type(pp).__name__)
+        self._pp[which] = pp
+
+    def __setattr__(self, k, v):
+        object.__setattr__(self, k, v)
+        if k == "diss_rate" and getattr(self, "_index", None) is not None:
+            self._system.engine.reaction_set_rate(self._index, v)
+
+
 class _ChemicalReaction(object):
     """integrator.ChemicalReaction(system, vl, storage, topology_manager, interval): nearest_mode,
     max_per_interval, add_reaction, disconnect (reaction_setup.py:416-427,506)."""
@@ -904,11 +927,18 @@ class _ChemicalReaction(object):
             for which, k in (("type_1", 1), ("type_2", 2)):
                 pp = r._pp.get(which)
                 old = getattr(r, which)
-                if pp is not None and old in pp.changes:
+                if pp is not None and old in pp.changes and pp.changes[old].type is not None:
                     ch = pp.changes[old]
                     kw["new_type_%d" % k] = int(ch.type)
                     kw["new_mass_%d" % k] = float(ch.mass)
                     kw["new_q_%d" % k] = float(ch.q or 0.0)
+            if isinstance(r, _DissociationReaction):
+                if r._constraints or r.fpl is None or r.fpl.handle is None:
+                    raise RuntimeError("DissociationReaction: needs a FixedPairList with an interaction attached and takes no constraints")
+                r._index = e.dissociation_add(r.type_1, r.type_2, r.delta_1, r.delta_2, r.min_state_1, r.max_state_1, r.min_state_2,
+                                              r.max_state_2, r.diss_rate, r.cutoff, r.fpl.handle, unexclude=r.unexclude, active=r.active, **kw)
+                r._system = self.system
+                continue
             bond_list = -1
             if not r.is_virtual:
                 if r.fpl.handle is None:
@@ -1052,7 +1082,7 @@ integrator = _ns(
     BerendsenThermostat=_BerendsenThermostat, BerendsenBarostat=_unsupported("integrator.BerendsenBarostat"),
     Isokinetic=_Isokinetic, LangevinBarostat=_unsupported("integrator.LangevinBarostat"),
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
-    DissociationReaction=_unsupported("integrator.DissociationReaction"), ATRPActivator=_ATRPActivator,
+    DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
     ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"), FixDistances=_unsupported("integrator.FixDistances"),
     ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_unsupported("integrator.BasicDynamicResolution"),
     PostProcessChangeNeighboursProperty=_PostProcessChangeNeighboursProperty,

@@ -303,9 +303,62 @@ typedef struct chem_atrp_stats {     /* one row per firing (the reference writes
 int chem_atrp_init(chem_ctx* ctx, const chem_atrp_desc* desc);
 int chem_atrp_add_center(chem_ctx* ctx, int type, int state, int is_activator, int new_type, double new_mass, double new_q, int delta_state);
 int64_t chem_atrp_get_stats(chem_ctx* ctx, chem_atrp_stats* out, int64_t cap);
-/* integrator.addExtension(ar) / ar.disconnect()  start_simulation.py:735-741,776-777 */
+/* One dissociation reaction  T1(min1,max1):T2(min2,max2) -> N1(d1) + N2(d2): breaks bonds of the pair list `bond_list`.
+ * Replaces espressopp.integrator.DissociationReaction(type_1, type_2, delta_1, delta_2, min_state_1, max_state_1,
+ * min_state_2, max_state_2, rate, fpl, cutoff) + .diss_rate + .active and the PostProcessChangeProperty type change
+ * (reaction_setup.py:257-356; examples/atrp_activator/atrp.cfg:77-84 `I(0,5):I(0,5) -> I(1) + I(1)`).  The arithmetic
+ * lives in the external ESPResSo++ fork; this rule set is this build's restatement of the call site's contract
+ * ([EXT-RECALL]).
+ *
+ * Runs every `interval` steps (chem_reaction_init) at the reaction step, BEFORE the association scan of that step.
+ *   candidates  every entry (a, b) of `bond_list`, in list order.  a takes role 1 if type[a] == type_1 and
+ *               type[b] == type_2, otherwise the swap is tried; if both fit (equal types) the particle with the lower
+ *               id takes role 1.  Current types; both chemical states must lie in their half-open windows, read
+ *               before any of this step's dissociation events.
+ *   distance    exact fp64 minimum-image r^2 of the decoded positions, no FMA contraction (as the association scan).
+ *   decision    the bond breaks if  cutoff > 0 && r^2 >= cutoff^2,  or if  u01(out[0]) < p  with
+ *               p = diss_rate * dt * interval  (fp64, in that order) and
+ *               out = dissociation_draw(seed, step, tag_lo, tag_hi, r)  (include/chem_philox.h; seed of
+ *               chem_reaction_init, step as the event reports it, r the index this call returned).  Several
+ *               dissociation reactions on one list are tried in index order, the first that breaks the bond wins.
+ *   independence every qualifying bond breaks on its own: no one-event-per-particle resolve, no max_per_interval; a
+ *               particle that loses k bonds in one step receives k * delta.
+ *   apply       state += delta_{1,2}; where new_type_{1,2} >= 0 type, mass and q change AT ONCE (the delayed change of
+ *               the reference's BasicDynamicResolution(alpha) is not modelled; where one particle gets several new
+ *               types in one step the last event in list order wins).  The entry leaves `bond_list` (order of the
+ *               survivors kept) and the pair leaves the bond graph (unless another pair list still holds it).  mol_id of
+ *               the two fragments becomes the lowest particle of each bonded cluster (nothing changes if a still
+ *               reaches b); res_id stays: a merge cannot be undone.  unexclude != 0 lifts the 1-2 exclusion (a, b).
+ *               Every triple / quadruple that holds a, b as consecutive members is removed.  Known limit: the 1-3 / 1-4
+ *               exclusions those tuples once caused stay.
+ *   afterwards  the association scan of the same step sees the new states, types, labels and exclusions (a pair that
+ *               just broke may bond again at once if it qualifies); forces change with the next evaluation, in front
+ *               of which the lists are rebuilt.
+ *   event log   one chem_event per broken bond: `reaction` = the returned index (one index space with
+ *               chem_reaction_add), id_a / id_b the role-1 / role-2 particle, r2 as above, pad = 0.  The events of a
+ *               step form a block of their own in front of that step's association events; chem_get_events sorts
+ *               inside each block as described at chem_event.
+ * Not on the decomposed path: chem_comm_init* after this call, or this call after chem_comm_init*, is CHEM_ENOTIMPL. */
+typedef struct chem_dissociation_desc {
+  int32_t type_1, type_2;
+  int32_t delta_1, delta_2;
+  int32_t min_state_1, max_state_1;   /* half-open [min,max) */
+  int32_t min_state_2, max_state_2;
+  double  diss_rate;
+  double  cutoff;                     /* <= 0: no distance rule */
+  int32_t bond_list;                  /* handle of the arity-2 list that is scanned */
+  int32_t unexclude;                  /* 1: a broken pair interacts through the pair potential again */
+  int32_t active;
+  int32_t new_type_1, new_type_2;     /* -1: unchanged */
+  int32_t pad;
+  double  new_mass_1, new_mass_2;     /* used when the type changes */
+  double  new_q_1, new_q_2;
+} chem_dissociation_desc;
+/* ar.add_reaction(DissociationReaction(...))  reaction_setup.py:330-356; returns the reaction index */
+int chem_dissociation_add(chem_ctx* ctx, const chem_dissociation_desc* d);
+/* integrator.addExtension(ar) / ar.disconnect()  start_simulation.py:735-741,776-777: both kinds of reaction */
 int chem_reactions_enable(chem_ctx* ctx, int on);
-/* per-reaction rate update (Arrhenius hook, start_simulation.py:785-796) */
+/* per-reaction rate update (Arrhenius hook, start_simulation.py:785-796); on an index of chem_dissociation_add: diss_rate */
 int chem_reaction_set_rate(chem_ctx* ctx, int reaction, double rate);
 
 /* ---- the hot call -------------------------------------------------------------------- */

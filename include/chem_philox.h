@@ -63,6 +63,15 @@ CHEM_HD void reaction_draw(uint64_t seed, uint64_t step, uint32_t tag_lo, uint32
   philox4x32_10(ctr, key, out);
 }
 
+/* Dissociation draw for the bond between the particles (tag_lo < tag_hi), dissociation reaction r (the index
+ * chem_dissociation_add returned), at integrator step `step`: counter layout of reaction_draw, a key of its own.
+ * out[0]: the uniform compared with diss_rate * dt * interval. */
+CHEM_HD void dissociation_draw(uint64_t seed, uint64_t step, uint32_t tag_lo, uint32_t tag_hi, uint32_t r, uint32_t out[4]) {
+  uint32_t ctr[4] = {tag_lo, tag_hi, (uint32_t)step, (r << 24) ^ (uint32_t)(step >> 32)};
+  uint32_t key[2] = {(uint32_t)seed ^ 0x44495353u, (uint32_t)(seed >> 32)};
+  philox4x32_10(ctr, key, out);
+}
+
 /* ATRPActivator (chem_atrp_init): selection key out[0] and acceptance uniform out[1] of particle `tag` at step `step`. */
 CHEM_HD void atrp_draw(uint64_t seed, uint64_t step, uint32_t tag, uint32_t out[4]) {
   uint32_t ctr[4] = {tag, (uint32_t)step, (uint32_t)(step >> 32), 0x41545250u};
