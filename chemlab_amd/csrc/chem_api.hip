@@ -19,6 +19,7 @@
 
 #include "chem_comm.hpp"
 #include "chem_host.hpp"
+#include "chem_react_host.hpp"
 #include "md_kernels.hpp"
 
 namespace chem {
@@ -102,10 +103,8 @@ struct Ctx {
   std::vector<chem_nb_change> nb_rules;   // PostProcessChangeNeighboursProperty (chem_reaction_neighbour_change)
   // RestrictReaction.define_connection (chem_reaction_restrict): (tag lo, tag hi) -> reaction bits; CSR rebuilt when it changed
   std::map<std::pair<int32_t, int32_t>, uint32_t> restrict_map; uint32_t restricted_mask = 0; bool restrict_dirty = false;
-  struct NbCons { int role = 0, nb_type = 0, min_state = 0, max_state = 0; };   // ReactionConstraintNeighbourState (chem_reaction_constraint)
-  std::vector<NbCons> constraints;
+  std::vector<NbCons> constraints;   // ReactionConstraintNeighbourState (chem_reaction_constraint)
   // integrator.ATRPActivator (chem_atrp_init; reaction_post_process.py:380-426)
-  struct AtrpCenter { int type, state, is_activator, new_type, delta_state; double new_mass, new_q; };
   bool atrp_on = false; chem_atrp_desc atrp{}; std::vector<AtrpCenter> atrp_centers; std::vector<chem_atrp_stats> atrp_stats;
   std::vector<chem_event> events;   // expanded, canonical order (filled lazily from the arena by chem_get_events)
   // event arena: SoA copy of the device records of every reaction step, appended in device order (amortised growth:
@@ -678,8 +677,14 @@ template <typename R> struct CtxT : Ctx {
     return m;
   }
 
+  // top.state lags the device after reaction steps: bring it up to date where the host is about to read it
+  void refresh_state_mirror(bool force = false) {
+    if (!force && !state_mirror_stale) return;
+    std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false;
+  }
+
   void upload_labels() {
-    if (state_mirror_stale) { std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false; }
+    refresh_state_mirror();
     state.upload(top.state, stream); res_id.upload(top.res_id, stream); mol_id.upload(top.mol_id, stream);
     HIPCHK(hipStreamSynchronize(stream));
     labels_dirty = false;
@@ -1568,6 +1573,33 @@ template <typename R> struct CtxT : Ctx {
     asA.alloc(nglob); asB.alloc(nglob); best1.alloc(nglob); best2.alloc(nglob); evcount.alloc(1); rs_dev.alloc(1);
     if (dd_on) { cand_loc.alloc((size_t)cand_cap); cnt_all.alloc(64); }
   }
+  // ---- idioms shared by the routines of the reaction cadence (react_step, diss_step, atrp_step) ----
+  bool any_typed_list() const { for (auto& l : top.lists) if (l.by_types) return true; return false; }
+  void request_rebuild() { resort = true; set_ctl_field(&DevCtl::force_rebuild, 1); }
+  // property changes decided on the host (the mirrors already hold them) -> device arrays.  wait = false: the caller
+  // keeps `chg` alive and synchronises the stream itself
+  DBuf<PropChangeDev> prop_dev;
+  void apply_prop_changes(const std::vector<HostTopology::PropChange>& chg, bool wait = true) {
+    static_assert(sizeof(HostTopology::PropChange) == sizeof(PropChangeDev), "layout");
+    if (chg.empty()) return;
+    prop_dev.alloc(chg.size());
+    HIPCHK(hipMemcpyAsync(prop_dev.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), prop_dev.p, state.p, rtag.p, x4.p, v4.p);
+    if (wait) HIPCHK(hipStreamSynchronize(stream));
+  }
+  // the record count of every rank, in rank order (decomposed path)
+  std::vector<int> allgather_counts(int nloc) {
+    if (!cnt_all.p) cnt_all.alloc(64);
+    std::vector<int> cnts(P, 0);
+    HIPCHK(hipMemcpyAsync(cnt_all.p + rk, &nloc, sizeof(int), hipMemcpyHostToDevice, stream));
+    tr->allgather(cnt_all.p + rk, cnt_all.p, sizeof(int), stream);
+    HIPCHK(hipMemcpyAsync(cnts.data(), cnt_all.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return cnts;
+  }
+
+  // ---- the association step: every `interval` steps.  The phases below run in this order; the pure host algorithms
+  // they call (tables, event order, trim) are in chem_react_host.hpp ----
   void react_step() {
     tm.reaction_steps++;
     if (reactions.empty()) return;
@@ -1577,6 +1609,26 @@ template <typename R> struct CtxT : Ctx {
     const double t0 = now_s();
     join_thread();   // labels of the previous reaction step must be on the device before the scan
     alloc_reaction_buffers();
+    const ReactApplySet ras = upload_reaction_set();
+    Trace trc("react");
+    upload_restrictions();
+    const bool any_cons = upload_constraint_bits();
+    launch_reaction_scan(ConnTable{restricted_mask ? conn_start.p : nullptr, conn_partner.p, conn_mask.p, any_cons ? cons_ok.p : nullptr});
+    const DevCtl h = read_ctl();
+    trc.lap("scan");
+    if (h.cand_overflow) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow");
+    const int nc = dd_on ? gather_candidates(h.cand_count) : h.cand_count;
+    if (nc == 0) { tm.reaction_wall_s += now_s() - t0; return; }
+    int* status = resolve_candidates(nc, trc);
+    trim_to_max_per_interval(nc, status);
+    const EventSpan hev = apply_and_download_events(nc, status, ras, trc);
+    commit_events(hev, trc);
+    trc.lap("end");
+    tm.reaction_wall_s += now_s() - t0;
+  }
+
+  // device descriptors of the reaction table; returns the half the apply kernel takes by value
+  ReactApplySet upload_reaction_set() {
     ReactSet rs{};
     rs.n = (int)reactions.size(); rs.seed = react_seed; rs.step = (uint64_t)step; rs.nearest = nearest;
     ReactApplySet ras{};
@@ -1593,45 +1645,35 @@ template <typename R> struct CtxT : Ctx {
     }
     HIPCHK(hipMemcpyAsync(rs_dev.p, &rs, sizeof(ReactSet), hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    Trace trc("react");
-    // No rebuild here: the particle order must not change between the force evaluation of this step and
-    // the first kick of the next one (forces are not re-sorted), and on the decomposed path a rebuild
-    // would migrate particles away from their forces.  Tiles: scan the staged stencils of the last
-    // rebuild (see k_react_scan_tiles).  Per-cell / brute-force lists: the int32 list is always current.
-    Candidate* cdst = dd_on ? cand_loc.p : cand.p;
-    if (restrict_dirty) {      // per-tag CSR of the allowed partners (both directions), built on the host: the map is set-up data
-      std::vector<int> hs((size_t)nglob + 1, 0), hp; std::vector<unsigned int> hm;
-      for (auto& kv : restrict_map) { hs[kv.first.first + 1]++; hs[kv.first.second + 1]++; }
-      for (int t = 0; t < nglob; ++t) hs[t + 1] += hs[t];
-      hp.resize(hs[nglob] ? hs[nglob] : 1); hm.resize(hp.size());
-      std::vector<int> cur(hs.begin(), hs.end() - 1);
-      for (auto& kv : restrict_map) {
-        hp[cur[kv.first.first]] = kv.first.second; hm[cur[kv.first.first]++] = kv.second;
-        hp[cur[kv.first.second]] = kv.first.first; hm[cur[kv.first.second]++] = kv.second;
-      }
-      conn_start.upload(hs, stream); conn_partner.upload(hp, stream); conn_mask.upload(hm, stream);
-      restrict_dirty = false;
-    }
+    return ras;
+  }
+
+  // per-tag CSR of the allowed partners (both directions), built on the host: the map is set-up data
+  void upload_restrictions() {
+    if (!restrict_dirty) return;
+    const RestrictCsr c = build_restrict_csr(restrict_map, nglob);
+    conn_start.upload(c.start, stream); conn_partner.upload(c.partner, stream); conn_mask.upload(c.mask, stream);
+    restrict_dirty = false;
+  }
+
+  // neighbour-state constraints, one bit per reaction and particle; returns whether any reaction carries one
+  bool upload_constraint_bits() {
     bool any_cons = false;
     for (auto& cs : constraints) any_cons |= cs.role != 0;
-    if (any_cons) {
-      // neighbour-state constraints: evaluated on the host per particle from the bond graph and the current states and
-      // types (the graph lives here; candidates carrying a constraint are rare), one bit per reaction
-      if (state_mirror_stale) { std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false; }
-      sync_type_mirrors();
-      std::vector<unsigned int> ok((size_t)nglob, 0u);
-      for (size_t q = 0; q < constraints.size(); ++q) {
-        const NbCons& cs = constraints[q];
-        if (!cs.role) continue;
-        const int own_type = cs.role == 1 ? reactions[q].type_1 : reactions[q].type_2;
-        for (int32_t t = 0; t < (int32_t)nglob; ++t) {
-          if (top.type[t] != own_type) continue;
-          for (int32_t nb : top.graph[t]) if (top.type[nb] == cs.nb_type && top.state[nb] >= cs.min_state && top.state[nb] < cs.max_state) { ok[t] |= 1u << q; break; }
-        }
-      }
-      cons_ok.upload(ok, stream);
-    }
-    const ConnTable conn{restricted_mask ? conn_start.p : nullptr, conn_partner.p, conn_mask.p, any_cons ? cons_ok.p : nullptr};
+    if (!any_cons) return false;
+    refresh_state_mirror();
+    sync_type_mirrors();
+    const std::vector<unsigned int> ok = constraint_bits(top, reactions, constraints);
+    cons_ok.upload(ok, stream);
+    return true;
+  }
+
+  // No rebuild here: the particle order must not change between the force evaluation of this step and
+  // the first kick of the next one (forces are not re-sorted), and on the decomposed path a rebuild
+  // would migrate particles away from their forces.  Tiles: scan the staged stencils of the last
+  // rebuild (see k_react_scan_tiles).  Per-cell / brute-force lists: the int32 list is always current.
+  void launch_reaction_scan(const ConnTable conn) {
+    Candidate* cdst = dd_on ? cand_loc.p : cand.p;
     if (use_tiles) {
       const int region_cap = std::max(1, cand_cap / std::max(ntiles, 1));
       tile_cnt.alloc(ntiles + 1); tile_off.alloc(ntiles + 1);
@@ -1647,35 +1689,33 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL(k_react_scan<R>, dim3(cdiv((long long)n * 8, 256)), dim3(256), 0, stream, G, n, x4.p, tag.p, nlist.p, nn.p, S, state.p,
                          res_id.p, mol_id.p, boxd, rs_dev.p, cdst, cand_cap, ctl.p, conn);
     }
-    DevCtl h = read_ctl();
-    trc.lap("scan");
-    if (h.cand_overflow) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow");
-    int nc = h.cand_count;
-    if (dd_on) {
-      // A boundary pair is seen by two ranks (real-ghost on each); the scan emits it only where the
-      // particle with the lower tag is owned, so the union over ranks holds every candidate once.
-      // All ranks then run the same deterministic resolve on the gathered set (one exchange).
-      std::vector<int> cnts(P, 0);
-      HIPCHK(hipMemcpyAsync(cnt_all.p + rk, &nc, sizeof(int), hipMemcpyHostToDevice, stream));
-      tr->allgather(cnt_all.p + rk, cnt_all.p, sizeof(int), stream);
-      HIPCHK(hipMemcpyAsync(cnts.data(), cnt_all.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      int mx = 0, tot = 0;
-      for (int v : cnts) { mx = std::max(mx, v); tot += v; }
-      if ((long long)mx * P > cand_cap || tot > cand_cap) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow (gathered)");
-      if (mx > 0) {
-        // padded all-gather into evout (scratch here), then compaction into cand in rank order
-        HIPCHK(hipMemcpyAsync(evout.p + (size_t)rk * mx, cand_loc.p, sizeof(Candidate) * nc, hipMemcpyDeviceToDevice, stream));
-        tr->allgather(evout.p + (size_t)rk * mx, evout.p, sizeof(Candidate) * mx, stream);
-        int off = 0;
-        for (int r = 0; r < P; ++r) {
-          if (cnts[r]) HIPCHK(hipMemcpyAsync(cand.p + off, evout.p + (size_t)r * mx, sizeof(Candidate) * cnts[r], hipMemcpyDeviceToDevice, stream));
-          off += cnts[r];
-        }
+  }
+
+  // A boundary pair is seen by two ranks (real-ghost on each); the scan emits it only where the
+  // particle with the lower tag is owned, so the union over ranks holds every candidate once.
+  // All ranks then run the same deterministic resolve on the gathered set (one exchange).
+  // nc local candidates in cand_loc -> all of them in cand, rank order; returns the global count.
+  int gather_candidates(int nc) {
+    const std::vector<int> cnts = allgather_counts(nc);
+    int mx = 0, tot = 0;
+    for (int v : cnts) { mx = std::max(mx, v); tot += v; }
+    if ((long long)mx * P > cand_cap || tot > cand_cap) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow (gathered)");
+    if (mx > 0) {
+      // padded all-gather into evout (scratch here), then compaction into cand in rank order
+      HIPCHK(hipMemcpyAsync(evout.p + (size_t)rk * mx, cand_loc.p, sizeof(Candidate) * nc, hipMemcpyDeviceToDevice, stream));
+      tr->allgather(evout.p + (size_t)rk * mx, evout.p, sizeof(Candidate) * mx, stream);
+      int off = 0;
+      for (int r = 0; r < P; ++r) {
+        if (cnts[r]) HIPCHK(hipMemcpyAsync(cand.p + off, evout.p + (size_t)r * mx, sizeof(Candidate) * cnts[r], hipMemcpyDeviceToDevice, stream));
+        off += cnts[r];
       }
-      nc = tot;
     }
-    if (nc == 0) { tm.reaction_wall_s += now_s() - t0; return; }
+    return tot;
+  }
+
+  // one partner per particle and side (two-sided min / keep), then the matching rounds; returns the status array
+  // that holds the outcome (2 = accepted)
+  int* resolve_candidates(int nc, Trace& trc) {
     const int ncb = cdiv(nc, 256), npb = cdiv(nglob, 256);
     hipLaunchKernelGGL(k_fill<int>, dim3(ncb), dim3(256), 0, stream, st0.p, 1, (size_t)nc);
     for (int side = 0; side < 2; ++side) {
@@ -1701,25 +1741,27 @@ template <typename R> struct CtxT : Ctx {
       if (read_ctl().alive == 0) break;
     }
     if (g_trace) { fprintf(stderr, "[chem trace] candidates %d\n", nc); trc.lap("rounds"); }
-    if (max_per_interval > 0) {
-      // ChemicalReaction.max_per_interval (reaction_setup.py:426-427): keep the max_per_interval accepted events of
-      // highest priority (nearest: r^2 then A's tag; random: pair hash then A's tag), as the oracle does.  Rare
-      // option: selection on the host from the downloaded candidate records.
-      std::vector<Candidate> hc; std::vector<int> hs;
-      cand.download(hc, nc, stream);
-      { hs.resize(nc); HIPCHK(hipMemcpyAsync(hs.data(), sin, sizeof(int) * nc, hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream)); }
-      std::vector<int> accd;
-      for (int k = 0; k < nc; ++k) if (hs[k] == 2) accd.push_back(k);
-      if ((int64_t)accd.size() > max_per_interval) {
-        auto key = [&](int k) { return std::make_pair(nearest ? (unsigned long long)reinterpret_cast<const long long&>(hc[k].d2) : (unsigned long long)hc[k].h, hc[k].a); };
-        std::sort(accd.begin(), accd.end(), [&](int p, int q) { return key(p) < key(q); });
-        for (size_t k = (size_t)max_per_interval; k < accd.size(); ++k) hs[accd[k]] = 0;
-        HIPCHK(hipMemcpyAsync(sin, hs.data(), sizeof(int) * nc, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-      }
-    }
+    return sin;
+  }
+
+  // ChemicalReaction.max_per_interval: rare option, selection on the host from the downloaded candidate records (trim_accepted)
+  void trim_to_max_per_interval(int nc, int* status) {
+    if (max_per_interval <= 0) return;
+    std::vector<Candidate> hc; std::vector<int> hs;
+    cand.download(hc, nc, stream);
+    { hs.resize(nc); HIPCHK(hipMemcpyAsync(hs.data(), status, sizeof(int) * nc, hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream)); }
+    if (!trim_accepted(hc, hs, max_per_interval, nearest != 0)) return;
+    HIPCHK(hipMemcpyAsync(status, hs.data(), sizeof(int) * nc, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+
+  // the event records are processed where the copy kernel put them (pinned, host-cached memory): no second copy
+  struct EventSpan { Candidate* p; size_t n; Candidate* begin() const { return p; } Candidate* end() const { return p + n; }
+                     Candidate* data() const { return p; } size_t size() const { return n; } Candidate& operator[](size_t k) const { return p[k]; } };
+  // accepted candidates -> states, types and masses on the device + the event records, in device order, in pin_ev
+  EventSpan apply_and_download_events(int nc, const int* status, const ReactApplySet& ras, Trace& trc) {
     HIPCHK(hipMemsetAsync(evcount.p, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_react_apply<R>, dim3(ncb), dim3(256), 0, stream, nc, cand.p, sin, ras, state.p, rtag.p, x4.p, v4.p, evout.p, evcount.p);
+    hipLaunchKernelGGL(k_react_apply<R>, dim3(cdiv(nc, 256)), dim3(256), 0, stream, nc, cand.p, status, ras, state.p, rtag.p, x4.p, v4.p, evout.p, evcount.p);
     int nev = 0;
     HIPCHK(hipMemcpyAsync(&nev, evcount.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -1735,72 +1777,26 @@ template <typename R> struct CtxT : Ctx {
     }
     HIPCHK(hipStreamSynchronize(stream));
     trc.lap("download");
-    // the event records are processed where the copy kernel put them (pinned, host-cached memory): no second copy
-    struct Span { Candidate* p; size_t n; Candidate* begin() const { return p; } Candidate* end() const { return p + n; }
-                  Candidate* data() const { return p; } size_t size() const { return n; } Candidate& operator[](size_t k) const { return p[k]; } };
-    const Span hev{pin_ev, (size_t)nev};
-    // Host mirrors + topology.  Only bond-forming events need the canonical order now (it fixes
-    // the order of the bond lists); the event log itself is put in canonical order lazily
-    // by chem_get_events.
-    auto ekey = [](const Candidate& p) { return ((uint64_t)(uint32_t)std::min(p.a, p.b) << 32) | (uint32_t)std::max(p.a, p.b); };
-    // bond-forming events in canonical order, extracted into a heap buffer; the pinned event array stays as the device wrote it.
-    // (0.6-0.8 ms at 2.5e5 events, as partitioning and sorting in place was: ONE pass over 6 MB the GPU has just written
-    //  through PCIe is most of it -- a device-side compaction of the bond-forming events would be the next step)
-    std::vector<Candidate>& bev = bond_ev;
-    bev.clear();
-    for (const Candidate& e : hev) if (!reactions[e.r].is_virtual) bev.push_back(e);
-    {
-      // A particle takes part in at most one event per reaction step, so min(a,b) alone is a unique
-      // key: LSD radix sort (3 x 11 bits) instead of a comparison sort of 10^5 events.
-      const size_t m = bev.size();
-      if (radix_tmp.size() < m) radix_tmp.resize(m);
-      Candidate* src = bev.data(); Candidate* dst = radix_tmp.data();
-      for (int pass = 0; pass < 3; ++pass) {
-        size_t cnt[2049] = {0};
-        const int sh = 11 * pass;
-        for (size_t k = 0; k < m; ++k) ++cnt[(((uint32_t)std::min(src[k].a, src[k].b) >> sh) & 2047u) + 1];
-        for (int d = 0; d < 2048; ++d) cnt[d + 1] += cnt[d];
-        for (size_t k = 0; k < m; ++k) dst[cnt[((uint32_t)std::min(src[k].a, src[k].b) >> sh) & 2047u]++] = src[k];
-        std::swap(src, dst);
-      }
-      if (src != bev.data()) std::copy(src, src + m, bev.data());
-      bool unique = true;
-      for (size_t k = 1; k < m && unique; ++k) unique = std::min(bev[k - 1].a, bev[k - 1].b) != std::min(bev[k].a, bev[k].b);
-      if (!unique) std::sort(bev.begin(), bev.end(), [&](const Candidate& p, const Candidate& q) { return ekey(p) < ekey(q); });
-    }
-    trc.lap("bond events");
-    std::vector<std::pair<int32_t, int32_t>> newbonds;
-    newbonds.reserve(hev.size());
-    bool types_changed = false;
-    // event log + host mirrors of the new types (only what the host itself needs later: types for
-    // bonded-slot resolution and the topology manager; chemical states live on the device).  Events
-    // touch disjoint particles, nothing below reads the mirrors unless a list is typed or tuples are
-    // spawned, so this runs beside the table builds and is joined at the end of the step.
-    // intra-/inter-cluster flag of every event from the cluster labels as they were BEFORE this step's bonds
-    // (the label thread of the previous reaction step was joined above, this step's has not started yet)
-    std::vector<int8_t> intra_flags;
-    if (opt_intra_inter) {
-      intra_flags.resize(hev.size());
-      for (size_t k = 0; k < hev.size(); ++k) intra_flags[k] = top.mol_id[hev[k].a] == top.mol_id[hev[k].b] ? 1 : 0;
-    }
-    // event log: appended to the arena in device order (canonical order is established lazily by chem_get_events)
-    for (size_t k = 0; k < hev.size() && !types_changed; ++k) { const chem_reaction_desc& d = reactions[hev[k].r]; types_changed = d.new_type_1 >= 0 || d.new_type_2 >= 0; }   // (conservative: the force list depends on the types)
-    // the host's type mirrors are needed right now only where the host itself resolves something by type
-    bool mirrors_first = top.spawns_tuples() || !nb_rules.empty();
-    for (auto& l : top.lists) mirrors_first |= l.by_types != 0;
-    // (otherwise the log is appended further down, while the device rebuilds its tables)
-    if (mirrors_first) { append_events(hev.data(), hev.size(), step, intra_flags); sync_type_mirrors(); }
-    const Candidate* log_ev = hev.data(); const size_t log_n = mirrors_first ? 0 : hev.size(); const int64_t log_step = step;   // what the thread still has to log
-    // (pin_ev is not touched again before the next reaction step, which joins the thread first)
-    std::thread mirror_thr;
-    std::exception_ptr mirror_err;
-    // (measured, round 3: inserting by hash shards on helper threads -- a persistent pool of 1..3 -- made this loop SLOWER,
-    //  1.0-1.7 ms -> 2.0-3.9 ms for 2.4-4.3e4 new bonds on the 2-socket host: the table lives on the caller's NUMA node)
-    // Where every bond is an excluded pair (bonds_excluded: checked at the last full upload, kept by construction since) and the
-    // scan honours the exclusions, a candidate pair cannot be bonded already, and a particle takes part in one event per step:
-    // every bond-forming event is a new bond.  The insertion into the list's de-duplication set -- one cache miss per bond in a
-    // table of 10^6, 0.2 -> 1.7 ms of this step as the conversion grows -- then moves to the bookkeeping thread.
-    const bool defer_seen = bonds_excluded && has_excl && !top.spawns_tuples() && nb_rules.empty();
+    return EventSpan{pin_ev, (size_t)nev};
+  }
+
+  // bond-forming events in canonical order, extracted into a heap buffer (bond_ev); the pinned event array stays as the device wrote it.
+  // (0.6-0.8 ms at 2.5e5 events, as partitioning and sorting in place was: ONE pass over 6 MB the GPU has just written
+  //  through PCIe is most of it -- a device-side compaction of the bond-forming events would be the next step)
+  void collect_bond_events(const EventSpan hev) {
+    bond_ev.clear();
+    for (const Candidate& e : hev) if (!reactions[e.r].is_virtual) bond_ev.push_back(e);
+    sort_bond_events(bond_ev, radix_tmp);
+  }
+
+  // bond_ev -> the bonded lists; appends the bonds that are new to `newbonds`, in canonical order
+  // (measured, round 3: inserting by hash shards on helper threads -- a persistent pool of 1..3 -- made this loop SLOWER,
+  //  1.0-1.7 ms -> 2.0-3.9 ms for 2.4-4.3e4 new bonds on the 2-socket host: the table lives on the caller's NUMA node)
+  // defer_seen: every bond-forming event is known to be a new bond (see commit_events); the insertion into the list's
+  // de-duplication set -- one cache miss per bond in a table of 10^6, 0.2 -> 1.7 ms of this step as the conversion
+  // grows -- is left to the bookkeeping thread (label_seen_lists).
+  void insert_new_bonds(bool defer_seen, std::vector<std::pair<int32_t, int32_t>>& newbonds) {
+    const std::vector<Candidate>& bev = bond_ev;
     label_seen_lists.clear();
     for (size_t k = 0; defer_seen && k < bev.size(); ++k) {
       const Candidate& e = bev[k];
@@ -1821,63 +1817,97 @@ template <typename R> struct CtxT : Ctx {
       int32_t t[2] = {e.a, e.b};
       if (top.list_insert(top.lists[d.bond_list], t)) newbonds.emplace_back(e.a, e.b);
     }
+  }
+
+  // PostProcessChangeNeighboursProperty: needs the bond graph with this step's bonds and the mirrors of the new
+  // types; events in canonical order, role 1 before role 2, rules in insertion order (as the oracle).  Returns whether
+  // any particle changed.
+  bool neighbour_changes(const EventSpan hev) {
+    if (nb_rules.empty()) return false;
+    std::vector<Candidate> ord;
+    for (auto& e : hev) for (auto& rl : nb_rules) if (rl.reaction == e.r) { ord.push_back(e); break; }
+    std::sort(ord.begin(), ord.end(), [](const Candidate& p, const Candidate& q) { return event_key(p) < event_key(q); });
+    bool reads_state = false;
+    for (auto& rl : nb_rules) reads_state |= rl.set_state == 2 || rl.min_state < rl.max_state;
+    if (reads_state) refresh_state_mirror(true);      // states as the events of this step left them (k_react_apply ran on the device)
+    std::vector<HostTopology::PropChange> chg;
+    for (auto& e : ord)
+      for (int role = 1; role <= 2; ++role)
+        for (auto& rl : nb_rules) if (rl.reaction == e.r && (rl.invoke_on & role)) top.neighbour_change(role == 1 ? e.a : e.b, rl, chg);
+    if (chg.empty()) return false;
+    apply_prop_changes(chg);
+    if (!reads_state) state_mirror_stale = true;      // (rules that set a state moved the device copy, not a refreshed mirror)
+    return true;
+  }
+
+  // the bookkeeping thread of this reaction step (joined by join_thread, which rethrows what it caught)
+  template <class F> void start_label_thread(F body) {
+    label_thr = std::thread([this, body = std::move(body)] { try { body(); } catch (...) { label_err = std::current_exception(); } });
+  }
+
+  // Host mirrors + topology.  Only bond-forming events need the canonical order now (it fixes
+  // the order of the bond lists); the event log itself is put in canonical order lazily
+  // by chem_get_events.
+  void commit_events(const EventSpan hev, Trace& trc) {
+    collect_bond_events(hev);
+    trc.lap("bond events");
+    // event log + host mirrors of the new types (only what the host itself needs later: types for
+    // bonded-slot resolution and the topology manager; chemical states live on the device).  Events
+    // touch disjoint particles, nothing below reads the mirrors unless a list is typed or tuples are
+    // spawned, so this runs beside the table builds and is joined at the end of the step.
+    // intra-/inter-cluster flag of every event from the cluster labels as they were BEFORE this step's bonds
+    // (the label thread of the previous reaction step was joined above, this step's has not started yet)
+    std::vector<int8_t> intra_flags;
+    if (opt_intra_inter) {
+      intra_flags.resize(hev.size());
+      for (size_t k = 0; k < hev.size(); ++k) intra_flags[k] = top.mol_id[hev[k].a] == top.mol_id[hev[k].b] ? 1 : 0;
+    }
+    bool types_changed = false;
+    for (size_t k = 0; k < hev.size() && !types_changed; ++k) { const chem_reaction_desc& d = reactions[hev[k].r]; types_changed = d.new_type_1 >= 0 || d.new_type_2 >= 0; }   // (conservative: the force list depends on the types)
+    // event log: appended to the arena in device order (canonical order is established lazily by chem_get_events).
+    // The host's type mirrors are needed right now only where the host itself resolves something by type;
+    // otherwise the log is appended on the thread, while the device rebuilds its tables.
+    const bool mirrors_first = top.spawns_tuples() || !nb_rules.empty() || any_typed_list();
+    if (mirrors_first) { append_events(hev.data(), hev.size(), step, intra_flags); sync_type_mirrors(); }
+    // what the thread still has to log (pin_ev is not touched again before the next reaction step, which joins the thread first)
+    const size_t log_n = mirrors_first ? 0 : hev.size();
+    auto log_events = [this, log_ev = hev.data(), log_n, log_step = step, intra_flags] { if (log_n) append_events(log_ev, log_n, log_step, intra_flags); };
+    // Where every bond is an excluded pair (bonds_excluded: checked at the last full upload, kept by construction since) and the
+    // scan honours the exclusions, a candidate pair cannot be bonded already, and a particle takes part in one event per step:
+    // every bond-forming event is a new bond.
+    const bool defer_seen = bonds_excluded && has_excl && !top.spawns_tuples() && nb_rules.empty();
+    std::vector<std::pair<int32_t, int32_t>> newbonds;
+    newbonds.reserve(hev.size());
+    insert_new_bonds(defer_seen, newbonds);
     state_mirror_stale = true;
     if (g_trace) fprintf(stderr, "[chem trace] events %zu new bonds %zu\n", hev.size(), newbonds.size());
     trc.lap("host events");
-    // PostProcessChangeNeighboursProperty: needs the bond graph with this step's bonds and the mirrors of the new
-    // types; events in canonical order, role 1 before role 2, rules in insertion order (as the oracle)
-    auto neighbour_changes = [&] {
-      if (nb_rules.empty()) return;
-      std::vector<Candidate> ord;
-      for (auto& e : hev) for (auto& rl : nb_rules) if (rl.reaction == e.r) { ord.push_back(e); break; }
-      std::sort(ord.begin(), ord.end(), [&](const Candidate& p, const Candidate& q) { return ekey(p) < ekey(q); });
-      bool reads_state = false;
-      for (auto& rl : nb_rules) reads_state |= rl.set_state == 2 || rl.min_state < rl.max_state;
-      if (reads_state) {      // states as the events of this step left them (k_react_apply ran on the device)
-        std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false;
-      }
-      std::vector<HostTopology::PropChange> chg;
-      for (auto& e : ord)
-        for (int role = 1; role <= 2; ++role)
-          for (auto& rl : nb_rules) if (rl.reaction == e.r && (rl.invoke_on & role)) top.neighbour_change(role == 1 ? e.a : e.b, rl, chg);
-      if (chg.empty()) return;
-      static_assert(sizeof(HostTopology::PropChange) == sizeof(PropChangeDev), "layout");
-      DBuf<PropChangeDev> dchg; dchg.alloc(chg.size());
-      HIPCHK(hipMemcpyAsync(dchg.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), dchg.p, state.p, rtag.p, x4.p, v4.p);
-      HIPCHK(hipStreamSynchronize(stream));
-      types_changed = true;
-      if (!reads_state) state_mirror_stale = true;      // (rules that set a state moved the device copy, not a refreshed mirror)
-    };
-    if (!newbonds.empty() && !nb_rules.empty()) {
-      // same dependency order as below, fully synchronous: graph -> (labels on the thread) -> spawned tuples (types as
-      // they are right after the events) -> neighbour property changes -> tables
+    if (newbonds.empty()) {
+      if (log_n) start_label_thread(std::move(log_events));     // no bonds, no label work: the thread only writes the log
+      types_changed |= neighbour_changes(hev);   // rules on reactions that form no bond
+    } else {
       label_bonds = newbonds; label_touched.clear(); labels_pending = true;
-      top.link_new_bonds(newbonds);
-      label_thr = std::thread([this] {
-        try { top.merge_new_bonds(label_bonds, label_touched); } catch (...) { label_err = std::current_exception(); }
-      });
-      top.spawn_for_new_bonds(newbonds);
-      if (label_thr.joinable()) label_thr.join();   // the flood fill reads the graph only; types are not touched by it, but keep it simple
-      neighbour_changes();
-      upload_excl(false);
-      upload_bonded(false);
-      resort = true;
-      set_ctl_field(&DevCtl::force_rebuild, 1);
-    } else if (!newbonds.empty()) {
-      // Host work of a bond-forming step, arranged by what depends on what:
-      //   bonded CSR  <- lists            exclusion CSR <- exclusions <- (spawned tuples <- graph)
-      //   cluster labels <- graph, read again only by the NEXT reaction scan -> host thread, joined lazily
-      label_bonds = newbonds; label_touched.clear(); labels_pending = true;
-      if (!top.spawns_tuples()) {
-        // the device tables only need the new tuples / pairs: the bond graph, the cluster labels AND the host's own
-        // exclusion rows (read by chem_get_exclusions only) are brought up to date on the thread, beside the MD steps
-        top.excl_log.reserve(top.excl_log.size() + newbonds.size());
-        const size_t log0 = top.excl_log.size();
-        for (auto& e : newbonds) top.excl_log.emplace_back(e.first, e.second);   // (a bond's pair is always new: list_insert deduplicated)
-        label_thr = std::thread([this, log0, log_ev, log_n, log_step, intra_flags] {
-          try {
-            if (log_n) append_events(log_ev, log_n, log_step, intra_flags);
+      if (!nb_rules.empty()) {
+        // same dependency order as below, fully synchronous: graph -> (labels on the thread) -> spawned tuples (types as
+        // they are right after the events) -> neighbour property changes -> tables
+        top.link_new_bonds(newbonds);
+        start_label_thread([this] { top.merge_new_bonds(label_bonds, label_touched); });
+        top.spawn_for_new_bonds(newbonds);
+        if (label_thr.joinable()) label_thr.join();   // the flood fill reads the graph only; types are not touched by it, but keep it simple
+        types_changed |= neighbour_changes(hev);
+        upload_excl(false);
+        upload_bonded(false);
+      } else {
+        // Host work of a bond-forming step, arranged by what depends on what:
+        //   bonded CSR  <- lists            exclusion CSR <- exclusions <- (spawned tuples <- graph)
+        //   cluster labels <- graph, read again only by the NEXT reaction scan -> host thread, joined lazily
+        if (!top.spawns_tuples()) {
+          // the device tables only need the new tuples / pairs: the bond graph, the cluster labels AND the host's own
+          // exclusion rows (read by chem_get_exclusions only) are brought up to date on the thread, beside the MD steps
+          top.excl_log.reserve(top.excl_log.size() + newbonds.size());
+          for (auto& e : newbonds) top.excl_log.emplace_back(e.first, e.second);   // (a bond's pair is always new: list_insert deduplicated)
+          start_label_thread([this, log_events = std::move(log_events)] {
+            log_events();
             for (size_t k = 0; k < label_seen_lists.size(); ++k) {      // (deferred de-duplication keys of this step's bonds)
               const int32_t t[2] = {label_bonds[k].first, label_bonds[k].second};
               top.lists[label_seen_lists[k]].seen.insert(tuple_key(t, 2));
@@ -1885,42 +1915,24 @@ template <typename R> struct CtxT : Ctx {
             top.link_new_bonds(label_bonds); top.merge_new_bonds(label_bonds, label_touched);
             // rows + pair count; the log already holds these pairs
             for (auto& e : label_bonds) { if (HostTopology::sorted_insert(top.excl[e.first], e.second)) { HostTopology::sorted_insert(top.excl[e.second], e.first); ++top.n_excl_pairs; } }
-            (void)log0;
-          } catch (...) { label_err = std::current_exception(); }
-        });
-        trc.lap("threads started");
-      } else {
-        top.link_new_bonds(newbonds);
-        label_thr = std::thread([this] {
-          try { top.merge_new_bonds(label_bonds, label_touched); } catch (...) { label_err = std::current_exception(); }
-        });
-        top.spawn_for_new_bonds(newbonds);
-        trc.lap("link+spawn");
+          });
+          trc.lap("threads started");
+        } else {
+          top.link_new_bonds(newbonds);
+          start_label_thread([this] { top.merge_new_bonds(label_bonds, label_touched); });
+          top.spawn_for_new_bonds(newbonds);
+          trc.lap("link+spawn");
+        }
+        upload_excl(false, false);
+        upload_bonded(false, false);
+        trc.lap("table builds enqueued");
+        HIPCHK(hipStreamSynchronize(stream));
+        trc.lap("uploads");
       }
-      upload_excl(false, false);
-      upload_bonded(false, false);
-      trc.lap("table builds enqueued");
-      HIPCHK(hipStreamSynchronize(stream));
-      trc.lap("uploads");
-      resort = true;
-      set_ctl_field(&DevCtl::force_rebuild, 1);
+      request_rebuild();
     }
-    if (mirror_thr.joinable()) mirror_thr.join();
-    if (mirror_err) std::rethrow_exception(mirror_err);
-    if (log_n && newbonds.empty()) {     // no bonds, no label work: the thread only writes the log
-      label_thr = std::thread([this, log_ev, log_n, log_step, intra_flags] {
-        try { append_events(log_ev, log_n, log_step, intra_flags); } catch (...) { label_err = std::current_exception(); }
-      });
-    }
-    if (newbonds.empty()) neighbour_changes();   // rules on reactions that form no bond
-    if (types_changed) { resort = true; set_ctl_field(&DevCtl::force_rebuild, 1); }   // force list depends on types
-    if (newbonds.empty() && types_changed) {
-      bool any_typed = false;
-      for (auto& l : top.lists) any_typed |= l.by_types != 0;
-      if (any_typed) upload_bonded(false);     // same tuples, slots re-resolved against the new types
-    }
-    trc.lap("end");
-    tm.reaction_wall_s += now_s() - t0;
+    if (types_changed) request_rebuild();   // force list depends on types
+    if (newbonds.empty() && types_changed && any_typed_list()) upload_bonded(false);     // same tuples, slots re-resolved against the new types
   }
 
   // ---- dissociation reactions: every `interval` steps, in front of the association scan (rule set: include/chem_mi355.h) ----
@@ -1964,7 +1976,7 @@ template <typename R> struct CtxT : Ctx {
       return lp != lq ? lp < lq : p.h < q.h;
     });
     // property changes on the mirrors, in canonical order; states as they are on the device
-    if (state_mirror_stale) { std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false; }
+    refresh_state_mirror();
     sync_type_mirrors();
     std::vector<int32_t> changed;
     std::vector<HostTopology::BrokenBond> broken;
@@ -1980,12 +1992,10 @@ template <typename R> struct CtxT : Ctx {
     }
     std::sort(changed.begin(), changed.end());
     changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
-    std::vector<PropChangeDev> chg;
+    std::vector<HostTopology::PropChange> chg;
     chg.reserve(changed.size());
-    for (int32_t t : changed) chg.push_back(PropChangeDev{t, top.type[t], 1, top.state[t], top.mass[t], top.q[t]});
-    DBuf<PropChangeDev> dchg; dchg.alloc(chg.size());
-    HIPCHK(hipMemcpyAsync(dchg.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), dchg.p, state.p, rtag.p, x4.p, v4.p);
+    for (int32_t t : changed) chg.push_back(HostTopology::PropChange{t, top.type[t], 1, top.state[t], top.mass[t], top.q[t]});
+    apply_prop_changes(chg, false);      // (runs beside the host removal below)
     append_events(rec.data(), rec.size(), step, std::vector<int8_t>());
     arena.mirror_pos = arena.size();
     std::vector<int32_t> touched;
@@ -1998,8 +2008,7 @@ template <typename R> struct CtxT : Ctx {
     upload_bonded(true);      // (re-proves bonds_excluded: a break that keeps its exclusion ends the inline-bond mode; typed slots against the new types)
     mol_id.upload(top.mol_id, stream);
     HIPCHK(hipStreamSynchronize(stream));
-    resort = true;
-    set_ctl_field(&DevCtl::force_rebuild, 1);
+    request_rebuild();
     trc.lap("table rebuild");
     tm.reaction_wall_s += now_s() - t0;
   }
@@ -2010,54 +2019,13 @@ template <typename R> struct CtxT : Ctx {
   void atrp_step() {
     HIPCHK(hipStreamSynchronize(stream));
     join_async();
-    if (state_mirror_stale) { std::vector<int> hs; state.download(hs, nglob, stream); top.state.assign(hs.begin(), hs.end()); state_mirror_stale = false; }
-    struct Sel { uint32_t key; int32_t tag; uint32_t u; int center; };
-    auto center_of = [&](int32_t t) {
-      for (size_t c = 0; c < atrp_centers.size(); ++c) if (atrp_centers[c].type == top.type[t] && atrp_centers[c].state == top.state[t]) return (int)c;
-      return -1;
-    };
-    std::vector<Sel> pool;
-    int64_t ncand = 0;
-    for (int32_t t = 0; t < (int32_t)top.n; ++t) {
-      const int c = center_of(t);
-      if (c >= 0) ++ncand;
-      if (c < 0 && !atrp.select_from_all) continue;
-      uint32_t r[4];
-      chem_philox::atrp_draw(atrp.seed, (uint64_t)step, (uint32_t)t, r);
-      pool.push_back(Sel{r[0], t, r[1], c});
-    }
-    auto less = [](const Sel& a, const Sel& b) { return a.key != b.key ? a.key < b.key : a.tag < b.tag; };
-    if ((int64_t)pool.size() > atrp.num_particles) { std::nth_element(pool.begin(), pool.begin() + atrp.num_particles, pool.end(), less); pool.resize((size_t)atrp.num_particles); }
-    std::sort(pool.begin(), pool.end(), less);
-    const double dc = atrp.delta_catalyst / (double)atrp.num_particles;
-    chem_atrp_stats st{}; st.step = step; st.candidates = ncand; st.selected = (int64_t)pool.size();
-    std::vector<PropChangeDev> chg;
-    bool types_changed = false;
-    for (auto& sl : pool) {
-      if (sl.center < 0) continue;
-      const AtrpCenter& c = atrp_centers[sl.center];
-      const double p = c.is_activator ? atrp.k_deactivate * atrp.ratio_deactivator : atrp.k_activate * atrp.ratio_activator;
-      if (!(chem_philox::u01(sl.u) < p)) continue;
-      const int32_t t = sl.tag;
-      if (c.new_type >= 0 && c.new_type != top.type[t]) { top.type[t] = c.new_type; top.mass[t] = c.new_mass; top.q[t] = c.new_q; types_changed = true; }
-      top.state[t] += c.delta_state;
-      chg.push_back(PropChangeDev{t, top.type[t], 1, top.state[t], top.mass[t], top.q[t]});
-      if (c.is_activator) { const double m = std::min(dc, atrp.ratio_deactivator); atrp.ratio_deactivator -= m; atrp.ratio_activator += m; st.deactivated++; }
-      else { const double m = std::min(dc, atrp.ratio_activator); atrp.ratio_activator -= m; atrp.ratio_deactivator += m; st.activated++; }
-    }
-    st.ratio_activator = atrp.ratio_activator; st.ratio_deactivator = atrp.ratio_deactivator;
-    atrp_stats.push_back(st);
-    if (chg.empty()) return;
-    DBuf<PropChangeDev> dchg; dchg.alloc(chg.size());
-    HIPCHK(hipMemcpyAsync(dchg.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), dchg.p, state.p, rtag.p, x4.p, v4.p);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (types_changed) {     // the force list and the typed bonded slots depend on the types
-      bool any_typed = false;
-      for (auto& l : top.lists) any_typed |= l.by_types != 0;
-      if (any_typed) upload_bonded(false);
-      resort = true;
-      set_ctl_field(&DevCtl::force_rebuild, 1);
+    refresh_state_mirror();
+    const AtrpOutcome o = atrp_select(top, atrp, atrp_centers, step);      // (mirrors and catalyst ratios updated)
+    atrp_stats.push_back(o.stats);
+    apply_prop_changes(o.changes);
+    if (o.types_changed) {     // the force list and the typed bonded slots depend on the types
+      if (any_typed_list()) upload_bonded(false);
+      request_rebuild();
     }
   }
 
@@ -2066,13 +2034,8 @@ template <typename R> struct CtxT : Ctx {
   DBuf<unsigned char> gbuf;
   std::vector<unsigned char> gather_records(const std::vector<unsigned char>& loc, size_t rec) {
     if (!dd_on || P == 1) return loc;
-    if (!cnt_all.p) cnt_all.alloc(64);
-    int nloc = (int)(loc.size() / rec);
-    std::vector<int> cnts(P, 0);
-    HIPCHK(hipMemcpyAsync(cnt_all.p + rk, &nloc, sizeof(int), hipMemcpyHostToDevice, stream));
-    tr->allgather(cnt_all.p + rk, cnt_all.p, sizeof(int), stream);
-    HIPCHK(hipMemcpyAsync(cnts.data(), cnt_all.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    const int nloc = (int)(loc.size() / rec);
+    const std::vector<int> cnts = allgather_counts(nloc);
     size_t mx = 0, tot = 0;
     for (int v : cnts) { mx = std::max<size_t>(mx, v); tot += v; }
     std::vector<unsigned char> all(tot * rec);
@@ -2614,7 +2577,7 @@ int chem_reaction_constraint(chem_ctx* ctx, int reaction, int role, int nb_type,
   REQUIRE(reaction >= 0 && reaction < (int)c.reactions.size() && reaction < 32, CHEM_EINVAL, "reaction_constraint: reaction index");
   REQUIRE((role == 1 || role == 2) && nb_type >= 0 && nb_type < CHEM_MAX_TYPES, CHEM_EINVAL, "reaction_constraint: role must be 1 or 2, nb_type a type id");
   if (c.constraints.size() < c.reactions.size()) c.constraints.resize(c.reactions.size());
-  c.constraints[reaction] = Ctx::NbCons{role, nb_type, min_state, max_state};
+  c.constraints[reaction] = NbCons{role, nb_type, min_state, max_state};
   return 0;
   API_END(ctx)
 }
@@ -2651,7 +2614,7 @@ int chem_atrp_add_center(chem_ctx* ctx, int type, int state, int is_activator, i
   Ctx& c = CTX;
   REQUIRE(type >= 0 && type < CHEM_MAX_TYPES && new_type < CHEM_MAX_TYPES, CHEM_EINVAL, "atrp_add_center: types");
   REQUIRE(new_type < 0 || new_mass > 0, CHEM_EINVAL, "atrp_add_center: new_mass");
-  c.atrp_centers.push_back(Ctx::AtrpCenter{type, state, is_activator ? 1 : 0, new_type, delta_state, new_mass, new_q});
+  c.atrp_centers.push_back(AtrpCenter{type, state, is_activator ? 1 : 0, new_type, delta_state, new_mass, new_q});
   c.pair_dirty = true;    // (the type-pair tables must cover the new type)
   return 0;
   API_END(ctx)

@@ -1,0 +1,216 @@
+"""CPU-only tests of the host algorithms of the reaction step (chemlab_amd/csrc/chem_react_host.hpp: sort_bond_events,
+trim_accepted, build_restrict_csr, constraint_bits, atrp_select -- what CtxT::react_step and CtxT::atrp_step call between
+their device launches).  Each is compared with a brute-force Python model; the ATRP selection, whose draws are Philox
+streams Python cannot reproduce, is checked through its invariants (the GPU-vs-oracle ATRP tests are its parity check).
+The harness is compiled with g++ from tests/host/.
+
+sort_bond_events: the events of one step touch disjoint particles, so 4500 of them need 9000 tags; that case draws from
+10000 tags, the smaller ones from 5000."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("host") / "reaction_harness")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "host", "reaction_harness.cpp"), "-o", exe])
+    return exe
+
+
+def run(harness, script):
+    return subprocess.run([harness], input="\n".join(script) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
+
+
+# ---- sort_bond_events ------------------------------------------------------------------------------------------------
+
+def check_sort(harness, pairs):
+    out = run(harness, ["sort %d " % len(pairs) + " ".join("%d %d" % p for p in pairs)])
+    assert out[0] == "sorted %d" % len(pairs)
+    got = [tuple(int(x) for x in l.split()) for l in out[1:1 + len(pairs)]]
+    for a, b, r in got:     # every record arrives whole: same orientation, same payload
+        assert pairs[r] == (a, b)
+    assert sorted(r for _, _, r in got) == list(range(len(pairs)))
+    assert [(min(a, b), max(a, b)) for a, b, _ in got] == sorted((min(p), max(p)) for p in pairs)
+
+
+def disjoint_pairs(rng, m, lo, hi):
+    tags = set()
+    while len(tags) < 2 * m:
+        tags.update(int(x) for x in rng.integers(lo, hi, size=2 * m - len(tags)))
+    tags = rng.permutation(np.array(sorted(tags), dtype=np.int64))
+    return [(int(tags[2 * k]), int(tags[2 * k + 1])) for k in range(m)]
+
+
+@pytest.mark.parametrize("m", [0, 1, 2, 2047, 2048, 2049, 4500])
+def test_sort_radix_path(harness, m):
+    rng = np.random.default_rng(100 + m)
+    check_sort(harness, disjoint_pairs(rng, m, 0, 5000 if 2 * m <= 5000 else 10000))
+
+
+def test_sort_third_pass(harness):
+    # min(a,b) above 2^22: the keys differ in the bits only the third 11-bit pass looks at
+    rng = np.random.default_rng(7)
+    pairs = disjoint_pairs(rng, 3000, 2 ** 22 + 1, 2 ** 31 - 1)
+    assert min(min(p) for p in pairs) > 2 ** 22
+    check_sort(harness, pairs)
+
+
+def test_sort_fallback_on_shared_min(harness):
+    # two events share min(a,b): the radix key is not unique, the full key decides
+    rng = np.random.default_rng(8)
+    pairs = [p for p in disjoint_pairs(rng, 300, 100, 5000)]
+    pairs.insert(17, (5, 99)); pairs.insert(200, (7, 5)); pairs.insert(250, (5, 6))
+    check_sort(harness, pairs)
+
+
+# ---- trim_accepted ---------------------------------------------------------------------------------------------------
+
+def d2_bits(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+@pytest.mark.parametrize("nearest", [0, 1])
+@pytest.mark.parametrize("over", [-3, 0, 3])
+def test_trim_accepted(harness, nearest, over):
+    rng = np.random.default_rng(20 + 10 * nearest + over)
+    m = 80
+    a = rng.permutation(1000)[:m]                             # A's tag: one event per particle
+    d2 = rng.choice([0.25, 0.5, 0.7071067811865476, 1.0, 1.0000000000000002], size=m)   # few values: ties broken by a
+    h = rng.choice([3, 17, 2 ** 31 + 5, 2 ** 32 - 1], size=m)
+    status = rng.choice([0, 1, 2, 2], size=m)
+    acc = [k for k in range(m) if status[k] == 2]
+    cap = len(acc) - over                                     # accepted count below / equal to / above the cap
+    assert cap > 0
+    keyed = sorted(acc, key=lambda k: ((d2_bits(float(d2[k])) if nearest else int(h[k])), int(a[k])))
+    want = [int(s) for s in status]
+    for k in keyed[cap:]:
+        want[k] = 0
+    out = run(harness, ["trim %d %d %d " % (nearest, cap, m) +
+                        " ".join("%d %d %d %d" % (a[k], h[k], d2_bits(float(d2[k])), status[k]) for k in range(m))])
+    got = [int(x) for x in out[0].split()[1:]]
+    assert got[0] == (1 if len(acc) > cap else 0)
+    assert got[1:] == want
+    assert sum(1 for s in got[1:] if s == 2) == min(len(acc), cap)
+
+
+# ---- build_restrict_csr ----------------------------------------------------------------------------------------------
+
+def test_restrict_csr(harness):
+    rng = np.random.default_rng(31)
+    n, lonely = 200, 17
+    mp = {}
+    while len(mp) < 150:
+        lo, hi = sorted(int(x) for x in rng.integers(0, n, size=2))
+        if lo == hi or lonely in (lo, hi):
+            continue
+        mp[(lo, hi)] = mp.get((lo, hi), 0) | int(rng.integers(1, 8))
+    mp[(3, n - 1)] = 5                                        # the last tag has a row
+    out = run(harness, ["csr %d %d " % (n, len(mp)) + " ".join("%d %d %d" % (k[0], k[1], v) for k, v in mp.items()),
+                        "csr 4 0"])
+    start, partner, mask = ([int(x) for x in l.split()[1:]] for l in out[:3])
+    want = [set() for _ in range(n)]
+    for (lo, hi), v in mp.items():
+        want[lo].add((hi, v)); want[hi].add((lo, v))
+    assert len(start) == n + 1 and start[0] == 0 and start[n] == 2 * len(mp) == len(partner) == len(mask)
+    for t in range(n):
+        row = list(zip(partner[start[t]:start[t + 1]], mask[start[t]:start[t + 1]]))
+        assert len(row) == len(want[t]) and set(row) == want[t]
+    assert start[lonely] == start[lonely + 1] and start[n - 1] < start[n]
+    # an empty map: all rows empty, the uploaded arrays still hold one element
+    assert out[3].split()[1:] == ["0"] * 5 and len(out[4].split()) == 2 and len(out[5].split()) == 2
+
+
+# ---- constraint_bits -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("window2", [(1, 4), (2, 2)])      # the second one is empty (min = max)
+def test_constraint_bits(harness, window2):
+    rng = np.random.default_rng(41)
+    n = 300
+    types = rng.integers(0, 4, size=n)
+    states = rng.integers(0, 5, size=n)
+    edges = set()
+    while len(edges) < 450:
+        a, b = (int(x) for x in rng.integers(0, n, size=2))
+        if a != b:
+            edges.add((min(a, b), max(a, b)))
+    reactions = [(0, 1), (1, 2), (2, 3)]
+    cons = [(1, 2, 1, 3), (0, 1, 0, 5), (2, 0) + window2]     # (role, nb_type, min_state, max_state): roles 1, 0 and 2
+    script = ["n %d" % n] + ["type %d %d" % (t, types[t]) for t in range(n)] + ["state %d %d" % (t, states[t]) for t in range(n)]
+    script += ["edge %d %d" % e for e in sorted(edges)] + ["reaction %d %d" % r for r in reactions]
+    script += ["constraint %d %d %d %d" % c for c in cons] + ["cons"]
+    got = [int(x) for x in run(harness, script)[0].split()[1:]]
+    nbrs = [[] for _ in range(n)]
+    for a, b in edges:
+        nbrs[a].append(b); nbrs[b].append(a)
+    want = [0] * n
+    for q, (role, nb_type, lo, hi) in enumerate(cons):
+        if role == 0:
+            continue
+        own = reactions[q][role - 1]
+        for t in range(n):
+            if types[t] == own and any(types[x] == nb_type and lo <= states[x] < hi for x in nbrs[t]):
+                want[t] |= 1 << q
+    assert got == want
+    assert any(w & 1 for w in want) and not any(w & 2 for w in want)
+    assert any(w & 4 for w in want) == (window2[0] < window2[1])
+
+
+# ---- atrp_select -----------------------------------------------------------------------------------------------------
+
+def atrp_script(n, types, states, num, select_all, ra, rd, delta, step):
+    s = ["n %d" % n] + ["type %d %d" % (t, types[t]) for t in range(n)] + ["state %d %d" % (t, states[t]) for t in range(n)]
+    s += ["atrp %d %d %.17g %.17g %.17g 0.9 0.8 12345" % (num, select_all, ra, rd, delta),
+          "center 0 0 0 1 1 2.5 0.25", "center 1 1 1 0 -1 1.0 0.0", "fire %d" % step]
+    return s
+
+
+@pytest.mark.parametrize("select_all", [0, 1])
+@pytest.mark.parametrize("num,delta", [(50, 0.05), (1000, 0.05), (120, 400.0)])      # pool above / below num_particles; catalyst pool that runs dry
+def test_atrp_select(harness, select_all, num, delta):
+    rng = np.random.default_rng(51)
+    n = 400
+    types = rng.integers(0, 3, size=n)
+    states = rng.integers(0, 2, size=n)
+    ra, rd = 0.6, 0.4
+    script = atrp_script(n, types, states, num, select_all, ra, rd, delta, 70)
+    out = run(harness, script)
+    assert out == run(harness, script)                      # same (seed, step): same outcome
+    st = out[0].split()
+    step, ncand, selected, act, deact = (int(x) for x in st[1:6])
+    centre = [(types[t] == 0 and states[t] == 0) or (types[t] == 1 and states[t] == 1) for t in range(n)]
+    assert step == 70 and ncand == sum(centre)
+    assert selected == min(n if select_all else ncand, num)
+    ra1, rd1 = (float(x) for x in out[1].split()[1:])
+    assert (float(st[6]), float(st[7])) == (ra1, rd1)
+    assert ra1 >= 0 and rd1 >= 0
+    # every flip moves m from one pool to the other: two roundings of at most 2^-53 each (the pools stay <= 1)
+    assert abs((ra1 + rd1) - (ra + rd)) <= 2 * (act + deact + 1) * 2.0 ** -53
+    nchg = int(out[2].split()[1])
+    assert act + deact == nchg and 0 < nchg <= selected
+    if delta > num:                                          # a flip's share exceeds the whole pool: it takes all of it, no more
+        assert min(ra1, rd1) == 0.0
+    mirrors = [tuple(int(x) for x in w.split(":")) for w in out[3 + nchg].split()[1:]]
+    seen = set()
+    for l in out[3:3 + nchg]:
+        tag, ty, set_state, state = (int(x) for x in l.split()[:4])
+        mass, q = (float(x) for x in l.split()[4:])
+        assert centre[tag] and tag not in seen and set_state == 1
+        seen.add(tag)
+        if types[tag] == 0:
+            assert (ty, state, mass, q) == (1, 1, 2.5, 0.25)
+        else:
+            assert (ty, state, mass, q) == (0, 0, 1.0, 0.0)
+        assert mirrors[tag] == (ty, state)
+    for t in range(n):
+        if t not in seen:
+            assert mirrors[t] == (types[t], states[t])
+    assert int(st[8]) == 1
+    # another step draws another selection
+    assert run(harness, atrp_script(n, types, states, num, select_all, ra, rd, delta, 80))[3:] != out[3:]
