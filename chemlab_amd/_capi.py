@@ -164,6 +164,8 @@ PRODUCT_ONLY = {
     "comm_init_local": (_i, [_P, _i, _i, _i]),
     "comm_init_ipc": (_i, [_P, _i, _i, C.c_char_p]),
     "dissociation_add": (_i, [_P, C.POINTER(DissociationDesc)]),   # (the CPU oracle has no bond removal)
+    "nb_table_interp": (_i, [_P, _i, _i, _i64, _d, _d, _pd, _pd, _d, _i]),   # (the CPU oracle interpolates linearly only)
+    "table_create_interp": (_i, [_P, _i64, _d, _d, _pd, _pd, _i]),
 }
 
 

@@ -20,6 +20,7 @@
 #include "chem_comm.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
+#include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
 
 namespace chem {
@@ -198,6 +199,7 @@ template <typename R> struct CtxT : Ctx {
   using V4 = Vec4<R>;
   int pair_bs = 512;
   bool lj_only = true;
+  bool cubic_tab = false;   // a type pair of kind 3 exists: the general-mode force kernels are launched in their CUBIC instantiation
   bool state_mirror_stale = false;   // top.state lags the device after reaction steps
   int tile_cap = 0;       // LDS slots of one staged tile (dynamic LDS)
   size_t tile_lds_bytes() const { return (size_t)(tile_cap + 5) * sizeof(V4) + 16; }
@@ -574,7 +576,7 @@ template <typename R> struct CtxT : Ctx {
 #define SETB(T, E, M) SETA((k_pair_tiles<R, T, E, 256, M>)); SETA((k_pair_tiles<R, T, E, 512, M>)); SETA((k_pair_tiles<R, T, E, 1024, M>)); \
                       if (T == 1 && !E) SETA((k_pair_tiles<R, 1, false, 512, M, true>))
 #define SETT(E, M) SETB(1, E, M); SETB(2, E, M); SETB(4, E, M); SETB(8, E, M)
-    SETT(false, 2); SETT(false, 1); SETT(false, 0); SETT(true, 0);
+    SETT(false, 2); SETT(false, 1); SETT(false, 0); SETT(true, 0); SETT(false, 3); SETT(true, 3);
 #undef SETT
 #undef SETB
 #undef SETA
@@ -702,6 +704,7 @@ template <typename R> struct CtxT : Ctx {
     std::vector<PairCore<R>> hc((size_t)nt * nt);
     std::vector<PairExt<R>> he((size_t)nt * nt);
     std::vector<V4> htab;
+    bool cubic = false;
     for (int a = 0; a < nt; ++a) for (int b = 0; b < nt; ++b) {
       const HostPairPot& p = pp[a][b];
       PairCore<R> c{(R)-1, 0, 0, 0}; PairExt<R> e{0, 0, 0, 0, 0, 0, 0, 0};
@@ -709,6 +712,14 @@ template <typename R> struct CtxT : Ctx {
         const double s6 = std::pow(p.sig, 6), s12 = s6 * s6;
         c.rc2 = (R)(p.rc * p.rc); c.lj1 = (R)(48.0 * p.eps * s12); c.lj2 = (R)(24.0 * p.eps * s6); c.kind = (R)1;
         e.e1 = (R)(4.0 * p.eps * s12); e.e2 = (R)(4.0 * p.eps * s6); e.shift = (R)p.shift;
+      } else if (p.kind == 2 && p.itype != TAB_LINEAR) {      // spline kinds: two rows of coefficients per interval
+        c.rc2 = (R)(p.rc * p.rc); c.kind = (R)3; cubic = true;
+        e.r0 = (R)p.r0; e.inv_dr = (R)(1.0 / p.dr); e.toff = (int)htab.size(); e.nrow = (int)p.e.size();
+        const std::vector<double> co = pack_pair_rows(p.e.data(), p.f.data(), p.e.size(), p.itype);
+        for (size_t k = 0; k < co.size(); k += 4) {
+          V4 row; row.x = (R)co[k]; row.y = (R)co[k + 1]; row.z = (R)co[k + 2]; row.w = (R)co[k + 3];
+          htab.push_back(row);
+        }
       } else if (p.kind == 2) {
         c.rc2 = (R)(p.rc * p.rc); c.kind = (R)2;
         e.r0 = (R)p.r0; e.inv_dr = (R)(1.0 / p.dr); e.toff = (int)htab.size(); e.nrow = (int)p.e.size();
@@ -722,6 +733,7 @@ template <typename R> struct CtxT : Ctx {
       hc[(size_t)a * nt + b] = c; he[(size_t)a * nt + b] = e;
     }
     lj_only = htab.empty();
+    cubic_tab = cubic;
     // type pairs with a potential; uniform LJ = every active pair shares one parameter set
     std::memset(&act, 0, sizeof(act));
     uniform_lj = lj_only;
@@ -757,8 +769,12 @@ template <typename R> struct CtxT : Ctx {
     if (btab_uploaded == top.btables.size()) return;
     std::vector<double2> rows; std::vector<double4> info;
     for (const HostBondTable& t : top.btables) {
-      info.push_back(make_double4((double)rows.size(), (double)t.e.size(), t.r0, 1.0 / t.dr));
-      for (size_t k = 0; k < t.e.size(); ++k) rows.push_back(make_double2(t.e[k], t.f[k]));
+      info.push_back(make_double4((double)rows.size(), t.itype == TAB_LINEAR ? (double)t.e.size() : -(double)t.e.size(), t.r0, 1.0 / t.dr));   // (sign: BTab)
+      if (t.itype == TAB_LINEAR) for (size_t k = 0; k < t.e.size(); ++k) rows.push_back(make_double2(t.e[k], t.f[k]));
+      else {
+        const std::vector<double> co = pack_bond_rows(t.e.data(), t.f.data(), t.e.size(), t.itype);
+        for (size_t k = 0; k < co.size(); k += 2) rows.push_back(make_double2(co[k], co[k + 1]));
+      }
     }
     btab_rows.upload(rows, stream); btab_info.upload(info, stream);
     HIPCHK(hipStreamSynchronize(stream));
@@ -1264,8 +1280,8 @@ template <typename R> struct CtxT : Ctx {
 #define LTB(T, M) do { if ((dbg_on || opt_ablate) && !ENERGY) { if (T != 1 || pair_bs != 512) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate need tpp=1 and pair_block=512"); LTD(1, M, 512, true); } \
                        else if (pair_bs == 256) LT(T, M, 256); else if (pair_bs == 512) LT(T, M, 512); else LT(T, M, 1024); } while (0)
 #define LTT(M) do { switch (tpp) { case 1: LTB(1, M); break; case 2: LTB(2, M); break; case 8: LTB(8, M); break; default: LTB(4, M); break; } } while (0)
-      const int mode = ENERGY ? 0 : (uniform_lj ? 2 : (lj_only ? 1 : 0));
-      if (mode == 2) LTT(2); else if (mode == 1) LTT(1); else LTT(0);
+      const int mode = ENERGY ? (cubic_tab ? 3 : 0) : (uniform_lj ? 2 : (lj_only ? 1 : (cubic_tab ? 3 : 0)));
+      if (mode == 2) LTT(2); else if (mode == 1) LTT(1); else if (mode == 3) LTT(3); else LTT(0);
 #undef LTT
 #undef LTB
 #undef LT
@@ -1273,13 +1289,15 @@ template <typename R> struct CtxT : Ctx {
       return ntiles;
     }
     const int nb = cdiv((long long)n * tpp, 256);
-#define LP(T) hipLaunchKernelGGL((k_pair_force<R, T, ENERGY>), dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, \
+#define LPC(T, CU) hipLaunchKernelGGL((k_pair_force<R, T, ENERGY, CU>), dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, \
                                  pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p)
+#define LP(T) do { if (cubic_tab) LPC(T, true); else LPC(T, false); } while (0)
     switch (tpp) {
       case 1: LP(1); break; case 2: LP(2); break; case 4: LP(4); break; case 8: LP(8); break;
       case 16: LP(16); break; case 32: LP(32); break; default: LP(64); break;
     }
 #undef LP
+#undef LPC
     return nb;
   }
 
@@ -2387,10 +2405,16 @@ int chem_nb_lj(chem_ctx* ctx, int t1, int t2, double eps, double sig, double rc,
 }
 
 int chem_nb_table(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double dr, const double* e, const double* f, double rc) {
+  return chem_nb_table_interp(ctx, t1, t2, nrow, r0, dr, e, f, rc, TAB_LINEAR);
+}
+
+int chem_nb_table_interp(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double dr, const double* e, const double* f, double rc, int itype) {
   API_BEGIN
   REQUIRE(t1 >= 0 && t2 >= 0 && t1 < CHEM_MAX_TYPES && t2 < CHEM_MAX_TYPES, CHEM_EINVAL, "nb_table: type out of range");
+  REQUIRE(itype >= TAB_LINEAR && itype <= TAB_CUBIC, CHEM_EINVAL, "nb_table: itype must be 1 (linear), 2 (Akima) or 3 (natural cubic spline)");
   REQUIRE(nrow >= 2 && dr > 0 && e && f && rc > 0, CHEM_EINVAL, "nb_table: need >=2 rows, dr>0");
-  HostPairPot p; p.kind = 2; p.rc = rc; p.r0 = r0; p.dr = dr; p.e.assign(e, e + nrow); p.f.assign(f, f + nrow);
+  REQUIRE(tab_args_ok(itype, nrow), CHEM_EINVAL, "nb_table: the spline kinds (itype 2, 3) need >= 4 rows");
+  HostPairPot p; p.kind = 2; p.itype = itype; p.rc = rc; p.r0 = r0; p.dr = dr; p.e.assign(e, e + nrow); p.f.assign(f, f + nrow);
   CTX.pp[t1][t2] = p; CTX.pp[t2][t1] = p; CTX.pair_dirty = true;
   return 0;
   API_END(ctx)
@@ -2411,9 +2435,15 @@ int chem_list_create(chem_ctx* ctx, int arity, int kind, int by_types) {
 }
 
 int chem_table_create(chem_ctx* ctx, int64_t nrow, double r0, double dr, const double* e, const double* f) {
+  return chem_table_create_interp(ctx, nrow, r0, dr, e, f, TAB_LINEAR);
+}
+
+int chem_table_create_interp(chem_ctx* ctx, int64_t nrow, double r0, double dr, const double* e, const double* f, int itype) {
   API_BEGIN
+  REQUIRE(itype >= TAB_LINEAR && itype <= TAB_CUBIC, CHEM_EINVAL, "table_create: itype must be 1 (linear), 2 (Akima) or 3 (natural cubic spline)");
   REQUIRE(nrow >= 2 && dr > 0 && e && f, CHEM_EINVAL, "table_create: need >= 2 rows, dr > 0");
-  HostBondTable t; t.r0 = r0; t.dr = dr; t.e.assign(e, e + nrow); t.f.assign(f, f + nrow);
+  REQUIRE(tab_args_ok(itype, nrow), CHEM_EINVAL, "table_create: the spline kinds (itype 2, 3) need >= 4 rows");
+  HostBondTable t; t.r0 = r0; t.dr = dr; t.itype = itype; t.e.assign(e, e + nrow); t.f.assign(f, f + nrow);
   CTX.top.btables.push_back(std::move(t));
   CTX.bonded_dirty = true;
   return (int)CTX.top.btables.size() - 1;

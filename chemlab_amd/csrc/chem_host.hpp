@@ -139,6 +139,7 @@ struct HostList {
 
 struct HostPairPot {
   int kind = 0;  // 0 none, 1 LJ, 2 table
+  int itype = 1; // table: 1 linear, 2 Akima, 3 natural cubic spline (chem_tab_host.hpp)
   double eps = 0, sig = 0, rc = 0, shift = 0, r0 = 0, dr = 0;
   std::vector<double> e, f;
 };
@@ -147,7 +148,7 @@ struct HostPairPot {
 struct HBondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };
 struct HBondedEntry { int t0, t1, t2, meta; };
 
-struct HostBondTable { double r0 = 0, dr = 1; std::vector<double> e, f; };
+struct HostBondTable { double r0 = 0, dr = 1; int itype = 1; std::vector<double> e, f; };   // itype as HostPairPot
 
 struct HostTopology {
   int64_t n = 0;

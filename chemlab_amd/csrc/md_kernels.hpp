@@ -183,7 +183,9 @@ __device__ __forceinline__ double pos_delta(double a, double b, int d, const Box
 // LDS read per pair in fp32); PairExt holds energy and table terms.
 //   kind 1: ff = r^-6 (lj1 r^-6 - lj2) r^-2,  e = r^-6 (e1 r^-6 - e2) + shift
 //   kind 2: linear table interpolation, rows (f_k, f_k+1 - f_k, e_k, e_k+1 - e_k)
-template <typename R> struct PairCore { R rc2, lj1, lj2, kind; };   // kind as R: 0 none (rc2<0), 1 LJ, 2 table
+//   kind 3: piecewise cubic (Akima / natural spline, fitted on the host: chem_tab_host.hpp), two rows per interval,
+//           (f c0..c3) and (e c0..c3), y = c0 + w (c1 + w (c2 + w c3)); only the CUBIC instantiations know it
+template <typename R> struct PairCore { R rc2, lj1, lj2, kind; };   // kind as R: 0 none (rc2<0), 1 LJ, 2 table, 3 cubic table
 template <typename R> struct PairExt { R e1, e2, shift, r0, inv_dr; int toff, nrow, pad; };
 
 // ---- helpers -------------------------------------------------------------------------
@@ -968,12 +970,26 @@ __global__ __launch_bounds__(256) void k_nlist_brute(int n, const Vec4<R>* __res
 //     particle: lane t handles neighbours t, t+TPP, ...; partial forces are combined with a
 //     segmented xor-shuffle reduction.  Full list => no atomics, deterministic sums.
 // =======================================================================================
-template <typename R, bool ENERGY>
+// CUBIC: the host selects these instantiations only while a type pair of kind 3 exists, so that the others stay what they were
+template <typename R, bool ENERGY, bool CUBIC = false>
 __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
                                           const Vec4<R>* __restrict__ tab, R r2, R dx, R dy, R dz,
                                           R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir) {
   if (r2 <= pc.rc2) {
-    if (pc.kind == (R)1) {
+    if (CUBIC && pc.kind == (R)3) {
+      const PairExt<R> px = pext[pidx];
+      const R r = sqrt_r(r2);
+      R t = (r - px.r0) * px.inv_dr;
+      const R tmax = (R)(px.nrow - 1);
+      t = t < (R)0 ? (R)0 : (t > tmax ? tmax : t);
+      int k = (int)t;
+      if (k > px.nrow - 2) k = px.nrow - 2;
+      const R w = t - (R)k;
+      const Vec4<R> cf = tab[px.toff + 2 * k];      // force coefficients; the energy row behind it is read with ENERGY only
+      const R ff = (cf.x + w * (cf.y + w * (cf.z + w * cf.w))) / r;
+      fx += ff * dx; fy += ff * dy; fz += ff * dz;
+      if (ENERGY) { const Vec4<R> ce = tab[px.toff + 2 * k + 1]; e_tab += (double)(ce.x + w * (ce.y + w * (ce.z + w * ce.w))); vir += (double)(ff * r2); }
+    } else if (pc.kind == (R)1) {
       const R r2i = rcp_r(r2), r6i = r2i * r2i * r2i;
       const R ff = r6i * (pc.lj1 * r6i - pc.lj2) * r2i;
       fx += ff * dx; fy += ff * dy; fz += ff * dz;
@@ -995,7 +1011,7 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
   }
 }
 
-template <typename R, int TPP, bool ENERGY>
+template <typename R, int TPP, bool ENERGY, bool CUBIC = false>
 __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ nlist, const int* __restrict__ nn, int S,
                                                     Box<R> box, const PairCore<R>* __restrict__ pcore,
@@ -1029,7 +1045,7 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
         R r2 = dx * dx + dy * dy + dz * dz;
         r2 = (k + u < cnt) ? r2 : (R)1e30;     // padding entries (self index) never interact
         const int pidx = pbase + (int)xj.w;
-        pair_term<R, ENERGY>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+        pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
       }
     }
   }
@@ -2032,7 +2048,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(int ntiles, TileLDS<R>* __re
 }
 
 // ---- pair forces on tiles --------------------------------------------------------------
-template <typename R, bool ENERGY, bool LJONLY>
+template <typename R, bool ENERGY, bool LJONLY, bool CUBIC = false>
 __device__ __forceinline__ void pair_accum(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
                                            const Vec4<R>* __restrict__ tab, R r2, R dx, R dy, R dz,
                                            R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir) {
@@ -2042,7 +2058,7 @@ __device__ __forceinline__ void pair_accum(const PairCore<R> pc, const PairExt<R
     ff = (r2 <= pc.rc2) ? ff * pc.kind : (R)0;   // kind (1 for LJ) keeps the read a single ds_read_b128 (b96 costs 2x the LDS cycles)
     fx += ff * dx; fy += ff * dy; fz += ff * dz;
   } else {
-    pair_term<R, ENERGY>(pc, pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+    pair_term<R, ENERGY, CUBIC>(pc, pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
   }
 }
 
@@ -2067,6 +2083,7 @@ struct UniLJ { float rc2, lj1, lj2, pad; double drc2, dlj1, dlj2; };   // all li
 // One workgroup per tile; TPP lanes per home particle (lane `sub` takes chunks sub, sub+TPP, ...).
 // MODE 0: general (type-pair table in LDS, tables allowed)  1: LJ/off pairs only, branch-free
 //      2: uniform LJ -- every listed pair has the same parameters (kernel arguments / SGPRs)
+//      3: general as 0, with the piecewise-cubic table kind (launched only while a type pair of kind 3 exists)
 // Tiles of one launch: [base1, base1+n1) followed by [base2, ...).  The decomposed path launches the
 // tiles whose stencil stays inside the own layers ("interior": they need no ghost) while the halo
 // exchange is still in flight on the communication stream, and the two boundary tile layers after it.
@@ -2164,7 +2181,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
                                                    DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
                                                    double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
                                                    const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
-  constexpr bool LJONLY = MODE >= 1;
+  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3;
 #ifndef CHEM_NCH
 #define CHEM_NCH 3
 #endif
@@ -2327,7 +2344,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
               fx += ff * dx; fy += ff * dy; fz += ff * dz;
             } else {
               const int pidx = pbase + (int)xj.w;
-              pair_accum<R, ENERGY, LJONLY>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+              pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
             }
           }
         }
@@ -2385,7 +2402,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
               } else {
                 R tx = 0, ty = 0, tz = 0; double te1 = 0, te2 = 0, tv = 0;
                 const int pidx = pbase + (int)xj.w;
-                pair_accum<R, ENERGY, LJONLY>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, tx, ty, tz, te1, te2, tv);
+                pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, tx, ty, tz, te1, te2, tv);
                 fx -= tx; fy -= ty; fz -= tz; e_lj -= te1; e_tab -= te2; vir -= tv;
               }
             }
@@ -2451,8 +2468,33 @@ __device__ __forceinline__ double dist2_unfused(const D3& d) {
 }
 template <typename R> __device__ __forceinline__ D3 posD(const Vec4<R>& v, const BoxD& b) { return pos_real(v, b.qs, b.qh); }   // exact in both builds
 
-// bond tables (chem_table_create): rows = (e, f) pairs of all tables back to back, info[h] = (first row, rows, r0, 1/dr)
+// bond tables (chem_table_create[_interp]): rows = (e, f) pairs of all tables back to back,
+// info[h] = (first row, +-rows of the grid, r0, 1/dr); the sign of the second entry is the interpolation kind:
+//   > 0  linear: one pair per grid row;
+//   < 0  piecewise cubic (Akima or natural spline, fitted on the host: chem_tab_host.hpp): four pairs per interval,
+//        (e c0, f c0) .. (e c3, f c3), rows - 1 intervals.
+// (the kind as a field of its own cost k_bonded_work a register)
 struct BTab { const double2* rows; const double4* info; };
+// table h at x (a distance, or an angle in radians): u = e(x), fv = f(x); beyond the grid the end rows' values hold
+__device__ __forceinline__ void btab_lookup(const BTab& bt, const int h, const double x, double& u, double& fv) {
+  const double4 ti = bt.info[h];
+  const double2* row = bt.rows + (size_t)ti.x;
+  const int nr = (int)ti.y, nrow = nr < 0 ? -nr : nr;
+  const double t = (x - ti.z) * ti.w;
+  if (nr > 0) {
+    if (t <= 0) { u = row[0].x; fv = row[0].y; }
+    else if (t >= (double)(nrow - 1)) { u = row[nrow - 1].x; fv = row[nrow - 1].y; }
+    else { const int k = (int)t; const double w = t - (double)k; const double2 a = row[k], b = row[k + 1]; u = a.x + w * (b.x - a.x); fv = a.y + w * (b.y - a.y); }
+  } else {
+    const double tc = t > 0 ? (t < (double)(nrow - 1) ? t : (double)(nrow - 1)) : 0.0;      // (a NaN ends at 0)
+    int k = (int)tc;
+    if (k > nrow - 2) k = nrow - 2;
+    const double w = tc - (double)k;
+    const double2 c0 = row[4 * k], c1 = row[4 * k + 1], c2 = row[4 * k + 2], c3 = row[4 * k + 3];
+    u = c0.x + w * (c1.x + w * (c2.x + w * c3.x));
+    fv = c0.y + w * (c1.y + w * (c2.y + w * c3.y));
+  }
+}
 
 // one bonded term seen from member `me` of the tuple (j0..j3 = particle indices of the tuple in order)
 // BONDS_ONLY: the caller guarantees arity 2 and an analytic kind (harmonic, FENE, FENE+LJ, LJ pair) -- the angle, dihedral
@@ -2486,15 +2528,9 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
           ff = 24.0 * p[0] * (2.0 * s6 * s6 - s6) / (r * r);
         }
       }
-      else if (!BONDS_ONLY && bp.kind == CHEM_POT_TABULATED) {   // Tabulated(itype=1): linear interpolation of e(r), f(r); end rows beyond the grid
-        const double4 ti = bt.info[(int)p[0]];
-        const double2* row = bt.rows + (size_t)ti.x;
-        const int nrow = (int)ti.y;
-        const double t = (r - ti.z) * ti.w;
+      else if (!BONDS_ONLY && bp.kind == CHEM_POT_TABULATED) {   // Tabulated: e(r), f(r) from table p[0]
         double fv;
-        if (t <= 0) { u = row[0].x; fv = row[0].y; }
-        else if (t >= (double)(nrow - 1)) { u = row[nrow - 1].x; fv = row[nrow - 1].y; }
-        else { const int k = (int)t; const double w = t - (double)k; const double2 a = row[k], b = row[k + 1]; u = a.x + w * (b.x - a.x); fv = a.y + w * (b.y - a.y); }
+        btab_lookup(bt, (int)p[0], r, u, fv);
         ff = fv / r;
       }
       const double sgn = me == 0 ? 1.0 : -1.0;
@@ -2513,15 +2549,9 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
       double dU = 0;
       if (bp.kind == CHEM_POT_ANG_HARMONIC) { const double d = th - p[1]; u = p[0] * d * d; dU = 2.0 * p[0] * d; }
       else if (bp.kind == CHEM_POT_ANG_COSINE) { u = p[0] * (1.0 + cos(th - p[1])); dU = -p[0] * sin(th - p[1]); }
-      else if (bp.kind == CHEM_POT_ANG_TABULATED) {   // TabulatedAngular(itype=1): U(theta), -dU/dtheta on a uniform grid in radians
-        const double4 ti = bt.info[(int)p[0]];
-        const double2* row = bt.rows + (size_t)ti.x;
-        const int nrow = (int)ti.y;
-        const double t = (th - ti.z) * ti.w;
+      else if (bp.kind == CHEM_POT_ANG_TABULATED) {   // TabulatedAngular: U(theta), -dU/dtheta on a uniform grid in radians
         double fv;
-        if (t <= 0) { u = row[0].x; fv = row[0].y; }
-        else if (t >= (double)(nrow - 1)) { u = row[nrow - 1].x; fv = row[nrow - 1].y; }
-        else { const int k = (int)t; const double w = t - (double)k; const double2 a = row[k], b = row[k + 1]; u = a.x + w * (b.x - a.x); fv = a.y + w * (b.y - a.y); }
+        btab_lookup(bt, (int)p[0], th, u, fv);
         dU = -fv;
       }
       const double a = dU / s;
@@ -2549,15 +2579,9 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
         d -= 2.0 * M_PI * rint(d / (2.0 * M_PI));
         u = 0.5 * p[0] * d * d; dU = p[0] * d;
       }
-      else if (bp.kind == CHEM_POT_DIH_TABULATED) {   // TabulatedDihedral(itype=1): U(phi), -dU/dphi on a uniform grid over [-pi, pi]
-        const double4 ti = bt.info[(int)p[0]];
-        const double2* row = bt.rows + (size_t)ti.x;
-        const int nrow = (int)ti.y;
-        const double t = (phi - ti.z) * ti.w;
+      else if (bp.kind == CHEM_POT_DIH_TABULATED) {   // TabulatedDihedral: U(phi), -dU/dphi on a uniform grid over [-pi, pi]
         double fv;
-        if (t <= 0) { u = row[0].x; fv = row[0].y; }
-        else if (t >= (double)(nrow - 1)) { u = row[nrow - 1].x; fv = row[nrow - 1].y; }
-        else { const int k = (int)t; const double w = t - (double)k; const double2 a = row[k], b = row[k + 1]; u = a.x + w * (b.x - a.x); fv = a.y + w * (b.y - a.y); }
+        btab_lookup(bt, (int)p[0], phi, u, fv);
         dU = -fv;
       }
       const D3 g1 = (-lb / m2) * m, g4 = (lb / n2) * nn;

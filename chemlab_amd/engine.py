@@ -95,12 +95,23 @@ class Engine:
     def nb_lj(self, t1, t2, eps, sig, rc, shift_auto=True):
         self._ck(self.api.nb_lj(self.ctx, t1, t2, eps, sig, rc, 1 if shift_auto else 0))
 
-    def nb_table(self, t1, t2, r0, dr, e, f, rc):
+    def _interp_entry(self, name, itype):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("Tabulated itype %r: the CPU checker has linear tables (itype=1) only" % (itype,))
+        return fn
+
+    def nb_table(self, t1, t2, r0, dr, e, f, rc, itype=1):
+        """itype: 1 linear, 2 Akima, 3 natural cubic spline (include/chem_mi355.h, chem_nb_table_interp)."""
         e = np.ascontiguousarray(e, dtype=np.float64)
         f = np.ascontiguousarray(f, dtype=np.float64)
         assert e.shape == f.shape
-        self._ck(self.api.nb_table(self.ctx, t1, t2, e.shape[0], r0, dr, _ptr(e, C.c_double),
-                                   _ptr(f, C.c_double), rc))
+        if itype == 1:
+            self._ck(self.api.nb_table(self.ctx, t1, t2, e.shape[0], r0, dr, _ptr(e, C.c_double),
+                                       _ptr(f, C.c_double), rc))
+        else:
+            self._ck(self._interp_entry("nb_table_interp", itype)(self.ctx, t1, t2, e.shape[0], r0, dr, _ptr(e, C.c_double),
+                                                                  _ptr(f, C.c_double), rc, int(itype)))
 
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
@@ -134,10 +145,13 @@ class Engine:
         t = np.ascontiguousarray(list(types), dtype=np.int32)
         self._ck(self.api.thermostat_langevin_types(self.ctx, t.shape[0], _ptr(t, C.c_int32)))
 
-    def table_create(self, r0, dr, e, f):
-        """Bond table (rows of a .pot file); returns the handle to pass as list_set_params(h, [handle])."""
+    def table_create(self, r0, dr, e, f, itype=1):
+        """Bond table (rows of a .pot file); returns the handle to pass as list_set_params(h, [handle]).  itype as nb_table."""
         e = np.ascontiguousarray(e, dtype=np.float64); f = np.ascontiguousarray(f, dtype=np.float64)
         assert e.shape == f.shape
+        if itype != 1:
+            return self._ck(self._interp_entry("table_create_interp", itype)(self.ctx, e.shape[0], float(r0), float(dr), _ptr(e, C.c_double),
+                                                                             _ptr(f, C.c_double), int(itype)))
         return self._ck(self.api.table_create(self.ctx, e.shape[0], float(r0), float(dr), _ptr(e, C.c_double), _ptr(f, C.c_double)))
 
     def thermostat_rescale(self, kind, kT, param):

@@ -314,15 +314,22 @@ class _LennardJones(_Pot):
 
 
 class _Tabulated(_Pot):
-    """interaction.Tabulated(itype, filename, cutoff): rows `r e f` of an ESPResSo++ .pot file."""
+    """interaction.Tabulated(itype, filename, cutoff): rows `r e f` of an ESPResSo++ .pot file; itype 1 linear, 2 Akima,
+    3 natural cubic spline (rule set: include/chem_mi355.h, chem_nb_table_interp)."""
 
     def __init__(self, itype=1, filename=None, cutoff=None):
-        if itype != 1:
-            raise NotImplementedError("Tabulated itype %r (only linear interpolation, itype=1, is in scope)" % itype)
+        if itype not in (1, 2, 3):
+            raise NotImplementedError("Tabulated itype %r (1 linear, 2 Akima, 3 cubic spline)" % (itype,))
         self.itype, self.filename, self.cutoff = itype, filename, cutoff
         tab = np.loadtxt(filename)
         self.r, self.e, self.f = tab[:, 0], tab[:, 1], tab[:, 2]
         self.r0, self.dr = float(self.r[0]), float(self.r[1] - self.r[0])
+
+
+def _interp_kw(pot):
+    """Keyword for Engine.nb_table / table_create: none for linear tables, so that an engine with linear tables only (the
+    CPU checker) is driven exactly as before; a spline kind there is refused by Engine, never evaluated linearly."""
+    return {} if pot.itype == 1 else {"itype": pot.itype}
 
 
 class _MixedTabulated(_Pot):
@@ -469,7 +476,7 @@ class _VerletListTabulated(_VerletListInteraction):
 
     def setPotential(self, type1, type2, potential):
         self._pots[(min(type1, type2), max(type1, type2))] = potential
-        self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff)
+        self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
 
 
 class _VerletListMixedTabulated(_VerletListInteraction):
@@ -505,7 +512,7 @@ class _FixedListInteraction(object):
             eng = self.system.engine
             cache = pot.__dict__.setdefault("_handles", {})
             if id(eng) not in cache:
-                cache[id(eng)] = eng.table_create(pot.r0, pot.dr, pot.e, pot.f)
+                cache[id(eng)] = eng.table_create(pot.r0, pot.dr, pot.e, pot.f, **_interp_kw(pot))
             return kind, [float(cache[id(eng)])]
         if isinstance(pot, _LennardJones):      # FixedPairList[Types]LennardJones: 1-4 pairs
             return "LJ_BOND", [pot.epsilon, pot.sigma, pot.cutoff if pot.cutoff is not None else 1e30]

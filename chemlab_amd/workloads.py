@@ -229,8 +229,11 @@ def apply(spec, eng, thermostat=True, reactions=True):
                       state=spec.get("state"), res_id=spec.get("res_id"))
     for lj in spec.get("lj", []):               # (t1, t2, eps, sigma, rc[, shift_auto]): shift_auto defaults to on
         eng.nb_lj(*lj[:5], lj[5] if len(lj) > 5 else True)
-    for (t1, t2, r0, dr, e, f, rc) in spec.get("tables", []):
-        eng.nb_table(t1, t2, r0, dr, e, f, rc)
+    for tb in spec.get("tables", []):           # (t1, t2, r0, dr, e, f, rc[, itype]): linear interpolation without itype
+        if len(tb) > 7 and tb[7] != 1:
+            eng.nb_table(*tb[:7], itype=tb[7])
+        else:
+            eng.nb_table(*tb[:7])
     handles = {}
     for i, l in enumerate(spec.get("lists", [])):
         h = eng.list_create(l["arity"], l["kind"], False)

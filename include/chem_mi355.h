@@ -194,6 +194,25 @@ int chem_nb_lj(chem_ctx* ctx, int t1, int t2, double eps, double sig, double rc,
  * (tools/convert_gromacs2espp.py:84-107), uniform spacing dr starting at r0. */
 int chem_nb_table(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double dr,
                   const double* e, const double* f, double rc);
+/* Interpolation kinds of every tabulated potential (pairs, bonds, angles, dihedrals): the `itype` of
+ * interaction.Tabulated / TabulatedAngular / TabulatedDihedral.  1 = linear (the calls without `_interp`), 2 = Akima,
+ * 3 = natural cubic spline; anything else, and nrow < 4 for itype 2 and 3, is CHEM_EINVAL.  The arithmetic of the
+ * reference's InterpolationAkima / InterpolationCubic is in the external fork, so this rule set is this build's own:
+ *   - the e and the f column are interpolated independently (the force is the spline of f, not the derivative of the e spline);
+ *   - per interval k = 0 .. nrow-2 and column: y(w) = c0 + w (c1 + w (c2 + w c3)), w = (x - x_k) / dr in [0, 1];
+ *   - itype 2, Akima (1970): d_k = y_{k+1} - y_k, continued by d_-1 = 2 d_0 - d_1, d_-2 = 2 d_-1 - d_0,
+ *     d_{n-1} = 2 d_{n-2} - d_{n-3}, d_n = 2 d_{n-1} - d_{n-2}; node slope per grid step
+ *       t_k = (|d_{k+1} - d_k| d_{k-1} + |d_{k-1} - d_{k-2}| d_k) / s_k,  s_k = the sum of the two weights,
+ *     and t_k = (d_{k-1} + d_k) / 2 where s_k <= 1e-9 max_j s_j (the tie rule of scipy's Akima1DInterpolator);
+ *       c0 = y_k, c1 = t_k, c2 = 3 d_k - 2 t_k - t_{k+1}, c3 = t_k + t_{k+1} - 2 d_k;
+ *   - itype 3: second derivatives (times dr^2) M_0 = M_{n-1} = 0, M_{k-1} + 4 M_k + M_{k+1} = 6 (y_{k+1} - 2 y_k + y_{k-1});
+ *       c0 = y_k, c1 = d_k - (2 M_k + M_{k+1}) / 6, c2 = M_k / 2, c3 = (M_{k+1} - M_k) / 6;
+ *   - evaluation as for the linear kind: t = (x - r0) / dr clamped to [0, nrow-1], k = min(int(t), nrow-2), w = t - k,
+ *     Horner; beyond the grid the end rows' values hold.  Pairs: F_ij = f(r)/r * r_ij for r^2 <= rc^2, energy e(r) without
+ *     a shift.  Bonds: f(r)/r.  Angles: U(theta), -dU/dtheta in radians.  Dihedrals: over [-pi, pi], not periodic.
+ * A type pair may be re-sent with another kind (or as LJ) between two chem_run calls. */
+int chem_nb_table_interp(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double dr,
+                         const double* e, const double* f, double rc, int itype);
 
 /* ---- bonded lists -------------------------------------------------------------------- */
 /* FixedPairList/TripleList/QuadrupleList(storage) + FixedXListYyy(system, list, potential)
@@ -209,6 +228,8 @@ int chem_list_create(chem_ctx* ctx, int arity, int potential_kind, int by_types)
  * grid in radians, columns U(theta) and -dU/dtheta, list kind CHEM_POT_ANG_TABULATED; and interaction.TabulatedDihedral
  * (dihedrals func 8, table_d<N>.pot, gromacs_topology.py:1192-1198): grid over [-pi, pi], kind CHEM_POT_DIH_TABULATED. */
 int chem_table_create(chem_ctx* ctx, int64_t nrow, double r0, double dr, const double* e, const double* f);
+/* The same with an interpolation kind (see chem_nb_table_interp); itype = 1 is chem_table_create. */
+int chem_table_create_interp(chem_ctx* ctx, int64_t nrow, double r0, double dr, const double* e, const double* f, int itype);
 /* addBonds/addTriples/addQuadruples: ids is n*arity particle ids */
 int chem_list_add(chem_ctx* ctx, int list, int64_t n, const int64_t* ids);
 /* plain list: t1..t4 ignored (pass -1); Types list: setPotential(type1,type2[,type3[,type4]],pot) */
