@@ -588,6 +588,9 @@ template <typename R> struct CtxT : Ctx {
     nlist.alloc(ac * S);
     nnh.alloc(ac);
     if (use_tiles) { nl16.alloc(ac * S); HIPCHK(hipMemsetAsync(nl16.p, 0, ac * S * 2, stream)); tdesc.alloc(ntiles); }
+    // the energy launch of the tile path writes three words per TILE: a sparse box has more tiles than the particle count
+    // behind upload_particles' size allows for (57 particles in 2197 tiles: observe() wrote past the end, tests/test_gpu_geometry.py)
+    eout.alloc(3 * std::max((size_t)cdiv((long long)ac * 64, 256), (size_t)ntiles) + 8);
     tm.nlist_capacity = S;
   }
 

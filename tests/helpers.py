@@ -1,4 +1,6 @@
 """Shared test plumbing: build small systems on any Engine (oracle or HIP)."""
+import functools
+
 import numpy as np
 
 
@@ -324,3 +326,205 @@ def pair_matrix_spec(case, n=None, fixed=False, kind=None, kT=1.0, gamma=2.0, dt
     return dict(name="pair_matrix", n=n, box=[L] * 3, rc=rc, skin=skin, dt=dt, ids=np.arange(1, n + 1), types=types, pos=pos,
                 vel=W._maxwell(rng, n, kT, mass), mass=mass, state=np.zeros(n, np.int32), res_id=np.arange(1, n + 1, dtype=np.int32),
                 lj=lj, tables=tables, kT=kT, gamma=gamma, seed=case + 1, type_ids=type_ids)
+
+
+# ---- anisotropic boxes, empty regions and cell-count thresholds (tests/test_*_geometry.py) -------------------------------
+
+FILM_THICKNESS = 2.0          # film_z / film_x: band thickness in cell layers
+
+
+def _geometry_draw(nc, frac, fill, seed, rc, skin, dt, kT, band, bulk_v, spacing):
+    rng = np.random.default_rng(seed)
+    rl = rc + skin
+    if fill == "cluster_in_big_box":
+        L = np.array([108.0] * 3)                                # the headline box edge
+    else:
+        L = (np.asarray(nc, dtype=np.float64) + frac) * rl
+    m = np.maximum(np.floor(L / spacing), 1).astype(int)        # simple-cubic sites, spacing L / m >= `spacing` on every axis
+    a = L / m
+    if fill == "cluster_in_big_box":                             # (only the sites near the corner are ever needed)
+        g = [np.concatenate([np.arange(4), np.arange(m[d] - 4, m[d])]) for d in range(3)]
+    else:
+        g = [np.arange(m[d]) for d in range(3)]
+    idx = np.stack(np.meshgrid(*g, indexing="ij"), -1).reshape(-1, 3)
+    site = idx * a                                               # (a lattice plane on every face: the jitter puts particles on either side)
+    dc = site - L * np.rint(site / L)                            # minimum image to the corner (0, 0, 0)
+    rcorner = np.sqrt((dc * dc).sum(1))
+    if fill == "uniform":
+        keep = np.ones(len(site), bool)
+    elif fill == "corner_droplet":
+        keep = (rcorner < 3.5) | (rng.random(len(site)) < 0.10)
+    elif fill in ("film_z", "film_x"):
+        d = 2 if fill == "film_z" else 0
+        cell = L[d] / np.floor(L[d] / rl)
+        keep = np.mod(site[:, d] - band * cell, L[d]) < FILM_THICKNESS * cell
+    elif fill == "cluster_in_big_box":
+        keep = rcorner < 2.5
+    else:
+        raise ValueError(fill)
+    pos = site[keep] + rng.uniform(-0.05, 0.05, (int(keep.sum()), 3))
+    pos = np.mod(pos, L)
+    pos = np.where(pos >= L, 0.0, pos)
+    n = len(pos)
+    mass = np.ones(n)
+    v = rng.standard_normal((n, 3)) * np.sqrt(kT)
+    v -= v.mean(0)                                               # zero total momentum (unit masses)
+    if fill in ("film_z", "film_x"):
+        v[:, 2 if fill == "film_z" else 0] += bulk_v
+    return dict(name="geometry_" + fill, n=n, box=L.tolist(), rc=rc, skin=skin, dt=dt, ids=np.arange(1, n + 1),
+                types=np.zeros(n, np.int32), pos=pos, vel=v, mass=mass, state=np.zeros(n, np.int32),
+                res_id=np.arange(1, n + 1, dtype=np.int32), lj=[(0, 0, 1.0, 1.0, rc)], kT=kT, gamma=0.0, seed=seed,
+                rebuild_criterion=1, nc=[int(c) for c in np.floor(L / rl)], fill=fill)
+
+
+def geometry_spec(nc, frac, fill, seed, rc=2.0, skin=0.3, dt=0.004, kT=1.0, band=0.0, bulk_v=0.0, spacing=1.1, ranks=()):
+    """One LJ type on a jittered simple-cubic grid (spacing about `spacing`, jitter +-0.05: no overlaps) in a box of
+    (nc_d + frac) cells of edge rc + skin per axis: frac 0.5 puts every axis in the middle between two cell counts, 0.0 on
+    the threshold itself.  fill: "uniform"; "corner_droplet" (the sites within 3.5 of the corner (0, 0, 0) under minimum
+    image -- the droplet wraps on all three axes -- plus 10 % of the others as gas); "film_z" / "film_x" (a band
+    FILM_THICKNESS cell layers thick whose lower edge sits at `band` cell layers, wrapping across the periodic face when it
+    reaches it, with the bulk velocity `bulk_v` along its normal); "cluster_in_big_box" (about 60 sites around the corner
+    of a box of edge 108, nc and frac unused).  Maxwell velocities at kT with zero total momentum, NVE (gamma = 0), rebuilds
+    by true displacement.  ranks: slab counts P the spec must fit (slab_capacities).
+
+    The preconditions of the tests that use the spec are asserted HERE, and a draw that misses one is replaced by the draw
+    of seed + 1, so that no test has a reason to skip: the cell counts are the ones asked for, no pair lies within 1e-9 of
+    rc + skin (spec["min_gap"], spec["shell_pairs"]: brute_pairs), at most 7000 particles (pair_reference is all-pairs),
+    and on every rank of every P in `ranks` the real count and the fullest cell layer stay inside the slab capacities."""
+    for attempt in range(8):
+        spec = _geometry_draw(nc, frac, fill, seed + attempt, rc, skin, dt, kT, band, bulk_v, spacing)
+        if fill != "cluster_in_big_box":
+            assert spec["nc"] == [int(c) for c in np.floor(np.asarray(nc) + frac)], (spec["nc"], nc)      # (no seed can mend this one)
+        assert 2 <= spec["n"] <= 7000, spec["n"]
+        pairs, gap, shell = brute_pairs(spec)
+        ok = gap > 1e-9
+        for P in ranks:
+            for c in slab_capacities(spec, P):
+                ok = ok and c["n_real"] < c["cap"] - 2 * c["G"] and c["max_layer"] < c["G"] and spec["n"] < c["mcap"]
+        if ok:
+            spec.update(pairs=pairs, min_gap=gap, shell_pairs=shell, seed_used=seed + attempt)
+            return spec
+    raise AssertionError("no admissible draw for %r" % ((nc, frac, fill, seed),))
+
+
+def canonical_pairs(p):
+    """Id pairs as a sorted (m, 2) array, smaller id first."""
+    p = np.sort(np.asarray(p, dtype=np.int64).reshape(-1, 2), 1)
+    return p[np.lexsort((p[:, 1], p[:, 0]))]
+
+
+def brute_pairs(spec, shell=2e-6):
+    """(sorted id pairs with minimum-image distance below rc + skin, smallest |r - (rc + skin)| over all pairs, set of the id
+    pairs within `shell` of rc + skin -- the shell of force_error_without_cutoff_flips).  All pairs by numpy: no cells, so it
+    shares no threshold with the engine or the oracle.  Positions are folded first, as both do."""
+    L = np.asarray(spec["box"], dtype=np.float64)
+    x = np.asarray(spec["pos"], dtype=np.float64)
+    x = x - np.floor(x / L) * L
+    ids = np.asarray(spec["ids"], dtype=np.int64)
+    rl = spec["rc"] + spec["skin"]
+    n = len(x)
+    out, near, gap = [], [], np.inf
+    for i0 in range(0, n, 256):
+        d = x[i0:i0 + 256, None, :] - x[None, :, :]
+        d -= L * np.rint(d / L)
+        r = np.sqrt((d * d).sum(2))
+        r[np.arange(len(r)), i0 + np.arange(len(r))] = np.inf
+        gap = min(gap, np.abs(r - rl).min())
+        ii, jj = np.nonzero(r < rl)
+        m = i0 + ii < jj
+        out.append(np.stack([ids[i0 + ii[m]], ids[jj[m]]], 1))
+        ii, jj = np.nonzero(np.abs(r - rl) < shell)
+        near += [(int(min(a, b)), int(max(a, b))) for a, b in zip(ids[i0 + ii], ids[jj])]
+    return canonical_pairs(np.concatenate(out)), float(gap), set(near)
+
+
+def slab_capacities(spec, P):
+    """Per rank of a P-slab decomposition: the capacities the engine reserves and what the spec puts there at step 0.
+    Restates chem_api.hip setup_box (nzg, base, rem, ncz, z0) and upload_particles (per_layer, G, mcap, cap, the layer gz of
+    a particle); n_real = particles the rank owns, max_layer = its fullest cell layer (a ghost layer of its neighbour)."""
+    L = np.asarray(spec["box"], dtype=np.float64)
+    nzg = int(np.floor(L[2] / (spec["rc"] + spec["skin"])))
+    base, rem = nzg // P, nzg % P
+    z = np.asarray(spec["pos"], dtype=np.float64)[:, 2]
+    z = z - np.floor(z / L[2]) * L[2]
+    layer = np.bincount(np.clip(np.floor(z * nzg / L[2]).astype(int), 0, nzg - 1), minlength=nzg)
+    per_layer = spec["n"] / nzg
+    out = []
+    for rk in range(P):
+        ncz = base + (1 if rk < rem else 0)
+        z0 = rk * base + min(rk, rem)
+        G = int(per_layer * 1.5) + 1024
+        mcap = max(4096, int(per_layer / 4))
+        cap = 2 * G + int(per_layer * ncz * 1.2) + 2 * mcap + 4096
+        out.append(dict(z0=z0, ncz=ncz, G=G, mcap=mcap, cap=cap, n_real=int(layer[z0:z0 + ncz].sum()),
+                        max_layer=int(layer[z0:z0 + ncz].max())))
+    return out
+
+
+def list_difference(pairs_test, spec):
+    """Pairs that only one of (the engine's list, brute_pairs) holds, as a set of id pairs."""
+    a = {tuple(p) for p in canonical_pairs(pairs_test).tolist()}
+    b = {tuple(p) for p in spec["pairs"].tolist()}
+    return a ^ b
+
+
+# The cases of tests/test_gpu_geometry.py; tests/test_oracle_geometry.py checks every one of them against numpy on the CPU.
+LADDER = dict(brute=[(2, 7, 7), (7, 7, 2)],
+              cells=[(3, 3, 3), (3, 5, 9), (9, 5, 3), (4, 4, 12), (3, 40, 3)],
+              tiles=[(5, 5, 5), (5, 6, 7), (7, 5, 5), (12, 5, 5), (5, 5, 23)])
+LADDER_BOXES = [nc for path in ("brute", "cells", "tiles") for nc in LADDER[path]]
+LADDER_STEPS = 300
+SLAB_BOX = (5, 5, 23)
+# name: (fill, band, bulk velocity, kT, slab counts).  (5, 5, 23): two slabs own the layers 0-11 / 12-22, three 0-7 / 8-15 / 16-22.
+SLAB_CASES = {
+    "self_film_z": ("film_z", 22.0, 2.0, 1.0, (1,)),        # across the periodic z face, a single slab being its own neighbour
+    "self_film_x": ("film_x", 4.0, 2.0, 1.0, (1,)),         # across the periodic x face: empty columns in every z layer
+    "self_droplet": ("corner_droplet", 0.0, 0.0, 1.0, (1,)),
+    # the film ends 0.2 layers below the first rank boundary: every other rank owns nothing at step 0; 7 * 1.2 time units
+    # carry it 3.6 layers up, so that rank 1 receives its first particles by migration and rank 0 is emptied
+    "empty_rank_P2": ("film_z", 9.8, 7.0, 0.3, (2,)),
+    "empty_rank_P3": ("film_z", 5.8, 7.0, 0.3, (3,)),
+    # the film straddles the periodic z face and leaves rank P-1 for rank 0 with an image increment
+    "face_P2": ("film_z", 22.0, 7.0, 0.3, (2,)),
+    "face_P3": ("film_z", 22.0, 7.0, 0.3, (3,)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _ladder_spec(nc, frac, fill):
+    return geometry_spec(nc, frac, fill, seed=7000 + 10 * LADDER_BOXES.index(nc) + int(2 * frac))
+
+
+def ladder_spec(nc, frac, fill):
+    return dict(_ladder_spec(tuple(nc), frac, fill))
+
+
+@functools.lru_cache(maxsize=None)
+def _slab_spec(name):
+    fill, band, bulk_v, kT, ranks = SLAB_CASES[name]
+    return geometry_spec(SLAB_BOX, 0.5, fill, seed=7500 + sorted(SLAB_CASES).index(name), kT=kT, band=band, bulk_v=bulk_v, ranks=ranks)
+
+
+def slab_spec(name):
+    return dict(_slab_spec(name))
+
+
+@functools.lru_cache(maxsize=None)
+def _cluster_spec():
+    return geometry_spec(None, 0.0, "cluster_in_big_box", seed=7600, rc=2.5, skin=0.3)
+
+
+def cluster_spec():
+    return dict(_cluster_spec())
+
+
+@functools.lru_cache(maxsize=None)
+def _geometry_reference(key):
+    kind, args = key
+    spec = {"ladder": _ladder_spec, "slab": _slab_spec, "cluster": lambda: _cluster_spec()}[kind](*args)
+    return pair_reference(spec)
+
+
+def geometry_reference(kind, *args):
+    """pair_reference of a ladder / slab / cluster spec: (forces, epot_lj, epot_tab, virial_nb), computed once per session."""
+    return _geometry_reference((kind, tuple(args)))

@@ -12,7 +12,7 @@ import pytest
 
 from chemlab_amd import workloads as W
 from conftest import rel_err
-from helpers import force_error_without_cutoff_flips, sorted_events, total_epot
+from helpers import brute_pairs, force_error_without_cutoff_flips, geometry_spec, list_difference, sorted_events, total_epot
 
 pytestmark = pytest.mark.gpu
 
@@ -531,24 +531,60 @@ def test_driver_on_gpu_matches_driver_on_oracle(tmp_path, monkeypatch, oracle_mo
 
 
 # ---- edge cases and size-independent properties ---------------------------------------------------
-def test_positions_outside_the_box_and_on_its_faces_are_folded(make_gpu, make_oracle):
-    """Inputs the readers can produce: coordinates at exactly 0 and L, negative, several box lengths away."""
-    spec = W.lj_melt(n=2048, seed=9, jitter=0.05)
+@pytest.mark.parametrize("prec", [64, 32])
+@pytest.mark.parametrize("shape", ["cubic", "aniso"])
+def test_positions_outside_the_box_and_on_its_faces_are_folded(make_gpu, make_oracle, shape, prec):
+    """Inputs the readers can produce: coordinates at exactly 0 and L, negative, several box lengths away.
+    aniso: box edges 1 : 3 : 10 (3, 10 and 35 cells; a droplet on the corner plus gas), so that the per-axis scales of the
+    fp32 position codec differ by a factor of ten."""
+    if shape == "cubic":
+        spec = W.lj_melt(n=2048, seed=9, jitter=0.05)
+    else:
+        spec = geometry_spec((3, 10, 34.5), 0.5, "corner_droplet", seed=7700)
     L = spec["box"][0]
+    Lv = np.asarray(spec["box"], dtype=np.float64)
     pos = spec["pos"].copy()
     # rigid shifts (no overlaps are created) that put particle 3 exactly on x = 0, particle 4 on y = L and
     # particle 5 on z = -0.0; everything pushed past a face by that must be folded back by the engine
-    pos[:, 0] -= pos[3, 0]; pos[:, 1] += L - pos[4, 1]; pos[:, 2] -= pos[5, 2]
-    pos[3, 0] = 0.0; pos[4, 1] = L; pos[5, 2] = -0.0
-    pos[0] += [L, 0, 0]; pos[1] -= [0, 2 * L, 0]; pos[2] += [3 * L, -L, 5 * L]
+    pos[:, 0] -= pos[3, 0]; pos[:, 1] += Lv[1] - pos[4, 1]; pos[:, 2] -= pos[5, 2]
+    pos[3, 0] = 0.0; pos[4, 1] = Lv[1]; pos[5, 2] = -0.0
+    pos[0] += [L, 0, 0]; pos[1] -= [0, 2 * Lv[1], 0]; pos[2] += [3 * L, -Lv[1], 5 * Lv[2]]
+    # and the particle of particle 3's lattice plane that is nearest to it goes 1e-12 below the face x = 0: less than half a
+    # quantum of the fixed-point codec, L / 2^32 = 2e-9 or more (it moves by the jitter at most: no overlap either)
+    plane = [k for k in range(6, len(pos)) if abs(pos[k, 0] - np.rint(pos[k, 0] / L) * L) < 0.11]
+    below = min(plane, key=lambda k: np.abs(pos[k] - pos[3]).sum())
+    pos[below, 0] = np.floor(pos[below, 0] / L + 0.5) * L - 1e-12
     spec["pos"] = pos
-    g, o, _ = both(make_gpu, make_oracle, spec, 64, thermostat=False)
+    g, o, _ = both(make_gpu, make_oracle, spec, prec, thermostat=False)
     g.run(0); o.run(0)
-    assert np.array_equal(g.get_verlet_pairs(), o.get_verlet_pairs())
-    assert rel_err(g.get_state("FORCE"), o.get_state("FORCE")) < 1e-10
+    if prec == 64:
+        assert np.array_equal(g.get_verlet_pairs(), o.get_verlet_pairs())
+        assert rel_err(g.get_state("FORCE"), o.get_state("FORCE")) < 1e-10
+        g.run(20); o.run(20)
+        assert np.array_equal(g.get_state("IMAGE"), o.get_state("IMAGE"))
+        assert rel_err(g.get_state("POS_UNFOLDED"), o.get_state("POS_UNFOLDED")) < 1e-9
+        return
+    # fp32 build: int32 fixed point, q = rint((x - L/2) / (L / 2^31)), folded and image-counted on the host
+    quantum = Lv / 2.0 ** 31
+    xg, ug, ig = g.get_state("POS"), g.get_state("POS_UNFOLDED"), g.get_state("IMAGE")
+    assert (xg >= 0).all() and (xg < Lv).all()
+    bound = 0.5 * quantum + np.spacing(np.abs(pos))
+    print("fold %s fp32: worst |unfolded - input| / bound %.3f" % (shape, (np.abs(ug - pos) / bound).max()))
+    assert (np.abs(ug - pos) <= bound).all(), (np.abs(ug - pos) / bound).max()
+    want = np.floor(pos / Lv).astype(np.int64)
+    just_below = (want + 1) * Lv - pos <= 0.5 * quantum          # within half a quantum below a face: image + 1 at position 0 is as good
+    assert (ig[~just_below] == want[~just_below]).all()
+    assert ((ig[just_below] == want[just_below]) | ((ig[just_below] == want[just_below] + 1) & (xg[just_below] == 0.0))).all()
+    assert just_below[below, 0] and just_below.sum() >= 1
+    pairs, gap, shell_pairs = brute_pairs(spec)
+    assert gap > 1e-9
+    diff = list_difference(g.get_verlet_pairs(), dict(spec, pairs=pairs))
+    assert diff <= shell_pairs, sorted(diff - shell_pairs)[:5]
     g.run(20); o.run(20)
-    assert np.array_equal(g.get_state("IMAGE"), o.get_state("IMAGE"))
-    assert rel_err(g.get_state("POS_UNFOLDED"), o.get_state("POS_UNFOLDED")) < 1e-9
+    # (against the box edge, not the largest unfolded coordinate: particle 2 sits five boxes out, and that would forgive a whole-image slip)
+    err = (np.abs(g.get_state("POS_UNFOLDED") - o.get_state("POS_UNFOLDED")) / Lv).max()
+    print("fold %s fp32: POS_UNFOLDED / box edge after 20 steps %.2e" % (shape, err))
+    assert err < 2e-4, err
 
 
 @pytest.mark.parametrize("prec", [64, 32])
