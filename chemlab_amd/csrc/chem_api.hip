@@ -18,6 +18,7 @@
 #include <tuple>
 
 #include "chem_comm.hpp"
+#include "chem_geom_host.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
 #include "chem_tab_host.hpp"
@@ -72,6 +73,7 @@ template <typename T> struct DBuf {
 };
 
 static const bool g_trace = getenv("CHEM_TRACE") != nullptr;
+static const bool g_dd_nopoll = getenv("CHEM_DD_NOPOLL") != nullptr;   // decomposed path: the host reads the decision with a blocking copy instead of polling
 struct Trace {
   double t; const char* what;
   Trace(const char* w) : t(now_s()), what(w) {}
@@ -170,7 +172,7 @@ struct Ctx {
   int opt_ablate = 0;        // diagnostic only: 1 = pair kernel stops after staging, 2 = skips staging
   int opt_skip_inactive = 1; // force list omits type pairs without a potential
   int opt_bonds_inline = 1;  // harmonic 2-body bonds evaluated by the force kernel from its staged image (when the host can prove it applicable)
-  int opt_tile_split = 0;    // narrow tiles at the end of every tile row (pick_tile_split): 0 off, nb * 10 + w
+  int opt_tile_split = 0;    // narrow tiles at the end of every tile row (chem_geom_host.hpp plan_tiles): 0 off, nb * 10 + w
   int opt_bucket_cap = 0;    // testing: bucket rows of the fused rebuild narrower than 64 (provokes the mid-run overflow recovery)
   int64_t halts_recovered = 0;
   // slab domain decomposition (chem_comm_init)
@@ -202,9 +204,11 @@ template <typename R> struct CtxT : Ctx {
   bool cubic_tab = false;   // a type pair of kind 3 exists: the general-mode force kernels are launched in their CUBIC instantiation
   bool state_mirror_stale = false;   // top.state lags the device after reaction steps
   int tile_cap = 0;       // LDS slots of one staged tile (dynamic LDS)
-  size_t tile_lds_bytes() const { return (size_t)(tile_cap + 5) * sizeof(V4) + 16; }
+  static size_t tile_lds_bytes(int cap_) { return (size_t)(cap_ + 5) * sizeof(V4) + 16; }
+  size_t tile_lds_bytes() const { return tile_lds_bytes(tile_cap); }
   // force kernel: fp64 stages 24-byte slots + type bytes (two workgroups per CU instead of one)
-  size_t pair_lds_bytes() const { return sizeof(R) == 8 ? (size_t)(tile_cap + 5) * 25 + 64 : tile_lds_bytes(); }
+  static size_t pair_lds_bytes(int cap_) { return sizeof(R) == 8 ? (size_t)(cap_ + 5) * 25 + 64 : tile_lds_bytes(cap_); }
+  size_t pair_lds_bytes() const { return pair_lds_bytes(tile_cap); }
   // the list build has its own layout of the same block (fp32: SoA groups + type masks + slice boundaries)
   // (fp64 builds use the fp32 list image too -- the force list may be a superset -- and need their own 32-byte-per-slot
   //  image only where the exact int32 rows are built)
@@ -212,11 +216,13 @@ template <typename R> struct CtxT : Ctx {
   // reaction scan: the staged image + 4 bytes per slot of role words (k_react_roles)
   size_t scan_lds_bytes() const { return scan_roles_offset(tile_cap, sizeof(V4)) + (size_t)(tile_cap + 1) * sizeof(unsigned int); }
   bool scan_roles_staged() const { return scan_lds_bytes() <= kTileLdsBudget; }      // (otherwise the scan reads the role words from global memory)
-  size_t tile_lds_need() const { return std::max(std::max(tile_lds_bytes(), pair_lds_bytes()), list_lds_need()); }
-  size_t list_lds_need(bool exact_rows = true) const {
-    const size_t lb = list_lds_bytes(tile_cap, kMaxTypes);
-    return (sizeof(R) == 4 || exact_rows) ? std::max(tile_lds_bytes(), lb) : lb;
+  // what a tile of cap_ slots asks of the LDS, over every kernel that stages one (asked before tile_cap is set or grown)
+  static size_t tile_lds_need(int cap_) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_)), list_lds_need(cap_, true)); }
+  static size_t list_lds_need(int cap_, bool exact_rows) {
+    const size_t lb = list_lds_bytes(cap_, kMaxTypes);
+    return (sizeof(R) == 4 || exact_rows) ? std::max(tile_lds_bytes(cap_), lb) : lb;
   }
+  size_t list_lds_need(bool exact_rows = true) const { return list_lds_need(tile_cap, exact_rows); }
   // ---- position codec on the host (md_kernels.hpp "position codec"): fp32 build = int32 fixed point, fp64 build = reals
   static constexpr bool kFixed = sizeof(R) == 4;
   double q_scale(int d) const { return L[d] / 2147483648.0; }
@@ -373,28 +379,22 @@ template <typename R> struct CtxT : Ctx {
 
   // ---- uploads ------------------------------------------------------------------------
   void setup_box() {
-    const double rl = rc + skin_eff();
-    int nc[3]; bool cells = true;
-    for (int d = 0; d < 3; ++d) { nc[d] = (int)std::floor(L[d] / rl); if (nc[d] < 3) cells = false; }
+    const CellGrid cg = cell_grid(L, rc + skin_eff());
+    const int* nc = cg.nc; const bool cells = cg.cells;
     for (int d = 0; d < 3; ++d) {
       box.L[d] = (R)L[d]; box.invL[d] = (R)(1.0 / L[d]);
-      box.nc[d] = cells ? nc[d] : 0;
+      box.nc[d] = nc[d];
       box.cell_inv[d] = (R)((cells ? nc[d] : 1) / L[d]);
       boxd.L[d] = L[d]; boxd.invL[d] = 1.0 / L[d];
       box.qs[d] = boxd.qs[d] = q_scale(d); box.qh[d] = boxd.qh[d] = 0.5 * L[d];
       box.qsf[d] = (R)q_scale(d); box.qinvf[d] = (R)(1.0 / q_scale(d));
     }
     box.ncell = cells ? nc[0] * nc[1] * nc[2] : 1;
-    box.xs_nb = 1 << 20; box.xs_w = 1;      // (all tiles HX wide until pick_tile_split says otherwise)
+    box.xs_nb = 1 << 20; box.xs_w = 1;      // (all tiles HX wide until the tile plan says otherwise)
     box.zghost = 0; box.z0g = 0; box.nzg = cells ? nc[2] : 1; box.shz_lo = 0; box.shz_hi = 0;
     if (dd_on) {
-      if (!cells) throw ChemError(CHEM_EINVAL, "domain decomposition needs at least 3 cells of edge rc+skin per axis");
-      nzg = nc[2];
-      const int base = nzg / P, rem = nzg % P;
-      if (base < 2) throw ChemError(CHEM_EINVAL, "domain decomposition: fewer than 2 cell layers per rank along z");
-      ncz = base + (rk < rem ? 1 : 0);
-      z0 = rk * base + std::min(rk, rem);
-      lower = (rk + P - 1) % P; upper = (rk + 1) % P;
+      const SlabLayers sl = slab_layers(cg, P, rk);
+      nzg = sl.nzg; ncz = sl.ncz; z0 = sl.z0; lower = sl.lower; upper = sl.upper;
       box.zghost = 1; box.z0g = z0; box.nzg = nzg; box.nc[2] = ncz + 2;
       box.ncell = nc[0] * nc[1] * (ncz + 2);
       box.shz_lo = enc_shift(z0 == 0 ? -1.0 : 0.0, 2);
@@ -402,41 +402,16 @@ template <typename R> struct CtxT : Ctx {
     }
   }
 
-  // cells, neighbour-list capacity and everything else that depends on box/cutoff/skin
-  // Automatic list skin (measured on the 1M-particle melt, profiles/round3_list_skin.txt): two cells fewer per axis than the
-  // workload's skin would give, i.e. ~0.2 sigma more skin at rc + skin = 2.8 -- the lists live ~60 % longer for ~20 % more
-  // entries -- and always the whole cell edge (the slack between L / floor(L / rl) and rl is free skin).
   double pick_list_skin() const {
-    if (opt_list_skin == 0.0 || opt_criterion != 0 || !opt_tiles || (!dd_on && !opt_fused)) return 0.0;
-    const double rl = rc + skin;
-    double edge = 1e300;
-    for (int d = 0; d < 3; ++d) {
-      int nc = (int)std::floor(L[d] / (opt_list_skin > 0 ? rc + opt_list_skin : rl));
-      if (opt_list_skin < 0) { if ((dd_on ? nglob : n) < 100000) return 0.0; nc -= 2; }
-      if (nc < 5) return 0.0;
-      if (dd_on && d == 2 && nc / P < 2) return 0.0;      // (a slab needs two cell layers)
-      edge = std::min(edge, L[d] / nc);
-    }
-    const double s = edge * (1.0 - 1e-9) - rc;
-    return s > skin ? s : 0.0;
+    return chem::pick_list_skin(L, rc, skin, opt_list_skin, opt_criterion, opt_tiles != 0, opt_fused != 0, dd_on, P, dd_on ? nglob : n);
   }
-  // Narrow tiles (Box::xs_nb / xs_w, md_kernels.hpp tile_xrange): option tile_split = nb * 10 + w, 0 = off (default).
-  // Built to fill the last round of the force launch (1728 equal one-shot workgroups on 768 resident slots: 2.25 rounds of
-  // work) with shorter jobs, and measured: no gain at any mix -- C5: 7811 steps/s unsplit, 7549 with 10 wide + 6 one-cell
-  // tiles per row, 7721 with 11 + 3; 125k particles: 22980 unsplit, 20134 all one cell wide (profiles/round3_tile_split.txt).
-  // The workgroups of the last round run faster on their emptier CUs than the model assumed; the extra staging is not paid back.
   void debug_tiles(int32_t* out) override {
     if (geom_dirty) setup_geometry();
     const int ntx = use_tiles ? tile_ntx(box.nc[0], box.xs_nb, box.xs_w) : 0;
     out[0] = ntiles; out[1] = box.nc[0]; out[2] = use_tiles ? tile_nbx(box.nc[0], box.xs_nb) : 0; out[3] = box.xs_w;
     out[4] = ntx ? ntiles / ntx : 0; out[5] = tile_cap;
   }
-  void pick_tile_split() {
-    box.xs_nb = 1 << 20; box.xs_w = 1;
-    if (!use_tiles || opt_tile_split <= 0 || HX < 2) return;
-    const int nb = opt_tile_split / 10, w = std::max(1, std::min(opt_tile_split % 10, HX));
-    if (nb * HX < box.nc[0]) { box.xs_nb = nb; box.xs_w = w; }
-  }
+  // cells, neighbour-list capacity and everything else that depends on box/cutoff/skin (the rules: chem_geom_host.hpp)
   void setup_geometry() {
     skin_list = pick_list_skin();
     setup_geometry_once();
@@ -446,31 +421,11 @@ template <typename R> struct CtxT : Ctx {
     setup_box();
     cell_cnt.alloc(box.ncell + 1); cell_start.alloc(box.ncell + 1); cell_sub.alloc(box.ncell + 2);
     HIPCHK(hipMemsetAsync(cell_cnt.p, 0, sizeof(int) * (box.ncell + 1), stream));
-    const double vol = L[0] * L[1] * L[2], rl = rc + skin_eff();
-    const double expect = 4.0 / 3.0 * M_PI * rl * rl * rl * (dd_on ? nglob : n) / vol;
-    int ncap = nl_capacity_user > 0 ? nl_capacity_user : (int)(expect * 1.6 + 48);
-    ncap = std::min(ncap, std::max((dd_on ? nglob : n) - 1, 1));
-    S = (ncap + 15) / 16 * 16;
-    use_tiles = opt_tiles && box.nc[0] >= HX + 2 && box.nc[1] >= HY + 2 && (dd_on ? true : box.nc[2] >= HZ + 2);
-    if (dd_on && !(box.nc[0] >= HX + 2 && box.nc[1] >= HY + 2)) throw ChemError(CHEM_EINVAL, "domain decomposition needs >= 5 cells along x and y");
-    // (the per-cell kernels know nothing of ghost layers: with tiles=0 a slab used to run on and return wrong forces -- found by
-    //  tests/test_gpu_sweep.py case 100)
-    if (dd_on && !use_tiles) throw ChemError(CHEM_EINVAL, "domain decomposition needs the LDS-staged tiles: option tiles=0 is a single-domain switch");
-    if (use_tiles) {
-      // LDS capacity from the mean stencil occupancy (+12 % for density fluctuations), in 256-slot steps
-      const double per_cell = dd_on ? (double)nglob / ((double)box.nc[0] * box.nc[1] * nzg) : (double)n / box.ncell;
-      const int need = (int)(SX * SY * SZ * per_cell * 1.12) + 64;
-      tile_cap = std::max(1024, (need + 255) / 256 * 256);
-      // every kernel that stages a tile must fit: the force kernel's image AND the list build's (SoA groups + type masks +
-      // slice boundaries: ~22 B per slot against 16), next to the static __shared__ of k_rebuild_fused / k_nlist_tiles
-      if (tile_lds_need() > kTileLdsBudget) {   // cells too crowded: per-cell kernels
-        if (dd_on) throw ChemError(CHEM_ENOSPC, "domain decomposition needs the LDS-staged tiles, and a stencil of this density does not fit the LDS");
-        use_tiles = false;
-      }
-      else set_tile_lds_attr();
-    }
-    pick_tile_split();
-    ntiles = use_tiles ? tile_ntx(box.nc[0], box.xs_nb, box.xs_w) * ((box.nc[1] + HY - 1) / HY) * (((dd_on ? ncz : box.nc[2]) + HZ - 1) / HZ) : 0;
+    S = row_stride(L, rc + skin_eff(), dd_on ? nglob : n, nl_capacity_user);
+    const TilePlan tp = plan_tiles(box.nc[0], box.nc[1], dd_on ? ncz : box.nc[2], dd_on ? nzg : box.nc[2], dd_on ? nglob : n, dd_on, opt_tiles != 0,
+                                   opt_tile_split, [](int c) { return tile_lds_need(c); }, kTileLdsBudget);
+    use_tiles = tp.use_tiles; box.xs_nb = tp.xs_nb; box.xs_w = tp.xs_w; ntiles = tp.ntiles;
+    if (tp.tile_cap) { tile_cap = tp.tile_cap; if (use_tiles) set_tile_lds_attr(); }      // (a grid without tiles leaves the last capacity as it was)
     alloc_lists();
     setup_fused();
     setup_tile_order();
@@ -502,10 +457,9 @@ template <typename R> struct CtxT : Ctx {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, reinterpret_cast<const void*>(&k_rebuild_fused<R, 512, true>), 512, list_lds_need(true)) != hipSuccess || per_cu_d < 1) return;
     fused_grid_diag = std::min(std::min(per_cu_d * prop.multiProcessorCount, 1024) / 8 * 8, fused_grid);
     if (fused_grid_diag < 8) return;
-    auto shift_for = [&](int nitem, int lo, int maxseg) { int sh = lo; while (((nitem + (1 << sh) - 1) >> sh) > maxseg) ++sh; return sh; };
     // cell segments: 64 cells (the prefix inside a segment is one wave reduction in the sort phase), more when that
     // would give more than 1024 segments; tile segments: <= 1024 of them
-    seg_shift = shift_for(box.ncell, 6, 1024); tseg_shift = shift_for(ntiles, 0, 1024);
+    seg_shift = segment_shift(box.ncell, 6, 1024); tseg_shift = segment_shift(ntiles, 0, 1024);
     cell_loc.alloc(box.ncell + 1); seg_tot.alloc(1024); tile_n.alloc(ntiles + 1); tile_loc.alloc(ntiles + 1); tseg_tot.alloc(1024);
     // bucket rows of the binning pass: 64 members per cell = what one wave sorts (the LDS tiles already require a mean
     // cell occupancy far below that); a fuller cell raises ctl->bucket_overflow and the unfused chain takes over
@@ -519,26 +473,11 @@ template <typename R> struct CtxT : Ctx {
   }
   DBuf<int> tile_pos, tile_ord;
   void setup_tile_order() {
-    if (!use_tiles || dd_on || ntiles < 8) { tile_pos.free(); tile_ord.free(); return; }
-    const int ntx = tile_ntx(box.nc[0], box.xs_nb, box.xs_w), nty = (box.nc[1] + HY - 1) / HY;
-    auto home_cells = [&](int tile) {
-      const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
-      int cx0, hx;
-      tile_xrange(tx, box.nc[0], box.xs_nb, box.xs_w, cx0, hx);
-      return hx * std::min(HY, box.nc[1] - ty * HY) * std::min(HZ, box.nc[2] - tz * HZ);
-    };
-    std::vector<int> ord(ntiles), pos(ntiles);
-    const int q = ntiles >> 3, r = ntiles & 7;
-    for (int x = 0, off = 0; x < 8; ++x) {      // the contiguous ranges xcd_remap hands to the XCDs
-      const int cnt = q + (x < r ? 1 : 0);
-      for (int k = 0; k < cnt; ++k) ord[off + k] = off + k;
-      std::stable_sort(ord.begin() + off, ord.begin() + off + cnt, [&](int a_, int b_) { return home_cells(a_) > home_cells(b_); });
-      for (int k = 0; k < cnt; ++k) pos[ord[off + k]] = off + k;
-      off += cnt;
-    }
+    TileOrder o = use_tiles && !dd_on ? tile_order(box.nc, box.xs_nb, box.xs_w, ntiles) : TileOrder{};
+    if (o.ord.empty()) { tile_pos.free(); tile_ord.free(); return; }
     // (two copies each: the rebuild kernel double-buffers them by the parity of its rebuild count and rewrites them from the home counts)
-    pos.insert(pos.end(), pos.begin(), pos.begin() + ntiles); ord.insert(ord.end(), ord.begin(), ord.begin() + ntiles);
-    tile_pos.upload(pos, stream); tile_ord.upload(ord, stream);
+    for (std::vector<int>* v : {&o.pos, &o.ord}) { v->resize(2 * (size_t)ntiles); std::copy_n(v->begin(), ntiles, v->begin() + ntiles); }
+    tile_pos.upload(o.pos, stream); tile_ord.upload(o.ord, stream);
   }
   void launch_rebuild_fused() {
     FusedArgs<R> a{};
@@ -601,19 +540,14 @@ template <typename R> struct CtxT : Ctx {
     if (dd_on) {
       skin_list = pick_list_skin();   // (the slab bounds below must be those of the geometry set up afterwards)
       setup_box();   // slab bounds (z0, ncz, nzg)
-      // capacities: ghost layers are one cell layer each; reals fluctuate with the slab occupancy
-      const double per_layer = (double)nglob / nzg;
-      G = (int)(per_layer * 1.5) + 1024;
-      mcap = std::max(4096, (int)(per_layer / 4));
-      cap = 2 * G + (int)(per_layer * ncz * 1.2) + 2 * mcap + 4096;
+      const SlabCaps sc = slab_capacities(nglob, nzg, ncz);
+      G = sc.G; mcap = sc.mcap; cap = sc.cap;
       hx.assign(cap, V4{}); hv.assign(cap, V4{}); ht.assign(cap, 0); hi.assign(cap, make_int4(0, 0, 0, 0));
       int k = G;
       for (int t = 0; t < nglob; ++t) {
-        double z = pos0[3 * t + 2];
-        const double s = std::floor(z / L[2]);
-        z -= s * L[2]; if (z >= L[2]) z -= L[2];
-        int gz = (int)std::floor(z * nzg / L[2]); gz = std::min(std::max(gz, 0), nzg - 1);
-        if (gz < z0 || gz >= z0 + ncz) continue;
+        const SlabCoord zc = slab_layer_of(pos0[3 * t + 2], L[2], nzg);
+        const double z = zc.z, s = zc.s;
+        if (zc.layer < z0 || zc.layer >= z0 + ncz) continue;
         if (k >= cap - G) throw ChemError(CHEM_ENOSPC, "domain decomposition: slab holds more particles than the allocated capacity");
         // (x and y are folded by the first binning pass in the fp64 build; the fixed-point encoding wants them in the box now)
         const double fx_ = kFixed ? fold_coord(pos0[3 * t], L[0]) : pos0[3 * t], fy_ = kFixed ? fold_coord(pos0[3 * t + 1], L[1]) : pos0[3 * t + 1];
@@ -997,15 +931,26 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL(k_nlist_brute<R>, dim3(cdiv(n, 4)), dim3(256), 0, stream, n, x4.p, tag.p, box, rl2, excl_start.p,
                          excl_list.p, has_excl, nlist.p, nn.p, S, c);
   }
-  void launch_rebuild_chain() {   // single domain
-    const int nb = std::min(cdiv(n, 256), 2048);
+  // the binned particles [base, base + count) into cell order, the sorted copies of the cells [c_first, c_last) back in place
+  void launch_cell_sort(int base, int count, int c_first, int c_last) {
     DevCtl* c = ctl.p;
-    launch_sort_chain(0, n);
-    hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, stream, box.ncell, 0, cell_cnt.p, cell_start.p, c);
-    hipLaunchKernelGGL(k_place, dim3(nb), dim3(256), 0, stream, 0, n, cell_of.p, slot_of.p, cell_start.p, perm.p, c);
+    const int nb = std::max(1, std::min(cdiv(count, 256), 2048));
+    hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, stream, box.ncell, base, cell_cnt.p, cell_start.p, c);
+    hipLaunchKernelGGL(k_place, dim3(nb), dim3(256), 0, stream, base, count, cell_of.p, slot_of.p, cell_start.p, perm.p, c);
     hipLaunchKernelGGL(k_sort_gather<R>, dim3(std::min(cdiv(box.ncell, 4), 2048)), dim3(256), 0, stream, box.ncell, cell_start.p, perm.p,
                        x4.p, v4.p, tag.p, img4.p, x4o.p, v4o.p, tago.p, img4o.p, c, box, cell_sub.p);
-    hipLaunchKernelGGL(k_copyback<R>, dim3(nb), dim3(256), 0, stream, cell_start.p, 0, box.ncell, x4o.p, v4o.p, tago.p, img4o.p, x4.p, v4.p, tag.p, img4.p, rtag.p, x0.p, c);
+    if (dd_on) {
+      // what a slab clears before the sorted copies come back: the tag maps, and the sub-bin words of the two ghost layers
+      // (filled by the neighbours' particles afterwards: no sub-bin information for their cells)
+      const int nxy = box.nc[0] * box.nc[1];
+      if (gtag.n < (size_t)nglob) gtag.alloc(nglob);
+      hipLaunchKernelGGL(k_dd_clear, dim3(cdiv(std::max(nglob, nxy), 256)), dim3(256), 0, stream, rtag.p, gtag.p, nglob, cell_sub.p, cell_sub.p + (size_t)(ncz + 1) * nxy, nxy);
+    }
+    hipLaunchKernelGGL(k_copyback<R>, dim3(nb), dim3(256), 0, stream, cell_start.p, c_first, c_last, x4o.p, v4o.p, tago.p, img4o.p, x4.p, v4.p, tag.p, img4.p, rtag.p, x0.p, c);
+  }
+  void launch_rebuild_chain() {   // single domain
+    launch_sort_chain(0, n);
+    launch_cell_sort(0, n, 0, box.ncell);
     launch_list_chain();
   }
 
@@ -1079,17 +1024,8 @@ template <typename R> struct CtxT : Ctx {
     const int npend = n + from_lo + from_up;
     HIPCHK(hipMemsetAsync(mig[0].p, 0, 16, stream)); HIPCHK(hipMemsetAsync(mig[1].p, 0, 16, stream));
     if (from_lo + from_up) launch_sort_chain(G + n, from_lo + from_up);
-    // 4. sort the reals into [G, G + n_new)
-    DevCtl* c = ctl.p;
-    const int nb = std::max(1, std::min(cdiv(npend, 256), 2048));
-    hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, stream, box.ncell, G, cell_cnt.p, cell_start.p, c);
-    hipLaunchKernelGGL(k_place, dim3(nb), dim3(256), 0, stream, G, npend, cell_of.p, slot_of.p, cell_start.p, perm.p, c);
-    hipLaunchKernelGGL(k_sort_gather<R>, dim3(std::min(cdiv(box.ncell, 4), 2048)), dim3(256), 0, stream, box.ncell, cell_start.p, perm.p,
-                       x4.p, v4.p, tag.p, img4.p, x4o.p, v4o.p, tago.p, img4o.p, c, box, cell_sub.p);
-    // the ghost layers are filled by the neighbours' particles afterwards: no sub-bin information for their cells
-    if (gtag.n < (size_t)nglob) gtag.alloc(nglob);
-    hipLaunchKernelGGL(k_dd_clear, dim3(cdiv(std::max(nglob, nxy), 256)), dim3(256), 0, stream, rtag.p, gtag.p, nglob, cell_sub.p, cell_sub.p + (size_t)(ncz + 1) * nxy, nxy);
-    hipLaunchKernelGGL(k_copyback<R>, dim3(nb), dim3(256), 0, stream, cell_start.p, nxy, (ncz + 1) * nxy, x4o.p, v4o.p, tago.p, img4o.p, x4.p, v4.p, tag.p, img4.p, rtag.p, x0.p, c);
+    // 4. sort the reals into [G, G + n_new): the own (non-ghost) cell layers
+    launch_cell_sort(G, npend, nxy, (ncz + 1) * nxy);
     // 5. boundary-layer counts to the neighbours
     lcnt_dn.alloc(nxy + 1); lcnt_up.alloc(nxy + 1); gcnt_lo.alloc(nxy + 1); gcnt_up.alloc(nxy + 1);
     hipLaunchKernelGGL(k_layer_counts, dim3(cdiv(nxy + 1, 256)), dim3(256), 0, stream, nxy, ncz, cell_start.p, lcnt_dn.p, lcnt_up.p);
@@ -1106,8 +1042,7 @@ template <typename R> struct CtxT : Ctx {
     nglo = c7[5]; ngup = c7[6];
     if (nglo > G || G + n + ngup > cap) throw ChemError(CHEM_ENOSPC, "domain decomposition: ghost layer exceeds the reserved capacity");
     // 6. ghost particles: contiguous slices, received in place (lower ghosts right-aligned in front of the reals)
-    tr->exchange2(Transport::Msg{x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
-                                 x4.p + G - nglo, nglo * sizeof(V4)},
+    tr->exchange2(halo_msg(),
                   Transport::Msg{tag.p + halo_dn_off, halo_dn_cnt * sizeof(int), tag.p + halo_up_off, halo_up_cnt * sizeof(int), tag.p + G + n, ngup * sizeof(int),
                                  tag.p + G - nglo, nglo * sizeof(int)}, lower, upper, stream);
     hipLaunchKernelGGL(k_ghost_cells, dim3(1), dim3(1024), 0, stream, nxy, ncz, gcnt_lo.p, gcnt_up.p, cell_start.p);
@@ -1123,17 +1058,16 @@ template <typename R> struct CtxT : Ctx {
       collect_ints({&ctl.p->stage_overflow, &ctl.p->nl_overflow}, ov);
       if (!ov[0] && !ov[1]) break;
       if (ov[0]) {
-        const int want = (ov[0] + ov[0] / 8 + 255) / 256 * 256, old_cap = tile_cap;
-        if (want <= tile_cap) break;
+        const int want = grown_tile_cap(ov[0]), old_cap = tile_cap;
+        if (want <= tile_cap || tile_lds_need(want) > kTileLdsBudget) break;      // (stays flagged: reported by check_flags / rebuild_now)
         tile_cap = want;
-        if (tile_lds_need() > kTileLdsBudget) { tile_cap = old_cap; break; }      // (stays flagged: reported by check_flags / rebuild_now)
         set_tile_lds_attr();
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&ctl.p->stage_overflow, 0, 1, stream));
         if (g_trace) fprintf(stderr, "[chem trace] slab rebuild: staged-tile capacity %d -> %d slots\n", old_cap, tile_cap);
       }
       if (ov[1]) {
         if (nl_capacity_user > 0) break;
-        S = std::min(((int)(ov[1] * 1.25) + 31) / 16 * 16, std::max((nglob + 15) / 16 * 16, 16));
+        S = grown_row_stride(ov[1], nglob);
         alloc_lists();
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&ctl.p->nl_overflow, 0, 1, stream));
         if (g_trace) fprintf(stderr, "[chem trace] slab rebuild: list rows grown to %d entries\n", S);
@@ -1145,11 +1079,13 @@ template <typename R> struct CtxT : Ctx {
     ++dd_rebuilds;
   }
 
-  // per-step ghost position update: the same contiguous slices, straight into the ghost ranges
-  void halo_update() {
-    tr->exchange(x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
-                 x4.p + G - nglo, nglo * sizeof(V4), lower, upper, stream);
+  // ghost positions: the own boundary layers are contiguous slices of x4, received straight into the ghost ranges
+  Transport::Msg halo_msg() const {
+    return Transport::Msg{x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
+                          x4.p + G - nglo, nglo * sizeof(V4)};
   }
+  // per-step ghost position update
+  void halo_update() { tr->exchange(halo_msg(), lower, upper, stream); }
 
   DevCtl read_ctl() {
     DevCtl h;
@@ -1195,17 +1131,15 @@ template <typename R> struct CtxT : Ctx {
       if (h.stage_overflow) {
         // denser than the mean-occupancy estimate (clusters, chains): grow the staged-tile capacity while it
         // fits the LDS, then build again; beyond that the system is too crowded for tiles
-        const int want = (h.stage_overflow + h.stage_overflow / 8 + 255) / 256 * 256;
-        const int old_cap = tile_cap;
+        const int want = grown_tile_cap(h.stage_overflow);
         if (use_tiles && want > tile_cap) {
-          tile_cap = want;
-          if (tile_lds_need() <= kTileLdsBudget) {
+          if (tile_lds_need(want) <= kTileLdsBudget) {
+            if (g_trace) fprintf(stderr, "[chem trace] staged-tile capacity %d -> %d slots\n", tile_cap, want);
+            tile_cap = want;
             set_tile_lds_attr(); setup_fused();
             set_ctl_field(&DevCtl::stage_overflow, 0);
-            if (g_trace) fprintf(stderr, "[chem trace] staged-tile capacity %d -> %d slots\n", old_cap, tile_cap);
             continue;
           }
-          tile_cap = old_cap;
           if (!dd_on) {
             // the stencil no longer fits the LDS next to the list build's image: this system continues on the per-cell
             // kernels (int32 rows, positions through L1/L2) instead of failing
@@ -1219,9 +1153,8 @@ template <typename R> struct CtxT : Ctx {
         throw ChemError(CHEM_ENOSPC, "cell stencil holds " + std::to_string(h.stage_overflow) + " particles, LDS tile capacity " + std::to_string(use_tiles ? tile_cap : 1536) + " (local density too high for the LDS-staged tiles; set option tiles=0)");
       }
       if (!h.nl_overflow) { resort = false; tm.rebuild_wall_s += now_s() - t0; return; }
-      int newS = ((int)(h.nl_overflow * 1.25) + 31) / 16 * 16;
       if (nl_capacity_user > 0) throw ChemError(CHEM_ENOSPC, "neighbour capacity " + std::to_string(S) + " too small, need " + std::to_string(h.nl_overflow));
-      S = std::min(newS, std::max(((dd_on ? nglob : n) + 15) / 16 * 16, 16));
+      S = grown_row_stride(h.nl_overflow, dd_on ? nglob : n);
       alloc_lists();
       set_ctl_field(&DevCtl::nl_overflow, 0);
     }
@@ -1269,11 +1202,9 @@ template <typename R> struct CtxT : Ctx {
     }
     if (use_tiles) {
       // which tiles: all (default), or the interior / boundary subset of a slab (see TileSub)
-      const int ntxy = tile_ntx(box.nc[0], box.xs_nb, box.xs_w) * ((box.nc[1] + HY - 1) / HY);
-      TileSub ts{0, ntiles, 0};
-      int nsub = ntiles;
-      if (pair_subset == 1) { ts = TileSub{ntxy, ntiles - 2 * ntxy, 0}; nsub = ntiles - 2 * ntxy; }
-      else if (pair_subset == 2) { ts = TileSub{0, ntxy, ntiles - ntxy}; nsub = 2 * ntxy; }
+      const TileLayers tl = tile_subset(ntiles, ntxy(), pair_subset);
+      const TileSub ts{tl.base1, tl.n1, tl.base2};
+      const int nsub = tl.count;
       if (nsub <= 0) return 0;
 #define LTD(T, M, B, D) hipLaunchKernelGGL((k_pair_tiles<R, T, ENERGY, B, M, D>), dim3(nsub), dim3(B), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p, \
                                  nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, uni, eout.p, hs, ctl.p, pair_guard, opt_ablate, dbg_on ? dbgbuf.p : (long long*)nullptr, ts, pair_da, \
@@ -1381,26 +1312,21 @@ template <typename R> struct CtxT : Ctx {
   // one step's neighbour bookkeeping in slab mode: cross-rank max of the displacement, the ghost
   // position update (posted before the decision is known: it is needed unless we rebuild), and the
   // collective rebuild when the trigger fired.  One host synchronisation per step.
-  bool dd_overlap() const {
-    const int ntxy = tile_ntx(box.nc[0], box.xs_nb, box.xs_w) * ((box.nc[1] + HY - 1) / HY);
-    const bool want_overlap = opt_overlap > 0 || (opt_overlap < 0 && ntiles >= 8192);
-    return want_overlap && use_tiles && ntiles > 2 * ntxy && !getenv("CHEM_DD_NOPOLL");
-  }
+  int ntxy() const { return tiles_per_layer(box.nc[0], box.nc[1], box.xs_nb, box.xs_w); }      // tiles of one tile layer
+  bool dd_overlap() const { return halo_overlap(opt_overlap, use_tiles, ntiles, ntxy(), !g_dd_nopoll); }
   // decision by the force kernel's workgroups instead of a one-block launch between the halo exchange and the forces
-  bool dd_merged() const { return dd_on && opt_dd_merge && use_tiles && !dd_overlap() && !getenv("CHEM_DD_NOPOLL"); }
+  bool dd_merged() const { return dd_on && opt_dd_merge && use_tiles && !dd_overlap() && !g_dd_nopoll; }
   void dd_step_sync() {
     ensure_hflag();
     if (dd_merged()) {
       const bool fold = fold_on();
       if (fold) {
         // the integrate kernel has folded the block maxima into foldmax with atomics: the words travel with the halo, no fold launch
-        tr->exchange_with_scalar(x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
-                                 x4.p + G - nglo, nglo * sizeof(V4), lower, upper, reinterpret_cast<const double*>(foldmax.p), dd_vals.p, stream, kFoldSlots);
+        tr->exchange_with_scalar(halo_msg(), lower, upper, reinterpret_cast<const double*>(foldmax.p), dd_vals.p, stream, kFoldSlots);
       } else {
         hipLaunchKernelGGL(k_rebuild_decide<R>, dim3(1), dim3(1024), 0, stream, ctl.p, blockmax.p, cdiv(acap(), kIntPerBlock), 0.5 * skin_eff(), opt_criterion, 1,
                            (const double*)nullptr, 0, (volatile int*)nullptr, 0, 0.5 * skin);
-        tr->exchange_with_scalar(x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
-                                 x4.p + G - nglo, nglo * sizeof(V4), lower, upper, &ctl.p->step_m2, dd_vals.p, stream);
+        tr->exchange_with_scalar(halo_msg(), lower, upper, &ctl.p->step_m2, dd_vals.p, stream);
       }
       const int ticket = ++hticket;
       pair_da = DecideArgs{dd_vals.p, P, (volatile int*)hflag_dev, ticket, dd_par, opt_criterion, 0.5 * skin, fold ? foldmax.p : nullptr};
@@ -1420,12 +1346,8 @@ template <typename R> struct CtxT : Ctx {
     // Overlap: the halo exchange runs on the communication stream while the tiles that need no ghost
     // (every tile layer but the lowest and the highest of the slab) already compute their forces.
     // Those launches cannot know the decision yet; if it is "rebuild", everything is recomputed below.
-    const int ntxy = tile_ntx(box.nc[0], box.xs_nb, box.xs_w) * ((box.nc[1] + HY - 1) / HY);
-    // Measured with one rank (1M particles, RCCL to self): the cross-stream hand-over costs ~15 us and the
-    // boundary launch cannot fill the chip, so the overlap only pays once the interior force kernel is much
-    // longer than that -- automatic for slabs of >= 8192 tiles (~4M particles per GPU), option overlap_halo.
-    const bool want_overlap = opt_overlap > 0 || (opt_overlap < 0 && ntiles >= 8192);
-    const bool overlap = want_overlap && use_tiles && ntiles > 2 * ntxy && !getenv("CHEM_DD_NOPOLL");
+    // (when it pays: chem_geom_host.hpp halo_overlap)
+    const bool overlap = dd_overlap();
     hipStream_t xs = stream;
     if (overlap) {
       if (!cstream) {
@@ -1436,8 +1358,7 @@ template <typename R> struct CtxT : Ctx {
       HIPCHK(hipStreamWaitEvent(cstream, ev_fold, 0));
       xs = cstream;
     }
-    tr->exchange_with_scalar(x4.p + halo_dn_off, halo_dn_cnt * sizeof(V4), x4.p + halo_up_off, halo_up_cnt * sizeof(V4), x4.p + G + n, ngup * sizeof(V4),
-                             x4.p + G - nglo, nglo * sizeof(V4), lower, upper, &ctl.p->step_m2, dd_vals.p, xs);
+    tr->exchange_with_scalar(halo_msg(), lower, upper, &ctl.p->step_m2, dd_vals.p, xs);
     if (overlap) {
       HIPCHK(hipEventRecord(ev_halo, cstream));
       compute_forces(false, 1);                    // interior tiles, main stream, concurrent with the exchange
@@ -1450,7 +1371,7 @@ template <typename R> struct CtxT : Ctx {
     // rebuild is pending (then the host rebuilds and launches them again), otherwise the device never
     // waits for the host's poll + launch latency.
     compute_forces(true, overlap ? 2 : 0);
-    if (getenv("CHEM_DD_NOPOLL")) { DevCtl hc = read_ctl(); if (hc.need_rebuild) { rebuild_dd(); compute_forces(); } return; }
+    if (g_dd_nopoll) { DevCtl hc = read_ctl(); if (hc.need_rebuild) { rebuild_dd(); compute_forces(); } return; }
     volatile int* hf = hflag;
     poll_ticket(hflag + 1, ticket, "rebuild decision");
     if (hf[0]) { rebuild_dd(); compute_forces(); }

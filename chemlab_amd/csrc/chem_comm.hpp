@@ -44,9 +44,12 @@ struct Transport {
                         void* from_lo, size_t from_lo_bytes, int lower, int upper, hipStream_t s) = 0;
   // Two exchanges with the same neighbours in one communication phase (ghost positions + ghost tags).
   struct Msg { const void* dn; size_t dn_bytes; const void* up; size_t up_bytes; void* from_up; size_t from_up_bytes; void* from_lo; size_t from_lo_bytes; };
+  void exchange(const Msg& m, int lower, int upper, hipStream_t s) {
+    exchange(m.dn, m.dn_bytes, m.up, m.up_bytes, m.from_up, m.from_up_bytes, m.from_lo, m.from_lo_bytes, lower, upper, s);
+  }
   virtual void exchange2(const Msg& a, const Msg& b, int lower, int upper, hipStream_t s) {
-    exchange(a.dn, a.dn_bytes, a.up, a.up_bytes, a.from_up, a.from_up_bytes, a.from_lo, a.from_lo_bytes, lower, upper, s);
-    exchange(b.dn, b.dn_bytes, b.up, b.up_bytes, b.from_up, b.from_up_bytes, b.from_lo, b.from_lo_bytes, lower, upper, s);
+    exchange(a, lower, upper, s);
+    exchange(b, lower, upper, s);
   }
   // The same exchange plus, in the same communication phase, every rank's `my` value delivered to
   // slot [rank] of every other rank's `all` array (the step's displacement maximum: the list-rebuild
@@ -54,6 +57,9 @@ struct Transport {
   virtual void exchange_with_scalar(const void* dn, size_t dn_bytes, const void* up, size_t up_bytes, void* from_up, size_t from_up_bytes,
                                     void* from_lo, size_t from_lo_bytes, int lower, int upper, const double* my, double* all, hipStream_t s, int count = 1) = 0;
   // (count: 8-byte words per rank -- slot [rank * count .. ) of `all`)
+  void exchange_with_scalar(const Msg& m, int lower, int upper, const double* my, double* all, hipStream_t s, int count = 1) {
+    exchange_with_scalar(m.dn, m.dn_bytes, m.up, m.up_bytes, m.from_up, m.from_up_bytes, m.from_lo, m.from_lo_bytes, lower, upper, my, all, s, count);
+  }
   virtual void allreduce_max_f64(double* dev, size_t count, hipStream_t s) = 0;
   virtual void allreduce_sum_f64(double* dev, size_t count, hipStream_t s) = 0;
   // out must hold nranks*bytes; in may alias out + rank*bytes

@@ -13,6 +13,7 @@
 
 #include "../../include/chem_mi355.h"
 #include "../../include/chem_philox.h"
+#include "chem_geom_host.hpp"
 
 namespace chem {
 
@@ -1082,34 +1083,10 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
 // The staged order is a pure function of cell_start, which only changes at a rebuild, so the
 // build kernel and every later force launch see the same slot numbering.
 // =======================================================================================
-#ifndef CHEM_HX
-#define CHEM_HX 3
-#endif
-#ifndef CHEM_HY
-#define CHEM_HY 3
-#endif
-#ifndef CHEM_HZ
-#define CHEM_HZ 3
-#endif
-constexpr int HX = CHEM_HX, HY = CHEM_HY, HZ = CHEM_HZ;   // ~490 home particles at 18/cell: one pass of a 512-thread block; stencil 5^3 cells (x4.6)
-constexpr int SX = HX + 2, SY = HY + 2, SZ = HZ + 2;
+// HX, HY, HZ (CHEM_HX/HY/HZ, default 3), SX, SY, SZ and the tiles of a row along x (tile_nbx, tile_ntx, tile_xrange) live in
+// chem_geom_host.hpp, shared with the host's planning rules.
 constexpr int NROW = SY * SZ;          // x-rows of the stencil
 constexpr int NHSEG = HY * HZ;         // home x-runs (contiguous in memory)
-
-// Tiles along x: xs_nb tiles of HX cells, then tiles of xs_w cells (Box::xs_nb / xs_w).  A force launch of one-shot
-// workgroups ends with a partly filled last round (1728 equal tiles on 768 resident slots: 2.25 rounds take the time of 3);
-// a share of narrow tiles -- shorter jobs, scheduled last by the largest-first order -- fills it.  Splitting along x (the
-// fastest tile index) gives every XCD's contiguous tile range the same mix.
-__host__ __device__ inline int tile_nbx(int nx, int xs_nb) { return xs_nb * HX >= nx ? (nx + HX - 1) / HX : xs_nb; }      // wide tiles in a row (the last may be cut)
-__host__ __device__ inline int tile_ntx(int nx, int xs_nb, int xs_w) {
-  const int nb = tile_nbx(nx, xs_nb);
-  return nb * HX >= nx ? nb : nb + (nx - nb * HX + xs_w - 1) / xs_w;
-}
-__host__ __device__ inline void tile_xrange(int tx, int nx, int xs_nb, int xs_w, int& cx0, int& hx) {
-  const int nb = tile_nbx(nx, xs_nb);
-  if (tx < nb) { cx0 = tx * HX; hx = HX < nx - cx0 ? HX : nx - cx0; }
-  else { cx0 = nb * HX + (tx - nb) * xs_w; hx = xs_w < nx - cx0 ? xs_w : nx - cx0; }
-}
 
 // positions live in dynamic LDS (capacity chosen at run time from the cell occupancy):
 // sx[0..cap], slot `total` is a far-away dummy used as row padding

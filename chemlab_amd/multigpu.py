@@ -23,7 +23,7 @@ def node_grid(nranks):
 
 
 def slab_layers(nz_global, nranks):
-    """[z0, z1) cell layers owned by each rank -- mirrors CtxT::setup_box in chem_api.hip."""
+    """[z0, z1) cell layers owned by each rank -- mirrors slab_layers in csrc/chem_geom_host.hpp."""
     base, rem = divmod(int(nz_global), int(nranks))
     if base < 2:
         raise ValueError("fewer than 2 cell layers per rank along z: %d layers / %d ranks" % (nz_global, nranks))
@@ -36,7 +36,8 @@ def slab_layers(nz_global, nranks):
 
 
 def owner_of(z, box_z, rc, skin, nranks):
-    """Rank owning coordinate(s) z (folded into the box first)."""
+    """Rank owning coordinate(s) z (folded into the box first) -- mirrors slab_layer_of in csrc/chem_geom_host.hpp for the
+    cells of rc + skin."""
     nz = int(np.floor(box_z / (rc + skin)))
     layers = slab_layers(nz, nranks)
     zf = np.mod(np.asarray(z, dtype=np.float64), box_z)

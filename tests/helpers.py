@@ -1,5 +1,8 @@
 """Shared test plumbing: build small systems on any Engine (oracle or HIP)."""
 import functools
+import os
+import struct
+import subprocess
 
 import numpy as np
 
@@ -440,8 +443,8 @@ def brute_pairs(spec, shell=2e-6):
 
 def slab_capacities(spec, P):
     """Per rank of a P-slab decomposition: the capacities the engine reserves and what the spec puts there at step 0.
-    Restates chem_api.hip setup_box (nzg, base, rem, ncz, z0) and upload_particles (per_layer, G, mcap, cap, the layer gz of
-    a particle); n_real = particles the rank owns, max_layer = its fullest cell layer (a ghost layer of its neighbour)."""
+    Restates chem_geom_host.hpp slab_layers (nzg, base, rem, ncz, z0), slab_capacities (per_layer, G, mcap, cap) and
+    slab_layer_of (the layer gz of a particle) -- tests/test_host_geometry.py compares the two; n_real = particles the rank owns, max_layer = its fullest cell layer (a ghost layer of its neighbour)."""
     L = np.asarray(spec["box"], dtype=np.float64)
     nzg = int(np.floor(L[2] / (spec["rc"] + spec["skin"])))
     base, rem = nzg // P, nzg % P
@@ -528,3 +531,33 @@ def _geometry_reference(key):
 def geometry_reference(kind, *args):
     """pair_reference of a ladder / slab / cluster spec: (forces, epot_lj, epot_tab, virial_nb), computed once per session."""
     return _geometry_reference((kind, tuple(args)))
+
+
+# ---- the engine's planning rules on the CPU (chemlab_amd/csrc/chem_geom_host.hpp through tests/host/geometry_harness.cpp) --------
+
+def compile_geometry_harness(outdir):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(str(outdir), "geometry_harness")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tests", "host", "geometry_harness.cpp"), "-o", exe])
+    return exe
+
+
+def run_harness(exe, script):
+    """One output line (split into words) per script line."""
+    out = subprocess.run([exe], input="\n".join(script) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
+    assert len(out) == len(script) + 1 and out[-1] == "", (len(out), len(script))
+    return [l.split() for l in out[:-1]]
+
+
+def dbits(x):
+    """A double as the harness reads it: the decimal bit pattern."""
+    return "%d" % struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+
+
+def plan_line(spec, list_skin=-1.0, tiles=1, fused_rebuild=1, tile_split=0, dd=0, P=1, rk=0, bytes_per_slot=0, budget=0):
+    """The harness's "tiles" command for a spec: the plan CtxT::setup_geometry_once makes of its box, cutoff, skin, particle
+    count and rebuild criterion under the given options (defaults = the engine's).  Answer: ntiles, ncx, nwide, w, rows,
+    tile_cap (the six numbers of chem_debug_tiles), use_tiles, S, z0, ncz."""
+    return " ".join(["tiles"] + [dbits(v) for v in spec["box"]] + [dbits(spec["rc"]), dbits(spec["skin"]), "%d" % spec["n"], dbits(list_skin)] +
+                    ["%d" % v for v in (spec.get("rebuild_criterion", 0), tiles, fused_rebuild, tile_split, dd, P, rk, bytes_per_slot, budget)])

@@ -89,6 +89,30 @@ def test_geometry_ladder_static_against_numpy(make_gpu, nc, opts, frac, fill, pr
     _check_static(g, spec, H.geometry_reference("ladder", nc, frac, fill), prec, (nc, frac, fill, opts))
 
 
+def test_geometry_ladder_plan_is_the_host_headers(make_gpu, tmp_path):
+    """CtxT runs the plan of chem_geom_host.hpp: after run(0) the six numbers of chem_debug_tiles (tiles, cells along x, wide
+    tiles per row, narrow width, tile rows, tile capacity) are what tests/host/geometry_harness.cpp makes of the same box,
+    cutoff, skin and particle count, with an unlimited LDS budget (stencils of at most 1800 slots).  The ladder's boxes hold a
+    few hundred particles: the smallest that reach the brute-force, per-cell and tile paths; tests/test_host_geometry.py
+    checks the header's rules themselves on the CPU."""
+    exe = H.compile_geometry_harness(tmp_path)
+    variants = [(nc, {}) for nc in H.LADDER_BOXES] + [((12, 5, 5), {"tile_split": 11})]
+    assert len(variants) == 13
+    specs = [H.ladder_spec(nc, 0.5, "uniform") for nc, _ in variants]
+    plans = H.run_harness(exe, [H.plan_line(spec, **opts) for spec, (_, opts) in zip(specs, variants)])
+    for spec, (nc, opts), plan in zip(specs, variants, plans):
+        g = make_gpu(32)
+        for k, v in opts.items():
+            g.set_option(k, v)
+        W.apply(spec, g)
+        g.run(0)
+        out = (ctypes.c_int32 * 6)()
+        g.api.lib.chem_debug_tiles.restype = ctypes.c_int64
+        assert g.api.lib.chem_debug_tiles(ctypes.c_void_p(g.ctx), out) == 0
+        assert plan[0] == "tiles" and list(out) == [int(v) for v in plan[1:7]], (nc, opts, list(out), plan)
+        assert 0 <= out[5] <= 1800
+
+
 # ---- (b) the ladder, dynamic ----------------------------------------------------------------------------------------------
 _TRAJ = {}
 
