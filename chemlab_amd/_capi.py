@@ -25,7 +25,7 @@ PREC_F32, PREC_F64 = 32, 64
 
 POT = dict(HARMONIC=1, FENE=2, TABULATED=3, FENE_LJ=4, LJ_BOND=5, DIH_HARMONIC=23, ANG_HARMONIC=10, ANG_COSINE=11, ANG_TABULATED=12, DIH_NCOS=20, DIH_RB=21, DIH_TABULATED=22)
 STATE = dict(POS=1, VEL=2, FORCE=3, TYPE=4, STATE=5, RESID=6, MASS=7, ID=8, IMAGE=9, MOLID=10,
-             POS_UNFOLDED=11)
+             POS_UNFOLDED=11, CHARGE=12)
 
 
 class ChemLibraryError(RuntimeError):
@@ -166,6 +166,8 @@ PRODUCT_ONLY = {
     "dissociation_add": (_i, [_P, C.POINTER(DissociationDesc)]),   # (the CPU oracle has no bond removal)
     "nb_table_interp": (_i, [_P, _i, _i, _i64, _d, _d, _pd, _pd, _d, _i]),   # (the CPU oracle interpolates linearly only)
     "table_create_interp": (_i, [_P, _i64, _d, _d, _pd, _pd, _i]),
+    "nb_coulomb": (_i, [_P, _i, _i, _d, _d]),   # (the CPU oracle has no Coulomb term)
+    "get_coulomb": (_i, [_P, _pd, _pd]),
 }
 
 

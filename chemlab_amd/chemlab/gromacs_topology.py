@@ -116,9 +116,19 @@ def gen_particle_list(coordinate, topol, espressopp):
     return props, plist
 
 
-def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff=None, tables_=None, table_dir=".", cr_observs=None):
+def has_charges(gt):
+    """True when an atom or an atom type of the topology carries a non-zero charge.  Reaction products, neighbour rules and
+    ATRP centres take their charge from the atom type they name (reaction_setup.py), so the atom types cover them."""
+    return (any(float(a.get("charge") or 0.0) != 0.0 for a in gt.atoms.values()) or
+            any(float(t.get("charge") or 0.0) != 0.0 for t in gt.gt.atomtypes.values()))
+
+
+def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff=None, tables_=None, table_dir=".", cr_observs=None,
+                               qq_cutoff=0.0, log=None):
     """One VerletListLennardJones ('lj') and one VerletListTabulated ('lj-tab') for all type pairs
-    (:463-899).  A pair gets no potential when sigma <= 0 (:715)."""
+    (:463-899).  A pair gets no potential when sigma <= 0 (:715).  qq_cutoff > 0 and fudgeQQ > 0: one
+    VerletListCoulombTruncated ('coulomb') with prefactor 138.935485 * fudgeQQ on every used type pair (:866-878) --
+    unless nothing in the topology is charged: the term is then identically zero and is not registered."""
     tab_cutoff = lj_cutoff if tab_cutoff is None else tab_cutoff
     tables_ = tables_ or []
     cr = int(gt.gt.defaults["combinationrule"])
@@ -179,6 +189,17 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
             elif sig > 0.0:
                 lj.setPotential(type1=t1, type2=t2, potential=espressopp.interaction.LennardJones(epsilon=eps, sigma=sig, cutoff=lj_cutoff))
                 has_lj = True
+    pref_qq = 138.935485 * float(gt.gt.defaults.get("fudgeQQ", 1.0))
+    if qq_cutoff > 0.0 and pref_qq > 0.0:
+        if not has_charges(gt):
+            (log or (lambda *a: None))("coulomb_cutoff=%g: no atom or atom type carries a charge, the Coulomb term is zero and is not registered" % qq_cutoff)
+        else:
+            pot_qq = espressopp.interaction.CoulombTruncated(prefactor=pref_qq, cutoff=qq_cutoff)
+            qq = espressopp.interaction.VerletListCoulombTruncated(vl)
+            for i, n1 in enumerate(names):
+                for n2 in names[i:]:
+                    qq.setPotential(type1=gt.used_atomsym_atomtype[n1], type2=gt.used_atomsym_atomtype[n2], potential=pot_qq)
+            system.addInteraction(qq, "coulomb")
     if has_lj:
         system.addInteraction(lj, "lj")
     if has_tab:
@@ -372,13 +393,24 @@ def set_dihedral_interactions(espressopp, system, gt, dynamic_type_ids=(), table
     return out
 
 
-def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=()):
+def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=(), qq_cutoff=0.0):
     """[ pairs ] (1-4 interactions) -> FixedPairList[Types]LennardJones (:1314-1411): explicit `sigma epsilon` on the
     pair line, else [ pairtypes ]-less gen-pairs: combination rule of the two atom types with epsilon * fudgeLJ.
     (The reference combines atom type 0 with itself, :1341-1342, and calls combination() with three arguments on the
     static path, :1360 -- SURVEY Q5; here both atom types are used.)"""
     if not gt.pairs:
         return {}
+    # the 1-4 Coulomb pairs (FixedPairListTypesCoulombTruncated, :1391-1409) have no kernel: refused, never dropped.  A member
+    # counts as charged if it is so now, or if its type can change through a reaction and some atom type carries a charge
+    # (a product takes the charge of the atom type it names)
+    if qq_cutoff > 0.0 and float(gt.gt.defaults.get("fudgeQQ", 1.0)) > 0.0:
+        typed_q = any(float(t.get("charge") or 0.0) != 0.0 for t in gt.gt.atomtypes.values())
+        for (a, b) in gt.pairs:
+            for m in (a, b):
+                if float(gt.atoms[m].get("charge") or 0.0) != 0.0 or (typed_q and gt.atoms[m]["type_id"] in dynamic_type_ids):
+                    raise NotImplementedError("[ pairs ] entry %s-%s has a charged member (or one whose type, and with it its charge, can change): "
+                                              "1-4 Coulomb pairs (FixedPairListTypesCoulombTruncated, fudgeQQ > 0 with coulomb_cutoff > 0) are "
+                                              "outside the hot-path scope" % (a, b))
     cr = int(gt.gt.defaults["combinationrule"])
     fudge = float(gt.gt.defaults.get("fudgeLJ", 1.0))
     at = gt.gt.atomtypes

@@ -93,6 +93,10 @@ struct Ctx {
   std::vector<double> pos0, vel0;  // staged particle data (tag order) until first upload
   int ntypes = 1;
   HostPairPot pp[CHEM_MAX_TYPES][CHEM_MAX_TYPES];
+  // Truncated Coulomb term (chem_nb_coulomb): one (prefactor, rc) for every registered type pair, a symmetric type-pair bit mask
+  double coul_k = 0, coul_rc = 0; uint32_t coul_mask[CHEM_MAX_TYPES] = {}; bool coul_dirty = false;
+  bool coul_on() const { for (uint32_t m : coul_mask) if (m) return true; return false; }
+  double coul_epot = 0, coul_virial = 0;   // of the last energy evaluation (observe)
   bool lang = false; double kT = 0, gamma = 0; uint64_t lang_seed = 0; uint32_t lang_tmask = 0;
   bool react_init = false, react_on = false;
   int interval = 0, nearest = 1, max_per_interval = 0; uint64_t react_seed = 0;
@@ -136,8 +140,9 @@ struct Ctx {
       if (arena.r[k] < 0) continue;      // (a dissociation event: diss_step brought the mirrors up to date itself)
       const chem_reaction_desc& d = reactions[arena.r[k]];
       const int32_t ea = arena.a[k], eb = arena.b[k];
-      if (d.new_type_1 >= 0 && d.new_type_1 != top.type[ea]) { top.type[ea] = d.new_type_1; top.mass[ea] = d.new_mass_1; top.q[ea] = d.new_q_1; }
-      if (d.new_type_2 >= 0 && d.new_type_2 != top.type[eb]) { top.type[eb] = d.new_type_2; top.mass[eb] = d.new_mass_2; top.q[eb] = d.new_q_2; }
+      // (the charge follows the device's rule, k_react_apply_q: set wherever the reaction names a new type, also where the type stays)
+      if (d.new_type_1 >= 0) { if (d.new_type_1 != top.type[ea]) { top.type[ea] = d.new_type_1; top.mass[ea] = d.new_mass_1; top.q[ea] = d.new_q_1; } else top.q[ea] = d.new_q_1; }
+      if (d.new_type_2 >= 0) { if (d.new_type_2 != top.type[eb]) { top.type[eb] = d.new_type_2; top.mass[eb] = d.new_mass_2; top.q[eb] = d.new_q_2; } else top.q[eb] = d.new_q_2; }
     }
     arena.mirror_pos = arena.size();
   }
@@ -207,8 +212,9 @@ template <typename R> struct CtxT : Ctx {
   static size_t tile_lds_bytes(int cap_) { return (size_t)(cap_ + 5) * sizeof(V4) + 16; }
   size_t tile_lds_bytes() const { return tile_lds_bytes(tile_cap); }
   // force kernel: fp64 stages 24-byte slots + type bytes (two workgroups per CU instead of one)
-  static size_t pair_lds_bytes(int cap_) { return sizeof(R) == 8 ? (size_t)(cap_ + 5) * 25 + 64 : tile_lds_bytes(cap_); }
-  size_t pair_lds_bytes() const { return pair_lds_bytes(tile_cap); }
+  // (with a Coulomb pair registered: + one charge word per slot behind the image, k_pair_tiles MODE 4)
+  static size_t pair_lds_bytes(int cap_, bool coul = false) { return coul ? coul_img_bytes<R>(cap_) : (sizeof(R) == 8 ? (size_t)(cap_ + 5) * 25 + 64 : tile_lds_bytes(cap_)); }
+  size_t pair_lds_bytes() const { return pair_lds_bytes(tile_cap, coul_on()); }
   // the list build has its own layout of the same block (fp32: SoA groups + type masks + slice boundaries)
   // (fp64 builds use the fp32 list image too -- the force list may be a superset -- and need their own 32-byte-per-slot
   //  image only where the exact int32 rows are built)
@@ -217,7 +223,7 @@ template <typename R> struct CtxT : Ctx {
   size_t scan_lds_bytes() const { return scan_roles_offset(tile_cap, sizeof(V4)) + (size_t)(tile_cap + 1) * sizeof(unsigned int); }
   bool scan_roles_staged() const { return scan_lds_bytes() <= kTileLdsBudget; }      // (otherwise the scan reads the role words from global memory)
   // what a tile of cap_ slots asks of the LDS, over every kernel that stages one (asked before tile_cap is set or grown)
-  static size_t tile_lds_need(int cap_) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_)), list_lds_need(cap_, true)); }
+  static size_t tile_lds_need(int cap_, bool coul) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_, coul)), list_lds_need(cap_, true)); }
   static size_t list_lds_need(int cap_, bool exact_rows) {
     const size_t lb = list_lds_bytes(cap_, kMaxTypes);
     return (sizeof(R) == 4 || exact_rows) ? std::max(tile_lds_bytes(cap_), lb) : lb;
@@ -281,6 +287,7 @@ template <typename R> struct CtxT : Ctx {
   bool dd_record_bonds = false;      // slabs, bond pass: the next force launch records the partner slots (set by the slab rebuild)
   bool bonds_inline() {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
+    if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
     // the exclusion set must BE the bond set (bonds are a subset: bonds_excluded; both are duplicate-free): equal counts
     size_t nb2 = 0;
     for (const auto& l : top.lists) if (l.arity == 2) nb2 += (size_t)l.size();
@@ -423,7 +430,7 @@ template <typename R> struct CtxT : Ctx {
     HIPCHK(hipMemsetAsync(cell_cnt.p, 0, sizeof(int) * (box.ncell + 1), stream));
     S = row_stride(L, rc + skin_eff(), dd_on ? nglob : n, nl_capacity_user);
     const TilePlan tp = plan_tiles(box.nc[0], box.nc[1], dd_on ? ncz : box.nc[2], dd_on ? nzg : box.nc[2], dd_on ? nglob : n, dd_on, opt_tiles != 0,
-                                   opt_tile_split, [](int c) { return tile_lds_need(c); }, kTileLdsBudget);
+                                   opt_tile_split, [coul = coul_on()](int c) { return tile_lds_need(c, coul); }, kTileLdsBudget);
     use_tiles = tp.use_tiles; box.xs_nb = tp.xs_nb; box.xs_w = tp.xs_w; ntiles = tp.ntiles;
     if (tp.tile_cap) { tile_cap = tp.tile_cap; if (use_tiles) set_tile_lds_attr(); }      // (a grid without tiles leaves the last capacity as it was)
     alloc_lists();
@@ -519,6 +526,11 @@ template <typename R> struct CtxT : Ctx {
 #undef SETT
 #undef SETB
 #undef SETA
+    if (coul_on()) {      // MODE 4 (one lane per particle, 512 threads): the image + the charge words
+      const int qbytes = (int)pair_lds_bytes();
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+    }
   }
 
   void alloc_lists() {
@@ -637,6 +649,7 @@ template <typename R> struct CtxT : Ctx {
     for (auto& r : dissociations) { nt = std::max(nt, std::max(r.new_type_1, r.new_type_2) + 1); }
     for (auto& r : nb_rules) nt = std::max(nt, r.new_type + 1);
     for (auto& c : atrp_centers) nt = std::max(nt, std::max(c.type, c.new_type) + 1);
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) if (coul_mask[a]) nt = std::max(nt, a + 1);
     ntypes = nt;
     std::vector<PairCore<R>> hc((size_t)nt * nt);
     std::vector<PairExt<R>> he((size_t)nt * nt);
@@ -677,13 +690,14 @@ template <typename R> struct CtxT : Ctx {
     const HostPairPot* first = nullptr;
     for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = 0; b < CHEM_MAX_TYPES; ++b) {
       const HostPairPot& p = pp[a][b];
-      if (!opt_skip_inactive || p.kind) act.row[a] |= 1u << b;
+      if (!opt_skip_inactive || p.kind || ((coul_mask[a] >> b) & 1u)) act.row[a] |= 1u << b;   // (a pair may carry the Coulomb term alone)
       if (p.kind == 1) {
         if (!first) first = &p;
         else if (p.eps != first->eps || p.sig != first->sig || p.rc != first->rc) uniform_lj = false;
       }
     }
     if (!opt_skip_inactive || !first) uniform_lj = false;
+    if (coul_on()) { uniform_lj = false; lj_only = false; }
     all_active = true;   // every pair of types in use carries a potential: the list build skips the per-hit type filter
     for (int a = 0; a < nt; ++a) for (int b = 0; b < nt; ++b) if (!((act.row[a] >> b) & 1u)) all_active = false;
     if (uniform_lj) {
@@ -695,6 +709,24 @@ template <typename R> struct CtxT : Ctx {
     pcore.upload(hc, stream); pext.upload(he, stream); tab.upload(htab, stream);
     HIPCHK(hipStreamSynchronize(stream));
     pair_dirty = false;
+  }
+
+  // Charges by tag and the type-pair mask of the Coulomb term: allocated and kept up to date (k_react_apply, k_apply_props,
+  // modify_particle) only while a Coulomb pair is registered; every rank of a decomposition holds all of them.
+  DBuf<R> qtag; DBuf<unsigned int> cmask_dev; DBuf<double> eoutq;
+  R* qtag_arg() { return coul_on() ? qtag.p : nullptr; }
+  void upload_coul() {
+    coul_dirty = false;
+    if (!coul_on()) { HIPCHK(hipStreamSynchronize(stream)); qtag.free(); cmask_dev.free(); eoutq.free(); return; }      // the array exists only while a pair is registered
+    std::vector<R> hq((size_t)top.n);
+    for (size_t t = 0; t < hq.size(); ++t) hq[t] = (R)top.q[t];
+    std::vector<unsigned int> hm(coul_mask, coul_mask + CHEM_MAX_TYPES);
+    qtag.upload(hq, stream); cmask_dev.upload(hm, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  CoulArgs<R> coul_args(size_t nblocks) {
+    if (eoutq.n < 2 * nblocks + 8) eoutq.alloc(2 * nblocks + 8);
+    return CoulArgs<R>{qtag.p, tag.p, cmask_dev.p, eoutq.p, (R)coul_k, (R)(coul_rc * coul_rc)};
   }
 
   // ---- per-tag CSR tables built on the device from flat, append-only arrays (md_kernels.hpp "Per-tag CSR tables") ----
@@ -881,6 +913,7 @@ template <typename R> struct CtxT : Ctx {
     if (geom_dirty) setup_geometry();
     if (labels_dirty) upload_labels();
     if (pair_dirty) upload_pair();
+    if (coul_dirty) upload_coul();
     if (bonded_dirty) upload_bonded();
     if (excl_dirty) upload_excl();
   }
@@ -1059,7 +1092,7 @@ template <typename R> struct CtxT : Ctx {
       if (!ov[0] && !ov[1]) break;
       if (ov[0]) {
         const int want = grown_tile_cap(ov[0]), old_cap = tile_cap;
-        if (want <= tile_cap || tile_lds_need(want) > kTileLdsBudget) break;      // (stays flagged: reported by check_flags / rebuild_now)
+        if (want <= tile_cap || tile_lds_need(want, coul_on()) > kTileLdsBudget) break;      // (stays flagged: reported by check_flags / rebuild_now)
         tile_cap = want;
         set_tile_lds_attr();
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&ctl.p->stage_overflow, 0, 1, stream));
@@ -1133,7 +1166,7 @@ template <typename R> struct CtxT : Ctx {
         // fits the LDS, then build again; beyond that the system is too crowded for tiles
         const int want = grown_tile_cap(h.stage_overflow);
         if (use_tiles && want > tile_cap) {
-          if (tile_lds_need(want) <= kTileLdsBudget) {
+          if (tile_lds_need(want, coul_on()) <= kTileLdsBudget) {
             if (g_trace) fprintf(stderr, "[chem trace] staged-tile capacity %d -> %d slots\n", tile_cap, want);
             tile_cap = want;
             set_tile_lds_attr(); setup_fused();
@@ -1180,6 +1213,11 @@ template <typename R> struct CtxT : Ctx {
 
   template <bool ENERGY> int launch_pair(V4* fdst, int tpp) {
     const double hs = 0.5 * skin_eff();
+    const bool coul = coul_on();
+    if (coul) {      // the kernels with the Coulomb term are built for one lane per particle and 512-thread blocks
+      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a Coulomb pair registered only tpp = 1 (or 0, automatic) is built");
+      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a Coulomb pair registered only pair_block = 512 is built");
+    }
     const bool inline_now = bonds_inline();
     int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;      // (what the LAST rebuild did: both only change where a rebuild is forced)
     if (bond_mode == 2 && dd_on) {      // slabs: the host knows which launch follows a rebuild (mode 3 = mode 2 + record the partner slots now)
@@ -1214,6 +1252,13 @@ template <typename R> struct CtxT : Ctx {
 #define LTB(T, M) do { if ((dbg_on || opt_ablate) && !ENERGY) { if (T != 1 || pair_bs != 512) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate need tpp=1 and pair_block=512"); LTD(1, M, 512, true); } \
                        else if (pair_bs == 256) LT(T, M, 256); else if (pair_bs == 512) LT(T, M, 512); else LT(T, M, 1024); } while (0)
 #define LTT(M) do { switch (tpp) { case 1: LTB(1, M); break; case 2: LTB(2, M); break; case 8: LTB(8, M); break; default: LTB(4, M); break; } } while (0)
+      if (coul) {      // MODE 4: general + Coulomb, one instantiation per precision and ENERGY
+        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with the Coulomb term");
+        const CoulArgs<R> ca = coul_args((size_t)nsub);
+        hipLaunchKernelGGL((k_pair_tiles_q<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
+                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, ca);
+        return ntiles;
+      }
       const int mode = ENERGY ? (cubic_tab ? 3 : 0) : (uniform_lj ? 2 : (lj_only ? 1 : (cubic_tab ? 3 : 0)));
       if (mode == 2) LTT(2); else if (mode == 1) LTT(1); else if (mode == 3) LTT(3); else LTT(0);
 #undef LTT
@@ -1221,6 +1266,12 @@ template <typename R> struct CtxT : Ctx {
 #undef LT
 #undef LTD
       return ntiles;
+    }
+    if (coul) {
+      const int nbq = cdiv((long long)n * 4, 256);
+      hipLaunchKernelGGL((k_pair_force<R, 4, ENERGY, true, true>), dim3(nbq), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
+                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, coul_args((size_t)nbq));
+      return nbq;
     }
     const int nb = cdiv((long long)n * tpp, 256);
 #define LPC(T, CU) hipLaunchKernelGGL((k_pair_force<R, T, ENERGY, CU>), dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, \
@@ -1527,6 +1578,7 @@ template <typename R> struct CtxT : Ctx {
     prop_dev.alloc(chg.size());
     HIPCHK(hipMemcpyAsync(prop_dev.p, chg.data(), chg.size() * sizeof(PropChangeDev), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL((k_apply_props<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), prop_dev.p, state.p, rtag.p, x4.p, v4.p);
+    if (qtag_arg()) hipLaunchKernelGGL((k_apply_props_q<R>), dim3(cdiv((long long)chg.size(), 256)), dim3(256), 0, stream, (int)chg.size(), prop_dev.p, qtag.p);
     if (wait) HIPCHK(hipStreamSynchronize(stream));
   }
   // the record count of every rank, in rank order (decomposed path)
@@ -1704,6 +1756,11 @@ template <typename R> struct CtxT : Ctx {
   EventSpan apply_and_download_events(int nc, const int* status, const ReactApplySet& ras, Trace& trc) {
     HIPCHK(hipMemsetAsync(evcount.p, 0, sizeof(int), stream));
     hipLaunchKernelGGL(k_react_apply<R>, dim3(cdiv(nc, 256)), dim3(256), 0, stream, nc, cand.p, status, ras, state.p, rtag.p, x4.p, v4.p, evout.p, evcount.p);
+    if (qtag_arg()) {      // charges of the reactants, by tag
+      ReactQSet rqs{};
+      for (size_t q = 0; q < reactions.size(); ++q) rqs.r[q] = ReactQ{reactions[q].new_type_1, reactions[q].new_type_2, reactions[q].new_q_1, reactions[q].new_q_2};
+      hipLaunchKernelGGL(k_react_apply_q<R>, dim3(cdiv(nc, 256)), dim3(256), 0, stream, nc, (const Candidate*)cand.p, (const int*)status, rqs, qtag.p);
+    }
     int nev = 0;
     HIPCHK(hipMemcpyAsync(&nev, evcount.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -2009,6 +2066,11 @@ template <typename R> struct CtxT : Ctx {
       case CHEM_STATE_RESID: { std::vector<int> h; res_id.download(h, nglob, stream); std::copy(h.begin(), h.end(), i32); return nglob; }
       case CHEM_STATE_MOLID: { std::vector<int> h; mol_id.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) i32[t] = (int32_t)top.id[h[t]]; return nglob; }
       case CHEM_STATE_ID: for (int t = 0; t < nglob; ++t) i64[t] = top.id[t]; return nglob;
+      case CHEM_STATE_CHARGE: {      // the device's by-tag array while a Coulomb pair is registered, the host mirror otherwise
+        if (coul_on() && qtag.p) { std::vector<R> h; qtag.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) d[t] = (double)h[t]; }
+        else for (int t = 0; t < nglob; ++t) d[t] = top.q[t];
+        return nglob;
+      }
       default: break;
     }
     // per-particle data of the owned range [G, G+n)
@@ -2061,18 +2123,23 @@ template <typename R> struct CtxT : Ctx {
     hipLaunchKernelGGL(k_kinetic<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, ekout.p);
     std::vector<double> he, hk, hl;
     eout.download(he, 3 * (size_t)nb, stream); ekout.download(hk, 4 * (size_t)nkb, stream); elist.download(hl, CHEM_MAX_LISTS, stream);
-    double acc[8 + CHEM_MAX_LISTS] = {0};   // elj, etab, vir, ek, px, py, pz, -, lists...
+    double acc[9 + CHEM_MAX_LISTS] = {0};   // elj, etab, vir, ek, px, py, pz, ecoul, lists..., vir coul
     for (int b = 0; b < nb; ++b) { acc[0] += he[3 * b]; acc[1] += he[3 * b + 1]; acc[2] += he[3 * b + 2]; }
+    if (coul_on()) {
+      std::vector<double> hq; eoutq.download(hq, 2 * (size_t)nb, stream);
+      for (int b = 0; b < nb; ++b) { acc[7] += hq[2 * b]; acc[8 + CHEM_MAX_LISTS] += hq[2 * b + 1]; }
+    }
     for (int b = 0; b < nkb; ++b) { acc[3] += hk[4 * b]; acc[4] += hk[4 * b + 1]; acc[5] += hk[4 * b + 2]; acc[6] += hk[4 * b + 3]; }
     for (int l = 0; l < CHEM_MAX_LISTS; ++l) acc[8 + l] = hl[l];
     if (dd_on && P > 1) {
       HIPCHK(hipMemcpyAsync(redbuf.p, acc, sizeof(acc), hipMemcpyHostToDevice, stream));
-      tr->allreduce_sum_f64(redbuf.p, 8 + CHEM_MAX_LISTS, stream);
+      tr->allreduce_sum_f64(redbuf.p, 9 + CHEM_MAX_LISTS, stream);
       HIPCHK(hipMemcpyAsync(acc, redbuf.p, sizeof(acc), hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
     }
     out->step = step; out->npart = nglob; out->ekin = acc[3]; out->temperature = 2.0 * acc[3] / (3.0 * nglob);
-    out->epot_lj = acc[0]; out->epot_tab = acc[1]; out->virial_nb = acc[2];
+    coul_epot = acc[7]; coul_virial = acc[8 + CHEM_MAX_LISTS];
+    out->epot_lj = acc[0]; out->epot_tab = acc[1]; out->virial_nb = acc[2] + coul_virial;      // (sum over ALL non-bonded pairs)
     for (int k = 0; k < 3; ++k) out->momentum[k] = acc[4 + k];
     for (size_t l = 0; l < top.lists.size(); ++l) { out->epot_list[l] = acc[8 + l]; out->list_size[l] = top.lists[l].size(); }
   }
@@ -2179,6 +2246,7 @@ template <typename R> struct CtxT : Ctx {
     else if (what == CHEM_STATE_MASS) { R w = (R)value; HIPCHK(hipMemcpyAsync(&v4.p[idx].w, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_STATE) { int w = (int)value; HIPCHK(hipMemcpyAsync(state.p + t, &w, sizeof(int), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_RESID) { int w = (int)value; HIPCHK(hipMemcpyAsync(res_id.p + t, &w, sizeof(int), hipMemcpyHostToDevice, stream)); }
+    else if (what == CHEM_STATE_CHARGE && coul_on() && qtag.p && !coul_dirty) { R w = (R)value; HIPCHK(hipMemcpyAsync(qtag.p + t, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }   // (otherwise the host mirror alone: uploaded with the registration)
     HIPCHK(hipStreamSynchronize(stream));
   }
 };
@@ -2283,6 +2351,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   }
   if (!t.contiguous) for (int64_t k = 0; k < n; ++k) t.id2tag[t.id[k]] = (int32_t)k;
   c.particles_dirty = c.pair_dirty = c.bonded_dirty = c.excl_dirty = c.labels_dirty = true; c.resort = true;
+  c.coul_dirty = true;
   c.step = 0; c.events.clear(); c.arena.clear();
   return 0;
   API_END(ctx)
@@ -2296,6 +2365,7 @@ int chem_modify_particle(chem_ctx* ctx, int64_t id, int what, double value) {
   else if (what == CHEM_STATE_STATE) c.top.state[t] = (int)value;
   else if (what == CHEM_STATE_MASS) { REQUIRE(value > 0, CHEM_EINVAL, "mass"); c.top.mass[t] = value; }
   else if (what == CHEM_STATE_RESID) c.top.res_id[t] = (int)value;
+  else if (what == CHEM_STATE_CHARGE) c.top.q[t] = value;
   else throw ChemError(CHEM_EINVAL, "modify_particle: selector");
   c.modify_particle(t, what, value);
   return 0;
@@ -2324,6 +2394,42 @@ int chem_nb_lj(chem_ctx* ctx, int t1, int t2, double eps, double sig, double rc,
   HostPairPot p; p.kind = (sig > 0 && rc > 0) ? 1 : 0; p.eps = eps; p.sig = sig; p.rc = rc;
   if (p.kind && shift_auto) { const double s2 = sig * sig / (rc * rc), s6 = s2 * s2 * s2; p.shift = -4.0 * eps * (s6 * s6 - s6); }
   CTX.pp[t1][t2] = p; CTX.pp[t2][t1] = p; CTX.pair_dirty = true;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_nb_coulomb(chem_ctx* ctx, int t1, int t2, double prefactor, double rc) {
+  API_BEGIN
+  REQUIRE(t1 >= 0 && t2 >= 0 && t1 < CHEM_MAX_TYPES && t2 < CHEM_MAX_TYPES, CHEM_EINVAL, "nb_coulomb: type out of range");
+  Ctx& c = CTX;
+  const bool was_on = c.coul_on();
+  if (prefactor == 0 || !(rc > 0)) { c.coul_mask[t1] &= ~(1u << t2); c.coul_mask[t2] &= ~(1u << t1); }
+  else {
+    uint32_t others[CHEM_MAX_TYPES];
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) others[a] = c.coul_mask[a];
+    others[t1] &= ~(1u << t2); others[t2] &= ~(1u << t1);
+    bool any = false;
+    for (uint32_t m : others) any = any || m != 0;
+    REQUIRE(!any || (prefactor == c.coul_k && rc == c.coul_rc), CHEM_ENOTIMPL,
+            "nb_coulomb: every registered type pair must share one (prefactor, cutoff); registered " + std::to_string(c.coul_k) + ", " + std::to_string(c.coul_rc) +
+            ", asked for " + std::to_string(prefactor) + ", " + std::to_string(rc) + " on type pair (" + std::to_string(t1) + "," + std::to_string(t2) + ")");
+    c.coul_k = prefactor; c.coul_rc = rc;
+    c.coul_mask[t1] |= 1u << t2; c.coul_mask[t2] |= 1u << t1;
+  }
+  // the type-pair mask of the force list, the kernel selection and the charge array follow the registration; switching the
+  // term on or off also changes the LDS footprint the tiles are planned for
+  c.pair_dirty = true; c.coul_dirty = true; c.bonded_dirty = true; c.resort = true;
+  if (was_on != c.coul_on()) c.geom_dirty = true;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_get_coulomb(chem_ctx* ctx, double* epot, double* virial) {
+  API_BEGIN
+  chem_obs o;
+  CTX.observe(&o);
+  if (epot) *epot = CTX.coul_epot;
+  if (virial) *virial = CTX.coul_virial;
   return 0;
   API_END(ctx)
 }
@@ -2619,6 +2725,13 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
     if (p.kind && p.rc > CTX.rc * (1.0 + 1e-12))
       throw ChemError(CHEM_EINVAL, "run: cutoff " + std::to_string(p.rc) + " of type pair (" + std::to_string(a) + "," + std::to_string(b) +
                                    ") exceeds the list cutoff max_cutoff = " + std::to_string(CTX.rc));
+  }
+  if (CTX.rc > 0 && CTX.coul_on() && CTX.coul_rc > CTX.rc * (1.0 + 1e-12)) {
+    int a = 0, b = 0;
+    for (a = 0; a < CHEM_MAX_TYPES && !CTX.coul_mask[a]; ++a) {}
+    for (b = 0; b < CHEM_MAX_TYPES && !((CTX.coul_mask[a] >> b) & 1u); ++b) {}
+    throw ChemError(CHEM_EINVAL, "run: Coulomb cutoff " + std::to_string(CTX.coul_rc) + " of type pair (" + std::to_string(std::min(a, b)) + "," + std::to_string(std::max(a, b)) +
+                                 ") exceeds the list cutoff max_cutoff = " + std::to_string(CTX.rc));
   }
   CTX.run(nsteps);
   return 0;

@@ -971,6 +971,23 @@ __global__ __launch_bounds__(256) void k_nlist_brute(int n, const Vec4<R>* __res
 //     particle: lane t handles neighbours t, t+TPP, ...; partial forces are combined with a
 //     segmented xor-shuffle reduction.  Full list => no atomics, deterministic sums.
 // =======================================================================================
+// Truncated Coulomb term (VerletListCoulombTruncated, gromacs_topology.py:866-878; rule set in include/chem_mi355.h):
+// U = k qi qj / r, F_i = k qi qj r_ij / r^3 for r^2 <= rc_qq^2, unshifted, on top of the pair's LJ / table term.  One
+// (k, rc_qq) for all type pairs; mask[ti] bit tj = the pair carries the term; charges by tag.
+template <typename R> struct CoulArgs { const R* qtag; const int* tag; const unsigned int* mask; double* eout; R k, rc2; };
+__device__ __forceinline__ float rsqrt_r(float x) { return __builtin_amdgcn_rsqf(x); }   // 1 ulp
+__device__ __forceinline__ double rsqrt_r(double x) { return 1.0 / sqrt(x); }
+// kqi = k * qi of the home particle; on = the type pair's mask bit
+template <typename R, bool ENERGY>
+__device__ __forceinline__ void coul_term(R kqi, R qj, bool on, R rc2, R r2, R dx, R dy, R dz, R& fx, R& fy, R& fz, double& e_q, double& v_q) {
+  if (on && r2 <= rc2) {
+    const R ri = rsqrt_r(r2);
+    const R e = kqi * qj * ri, ff = e * ri * ri;
+    fx += ff * dx; fy += ff * dy; fz += ff * dz;
+    if (ENERGY) { e_q += (double)e; v_q += (double)(ff * r2); }
+  }
+}
+
 // CUBIC: the host selects these instantiations only while a type pair of kind 3 exists, so that the others stay what they were
 template <typename R, bool ENERGY, bool CUBIC = false>
 __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
@@ -1012,13 +1029,15 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
   }
 }
 
-template <typename R, int TPP, bool ENERGY, bool CUBIC = false>
+// COUL: plus the truncated Coulomb term, charges read through tag[j] (launched only while a Coulomb pair is registered; these
+// instantiations know both table kinds)
+template <typename R, int TPP, bool ENERGY, bool CUBIC = false, bool COUL = false>
 __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ nlist, const int* __restrict__ nn, int S,
                                                     Box<R> box, const PairCore<R>* __restrict__ pcore,
                                                     const PairExt<R>* __restrict__ pext, int ntypes,
                                                     const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
-                                                    double half_skin, DevCtl* ctl) {
+                                                    double half_skin, DevCtl* ctl, CoulArgs<R> ca = CoulArgs<R>{}) {
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   for (int k = threadIdx.x; k < ntypes * ntypes; k += blockDim.x) spc[k] = pcore[k];
   __syncthreads();
@@ -1027,18 +1046,26 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
   const int i = gid / TPP, sub = gid % TPP;
   R fx = 0, fy = 0, fz = 0;
   double e_lj = 0, e_tab = 0, vir = 0;
+  [[maybe_unused]] double e_q = 0, v_q = 0;
   if (i < n) {
     const Vec4<R> xi = x4[i];
     const int ti = (int)xi.w;
     const int cnt = nn[i];
     const int4* row = reinterpret_cast<const int4*>(nlist + (size_t)i * S);
     const int pbase = ti * ntypes;
+    [[maybe_unused]] R kqi = 0; [[maybe_unused]] unsigned int crow = 0;
+    if constexpr (COUL) { kqi = ca.k * ca.qtag[ca.tag[i]]; crow = ca.mask[ti]; }
     // lane `sub` takes 4 consecutive neighbours per trip: one 16-byte index load, then four
     // independent position gathers in flight (rows are padded with the self index)
     for (int k = sub * 4; k < cnt; k += TPP * 4) {
       const int4 jj = row[k >> 2];
       const Vec4<R> xa = x4[jj.x], xb = x4[jj.y], xc = x4[jj.z], xd = x4[jj.w];
       const Vec4<R> xs[4] = {xa, xb, xc, xd};
+      [[maybe_unused]] R qs[4] = {0, 0, 0, 0};
+      if constexpr (COUL) {
+        const int ta = ca.tag[jj.x], tb = ca.tag[jj.y], tc = ca.tag[jj.z], td = ca.tag[jj.w];
+        qs[0] = ca.qtag[ta]; qs[1] = ca.qtag[tb]; qs[2] = ca.qtag[tc]; qs[3] = ca.qtag[td];
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const Vec4<R> xj = xs[u];
@@ -1047,6 +1074,7 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
         r2 = (k + u < cnt) ? r2 : (R)1e30;     // padding entries (self index) never interact
         const int pidx = pbase + (int)xj.w;
         pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+        if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
       }
     }
   }
@@ -1059,14 +1087,23 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
   if (i < n && sub == 0) f4[i] = mk4<R>(fx, fy, fz, (R)0);
   if (ENERGY) {
     // full list: every pair is visited from both ends -> half weights
-    __shared__ double red[3][4];
+    __shared__ double red[COUL ? 5 : 3][4];
     for (int o = 32; o > 0; o >>= 1) { e_lj += __shfl_xor(e_lj, o); e_tab += __shfl_xor(e_tab, o); vir += __shfl_xor(vir, o); }
     if (lane_id() == 0) { red[0][threadIdx.x >> 6] = e_lj; red[1][threadIdx.x >> 6] = e_tab; red[2][threadIdx.x >> 6] = vir; }
+    if constexpr (COUL) {
+      for (int o = 32; o > 0; o >>= 1) { e_q += __shfl_xor(e_q, o); v_q += __shfl_xor(v_q, o); }
+      if (lane_id() == 0) { red[3][threadIdx.x >> 6] = e_q; red[4][threadIdx.x >> 6] = v_q; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
       double a = 0, b = 0, c = 0;
       for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { a += red[0][k]; b += red[1][k]; c += red[2][k]; }
       eout[3 * blockIdx.x + 0] = 0.5 * a; eout[3 * blockIdx.x + 1] = 0.5 * b; eout[3 * blockIdx.x + 2] = 0.5 * c;
+      if constexpr (COUL) {
+        double d = 0, e = 0;
+        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { d += red[3][k]; e += red[4][k]; }
+        ca.eout[2 * blockIdx.x + 0] = 0.5 * d; ca.eout[2 * blockIdx.x + 1] = 0.5 * e;
+      }
     }
   }
 }
@@ -1115,6 +1152,14 @@ constexpr float kRefCells = 2.5f;
 #define CHEM_DYN_LDS(R) \
   extern __shared__ __attribute__((aligned(16))) unsigned char chem_dyn_lds[]; \
   Vec4<R>* const sx = reinterpret_cast<Vec4<R>*>(chem_dyn_lds)
+
+// Bytes of the force kernel's staged image of a tile of `cap` slots (fp32: 16-byte slots; fp64: 24-byte slots + type bytes, see
+// tile_fill), and where the charge words of k_pair_tiles MODE 4 start behind it: one R per slot, 16-byte aligned.
+template <typename R> __host__ __device__ constexpr size_t pair_img_bytes(int cap) {
+  return sizeof(R) == 8 ? (size_t)(cap + 5) * 25 + 64 : (size_t)(cap + 5) * 16 + 16;
+}
+template <typename R> __host__ __device__ constexpr size_t coul_q_offset(int cap) { return (pair_img_bytes<R>(cap) + 15) & ~(size_t)15; }
+template <typename R> __host__ __device__ constexpr size_t coul_img_bytes(int cap) { return coul_q_offset<R>(cap) + (size_t)(cap + 4) * sizeof(R); }
 
 // Descriptor tables of one tile, computed ONCE per rebuild by k_tile_desc and kept in HBM
 // (~1.3 KB per tile); every later launch copies them into LDS with one coalesced read instead
@@ -1237,13 +1282,17 @@ __device__ __forceinline__ void slot_store(Vec4<R>* const sx, const int CAP, int
     d3_types<R>(sx, CAP)[dst] = (unsigned char)(int)p.w;
   } else sx[dst] = p;
 }
-template <typename R, int BS, bool LEAN = false, bool D3 = false>
+// QW (k_pair_tiles MODE 4, not LEAN): one charge word per slot into sq[], tag[g] -> qtag; these loads too are issued before the
+// first LDS write (two dependent latencies instead of one; the dummy slot carries charge 0)
+template <typename R, int BS, bool LEAN = false, bool D3 = false, bool QW = false>
 __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx, const int CAP,
-                                          const Vec4<R>* __restrict__ x4, int wmode) {
+                                          const Vec4<R>* __restrict__ x4, int wmode, const int* __restrict__ tagv = nullptr,
+                                          const R* __restrict__ qtag = nullptr, R* const sq = nullptr) {
   constexpr int NW = BS / 64, RPW = (NROW + NW - 1) / NW;
   const int t = threadIdx.x;
   const int w = t >> 6, l = t & 63;
   if (t == 0) slot_store<R, D3>(sx, CAP, T.geom[3], mk4<R>((R)1e18, (R)1e18, (R)1e18, (R)0));
+  if constexpr (QW) { if (t == 0) sq[T.geom[3]] = (R)0; }
   if constexpr (LEAN) {
     // register-lean variant (list build: staging is <2 % of the tile's time, occupancy matters more)
     for (int r = w; r < NROW; r += NW) {
@@ -1266,6 +1315,8 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
   }
   Vec4<R> pv[RPW][2];
   int pk_[RPW][2], pg[RPW][2];
+  [[maybe_unused]] int ptg[RPW][2];
+  [[maybe_unused]] R pq[RPW][2];
 #pragma unroll
   for (int rr = 0; rr < RPW; ++rr) {
     const int r = w + rr * NW;
@@ -1281,8 +1332,15 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
         const int g = T.cellg[r][k] + (e - T.celloff[r][k]);
         pk_[rr][c] = k; pg[rr][c] = g;
         pv[rr][c] = x4[g];
+        if constexpr (QW) ptg[rr][c] = tagv[g];
       }
     }
+  }
+  if constexpr (QW) {
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) pq[rr][c] = pk_[rr][c] >= 0 ? qtag[ptg[rr][c]] : (R)0;
   }
 #pragma unroll
   for (int rr = 0; rr < RPW; ++rr) {
@@ -1297,6 +1355,7 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
           p.x = pos_local(p.x, T.cellshx[r][k], T.org[0], T.qs[0]); p.y = pos_local(p.y, T.rowshy[r], T.org[1], T.qs[1]); p.z = pos_local(p.z, T.rowshz[r], T.org[2], T.qs[2]);
           if (wmode) p.w = idx_as_real((pg[rr][c] << 5) | (int)p.w, (R)0);
           slot_store<R, D3>(sx, CAP, dst, p);
+          if constexpr (QW) sq[dst] = pq[rr][c];
         }
       }
     }
@@ -1315,6 +1374,7 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
         p.x = pos_local(p.x, T.cellshx[r][k], T.org[0], T.qs[0]); p.y = pos_local(p.y, T.rowshy[r], T.org[1], T.qs[1]); p.z = pos_local(p.z, T.rowshz[r], T.org[2], T.qs[2]);
         if (wmode) p.w = idx_as_real((g << 5) | (int)p.w, (R)0);
         slot_store<R, D3>(sx, CAP, dst, p);
+        if constexpr (QW) sq[dst] = qtag[tagv[g]];
       }
     }
   }
@@ -2061,6 +2121,9 @@ struct UniLJ { float rc2, lj1, lj2, pad; double drc2, dlj1, dlj2; };   // all li
 // MODE 0: general (type-pair table in LDS, tables allowed)  1: LJ/off pairs only, branch-free
 //      2: uniform LJ -- every listed pair has the same parameters (kernel arguments / SGPRs)
 //      3: general as 0, with the piecewise-cubic table kind (launched only while a type pair of kind 3 exists)
+//      4: general as 3, plus the truncated Coulomb term (launched only while a Coulomb pair is registered; TPP 1, 512 threads).
+//         One charge word per slot is staged behind the image (coul_q_offset), read with the slot; the home particle's k*q,
+//         its row of the type-pair mask and rc_qq^2 are registers.  No inline bonds in this mode (the host keeps them off).
 // Tiles of one launch: [base1, base1+n1) followed by [base2, ...).  The decomposed path launches the
 // tiles whose stencil stays inside the own layers ("interior": they need no ghost) while the halo
 // exchange is still in flight on the communication stream, and the two boundary tile layers after it.
@@ -2148,17 +2211,20 @@ struct DecideArgs { const double* gathered; int n; volatile int* host_flag; int 
 // DIAG = true: diagnostic instantiation with per-block phase stamps (`dbg`) and early exits (`ablate`: 1 stop after
 // staging, 2 skip staging, 3 descriptor only, 4 dispatch only); the production instantiation carries neither.
 // guard != 0: speculative launch of the decomposed path -- leave at once while a rebuild is pending.
-template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG = false>
-__global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536) / 256) void k_pair_tiles(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+// (the body of k_pair_tiles and of k_pair_tiles_q, which alone takes the Coulomb arguments: the kernels of every other mode keep
+//  their argument block)
+template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG>
+__device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                    const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
                                                    const int* __restrict__ nnh, int S16,
                                                    const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
                                                    int ntypes, const Vec4<R>* __restrict__ tab, UniLJ uni, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
-                                                   DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
-                                                   double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
-                                                   const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
-  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3;
+                                                   DecideArgs da, uint4* __restrict__ bslots,
+                                                   double bond_K, double bond_r0, int bond_mode, ActMask bact,
+                                                   const BondRec<R>* __restrict__ brec,
+                                                   const CoulArgs<R> ca) {
+  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3 || MODE == 4, COUL = MODE == 4;
 #ifndef CHEM_NCH
 #define CHEM_NCH 3
 #endif
@@ -2245,11 +2311,14 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
   };
   if (slice < nhome) locate(slice);
   constexpr bool D3 = sizeof(R) == 8;     // fp64: 24-byte slots + type bytes (see tile_fill)
-  if (!DIAG || ablate != 2) tile_fill<R, BS, false, D3>(T, sx, CAP, x4, 0);
+  [[maybe_unused]] R* const sq = reinterpret_cast<R*>(chem_dyn_lds + (COUL ? coul_q_offset<R>(CAP) : 0));
+  if constexpr (COUL) tile_fill<R, BS, false, D3, true>(T, sx, CAP, x4, 0, ca.tag, ca.qtag, sq);
+  else if (!DIAG || ablate != 2) tile_fill<R, BS, false, D3>(T, sx, CAP, x4, 0);
   __syncthreads();
   if (DIAG && ablate == 1) return;   // diagnostic: staging only
   if (DIAG && dbg) st2 = wall_clock64();
   double e_lj = 0, e_tab = 0, vir = 0;
+  [[maybe_unused]] double e_q = 0, v_q = 0;
   for (int q0 = 0; q0 < nhome; q0 += NSL) {
     const int q = q0 + slice;
     R fx = 0, fy = 0, fz = 0;
@@ -2258,6 +2327,8 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
       Vec4<R> xi;
       if constexpr (D3) { xi = lds_gather3d(sx, hslot); xi.w = (R)d3_types<R>(sx, CAP)[hslot]; } else xi = sx[hslot];
       const int pbase = (int)xi.w * ntypes;
+      [[maybe_unused]] R kqi = 0; [[maybe_unused]] unsigned int crow = 0;
+      if constexpr (COUL) { kqi = ca.k * sq[hslot]; crow = ca.mask[(int)xi.w]; }
       // Uniform-LJ fp32 path: (x, y) of one neighbour live in an aligned register pair (the 16-byte LDS read returns
       // x y z w in four consecutive VGPRs), so the differences, their squares and the force accumulation of the x and y
       // components are PACKED fp32 instructions on that pair -- no register shuffling as when the compiler pairs up two
@@ -2303,11 +2374,13 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           Vec4<R> xs[4];
+          [[maybe_unused]] R qs[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {   // 4 LDS gathers in flight
             const unsigned int sl = (wds[2 * h + (u >> 1)] >> ((u & 1) * 16)) & 0xffff;
             if constexpr (D3) { xs[u] = lds_gather3d(sx, sl); if (MODE != 2 || ENERGY) xs[u].w = (R)d3_types<R>(sx, CAP)[sl]; }
             else xs[u] = lds_gather4<R>(sx, sl);
+            if constexpr (COUL) qs[u] = sq[sl];
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -2322,6 +2395,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
             } else {
               const int pidx = pbase + (int)xj.w;
               pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+              if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
             }
           }
         }
@@ -2348,7 +2422,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
         }
       }
       fx += (R)fxy.x; fy += (R)fxy.y;      // (packed x/y accumulators of the uniform-LJ fp32 path; zero otherwise)
-      if (bslots && sub == 0) {
+      if (!COUL && bslots && sub == 0) {
         // Inline harmonic bonds (FixedPairListHarmonic, gromacs_topology.py:949-961; reaction bonds reaction_setup.py:449-467):
         // the LDS slots of the bonded (= excluded) partners are recorded at every rebuild, the geometry comes from the staged
         // image (tile-local coordinates: 2.4e-7 in the fp32 build, exact in fp64) -- no bonded launch, no second pass over f4.
@@ -2406,16 +2480,51 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
     o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = 0; o[5] = tile;
   }
   if (ENERGY) {
-    __shared__ double red[3][BS / 64];
+    __shared__ double red[COUL ? 5 : 3][BS / 64];
     for (int o = 32; o > 0; o >>= 1) { e_lj += __shfl_xor(e_lj, o); e_tab += __shfl_xor(e_tab, o); vir += __shfl_xor(vir, o); }
     if (lane_id() == 0) { red[0][threadIdx.x >> 6] = e_lj; red[1][threadIdx.x >> 6] = e_tab; red[2][threadIdx.x >> 6] = vir; }
+    if constexpr (COUL) {
+      for (int o = 32; o > 0; o >>= 1) { e_q += __shfl_xor(e_q, o); v_q += __shfl_xor(v_q, o); }
+      if (lane_id() == 0) { red[3][threadIdx.x >> 6] = e_q; red[4][threadIdx.x >> 6] = v_q; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
       double a = 0, b = 0, c = 0;
       for (int k = 0; k < BS / 64; ++k) { a += red[0][k]; b += red[1][k]; c += red[2][k]; }
       eout[3 * blockIdx.x + 0] = 0.5 * a; eout[3 * blockIdx.x + 1] = 0.5 * b; eout[3 * blockIdx.x + 2] = 0.5 * c;
+      if constexpr (COUL) {
+        double d = 0, e = 0;
+        for (int k = 0; k < BS / 64; ++k) { d += red[3][k]; e += red[4][k]; }
+        ca.eout[2 * blockIdx.x + 0] = 0.5 * d; ca.eout[2 * blockIdx.x + 1] = 0.5 * e;
+      }
     }
   }
+}
+
+template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG = false>
+__global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536) / 256) void k_pair_tiles(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                   const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                   const int* __restrict__ nnh, int S16,
+                                                   const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                   int ntypes, const Vec4<R>* __restrict__ tab, UniLJ uni, double* __restrict__ eout,
+                                                   double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
+                                                   DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
+                                                   double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
+                                                   const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
+  static_assert(MODE != 4, "MODE 4 is k_pair_tiles_q");
+  pair_tiles_body<R, TPP, ENERGY, BS, MODE, DIAG>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, uni, eout, half_skin, ctl, guard, ablate, dbg,
+                                                  sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, brec, CoulArgs<R>{});
+}
+// MODE 4: one lane per particle, 512 threads; no inline bonds
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_q(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                   const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                   const int* __restrict__ nnh, int S16,
+                                                   const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                   int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                   double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CoulArgs<R> ca) {
+  pair_tiles_body<R, 1, ENERGY, 512, 4, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, ca);
 }
 
 // =======================================================================================
@@ -3568,6 +3677,26 @@ __global__ void k_apply_props(int nchg, const PropChangeDev* __restrict__ chg, i
   if (c.set_state) state[c.tag] = c.state;
   const int i = rtag[c.tag];
   if (i >= 0) { x4[i].w = (R)c.type; v4[i].w = (R)c.mass; }
+}
+
+// Charges by tag (the array of the Coulomb term, chem_nb_coulomb): launched behind k_react_apply / k_apply_props only while a
+// Coulomb pair is registered, so that those two kernels and their argument blocks stay what they were.  Every rank of a
+// decomposition holds all charges and applies every event.  A reaction sets the charge wherever it names a new type.
+struct ReactQ { int new_type_1, new_type_2; double new_q_1, new_q_2; };
+struct ReactQSet { ReactQ r[CHEM_MAX_REACTIONS]; };
+template <typename R>
+__global__ void k_react_apply_q(int nc, const Candidate* __restrict__ c, const int* __restrict__ st, ReactQSet rqs, R* __restrict__ qtag) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nc || st[k] != 2) return;
+  const Candidate cd = c[k];
+  const ReactQ rq = rqs.r[cd.r];
+  if (rq.new_type_1 >= 0) qtag[cd.a] = (R)rq.new_q_1;
+  if (rq.new_type_2 >= 0) qtag[cd.b] = (R)rq.new_q_2;
+}
+template <typename R>
+__global__ void k_apply_props_q(int nchg, const PropChangeDev* __restrict__ chg, R* __restrict__ qtag) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < nchg) qtag[chg[k].tag] = (R)chg[k].q;
 }
 
 // ---- dissociation reactions (chem_dissociation_add; rule set in include/chem_mi355.h) ----------------------------

@@ -113,6 +113,23 @@ class Engine:
             self._ck(self._interp_entry("nb_table_interp", itype)(self.ctx, t1, t2, e.shape[0], r0, dr, _ptr(e, C.c_double),
                                                                   _ptr(f, C.c_double), rc, int(itype)))
 
+    def nb_coulomb(self, t1, t2, prefactor, rc):
+        """Truncated Coulomb term U = prefactor q_i q_j / r for r <= rc on the type pair, on top of its LJ / table
+        (include/chem_mi355.h, chem_nb_coulomb); prefactor = 0 removes it.  One (prefactor, rc) for all pairs."""
+        fn = getattr(self.api, "nb_coulomb", None)
+        if fn is None:
+            raise NotImplementedError("CoulombTruncated: the CPU checker has no Coulomb term")
+        self._ck(fn(self.ctx, int(t1), int(t2), float(prefactor), float(rc)))
+
+    def get_coulomb(self):
+        """(energy, sum over pairs of r.F) of the Coulomb term at the current positions."""
+        fn = getattr(self.api, "get_coulomb", None)
+        if fn is None:
+            raise NotImplementedError("CoulombTruncated: the CPU checker has no Coulomb term")
+        e, v = C.c_double(0.0), C.c_double(0.0)
+        self._ck(fn(self.ctx, C.byref(e), C.byref(v)))
+        return e.value, v.value
+
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
         h = self._ck(self.api.list_create(self.ctx, arity, kind, 1 if by_types else 0))
@@ -261,7 +278,7 @@ class Engine:
             out = np.empty((n, 3), dtype=np.float64)
         elif what.upper() == "IMAGE":
             out = np.empty((n, 3), dtype=np.int32)
-        elif what.upper() == "MASS":
+        elif what.upper() in ("MASS", "CHARGE"):
             out = np.empty(n, dtype=np.float64)
         elif what.upper() == "ID":
             out = np.empty(n, dtype=np.int64)

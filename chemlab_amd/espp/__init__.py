@@ -164,11 +164,13 @@ class _DomainDecomposition(object):
         e = self.system.engine
         k = int(np.searchsorted(np.sort(self._ids), pid))
         g = lambda w: e.get_state(w)[k]
+        # (the CPU checker keeps no charges: an engine without the Coulomb entry points reports 0, as before)
+        q = float(g("CHARGE")) if getattr(getattr(e, "api", None), "nb_coulomb", None) is not None else 0.0
         return _Particle(id=pid, pos=Real3D(*g("POS")), v=Real3D(*g("VEL")), f=Real3D(*g("FORCE")), type=int(g("TYPE")),
-                         mass=float(g("MASS")), state=int(g("STATE")), res_id=int(g("RESID")), imageBox=Int3D(*g("IMAGE")), q=0.0)
+                         mass=float(g("MASS")), state=int(g("STATE")), res_id=int(g("RESID")), imageBox=Int3D(*g("IMAGE")), q=q)
 
     def modifyParticle(self, pid, prop, value):
-        self.system.engine.modify_particle(pid, {"type": "TYPE", "state": "STATE", "mass": "MASS", "res_id": "RESID"}[prop], value)
+        self.system.engine.modify_particle(pid, {"type": "TYPE", "state": "STATE", "mass": "MASS", "res_id": "RESID", "q": "CHARGE"}[prop], value)
 
 
 def _node_grid(n, *a, **k):
@@ -479,6 +481,23 @@ class _VerletListTabulated(_VerletListInteraction):
         self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
 
 
+class _CoulombTruncated(_Pot):
+    """interaction.CoulombTruncated(prefactor, cutoff): U = prefactor q_i q_j / r inside the cutoff, unshifted
+    (rule set: include/chem_mi355.h, chem_nb_coulomb)."""
+
+    def __init__(self, prefactor=1.0, cutoff=None):
+        self.prefactor, self.cutoff = prefactor, cutoff
+
+
+class _VerletListCoulombTruncated(_VerletListInteraction):
+    """interaction.VerletListCoulombTruncated(vl).setPotential(type1, type2, CoulombTruncated(...)) (gromacs_topology.py:866-878)."""
+    label = "coulomb"
+
+    def setPotential(self, type1, type2, potential):
+        self._pots[(min(type1, type2), max(type1, type2))] = potential
+        self.system.engine.nb_coulomb(type1, type2, potential.prefactor, potential.cutoff)
+
+
 class _VerletListMixedTabulated(_VerletListInteraction):
     """interaction.VerletListMixedTabulated(vl).setPotential(type1, type2, MixedTabulated(...)) (gromacs_topology.py:756-790)."""
     label = "mix_tab"
@@ -573,9 +592,7 @@ interaction = _ns(
     FixedPairListFENELennardJones=_FixedListInteraction, FixedPairListTypesFENELennardJones=_FixedListTypesInteraction,
     FixedPairListLennardJones=_FixedListInteraction, FixedPairListTypesLennardJones=_FixedListTypesInteraction,
     FixedQuadrupleListDihedralHarmonic=_FixedListInteraction, FixedQuadrupleListTypesDihedralHarmonic=_FixedListTypesInteraction,
-    # out of scope
-    CoulombTruncated=_unsupported("interaction.CoulombTruncated"),
-    VerletListCoulombTruncated=_unsupported("interaction.VerletListCoulombTruncated"),
+    CoulombTruncated=_CoulombTruncated, VerletListCoulombTruncated=_VerletListCoulombTruncated,
     TabulatedAngular=_TabulatedAngular, TabulatedDihedral=_TabulatedDihedral,
     FixedQuadrupleListTabulatedDihedral=_FixedListInteraction, FixedQuadrupleListTypesTabulatedDihedral=_FixedListTypesInteraction,
     FixedPairListTabulated=_FixedListInteraction, FixedPairListTypesTabulated=_FixedListTypesInteraction,
@@ -1126,8 +1143,10 @@ class _PotentialEnergy(_Observable):
         self.interaction = interaction_
 
     def compute(self):
-        o = self.system.engine.observe()
         i = self.interaction
+        if isinstance(i, _VerletListCoulombTruncated):
+            return self.system.engine.get_coulomb()[0]
+        o = self.system.engine.observe()
         if isinstance(i, _VerletListLennardJones):
             return o["epot_lj"]
         if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated)):    # (one tabulated-energy accumulator: plain and mixed tables together)

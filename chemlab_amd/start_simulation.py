@@ -168,11 +168,9 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     parser.save_to_file("%sparams.out" % args.output_prefix, args)
     if args.pressure is not None:
         raise NotImplementedError("barostats are outside the MI355X hot-path scope")
-    if args.coulomb_cutoff > 0:
-        log("note: coulomb_cutoff=%g ignored -- truncated Coulomb is outside the hot-path scope" % args.coulomb_cutoff)
     kb, mass_factor = args.kb, args.mass_factor
     lj_cutoff, cg_cutoff = args.lj_cutoff, args.cg_cutoff
-    max_cutoff = max(lj_cutoff, cg_cutoff)            # ignores coulomb_cutoff
+    max_cutoff = max(lj_cutoff, cg_cutoff)            # as the reference, without coulomb_cutoff: a larger one is refused at run()
     gt = gromacs_topology.GromacsTopology(args.top).read()
     conf = files_io.GROFile(args.conf).read()
     box = conf.box
@@ -233,14 +231,15 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     table_groups = args.table_groups.split(",") if args.table_groups else []
     cr_observs = {}                                       # conversion observables of mixed tables (start_simulation.py:298-299)
     gromacs_topology.set_nonbonded_interactions(espressopp, system, gt, verletlist, lj_cutoff, tab_cutoff=cg_cutoff, tables_=table_groups,
-                                                table_dir=os.path.dirname(os.path.abspath(args.top)), cr_observs=cr_observs)
+                                                table_dir=os.path.dirname(os.path.abspath(args.top)), cr_observs=cr_observs,
+                                                qq_cutoff=args.coulomb_cutoff, log=log)
     bonded = gromacs_topology.set_bonded_interactions(espressopp, system, gt, dynamic_types,
                                                       table_dir=os.path.dirname(os.path.abspath(args.top)))
     angles = gromacs_topology.set_angle_interactions(espressopp, system, gt, dynamic_types,
                                                      table_dir=os.path.dirname(os.path.abspath(args.top)))
     dihedrals = gromacs_topology.set_dihedral_interactions(espressopp, system, gt, dynamic_types,
                                                            table_dir=os.path.dirname(os.path.abspath(args.top)))
-    pairs14 = gromacs_topology.set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_types)   # start_simulation.py:308-309
+    pairs14 = gromacs_topology.set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_types, qq_cutoff=args.coulomb_cutoff)   # start_simulation.py:308-309
     if args.max_force > -1:                               # start_simulation.py:320-324, before the thermostat
         integrator.addExtension(espressopp.integrator.CapForce(system, args.max_force))
         log("Cap force to %s" % args.max_force)

@@ -226,7 +226,7 @@ def apply(spec, eng, thermostat=True, reactions=True):
     eng.set_cutoff(spec["rc"], spec["skin"])
     eng.set_dt(spec["dt"])
     eng.set_particles(spec["ids"], spec["types"], spec["pos"], spec["mass"], vel=spec.get("vel"),
-                      state=spec.get("state"), res_id=spec.get("res_id"))
+                      state=spec.get("state"), res_id=spec.get("res_id"), **({"q": spec["q"]} if "q" in spec else {}))
     for lj in spec.get("lj", []):               # (t1, t2, eps, sigma, rc[, shift_auto]): shift_auto defaults to on
         eng.nb_lj(*lj[:5], lj[5] if len(lj) > 5 else True)
     for tb in spec.get("tables", []):           # (t1, t2, r0, dr, e, f, rc[, itype]): linear interpolation without itype
@@ -234,6 +234,8 @@ def apply(spec, eng, thermostat=True, reactions=True):
             eng.nb_table(*tb[:7], itype=tb[7])
         else:
             eng.nb_table(*tb[:7])
+    for cq in spec.get("coulomb", []):          # (t1, t2, prefactor, rc): truncated Coulomb term on top of the pair's LJ / table
+        eng.nb_coulomb(*cq)
     handles = {}
     for i, l in enumerate(spec.get("lists", [])):
         h = eng.list_create(l["arity"], l["kind"], False)

@@ -83,6 +83,7 @@ extern "C" {
 #define CHEM_STATE_IMAGE   9   /* int32[n*3] periodic image counters               */
 #define CHEM_STATE_MOLID  10   /* int32[n]  lowest particle id of the bonded cluster */
 #define CHEM_STATE_POS_UNFOLDED 11 /* double[n*3] = pos + image*L                  */
+#define CHEM_STATE_CHARGE  12  /* double[n]; also a `what` of chem_modify_particle  */
 
 typedef struct chem_ctx chem_ctx;
 
@@ -181,7 +182,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
                        const double* pos, const double* vel, const double* mass,
                        const double* q, const int32_t* state, const int32_t* res_id);
 /* storage.modifyParticle(pid, 'type'|'state'|'mass', v)  examples/atrp_lj/hooks.py:63-65 */
-int chem_modify_particle(chem_ctx* ctx, int64_t id, int what /*CHEM_STATE_TYPE|STATE|MASS|RESID*/, double value);
+int chem_modify_particle(chem_ctx* ctx, int64_t id, int what /*CHEM_STATE_TYPE|STATE|MASS|RESID|CHARGE*/, double value);
 /* DynamicExcludeList(integrator, gt.exclusions)  start_simulation.py:189 */
 int chem_set_exclusions(chem_ctx* ctx, int64_t n, const int64_t* id_pairs);
 
@@ -213,6 +214,29 @@ int chem_nb_table(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double
  * A type pair may be re-sent with another kind (or as LJ) between two chem_run calls. */
 int chem_nb_table_interp(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0, double dr,
                          const double* e, const double* f, double rc, int itype);
+
+/* interaction.CoulombTruncated(prefactor, cutoff) via VerletListCoulombTruncated.setPotential(type1, type2, potential)
+ * gromacs_topology.py:866-878 (prefactor = 138.935485 * fudgeQQ, one potQQ for every type pair).  Registers the term for
+ * the type pair (symmetric); prefactor == 0 or rc <= 0 removes it.  All registered pairs must share one (prefactor, rc):
+ * anything else is CHEM_ENOTIMPL.  The arithmetic of CoulombTruncated is in the external fork, so this rule set is this
+ * build's own ([EXT-RECALL]).  With k = prefactor and rc_qq = rc, for every pair on the Verlet list that
+ * is not excluded and has r^2 <= rc_qq^2 (inclusive, as LJ's r^2 <= rc^2):
+ *     U = k q_i q_j / r,     F_i = k q_i q_j r_ij / r^3,     the energy is not shifted.
+ *   - the term comes ON TOP of whatever LJ or table the type pair carries; a pair without either (sigma = 0) still gets it;
+ *   - excluded pairs get nothing; type pairs that were not registered get nothing;
+ *   - rc_qq may be smaller or larger than the pair's LJ / table cutoff, but not larger than max_cutoff: chem_run refuses
+ *     that with CHEM_EINVAL naming the type pair;
+ *   - charges are per particle (chem_set_particles `q`); a reaction (new_q_1/2, set wherever the reaction names a new type),
+ *     neighbour rule, ATRP flip, dissociation or chem_modify_particle(CHEM_STATE_CHARGE) that changes a charge acts from the
+ *     next force evaluation on;
+ *   - while a pair is registered the force kernels are built for option tpp = 1 (or 0) and pair_block = 512 only: other
+ *     values are CHEM_EINVAL at the next evaluation; harmonic bonds are not evaluated inline (option bonds_inline has no
+ *     effect). */
+int chem_nb_coulomb(chem_ctx* ctx, int t1, int t2, double prefactor, double rc);
+/* Energy and sum over pairs of r.F of the Coulomb term, evaluated as chem_observe does (at the current positions; zeros while
+ * no pair is registered).  Either pointer may be NULL.  chem_obs.epot_lj / epot_tab keep their meaning; chem_obs.virial_nb,
+ * the sum over ALL non-bonded pairs, includes the Coulomb part. */
+int chem_get_coulomb(chem_ctx* ctx, double* epot, double* virial);
 
 /* ---- bonded lists -------------------------------------------------------------------- */
 /* FixedPairList/TripleList/QuadrupleList(storage) + FixedXListYyy(system, list, potential)
