@@ -168,6 +168,8 @@ PRODUCT_ONLY = {
     "table_create_interp": (_i, [_P, _i64, _d, _d, _pd, _pd, _i]),
     "nb_coulomb": (_i, [_P, _i, _i, _d, _d]),   # (the CPU oracle has no Coulomb term)
     "get_coulomb": (_i, [_P, _pd, _pd]),
+    "list_set_hybrid": (_i, [_P, _i, _d, _d]),   # (the CPU oracle has no hybrid lists)
+    "list_get_lambda": (_i64, [_P, _i, _pd, _i64]),
 }
 
 

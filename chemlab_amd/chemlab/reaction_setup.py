@@ -149,10 +149,13 @@ class SetupReactions(object):
             # integrator extensions (ATRPActivator) go to the driver, post-processes to the group's reactions (reaction_setup.py:470-483)
             self.extensions_to_integrator.extend(x for _, (x, inv) in group_ext if inv is None)
             group_pp = [(name, v) for name, v in group_ext if v[1] is not None]
-            fpl = e.FixedPairList(self.system.storage)
+            # --t_hybrid_bond N (reaction_setup.py:444-467): the group's bonds start at lambda = 0; the driver registers the list
+            # with integrator.FixedListDynamicResolution, which brings them to full strength over N steps
+            hybrid = getattr(self.args, "t_hybrid_bond", 0) > 0 if self.args is not None else False
+            fpl = e.FixedPairListLambda(self.system.storage, 0.0) if hybrid else e.FixedPairList(self.system.storage)
             pot_class = getattr(e.interaction, group["potential"])
             pot = pot_class(**group["potential_options"])
-            inter_class = getattr(e.interaction, "FixedPairList%s" % group["potential"])
+            inter_class = getattr(e.interaction, "FixedPairList%s%s" % ("Lambda" if hybrid else "", group["potential"]))
             inter = inter_class(self.system, fpl, pot)
             self.system.addInteraction(inter, "fpl_%s" % gname)
             self.fpls.append((gname, fpl, inter))

@@ -288,6 +288,7 @@ template <typename R> struct CtxT : Ctx {
   bool bonds_inline() {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
     if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
+    if (top.any_hybrid()) return false;      // (the force kernel knows one K, one r0 and no lambda: a hybrid list is never evaluated there)
     // the exclusion set must BE the bond set (bonds are a subset: bonds_excluded; both are duplicate-free): equal counts
     size_t nb2 = 0;
     for (const auto& l : top.lists) if (l.arity == 2) nb2 += (size_t)l.size();
@@ -347,6 +348,11 @@ template <typename R> struct CtxT : Ctx {
   int ntiles = 0;
   DBuf<int> excl_start, excl_list; int has_excl = 0;
   DBuf<int> bstart; DBuf<BondedEntry> bent; DBuf<BondedParam> bpar; int64_t nbent = 0; bool bonds_only = false;
+  // hybrid pair lists (chem_list_set_hybrid): (lambda0, rate) per parameter slot; has_hybrid selects the k_bonded*_hyb kernels.
+  // force_step_off: 1 while the run loop evaluates the forces of the step it is about to complete (positions of step + 1)
+  DBuf<double2> bhyb; bool has_hybrid = false; int64_t force_step_off = 0;
+  std::vector<std::array<double, 2>> stage_hyb;
+  HybridArgs hybrid_args() const { return HybridArgs{bhyb.p, (long long)(step + force_step_off)}; }
   DBuf<PairCore<R>> pcore; DBuf<PairExt<R>> pext;
   DBuf<DevCtl> ctl;
   DBuf<unsigned long long> blockmax;
@@ -798,6 +804,13 @@ template <typename R> struct CtxT : Ctx {
       }
     }
     bpar.alloc(std::max<size_t>(hp.size(), 1)); skeys.alloc(std::max<size_t>(hk.size(), 1));
+    has_hybrid = top.any_hybrid();
+    if (has_hybrid && nslot) {
+      static_assert(sizeof(std::array<double, 2>) == sizeof(double2), "layout");
+      top.hybrid_params(hp, stage_hyb);
+      bhyb.alloc(stage_hyb.size());
+      HIPCHK(hipMemcpyAsync(bhyb.p, stage_hyb.data(), stage_hyb.size() * sizeof(double2), hipMemcpyHostToDevice, stream));
+    }
     if (nslot) {
       HIPCHK(hipMemcpyAsync(bpar.p, hp.data(), hp.size() * sizeof(BondedParam), hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(skeys.p, hk.data(), hk.size() * sizeof(SlotKey), hipMemcpyHostToDevice, stream));
@@ -812,7 +825,12 @@ template <typename R> struct CtxT : Ctx {
       const size_t have = (size_t)l.size();
       for (size_t e = list_uploaded[li]; e < have; ++e) {
         const int32_t* t = &l.ent[e * l.arity];
-        ne.push_back(make_int4(t[0], t[1], l.arity > 2 ? t[2] : -1, l.arity > 3 ? t[3] : -1)); nl.push_back((int)li);
+        int z = l.arity > 2 ? t[2] : -1;
+        if (l.hybrid) {      // the birth step travels in the unused third tag (BondedEntry::t2)
+          if (l.birth[e] < 0 || l.birth[e] > 0x7fffffff) throw ChemError(CHEM_ESTATE, "hybrid list: birth step beyond 2^31 - 1");
+          z = encode_birth(l.birth[e]);
+        }
+        ne.push_back(make_int4(t[0], t[1], z, l.arity > 3 ? t[3] : -1)); nl.push_back((int)li);
       }
       fent_members += (have - list_uploaded[li]) * (size_t)(l.arity == 4 ? 8 : l.arity);
       list_uploaded[li] = have;
@@ -1309,10 +1327,17 @@ template <typename R> struct CtxT : Ctx {
       }
       if (timed) tbeg(3);
       const int nown = inl ? (int)std::min<int64_t>(nb_owner, excl_over) : nb_owner;   // (inline bonds: the list holds the owners with > kBondSlots exclusions only)
-      if (bonds_only) hipLaunchKernelGGL((k_bonded_work<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
+      if (has_hybrid) {      // lambda of every hybrid entry at the step these forces belong to
+        if (bonds_only) hipLaunchKernelGGL((k_bonded_work_hyb<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
+        else hipLaunchKernelGGL((k_bonded_work_hyb<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
+      }
+      else if (bonds_only) hipLaunchKernelGGL((k_bonded_work<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
       else hipLaunchKernelGGL((k_bonded_work<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
       if (timed) tend();
-    } else if (nbent > 0)
+    } else if (nbent > 0 && has_hybrid)
+      hipLaunchKernelGGL((k_bonded_hyb<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
+                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
+    else if (nbent > 0)
       hipLaunchKernelGGL((k_bonded<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
                          bpar.p, boxd, elist.p, ctl.p, btab_view());
     pair_guard = 0;
@@ -1470,6 +1495,7 @@ template <typename R> struct CtxT : Ctx {
       }
     }
     if (react_on && !reactions.empty()) reserve_reaction_tables();
+    force_step_off = 0;
     if (resort) rebuild_now();
     compute_forces();
     if (lang) launch_integrate<0>(true, true, step, 0);  // thermalize: f += friction + noise, stored
@@ -1498,9 +1524,11 @@ template <typename R> struct CtxT : Ctx {
       const bool react_due = react_on && interval > 0 && ((step + 1) % interval == 0);
       const bool atrp_due = atrp_on && ((step + 1) % atrp.interval == 0);
       const bool last = (s == nsteps - 1);
+      force_step_off = 1;      // (hybrid lists: these are the forces of step + 1, whose counter moves behind the integration)
       if (resume) { resume = false; rebuild_now(); compute_forces(); }   // (positions are drifted, forces of this step were never evaluated)
       else if (dd_on) dd_step_sync();   // decision, (rebuild,) forces
       else { decide_and_rebuild(); compute_forces(); }
+      force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
 
       if (last || react_due || atrp_due || !opt_fuse || resc_kind) {
@@ -1796,13 +1824,14 @@ template <typename R> struct CtxT : Ctx {
   // grows -- is left to the bookkeeping thread (label_seen_lists).
   void insert_new_bonds(bool defer_seen, std::vector<std::pair<int32_t, int32_t>>& newbonds) {
     const std::vector<Candidate>& bev = bond_ev;
+    top.cur_step = step;      // (the birth step of what a hybrid list gains here)
     label_seen_lists.clear();
     for (size_t k = 0; defer_seen && k < bev.size(); ++k) {
       const Candidate& e = bev[k];
       const chem_reaction_desc& d = reactions[e.r];
       HostList& l = top.lists[d.bond_list];
       const int32_t t[2] = {e.a, e.b};
-      l.ent.insert(l.ent.end(), t, t + 2);
+      l.push_pair(t, step);
       newbonds.emplace_back(e.a, e.b);
       label_seen_lists.push_back(d.bond_list);
     }
@@ -2116,7 +2145,10 @@ template <typename R> struct CtxT : Ctx {
     const int tpp = pick_tpp();
     const int nb = launch_pair<true>(x4o.p, tpp);  // scratch force buffer: leaves f4 untouched
     HIPCHK(hipMemsetAsync(elist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream));
-    if (nbent > 0)
+    if (nbent > 0 && has_hybrid)
+      hipLaunchKernelGGL((k_bonded_hyb<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
+                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
+    else if (nbent > 0)
       hipLaunchKernelGGL((k_bonded<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
                          bpar.p, boxd, elist.p, ctl.p, btab_view());
     const int nkb = cdiv(n, 256);
@@ -2336,7 +2368,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   if (!sorted) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return id[a] < id[b]; });
   t.n = n; t.id.resize(n); t.type.resize(n); t.state.resize(n); t.res_id.resize(n); t.mol_id.resize(n); t.mass.resize(n); t.q.resize(n);
   t.graph.assign(n, TagRow()); t.excl.assign(n, TagRow()); t.n_excl_pairs = 0; t.excl_log.clear(); t.id2tag.clear();
-  for (auto& l : t.lists) { l.ent.clear(); l.seen.clear(); }
+  for (auto& l : t.lists) { l.ent.clear(); l.seen.clear(); l.birth.clear(); }
   c.pos0.resize(3 * n); c.vel0.assign(3 * n, 0.0);
   t.contiguous = true; t.id0 = id[order[0]];
   for (int64_t k = 0; k < n; ++k) {
@@ -2486,6 +2518,7 @@ int chem_list_add(chem_ctx* ctx, int list, int64_t n, const int64_t* ids) {
   REQUIRE(list >= 0 && list < (int)t.lists.size(), CHEM_EINVAL, "list handle");
   REQUIRE(t.n > 0, CHEM_ESTATE, "set particles before list entries");
   HostList& l = t.lists[list];
+  t.cur_step = CTX.step;
   std::vector<std::pair<int32_t, int32_t>> nb;
   for (int64_t e = 0; e < n; ++e) {
     int32_t tg[4];
@@ -2529,6 +2562,30 @@ int64_t chem_get_list(chem_ctx* ctx, int list, int64_t* out, int64_t cap) {
   if (!out) return l.size();
   REQUIRE(cap >= l.size(), CHEM_ENOSPC, "get_list: capacity");
   for (size_t k = 0; k < l.ent.size(); ++k) out[k] = t.id[l.ent[k]];
+  return l.size();
+  API_END(ctx)
+}
+
+int chem_list_set_hybrid(chem_ctx* ctx, int list, double lambda0, double rate) {
+  API_BEGIN
+  HostTopology& t = CTX.top;
+  REQUIRE(list >= 0 && list < (int)t.lists.size(), CHEM_EINVAL, "list handle");
+  const int rc = t.lists[list].set_hybrid(lambda0, rate);
+  REQUIRE(rc != CHEM_EINVAL, CHEM_EINVAL, "list_set_hybrid: needs a pair list, lambda0 in [0, 1] and a finite rate >= 0");
+  REQUIRE(rc != CHEM_ESTATE, CHEM_ESTATE, "list_set_hybrid: the list already has entries (their birth steps are unknown)");
+  CTX.bonded_dirty = true; CTX.resort = true;      // (a context with a hybrid list leaves the inline-bond mode: rebuild)
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_list_get_lambda(chem_ctx* ctx, int list, double* out, int64_t cap) {
+  API_BEGIN
+  HostTopology& t = CTX.top;
+  REQUIRE(list >= 0 && list < (int)t.lists.size(), CHEM_EINVAL, "list handle");
+  const HostList& l = t.lists[list];
+  if (!out) return l.size();
+  REQUIRE(cap >= l.size(), CHEM_ENOSPC, "list_get_lambda: capacity");
+  for (int64_t e = 0; e < l.size(); ++e) out[e] = l.lambda_at((size_t)e, CTX.step);
   return l.size();
   API_END(ctx)
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -134,7 +135,25 @@ struct HostList {
   std::array<double, CHEM_MAX_POT_PARAMS> plain{};
   std::map<std::array<int, 4>, std::array<double, CHEM_MAX_POT_PARAMS>> typed;
   std::vector<std::array<int, 4>> registered;
+  // hybrid pair list (chem_list_set_hybrid): entry e acts with lambda(step) = min(1, lambda0 + rate (step - birth[e])).
+  // birth is aligned with the entries and kept by every path that adds, removes or compacts them; a list that is not
+  // hybrid keeps none (set_hybrid is refused once a list has entries, so their birth steps could never be read).
+  bool hybrid = false;
+  double lambda0 = 1.0, rate = 0.0;
+  std::vector<int64_t> birth;
   int64_t size() const { return (int64_t)ent.size() / arity; }
+  // one pair appended at step `now` (paths that bypass HostTopology::list_insert: the reaction step's deferred insert)
+  void push_pair(const int32_t* t, int64_t now) { ent.insert(ent.end(), t, t + 2); if (hybrid) birth.push_back(now); }
+  double lambda_at(size_t e, int64_t step) const { return hybrid ? hybrid_lambda(lambda0, rate, step - birth[e]) : 1.0; }
+  // the ONE definition of the ramp (the device evaluates the same expression: md_kernels.hpp hybrid_lambda)
+  static double hybrid_lambda(double lambda0, double rate, int64_t age) { const double l = lambda0 + rate * (double)age; return l < 1.0 ? l : 1.0; }
+  // chem_list_set_hybrid's rules; 0 = accepted
+  int set_hybrid(double l0, double r) {
+    if (arity != 2 || !std::isfinite(l0) || !std::isfinite(r) || l0 < 0.0 || l0 > 1.0 || r < 0.0) return CHEM_EINVAL;
+    if (!ent.empty()) return CHEM_ESTATE;
+    hybrid = true; lambda0 = l0; rate = r; birth.clear();
+    return 0;
+  }
 };
 
 struct HostPairPot {
@@ -147,6 +166,8 @@ struct HostPairPot {
 // Device-facing bonded parameter slot and CSR entry (mirrors md_kernels.hpp)
 struct HBondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };
 struct HBondedEntry { int t0, t1, t2, meta; };
+// birth step of a hybrid pair as it travels in the unused third tag: always negative, so that no reader takes it for a tag
+inline int32_t encode_birth(int64_t birth) { return ~(int32_t)birth; }
 
 struct HostBondTable { double r0 = 0, dr = 1; int itype = 1; std::vector<double> e, f; };   // itype as HostPairPot
 
@@ -163,6 +184,7 @@ struct HostTopology {
   std::vector<TagRow> excl;   // sorted, symmetric
   std::vector<HostList> lists;
   int64_t n_excl_pairs = 0;
+  int64_t cur_step = 0;     // the context's step counter (chem_get_step): the birth step of whatever a hybrid list gains now
 
   int tag_of(int64_t pid) const {
     if (contiguous) { int64_t t = pid - id0; return (t >= 0 && t < n) ? (int)t : -1; }
@@ -186,6 +208,7 @@ struct HostTopology {
   bool list_insert(HostList& l, const int32_t* t) {
     if (!l.seen.insert(tuple_key(t, l.arity))) return false;
     l.ent.insert(l.ent.end(), t, t + l.arity);
+    if (l.hybrid) l.birth.push_back(cur_step);
     return true;
   }
 
@@ -304,9 +327,11 @@ struct HostTopology {
       for (size_t e = 0; e + 2 <= l.ent.size(); e += 2) {
         const TupleKey k = tuple_key(&l.ent[e], 2);
         if (gone[li].contains(k)) { l.seen.erase(k); continue; }
+        if (l.hybrid) l.birth[w / 2] = l.birth[e / 2];
         l.ent[w] = l.ent[e]; l.ent[w + 1] = l.ent[e + 1]; w += 2;
       }
       l.ent.resize(w);
+      if (l.hybrid) l.birth.resize(w / 2);
     }
     // bond graph, exclusions
     TupleSet cut, unex;
@@ -385,21 +410,27 @@ struct HostTopology {
 
   // parameter slots of the bonded lists and the keys the device resolves them by (md_kernels.hpp SlotKey):
   // one slot per plain list, one per (typed list, type tuple), in list order
+  // pad of a slot and of its key = 1 for a hybrid list: the slot's (lambda0, rate) travel in a parallel array (hybrid_params)
   struct HSlotKey { int list, t0, t1, t2, t3, by_types, arity, pad; };
+  bool any_hybrid() const { for (auto& l : lists) if (l.hybrid) return true; return false; }
+  void hybrid_params(const std::vector<HBondedParam>& bpar, std::vector<std::array<double, 2>>& hyb) const {
+    hyb.clear();
+    for (auto& bp : bpar) hyb.push_back(bp.pad ? std::array<double, 2>{lists[bp.list].lambda0, lists[bp.list].rate} : std::array<double, 2>{1.0, 0.0});
+  }
   void build_params(std::vector<HBondedParam>& bpar, std::vector<HSlotKey>& keys) const {
     bpar.clear(); keys.clear();
     for (size_t li = 0; li < lists.size(); ++li) {
       const HostList& l = lists[li];
       if (!l.by_types) {
         if (!l.has_plain) continue;
-        HBondedParam bp{l.kind, (int)li, l.arity, 0, {0}};
+        HBondedParam bp{l.kind, (int)li, l.arity, l.hybrid ? 1 : 0, {0}};
         std::copy(l.plain.begin(), l.plain.end(), bp.p);
-        bpar.push_back(bp); keys.push_back(HSlotKey{(int)li, -1, -1, -1, -1, 0, l.arity, 0});
+        bpar.push_back(bp); keys.push_back(HSlotKey{(int)li, -1, -1, -1, -1, 0, l.arity, l.hybrid ? 1 : 0});
       } else {
         for (auto& kv : l.typed) {
-          HBondedParam bp{l.kind, (int)li, l.arity, 0, {0}};
+          HBondedParam bp{l.kind, (int)li, l.arity, l.hybrid ? 1 : 0, {0}};
           std::copy(kv.second.begin(), kv.second.end(), bp.p);
-          bpar.push_back(bp); keys.push_back(HSlotKey{(int)li, kv.first[0], kv.first[1], kv.first[2], kv.first[3], 1, l.arity, 0});
+          bpar.push_back(bp); keys.push_back(HSlotKey{(int)li, kv.first[0], kv.first[1], kv.first[2], kv.first[3], 1, l.arity, l.hybrid ? 1 : 0});
         }
       }
     }
@@ -417,13 +448,13 @@ struct HostTopology {
       const HostList& l = lists[li];
       if (!l.by_types) {
         if (l.has_plain) {
-          HBondedParam bp{l.kind, (int)li, l.arity, 0, {0}};
+          HBondedParam bp{l.kind, (int)li, l.arity, l.hybrid ? 1 : 0, {0}};
           std::copy(l.plain.begin(), l.plain.end(), bp.p);
           plain_slot[li] = (int)bpar.size(); bpar.push_back(bp);
         }
       } else {
         for (auto& kv : l.typed) {
-          HBondedParam bp{l.kind, (int)li, l.arity, 0, {0}};
+          HBondedParam bp{l.kind, (int)li, l.arity, l.hybrid ? 1 : 0, {0}};
           std::copy(kv.second.begin(), kv.second.end(), bp.p);
           typed_slot[li][kv.first] = (int)bpar.size(); bpar.push_back(bp);
         }
@@ -461,7 +492,7 @@ struct HostTopology {
         if (slot < 0) continue;
         for (int k = 0; k < l.arity; ++k) {
           int32_t& pos = fill[tt[k]];
-          bent[pos++] = HBondedEntry{tt[0], tt[1], l.arity > 2 ? tt[2] : 0, slot | (k << 28)};
+          bent[pos++] = HBondedEntry{tt[0], tt[1], l.arity > 2 ? tt[2] : (l.hybrid ? encode_birth(l.birth[e / 2]) : 0), slot | (k << 28)};
           if (l.arity == 4) bent[pos++] = HBondedEntry{tt[3], 0, 0, 0};
         }
       }

@@ -83,7 +83,17 @@ struct DevCtl {
 // bonded tables (per-tag CSR, see K4-K6 below; declared here because the list build records the LDS slots of bonded partners)
 constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 16-byte quads)
 struct BondedEntry { int t0, t1, t2, meta; };   // tuple tags in order (self included); meta = slot | mypos<<28; quadruples use a 2nd entry for t3
-struct BondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };
+                                                // pairs: t2 = 0, or ~birth step (< 0) for an entry of a hybrid list (chem_list_set_hybrid)
+struct BondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };   // pad = 1: slot of a hybrid list, (lambda0, rate) in HybridArgs::par[slot]
+// Hybrid pair lists: what the HYB instantiations of the bonded kernels get beside the regular arguments.  lambda of an entry is a
+// pure function of (step, birth step); chem_host.hpp HostList::hybrid_lambda is the same expression on the host.
+struct HybridArgs { const double2* par; long long step; };
+__device__ __forceinline__ double hybrid_lambda(const HybridArgs& hy, const BondedParam& bp, const int slot, const int t2) {
+  if (!bp.pad) return 1.0;
+  const double2 h = hy.par[slot];
+  const double l = h.x + h.y * (double)(hy.step - (long long)(~t2));
+  return l < 1.0 ? l : 1.0;
+}
 
 template <typename R> struct Box {
   R L[3], invL[3];
@@ -2585,9 +2595,11 @@ __device__ __forceinline__ void btab_lookup(const BTab& bt, const int h, const d
 // one bonded term seen from member `me` of the tuple (j0..j3 = particle indices of the tuple in order)
 // BONDS_ONLY: the caller guarantees arity 2 and an analytic kind (harmonic, FENE, FENE+LJ, LJ pair) -- the angle, dihedral
 // and table code is not compiled in, which is what brings the per-step kernel from 209 to a few dozen registers
-template <typename R, bool ENERGY, bool BONDS_ONLY = false>
+// HYB: the pair term (force and energy) is scaled by `lam` (hybrid lists); not compiled into the other instantiations
+template <typename R, bool ENERGY, bool BONDS_ONLY = false, bool HYB = false>
 __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me, const int j0, const int j1, const int j2, const int j3,
-                                            const Vec4<R>* __restrict__ x4, const BoxD& box, D3& f, double* __restrict__ elist, DevCtl* ctl, const BTab& bt) {
+                                            const Vec4<R>* __restrict__ x4, const BoxD& box, D3& f, double* __restrict__ elist, DevCtl* ctl, const BTab& bt,
+                                            const double lam = 1.0) {
     const double* p = bp.p;
     double u = 0;
     if (BONDS_ONLY || bp.arity == 2) {
@@ -2619,6 +2631,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
         btab_lookup(bt, (int)p[0], r, u, fv);
         ff = fv / r;
       }
+      if (HYB) { ff *= lam; u *= lam; }
       const double sgn = me == 0 ? 1.0 : -1.0;
       f = f + (sgn * ff) * d;
     } else if (BONDS_ONLY) {
@@ -2707,6 +2720,34 @@ __global__ __launch_bounds__(256) void k_bonded(int i0, int n, const Vec4<R>* __
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
   f4[i] = fo;
 }
+// The same with at least one hybrid list in the context (chosen on the host: CtxT::has_hybrid): a pair entry is scaled by its
+// lambda.  A kernel of its own, not a flag of k_bonded, so that k_bonded stays the code it was.
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(256) void k_bonded_hyb(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                    const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                    const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                    const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt,
+                                                    HybridArgs hy) {
+  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= i0 + n) return;
+  const int tg = tag[i];
+  const int e0 = bstart[tg], e1 = bstart[tg + 1];
+  if (e0 == e1) return;
+  D3 f = {0, 0, 0};
+  for (int e = e0; e < e1; ++e) {
+    const BondedEntry be = bent[e];
+    const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+    const BondedParam& bp = bpar[slot];
+    const int ar = bp.arity;
+    const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
+    int j3 = 0;
+    if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }
+    bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
+  }
+  Vec4<R> fo = f4[i];
+  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
+  f4[i] = fo;
+}
 
 // exclusive scan over the block (BS threads, BS/64 <= 16 waves); returns the exclusive prefix of v,
 // *total = block sum.  Two barriers; safe to call back to back.
@@ -2760,7 +2801,8 @@ __device__ __forceinline__ void dev_bonded_prep_chunk(int ib, int iend, const in
     // the parameter slot / own position -- and nothing else
     const int eo = s_ebase + erank;
     if (has) bwork[s_base + rank] = make_int4(i, eo, e1 - e0, 0);
-    for (int e = e0; e < e1; ++e) { const BondedEntry be = bent[e]; bj[eo + (e - e0)] = make_int4(rtag[be.t0], rtag[be.t1], rtag[be.t2], be.meta); }
+    // (t2 < 0: the birth step of a hybrid pair, no tag -- handed on as it is)
+    for (int e = e0; e < e1; ++e) { const BondedEntry be = bent[e]; bj[eo + (e - e0)] = make_int4(rtag[be.t0], rtag[be.t1], be.t2 < 0 ? be.t2 : rtag[be.t2], be.meta); }
     __syncthreads();
   }
 }
@@ -2792,6 +2834,30 @@ __global__ __launch_bounds__(256) void k_bonded_work(const Vec4<R>* __restrict__
     int j3 = 0;
     if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
     bonded_term<R, false, BONDS_ONLY>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt);
+  }
+  Vec4<R> fo = f4[wk.x];
+  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
+  f4[wk.x] = fo;
+}
+// ... with at least one hybrid list in the context (see k_bonded_hyb): jj.z of a hybrid pair is ~birth step, handed on by the
+// work-list build
+template <typename R, bool BONDS_ONLY = false>
+__global__ __launch_bounds__(256) void k_bonded_work_hyb(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
+                                                         const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt,
+                                                         HybridArgs hy) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (int)(ctl->bw64 & 0xffffffffull) || (guard && ctl->need_rebuild) || ctl->halt) return;
+  const int4 wk = bwork[k];
+  D3 f = {0, 0, 0};
+  for (int e = wk.y; e < wk.y + wk.z; ++e) {
+    const int4 jj = bj[e];
+    const int meta = jj.w;
+    const int slot = meta & 0x0fffffff, me = (meta >> 28) & 3;
+    const BondedParam& bp = bpar[slot];
+    int j3 = 0;
+    if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
+    const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
+    bonded_term<R, false, BONDS_ONLY, true>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt, lam);
   }
   Vec4<R> fo = f4[wk.x];
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
@@ -3895,7 +3961,7 @@ __global__ void k_bt_fill(int ne, const int4* __restrict__ fent, const int* __re
   const int tg[4] = {tt.x, tt.y, tt.z, tt.w};
   for (int q = 0; q < arity; ++q) {
     const int pos = start[tg[q]] + atomicAdd(&cursor[tg[q]], w);
-    bent[pos] = BondedEntry{tt.x, tt.y, arity > 2 ? tt.z : 0, slot | (q << 28)};
+    bent[pos] = BondedEntry{tt.x, tt.y, (arity > 2 || keys[slot].pad) ? tt.z : 0, slot | (q << 28)};      // (pad: hybrid pair list, z = ~birth step)
     bkey[pos] = 2 * e;
     if (arity == 4) { bent[pos + 1] = BondedEntry{tt.w, 0, 0, 0}; bkey[pos + 1] = 2 * e + 1; }
   }

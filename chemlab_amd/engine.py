@@ -154,6 +154,25 @@ class Engine:
             self._ck(self.api.get_list(self.ctx, h, _ptr(out, C.c_int64), n))
         return out
 
+    def list_set_hybrid(self, h, lambda0, rate):
+        """Make the (still empty) pair list `h` hybrid: every entry acts with lambda = min(1, lambda0 + rate * (step - birth
+        step)) on its force and energy (include/chem_mi355.h, chem_list_set_hybrid)."""
+        fn = getattr(self.api, "list_set_hybrid", None)
+        if fn is None:
+            raise NotImplementedError("hybrid bonds: the CPU checker has no FixedPairListLambda")
+        self._ck(fn(self.ctx, int(h), float(lambda0), float(rate)))
+
+    def list_get_lambda(self, h):
+        """lambda of every entry of list `h` at the current step, in the order of get_list."""
+        fn = getattr(self.api, "list_get_lambda", None)
+        if fn is None:
+            raise NotImplementedError("hybrid bonds: the CPU checker has no FixedPairListLambda")
+        n = self._ck(fn(self.ctx, int(h), None, 0))
+        out = np.empty(n, dtype=np.float64)
+        if n:
+            self._ck(fn(self.ctx, int(h), _ptr(out, C.c_double), n))
+        return out
+
     def thermostat_langevin(self, kT, gamma, seed=0):
         self._ck(self.api.thermostat_langevin(self.ctx, float(kT), float(gamma), int(seed)))
 

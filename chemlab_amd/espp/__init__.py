@@ -282,6 +282,38 @@ class FixedPairList(_FixedList):
     getBonds = getAllBonds
 
 
+class FixedPairListLambda(FixedPairList):
+    """espressopp.FixedPairListLambda(storage, init_lambda) (reaction_setup.py:444-467): a pair list whose entries act with
+    lambda = min(1, init_lambda + rate * (step - birth step)); the rate comes from
+    integrator.FixedListDynamicResolution.register_pair_list (include/chem_mi355.h, chem_list_set_hybrid)."""
+
+    def __init__(self, storage, init_lambda=0.0):
+        FixedPairList.__init__(self, storage)
+        self.init_lambda, self.rate = float(init_lambda), 0.0
+
+    def _bind(self, kind, by_types):
+        if self.handle is None:      # (hybrid before the first entry: the engine refuses it on a list that has entries)
+            e = self.system.engine
+            h = e.list_create(self.arity, kind, by_types)
+            e.list_set_hybrid(h, self.init_lambda, self.rate)
+            self.handle = h
+            if self._pending:
+                e.list_add(h, self._pending)
+            self._pending = []
+        return self.handle
+
+    def _set_rate(self, rate):
+        self.rate = float(rate)
+        if self.handle is not None:
+            self.system.engine.list_set_hybrid(self.handle, self.init_lambda, self.rate)
+
+    def getAllLambda(self):
+        """lambda of every bond at the current step, in the order of getAllBonds."""
+        if self.handle is None:
+            return [self.init_lambda] * len(self._pending)
+        return self.system.engine.list_get_lambda(self.handle).tolist()
+
+
 class FixedTripleList(_FixedList):
     arity = 3
 
@@ -574,6 +606,16 @@ class _FixedListTypesInteraction(_FixedListInteraction):
         self._typed = {}
 
 
+class _FixedListLambdaInteraction(_FixedListInteraction):
+    """interaction.FixedPairListLambda<Potential>(system, fpl, potential): the potential's force and energy times the lambda of
+    each bond of a FixedPairListLambda."""
+
+    def __init__(self, system, flist, potential=None):
+        if not isinstance(flist, FixedPairListLambda):
+            raise TypeError("interaction.FixedPairListLambda*: the list must be an espressopp.FixedPairListLambda")
+        _FixedListInteraction.__init__(self, system, flist, potential)
+
+
 def _ns(**kw):
     return types.SimpleNamespace(**kw)
 
@@ -597,7 +639,8 @@ interaction = _ns(
     FixedQuadrupleListTabulatedDihedral=_FixedListInteraction, FixedQuadrupleListTypesTabulatedDihedral=_FixedListTypesInteraction,
     FixedPairListTabulated=_FixedListInteraction, FixedPairListTypesTabulated=_FixedListTypesInteraction,
     FixedTripleListTabulatedAngular=_FixedListInteraction, FixedTripleListTypesTabulatedAngular=_FixedListTypesInteraction,
-    FixedPairListLambdaHarmonic=_unsupported("interaction.FixedPairListLambdaHarmonic"),
+    FixedPairListLambdaHarmonic=_FixedListLambdaInteraction, FixedPairListLambdaFENE=_FixedListLambdaInteraction,
+    FixedPairListLambdaFENELennardJones=_FixedListLambdaInteraction, FixedPairListLambdaTabulated=_FixedListLambdaInteraction,
     VerletListDynamicResolutionLennardJones=_unsupported("interaction.VerletListDynamicResolutionLennardJones"),
     MixedTabulated=_MixedTabulated, VerletListMixedTabulated=_VerletListMixedTabulated, MultiTabulated=_unsupported("interaction.MultiTabulated"),
 )
@@ -1097,8 +1140,27 @@ class _ExtAnalyze(object):
         pass
 
 
+class _FixedListDynamicResolution(object):
+    """integrator.FixedListDynamicResolution(system) + register_pair_list(fpl, rate) (start_simulation.py:289-293): every
+    bond of the list gains `rate` of lambda per MD step up to 1.  Nothing runs per step here: the engine evaluates lambda
+    from the step counter and the bond's birth step."""
+
+    def __init__(self, system):
+        self.system = system
+        self.pair_lists = []
+
+    def register_pair_list(self, fpl, rate):
+        if not isinstance(fpl, FixedPairListLambda):
+            raise TypeError("FixedListDynamicResolution.register_pair_list: needs an espressopp.FixedPairListLambda")
+        fpl._set_rate(rate)
+        self.pair_lists.append((fpl, float(rate)))
+
+    def _connect(self, integrator):
+        pass
+
+
 integrator = _ns(
-    VelocityVerlet=_VelocityVerlet, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
+    VelocityVerlet=_VelocityVerlet, FixedListDynamicResolution=_FixedListDynamicResolution, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
     Reaction=_Reaction, PostProcessChangeProperty=_PostProcessChangeProperty,
     PostProcessChangePropertyByTopologyManager=_PostProcessChangeProperty, ReactionConstraintNeighbourState=_ReactionConstraintNeighbourState,
     TopologyParticleProperties=_TopologyParticleProperties, TopologyManager=_TopologyManager, ExtAnalyze=_ExtAnalyze,
@@ -1172,6 +1234,19 @@ class _NFixedPairListEntries(_Observable):
 
     def compute(self):
         return self.fpl.totalSize()
+
+
+class _ResolutionFixedPairList(_Observable):
+    """analysis.ResolutionFixedPairList(system, fpl) (start_simulation.py:495-498): mean lambda of the list's bonds, 0.0 for
+    an empty list."""
+
+    def __init__(self, system, fpl):
+        _Observable.__init__(self, system)
+        self.fpl = fpl
+
+    def compute(self):
+        lam = self.fpl.getAllLambda()
+        return float(sum(lam)) / len(lam) if len(lam) else 0.0
 
 
 class _CMVelocity(_Observable):
@@ -1259,7 +1334,7 @@ analysis = _ns(
     Temperature=_Temperature, KineticEnergy=_KineticEnergy, PotentialEnergy=_PotentialEnergy, NPart=_NPart, MaxPID=_MaxPID,
     NFixedPairListEntries=_NFixedPairListEntries, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
-    SystemMonitorOutputCSV=_SystemMonitorOutputCSV,
+    SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
     Pressure=_unsupported("analysis.Pressure"), PressureTensor=_unsupported("analysis.PressureTensor"),
 )
 

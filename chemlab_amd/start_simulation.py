@@ -280,6 +280,11 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
         dynamic_exclusion_list.observe_quadruple(fql)
         for types_ in inter._typed:
             topology_manager.register_quadruplet(fql, *types_)
+    if args.t_hybrid_bond > 0:                            # start_simulation.py:289-293
+        list_dynamic_resolution = espressopp.integrator.FixedListDynamicResolution(system)
+        for _, fpl, _ in chem_fpls:
+            list_dynamic_resolution.register_pair_list(fpl, 1.0 / args.t_hybrid_bond)
+        integrator.addExtension(list_dynamic_resolution)
     topology_manager.initialize_topology()
     integrator.addExtension(topology_manager)
     # observables (start_simulation.py:447-569)
@@ -291,6 +296,9 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
         mon.add_observable(system.getNameOfInteraction(k), espressopp.analysis.PotentialEnergy(system, system.getInteraction(k)), False)
     for i, (gname, fpl, _) in enumerate(chem_fpls):
         mon.add_observable("count_%d" % i, espressopp.analysis.NFixedPairListEntries(system, fpl))
+    if args.t_hybrid_bond > 0:                            # start_simulation.py:495-498
+        for i, (gname, fpl, _) in enumerate(chem_fpls):
+            mon.add_observable("res_fpl_%d" % i, espressopp.analysis.ResolutionFixedPairList(system, fpl))
     for (cr_type, cr_total, _), obs in sorted(cr_observs.items(), key=lambda kv: kv[0][:2]):
         # computed with every energy row: that is also what moves the mixed (func 10) tables along with the conversion
         mon.add_observable("cr_%s_%s" % (cr_type, cr_total), obs)

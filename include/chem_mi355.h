@@ -261,6 +261,23 @@ int chem_list_set_params(chem_ctx* ctx, int list, int t1, int t2, int t3, int t4
                          const double* p, int np);
 /* getAllBonds/getAllTriples/getAllQuadruples: out receives count*arity ids */
 int64_t chem_get_list(chem_ctx* ctx, int list, int64_t* out, int64_t cap_entries);
+/* FixedPairListLambda(storage, init_lambda) + integrator.FixedListDynamicResolution.register_pair_list(fpl, rate)
+ * reaction_setup.py:444-467, start_simulation.py:289-293: a HYBRID pair list.  Every entry remembers its birth step -- the
+ * value of chem_get_step() when it was added, by a reaction, by chem_list_add or otherwise -- and the forces that are
+ * current at step s (those chem_get_state(CHEM_STATE_FORCE) shows, those the step from s to s+1 starts with) use, per entry,
+ *     lambda = min(1, lambda0 + rate * (s - birth)):
+ * the entry's force is lambda F, its share of chem_obs.epot_list is lambda U.  lambda is a pure function of the two step
+ * numbers (no array that is updated per step), so it is the same on every rank and for run(a); run(b) as for run(a+b).
+ * The pair is excluded from the non-bonded terms as soon as the bond exists, whatever its lambda; angles and dihedrals
+ * spawned around it act at full strength; a dissociation reaction removes the birth step with the entry, a pair that
+ * bonds again starts at lambda0.  Any pair kind, plain or by types.  Harmonic bonds of a context that has a hybrid list
+ * are not evaluated inline (option bonds_inline has no effect).  (Parity unpinned: DESIGN.md "Hybrid bonds".)
+ * CHEM_EINVAL: list of arity != 2, lambda0 outside [0, 1], rate < 0, a non-finite value; CHEM_ESTATE: the list already
+ * has entries (calling it again on an empty list, e.g. to set the rate later, is allowed). */
+int chem_list_set_hybrid(chem_ctx* ctx, int list, double lambda0, double rate);
+/* analysis.ResolutionFixedPairList (start_simulation.py:495-498): lambda of every entry at the current step, in the order
+ * of chem_get_list (same count convention); 1.0 for every entry of a list that is not hybrid. */
+int64_t chem_list_get_lambda(chem_ctx* ctx, int list, double* out, int64_t cap_entries);
 
 /* ---- thermostat ---------------------------------------------------------------------- */
 /* integrator.LangevinThermostat: .temperature (=T*kb), .gamma  start_simulation.py:330-336.
