@@ -68,6 +68,43 @@ def test_fene_bond_closed_form(make_oracle):
     assert f[1, 0] == pytest.approx(-K * r / (1 - (r / rmax) ** 2), rel=1e-13)
 
 
+def test_fene_lj_bond_closed_form(make_oracle):
+    # bonds func 9, FENELennardJones(K, r0, rMax, sigma, epsilon): FENE + 4 eps ((s/r)^12 - (s/r)^6), unshifted (doc/topology.rst:68-75)
+    K, r0, rmax, sig, eps, r = 30.0, 0.2, 1.5, 1.05, 0.8, 1.1
+    e = setup_small(make_oracle(), [[5, 5, 5], [5 + r, 5, 5]])
+    h = e.list_create(2, "FENE_LJ")
+    e.list_set_params(h, [K, r0, rmax, sig, eps])
+    e.list_add(h, [[1, 2]])
+    f, obs = forces_energy(e)
+    q, s6 = (r - r0) / rmax, (sig / r) ** 6
+    assert obs["epot_list"][0] == pytest.approx(-0.5 * K * rmax ** 2 * np.log(1 - q ** 2) + 4 * eps * (s6 ** 2 - s6), rel=1e-13)
+    assert f[1, 0] == pytest.approx(-K * (r - r0) / (1 - q ** 2) + 24 * eps * (2 * s6 ** 2 - s6) / r, rel=1e-13)
+    assert f[0, 0] == pytest.approx(-f[1, 0], rel=1e-13) and np.allclose(f[:, 1:], 0)
+
+
+@pytest.mark.parametrize("a_deg,phi0_deg,d_deg", [(60.0, 20.0, 40.0), (-100.0, -30.0, -70.0), (170.0, -175.0, -15.0), (-170.0, 175.0, 15.0)])
+def test_dihedral_harmonic_closed_form(make_oracle, a_deg, phi0_deg, d_deg):
+    # dihedrals func 12, DihedralHarmonic(K, phi0): U = K/2 (phi - phi0)^2 with the difference wrapped to (-pi, pi]
+    # (doc/topology.rst:120-128); the last two cases cross the wrap.  Particle 4 sits at distance 1 from the axis 2-3:
+    # |grad phi| = 1 there, along the tangent
+    K, a = 4.0, np.deg2rad(a_deg)
+    pos = np.array([[6.0, 5.0, 5.0], [5.0, 5.0, 5.0], [5.0, 5.0, 6.0], [5.0 + np.cos(a), 5.0 + np.sin(a), 6.0]])
+    e = setup_small(make_oracle(), pos)
+    h = e.list_create(4, "DIH_HARMONIC")
+    b1, b2, b3 = pos[1] - pos[0], pos[2] - pos[1], pos[3] - pos[2]
+    m, n = np.cross(b1, b2), np.cross(b2, b3)
+    phi = np.arctan2(np.linalg.norm(b2) * (b1 @ n), m @ n)
+    s = np.sign(phi) * np.sign(a)                                 # the IUPAC sign against the construction's
+    assert abs(phi) == pytest.approx(abs(a), rel=1e-14)
+    e.list_set_params(h, [K, s * np.deg2rad(phi0_deg)])
+    e.list_add(h, [[1, 2, 3, 4]])
+    f, obs = forces_energy(e)
+    d = np.deg2rad(d_deg)                                          # phi - phi0, wrapped, in the construction's sign
+    assert obs["epot_list"][0] == pytest.approx(0.5 * K * d * d, rel=1e-12)
+    assert np.allclose(f[3], -K * d * np.array([-np.sin(a), np.cos(a), 0.0]), rtol=1e-12, atol=1e-13)
+    assert np.allclose(f.sum(0), 0, atol=1e-12)
+
+
 @pytest.mark.parametrize("kind,params", [("ANG_HARMONIC", [2.5, np.deg2rad(119.0)]), ("ANG_COSINE", [3.0, np.deg2rad(140.0)])])
 def test_angle_energy_and_fd(make_oracle, kind, params):
     pos = np.array([[5.9, 5.1, 5.0], [5.0, 5.0, 5.2], [5.3, 5.8, 4.7]])
