@@ -393,17 +393,24 @@ def set_dihedral_interactions(espressopp, system, gt, dynamic_type_ids=(), table
     return out
 
 
-def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=(), qq_cutoff=0.0):
+def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=(), qq_cutoff=0.0, pairs_coulomb=False):
     """[ pairs ] (1-4 interactions) -> FixedPairList[Types]LennardJones (:1314-1411): explicit `sigma epsilon` on the
     pair line, else [ pairtypes ]-less gen-pairs: combination rule of the two atom types with epsilon * fudgeLJ.
     (The reference combines atom type 0 with itself, :1341-1342, and calls combination() with three arguments on the
-    static path, :1360 -- SURVEY Q5; here both atom types are used.)"""
+    static path, :1360 -- SURVEY Q5; here both atom types are used.)
+
+    pairs_coulomb=True adds the 1-4 Coulomb pairs (:1391-1409) when qq_cutoff > 0, 138.935485 * fudgeQQ > 0 and something is
+    charged (has_charges): one CoulombTruncated(prefactor, qq_cutoff) on every static 1-4 list (`coulomb_14_<k>`) and, by
+    types, on the dynamic one (the next number), for the type pairs that get the dynamic LJ.  The reference constructs the
+    static interactions and leaves their addInteraction commented out (:1401), i.e. static pairs keep their 1-4 LJ and lose
+    their 1-4 Coulomb; here they act -- nobody asks for that model and this project never drops a term silently (DESIGN.md
+    section 3).  The default refuses charged pairs as before the term had a kernel: existing callers pin that call."""
     if not gt.pairs:
         return {}
-    # the 1-4 Coulomb pairs (FixedPairListTypesCoulombTruncated, :1391-1409) have no kernel: refused, never dropped.  A member
-    # counts as charged if it is so now, or if its type can change through a reaction and some atom type carries a charge
+    # the refusal of the time before the 1-4 Coulomb kernel, kept for callers that do not ask for the term (never dropped).  A
+    # member counts as charged if it is so now, or if its type can change through a reaction and some atom type carries a charge
     # (a product takes the charge of the atom type it names)
-    if qq_cutoff > 0.0 and float(gt.gt.defaults.get("fudgeQQ", 1.0)) > 0.0:
+    if not pairs_coulomb and qq_cutoff > 0.0 and float(gt.gt.defaults.get("fudgeQQ", 1.0)) > 0.0:
         typed_q = any(float(t.get("charge") or 0.0) != 0.0 for t in gt.gt.atomtypes.values())
         for (a, b) in gt.pairs:
             for m in (a, b):
@@ -433,6 +440,10 @@ def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=()
             eps *= fudge
         groups.setdefault((sig, eps), []).append((a, b))
     out = {}
+    pref_qq = 138.935485 * float(gt.gt.defaults.get("fudgeQQ", 1.0))
+    pot_qq, qq_count = None, 0
+    if pairs_coulomb and qq_cutoff > 0.0 and pref_qq > 0.0 and has_charges(gt):
+        pot_qq = espressopp.interaction.CoulombTruncated(prefactor=pref_qq, cutoff=qq_cutoff)
     for k, ((sig, eps), bl) in enumerate(groups.items()):
         fpl = espressopp.FixedPairList(system.storage)
         fpl.addBonds(bl)
@@ -440,6 +451,11 @@ def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=()
         inter = espressopp.interaction.FixedPairListLennardJones(system, fpl, espressopp.interaction.LennardJones(epsilon=eps, sigma=sig, cutoff=lj_cutoff))
         system.addInteraction(inter, "lj14_%d" % k)
         out["lj14_%d" % k] = (fpl, inter)
+        if pot_qq is not None:      # on the SAME list object, as the reference does; added to the system, which it does not (:1401)
+            inter = espressopp.interaction.FixedPairListCoulombTruncated(system, fpl, pot_qq)
+            system.addInteraction(inter, "coulomb_14_%d" % qq_count)
+            out["coulomb_14_%d" % qq_count] = (fpl, inter)
+            qq_count += 1
     if dyn:
         fpl = espressopp.FixedPairList(system.storage)
         fpl.addBonds(dyn)
@@ -456,4 +472,14 @@ def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=()
                         inter.setPotential(t1, t2, espressopp.interaction.LennardJones(sigma=sig, epsilon=fudge * eps, cutoff=lj_cutoff))
         system.addInteraction(inter, "dyn_lj14")
         out["lj14_dynamic"] = (fpl, inter)
+        if pot_qq is not None:
+            # the type pairs of the dynamic LJ above (:1405-1408), those whose combined sigma is 0 included: no LJ is not no charge
+            inter = espressopp.interaction.FixedPairListTypesCoulombTruncated(system, fpl)
+            for i, n1 in enumerate(names):
+                for n2 in names[i:]:
+                    t1, t2 = gt.used_atomsym_atomtype[n1], gt.used_atomsym_atomtype[n2]
+                    if t1 in dynamic_type_ids or t2 in dynamic_type_ids:
+                        inter.setPotential(t1, t2, pot_qq)
+            system.addInteraction(inter, "coulomb_14_%d" % qq_count)
+            out["coulomb_14_%d" % qq_count] = (fpl, inter)
     return out

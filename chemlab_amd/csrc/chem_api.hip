@@ -96,6 +96,9 @@ struct Ctx {
   // Truncated Coulomb term (chem_nb_coulomb): one (prefactor, rc) for every registered type pair, a symmetric type-pair bit mask
   double coul_k = 0, coul_rc = 0; uint32_t coul_mask[CHEM_MAX_TYPES] = {}; bool coul_dirty = false;
   bool coul_on() const { for (uint32_t m : coul_mask) if (m) return true; return false; }
+  // the by-tag charge array is alive: a non-bonded Coulomb pair is registered or a 1-4 Coulomb list (CHEM_POT_COULOMB_BOND) exists.
+  // Asked wherever charges are kept current; the pair kernel's mode, LDS plan and option limits follow coul_on() alone.
+  bool charges_on() const { return coul_on() || top.any_coulomb_bond(); }
   double coul_epot = 0, coul_virial = 0;   // of the last energy evaluation (observe)
   bool lang = false; double kT = 0, gamma = 0; uint64_t lang_seed = 0; uint32_t lang_tmask = 0;
   bool react_init = false, react_on = false;
@@ -289,6 +292,9 @@ template <typename R> struct CtxT : Ctx {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
     if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
     if (top.any_hybrid()) return false;      // (the force kernel knows one K, one r0 and no lambda: a hybrid list is never evaluated there)
+    // (a 1-4 Coulomb list with parameters is a second slot, so harmonic_only already rules it out; one without parameters does
+    //  nothing but would pass that proof -- inline bonds stay off next to any Coulomb term, so ask directly)
+    if (top.any_coulomb_bond()) return false;
     // the exclusion set must BE the bond set (bonds are a subset: bonds_excluded; both are duplicate-free): equal counts
     size_t nb2 = 0;
     for (const auto& l : top.lists) if (l.arity == 2) nb2 += (size_t)l.size();
@@ -349,8 +355,9 @@ template <typename R> struct CtxT : Ctx {
   DBuf<int> excl_start, excl_list; int has_excl = 0;
   DBuf<int> bstart; DBuf<BondedEntry> bent; DBuf<BondedParam> bpar; int64_t nbent = 0; bool bonds_only = false;
   // hybrid pair lists (chem_list_set_hybrid): (lambda0, rate) per parameter slot; has_hybrid selects the k_bonded*_hyb kernels.
+  // has_coul14: a 1-4 Coulomb list exists -> the k_bonded*_q kernels (charges by tag, lambda code included)
   // force_step_off: 1 while the run loop evaluates the forces of the step it is about to complete (positions of step + 1)
-  DBuf<double2> bhyb; bool has_hybrid = false; int64_t force_step_off = 0;
+  DBuf<double2> bhyb; bool has_hybrid = false, has_coul14 = false; int64_t force_step_off = 0;
   std::vector<std::array<double, 2>> stage_hyb;
   HybridArgs hybrid_args() const { return HybridArgs{bhyb.p, (long long)(step + force_step_off)}; }
   DBuf<PairCore<R>> pcore; DBuf<PairExt<R>> pext;
@@ -718,12 +725,13 @@ template <typename R> struct CtxT : Ctx {
   }
 
   // Charges by tag and the type-pair mask of the Coulomb term: allocated and kept up to date (k_react_apply, k_apply_props,
-  // modify_particle) only while a Coulomb pair is registered; every rank of a decomposition holds all of them.
+  // modify_particle) only while a Coulomb pair is registered or a 1-4 Coulomb list exists (charges_on); every rank of a
+  // decomposition holds all of them.
   DBuf<R> qtag; DBuf<unsigned int> cmask_dev; DBuf<double> eoutq;
-  R* qtag_arg() { return coul_on() ? qtag.p : nullptr; }
+  R* qtag_arg() { return charges_on() ? qtag.p : nullptr; }
   void upload_coul() {
     coul_dirty = false;
-    if (!coul_on()) { HIPCHK(hipStreamSynchronize(stream)); qtag.free(); cmask_dev.free(); eoutq.free(); return; }      // the array exists only while a pair is registered
+    if (!charges_on()) { HIPCHK(hipStreamSynchronize(stream)); qtag.free(); cmask_dev.free(); eoutq.free(); return; }      // the array exists only while somebody reads it
     std::vector<R> hq((size_t)top.n);
     for (size_t t = 0; t < hq.size(); ++t) hq[t] = (R)top.q[t];
     std::vector<unsigned int> hm(coul_mask, coul_mask + CHEM_MAX_TYPES);
@@ -788,7 +796,7 @@ template <typename R> struct CtxT : Ctx {
     nslot = (int)hp.size();
     // analytic pair terms only (the chain-growth systems): the per-step kernel without the angle / dihedral / table code
     bonds_only = nslot > 0;
-    for (const auto& q : hp) bonds_only &= q.arity == 2 && (q.kind == CHEM_POT_HARMONIC || q.kind == CHEM_POT_FENE || q.kind == CHEM_POT_FENE_LJ || q.kind == CHEM_POT_LJ_BOND);
+    for (const auto& q : hp) bonds_only &= q.arity == 2 && (q.kind == CHEM_POT_HARMONIC || q.kind == CHEM_POT_FENE || q.kind == CHEM_POT_FENE_LJ || q.kind == CHEM_POT_LJ_BOND || q.kind == CHEM_POT_COULOMB_BOND);
     harmonic_only = nslot == 1 && hp[0].arity == 2 && hp[0].kind == CHEM_POT_HARMONIC;      // ONE harmonic parameter set (kernel arguments of the force launch)
     if (harmonic_only) { inline_K = hp[0].p[0]; inline_r0 = hp[0].p[1]; }
     if (full && harmonic_only) {
@@ -805,7 +813,8 @@ template <typename R> struct CtxT : Ctx {
     }
     bpar.alloc(std::max<size_t>(hp.size(), 1)); skeys.alloc(std::max<size_t>(hk.size(), 1));
     has_hybrid = top.any_hybrid();
-    if (has_hybrid && nslot) {
+    has_coul14 = top.any_coulomb_bond();
+    if ((has_hybrid || has_coul14) && nslot) {      // (the _q kernels carry the lambda code: (1, 0) for slots that are not hybrid)
       static_assert(sizeof(std::array<double, 2>) == sizeof(double2), "layout");
       top.hybrid_params(hp, stage_hyb);
       bhyb.alloc(stage_hyb.size());
@@ -1327,14 +1336,21 @@ template <typename R> struct CtxT : Ctx {
       }
       if (timed) tbeg(3);
       const int nown = inl ? (int)std::min<int64_t>(nb_owner, excl_over) : nb_owner;   // (inline bonds: the list holds the owners with > kBondSlots exclusions only)
-      if (has_hybrid) {      // lambda of every hybrid entry at the step these forces belong to
+      if (has_coul14) {      // 1-4 Coulomb list: charges by tag, read at every evaluation
+        if (bonds_only) hipLaunchKernelGGL((k_bonded_work_q<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args(), (const R*)qtag.p, (const int*)tag.p);
+        else hipLaunchKernelGGL((k_bonded_work_q<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args(), (const R*)qtag.p, (const int*)tag.p);
+      }
+      else if (has_hybrid) {      // lambda of every hybrid entry at the step these forces belong to
         if (bonds_only) hipLaunchKernelGGL((k_bonded_work_hyb<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
         else hipLaunchKernelGGL((k_bonded_work_hyb<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
       }
       else if (bonds_only) hipLaunchKernelGGL((k_bonded_work<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
       else hipLaunchKernelGGL((k_bonded_work<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
       if (timed) tend();
-    } else if (nbent > 0 && has_hybrid)
+    } else if (nbent > 0 && has_coul14)
+      hipLaunchKernelGGL((k_bonded_q<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
+                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+    else if (nbent > 0 && has_hybrid)
       hipLaunchKernelGGL((k_bonded_hyb<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
                          bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
     else if (nbent > 0)
@@ -2095,8 +2111,8 @@ template <typename R> struct CtxT : Ctx {
       case CHEM_STATE_RESID: { std::vector<int> h; res_id.download(h, nglob, stream); std::copy(h.begin(), h.end(), i32); return nglob; }
       case CHEM_STATE_MOLID: { std::vector<int> h; mol_id.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) i32[t] = (int32_t)top.id[h[t]]; return nglob; }
       case CHEM_STATE_ID: for (int t = 0; t < nglob; ++t) i64[t] = top.id[t]; return nglob;
-      case CHEM_STATE_CHARGE: {      // the device's by-tag array while a Coulomb pair is registered, the host mirror otherwise
-        if (coul_on() && qtag.p) { std::vector<R> h; qtag.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) d[t] = (double)h[t]; }
+      case CHEM_STATE_CHARGE: {      // the device's by-tag array while it is alive (charges_on), the host mirror otherwise
+        if (charges_on() && qtag.p) { std::vector<R> h; qtag.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) d[t] = (double)h[t]; }
         else for (int t = 0; t < nglob; ++t) d[t] = top.q[t];
         return nglob;
       }
@@ -2145,7 +2161,10 @@ template <typename R> struct CtxT : Ctx {
     const int tpp = pick_tpp();
     const int nb = launch_pair<true>(x4o.p, tpp);  // scratch force buffer: leaves f4 untouched
     HIPCHK(hipMemsetAsync(elist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream));
-    if (nbent > 0 && has_hybrid)
+    if (nbent > 0 && has_coul14)
+      hipLaunchKernelGGL((k_bonded_q<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
+                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+    else if (nbent > 0 && has_hybrid)
       hipLaunchKernelGGL((k_bonded_hyb<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
                          bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
     else if (nbent > 0)
@@ -2278,7 +2297,7 @@ template <typename R> struct CtxT : Ctx {
     else if (what == CHEM_STATE_MASS) { R w = (R)value; HIPCHK(hipMemcpyAsync(&v4.p[idx].w, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_STATE) { int w = (int)value; HIPCHK(hipMemcpyAsync(state.p + t, &w, sizeof(int), hipMemcpyHostToDevice, stream)); }
     else if (what == CHEM_STATE_RESID) { int w = (int)value; HIPCHK(hipMemcpyAsync(res_id.p + t, &w, sizeof(int), hipMemcpyHostToDevice, stream)); }
-    else if (what == CHEM_STATE_CHARGE && coul_on() && qtag.p && !coul_dirty) { R w = (R)value; HIPCHK(hipMemcpyAsync(qtag.p + t, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }   // (otherwise the host mirror alone: uploaded with the registration)
+    else if (what == CHEM_STATE_CHARGE && charges_on() && qtag.p && !coul_dirty) { R w = (R)value; HIPCHK(hipMemcpyAsync(qtag.p + t, &w, sizeof(R), hipMemcpyHostToDevice, stream)); }   // (otherwise the host mirror alone: uploaded with the registration)
     HIPCHK(hipStreamSynchronize(stream));
   }
 };
@@ -2485,13 +2504,15 @@ int chem_nb_table_interp(chem_ctx* ctx, int t1, int t2, int64_t nrow, double r0,
 int chem_list_create(chem_ctx* ctx, int arity, int kind, int by_types) {
   API_BEGIN
   REQUIRE(arity >= 2 && arity <= 4, CHEM_EINVAL, "list arity must be 2, 3 or 4");
-  const bool ok = (arity == 2 && (kind == CHEM_POT_HARMONIC || kind == CHEM_POT_FENE || kind == CHEM_POT_TABULATED || kind == CHEM_POT_FENE_LJ || kind == CHEM_POT_LJ_BOND)) ||
+  const bool ok = (arity == 2 && (kind == CHEM_POT_HARMONIC || kind == CHEM_POT_FENE || kind == CHEM_POT_TABULATED || kind == CHEM_POT_FENE_LJ || kind == CHEM_POT_LJ_BOND ||
+                                  kind == CHEM_POT_COULOMB_BOND)) ||
                   (arity == 3 && (kind == CHEM_POT_ANG_HARMONIC || kind == CHEM_POT_ANG_COSINE || kind == CHEM_POT_ANG_TABULATED)) ||
                   (arity == 4 && (kind == CHEM_POT_DIH_NCOS || kind == CHEM_POT_DIH_RB || kind == CHEM_POT_DIH_TABULATED || kind == CHEM_POT_DIH_HARMONIC));
   REQUIRE(ok, CHEM_ENOTIMPL, "potential kind not supported for this arity");
   REQUIRE((int)CTX.top.lists.size() < CHEM_MAX_LISTS, CHEM_ENOSPC, "too many lists");
   HostList l; l.arity = arity; l.kind = kind; l.by_types = by_types ? 1 : 0;
   CTX.top.lists.push_back(std::move(l));
+  if (kind == CHEM_POT_COULOMB_BOND) { CTX.coul_dirty = true; CTX.bonded_dirty = true; CTX.resort = true; }   // the charge array comes alive with the list; inline bonds go
   return (int)CTX.top.lists.size() - 1;
   API_END(ctx)
 }
@@ -2540,6 +2561,8 @@ int chem_list_set_params(chem_ctx* ctx, int list, int t1, int t2, int t3, int t4
   if (t.lists[list].kind == CHEM_POT_TABULATED || t.lists[list].kind == CHEM_POT_ANG_TABULATED || t.lists[list].kind == CHEM_POT_DIH_TABULATED)
     REQUIRE(p[0] >= 0 && p[0] < (double)t.btables.size() && p[0] == (double)(int)p[0], CHEM_EINVAL, "tabulated bonded terms: parameter must be a handle from chem_table_create");
   HostList& l = t.lists[list];
+  if (l.kind == CHEM_POT_COULOMB_BOND)
+    REQUIRE(np == 2 && std::isfinite(p[0]) && std::isfinite(p[1]) && p[1] > 0, CHEM_EINVAL, "1-4 Coulomb pairs: parameters are { prefactor, cutoff > 0 }, both finite");
   std::array<double, CHEM_MAX_POT_PARAMS> v{};
   std::copy(p, p + np, v.begin());
   if (!l.by_types) { l.plain = v; l.has_plain = true; }

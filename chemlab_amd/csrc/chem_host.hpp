@@ -413,6 +413,7 @@ struct HostTopology {
   // pad of a slot and of its key = 1 for a hybrid list: the slot's (lambda0, rate) travel in a parallel array (hybrid_params)
   struct HSlotKey { int list, t0, t1, t2, t3, by_types, arity, pad; };
   bool any_hybrid() const { for (auto& l : lists) if (l.hybrid) return true; return false; }
+  bool any_coulomb_bond() const { for (auto& l : lists) if (l.kind == CHEM_POT_COULOMB_BOND) return true; return false; }   // 1-4 Coulomb lists: they read the charge array
   void hybrid_params(const std::vector<HBondedParam>& bpar, std::vector<std::array<double, 2>>& hyb) const {
     hyb.clear();
     for (auto& bp : bpar) hyb.push_back(bp.pad ? std::array<double, 2>{lists[bp.list].lambda0, lists[bp.list].rate} : std::array<double, 2>{1.0, 0.0});

@@ -2596,10 +2596,11 @@ __device__ __forceinline__ void btab_lookup(const BTab& bt, const int h, const d
 // BONDS_ONLY: the caller guarantees arity 2 and an analytic kind (harmonic, FENE, FENE+LJ, LJ pair) -- the angle, dihedral
 // and table code is not compiled in, which is what brings the per-step kernel from 209 to a few dozen registers
 // HYB: the pair term (force and energy) is scaled by `lam` (hybrid lists); not compiled into the other instantiations
-template <typename R, bool ENERGY, bool BONDS_ONLY = false, bool HYB = false>
+// COUL: the 1-4 Coulomb kind (CHEM_POT_COULOMB_BOND) with the two members' charges q0, q1; not compiled into the others either
+template <typename R, bool ENERGY, bool BONDS_ONLY = false, bool HYB = false, bool COUL = false>
 __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me, const int j0, const int j1, const int j2, const int j3,
                                             const Vec4<R>* __restrict__ x4, const BoxD& box, D3& f, double* __restrict__ elist, DevCtl* ctl, const BTab& bt,
-                                            const double lam = 1.0) {
+                                            const double lam = 1.0, const double q0 = 0.0, const double q1 = 0.0) {
     const double* p = bp.p;
     double u = 0;
     if (BONDS_ONLY || bp.arity == 2) {
@@ -2625,6 +2626,9 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
           u = 4.0 * p[0] * ((s6 * s6 - s6) - (c6 * c6 - c6));
           ff = 24.0 * p[0] * (2.0 * s6 * s6 - s6) / (r * r);
         }
+      }
+      else if (COUL && bp.kind == CHEM_POT_COULOMB_BOND) {   // FixedPairListCoulombTruncated(prefactor, cutoff): 1-4 pairs, no shift
+        if (r <= p[1]) { u = p[0] * (q0 * q1) / r; ff = u / (r * r); }
       }
       else if (!BONDS_ONLY && bp.kind == CHEM_POT_TABULATED) {   // Tabulated: e(r), f(r) from table p[0]
         double fv;
@@ -2749,6 +2753,38 @@ __global__ __launch_bounds__(256) void k_bonded_hyb(int i0, int n, const Vec4<R>
   f4[i] = fo;
 }
 
+// The same with at least one 1-4 Coulomb list (CHEM_POT_COULOMB_BOND) in the context (chosen on the host: CtxT::has_coul14).  The
+// two members of a Coulomb entry read their charges by tag (qtag, type R; the product is formed in fp64); the lambda code is
+// carried along (1 for entries of lists that are not hybrid), so a context with both kinds of list needs no fourth family.
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(256) void k_bonded_q(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                  const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                  const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                  const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt,
+                                                  HybridArgs hy, const R* __restrict__ qtag) {
+  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= i0 + n) return;
+  const int tg = tag[i];
+  const int e0 = bstart[tg], e1 = bstart[tg + 1];
+  if (e0 == e1) return;
+  D3 f = {0, 0, 0};
+  for (int e = e0; e < e1; ++e) {
+    const BondedEntry be = bent[e];
+    const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+    const BondedParam& bp = bpar[slot];
+    const int ar = bp.arity;
+    const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
+    int j3 = 0;
+    if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }
+    double q0 = 0, q1 = 0;
+    if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
+    bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
+  }
+  Vec4<R> fo = f4[i];
+  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
+  f4[i] = fo;
+}
+
 // exclusive scan over the block (BS threads, BS/64 <= 16 waves); returns the exclusive prefix of v,
 // *total = block sum.  Two barriers; safe to call back to back.
 template <int BS>
@@ -2858,6 +2894,34 @@ __global__ __launch_bounds__(256) void k_bonded_work_hyb(const Vec4<R>* __restri
     if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
     const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
     bonded_term<R, false, BONDS_ONLY, true>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt, lam);
+  }
+  Vec4<R> fo = f4[wk.x];
+  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
+  f4[wk.x] = fo;
+}
+
+// ... with at least one 1-4 Coulomb list in the context (see k_bonded_q).  The work-list records carry particle indices, so a
+// charge is qtag[tag[j]] -- ghosts included, as in CoulArgs -- and is read at every evaluation: nothing in a record can go stale
+// when a charge changes between two list builds.
+template <typename R, bool BONDS_ONLY = false>
+__global__ __launch_bounds__(256) void k_bonded_work_q(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
+                                                       const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt,
+                                                       HybridArgs hy, const R* __restrict__ qtag, const int* __restrict__ tag) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (int)(ctl->bw64 & 0xffffffffull) || (guard && ctl->need_rebuild) || ctl->halt) return;
+  const int4 wk = bwork[k];
+  D3 f = {0, 0, 0};
+  for (int e = wk.y; e < wk.y + wk.z; ++e) {
+    const int4 jj = bj[e];
+    const int meta = jj.w;
+    const int slot = meta & 0x0fffffff, me = (meta >> 28) & 3;
+    const BondedParam& bp = bpar[slot];
+    int j3 = 0;
+    if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
+    const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
+    double q0 = 0, q1 = 0;
+    if (bp.kind == CHEM_POT_COULOMB_BOND && (jj.x | jj.y) >= 0) { q0 = (double)qtag[tag[jj.x]]; q1 = (double)qtag[tag[jj.y]]; }   // (a missing partner: bonded_term reports it)
+    bonded_term<R, false, BONDS_ONLY, true, true>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
   }
   Vec4<R> fo = f4[wk.x];
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;

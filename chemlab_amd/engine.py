@@ -132,6 +132,8 @@ class Engine:
 
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
+        if kind == _capi.POT["COULOMB_BOND"] and getattr(self.api, "nb_coulomb", None) is None:
+            raise NotImplementedError("1-4 Coulomb pairs: the CPU checker has no Coulomb term")
         h = self._ck(self.api.list_create(self.ctx, arity, kind, 1 if by_types else 0))
         self._lists[h] = arity
         return h

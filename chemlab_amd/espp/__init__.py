@@ -234,27 +234,42 @@ class VerletList(object):
 
 # ---- fixed lists ---------------------------------------------------------------------------
 class _FixedList(object):
+    """One espressopp list object may carry interactions of several kinds (the 1-4 pairs: LennardJones and CoulombTruncated on
+    the same FixedPairList, gromacs_topology.py:1391-1409); a library list has one kind.  So there is one library handle per
+    kind: `handle` is the first (what reactions, the topology manager and getAll* see), a bind with another kind creates a
+    further library list with the entries added through this object so far, and later additions go to all of them."""
     arity = 2
 
     def __init__(self, storage):
         self.system = storage.system
         self.handle = None
+        self._handles = {}      # kind -> library handle, in the order of binding
         self._pending = []
+        self._entries = []      # everything _add has seen (what a further kind starts with)
 
     def _add(self, entries):
         entries = [tuple(int(x) for x in e) for e in entries]
+        self._entries.extend(entries)
         if self.handle is None:
             self._pending.extend(entries)
         elif entries:
-            self.system.engine.list_add(self.handle, entries)
+            for h in self._handles.values():
+                self.system.engine.list_add(h, entries)
+
+    def _create(self, kind, by_types):
+        return self.system.engine.list_create(self.arity, kind, by_types)
 
     def _bind(self, kind, by_types):
+        if kind in self._handles:
+            return self._handles[kind]
+        h = self._create(kind, by_types)
+        if self._entries:
+            self.system.engine.list_add(h, self._entries)
         if self.handle is None:
-            self.handle = self.system.engine.list_create(self.arity, kind, by_types)
-            if self._pending:
-                self.system.engine.list_add(self.handle, self._pending)
+            self.handle = h
             self._pending = []
-        return self.handle
+        self._handles[kind] = h
+        return h
 
     def _all(self):
         if self.handle is None:
@@ -291,21 +306,16 @@ class FixedPairListLambda(FixedPairList):
         FixedPairList.__init__(self, storage)
         self.init_lambda, self.rate = float(init_lambda), 0.0
 
-    def _bind(self, kind, by_types):
-        if self.handle is None:      # (hybrid before the first entry: the engine refuses it on a list that has entries)
-            e = self.system.engine
-            h = e.list_create(self.arity, kind, by_types)
-            e.list_set_hybrid(h, self.init_lambda, self.rate)
-            self.handle = h
-            if self._pending:
-                e.list_add(h, self._pending)
-            self._pending = []
-        return self.handle
+    def _create(self, kind, by_types):      # (hybrid before the first entry: the engine refuses it on a list that has entries)
+        e = self.system.engine
+        h = e.list_create(self.arity, kind, by_types)
+        e.list_set_hybrid(h, self.init_lambda, self.rate)
+        return h
 
     def _set_rate(self, rate):
         self.rate = float(rate)
-        if self.handle is not None:
-            self.system.engine.list_set_hybrid(self.handle, self.init_lambda, self.rate)
+        for h in self._handles.values():
+            self.system.engine.list_set_hybrid(h, self.init_lambda, self.rate)
 
     def getAllLambda(self):
         """lambda of every bond at the current step, in the order of getAllBonds."""
@@ -567,27 +577,32 @@ class _FixedListInteraction(object):
             return kind, [float(cache[id(eng)])]
         if isinstance(pot, _LennardJones):      # FixedPairList[Types]LennardJones: 1-4 pairs
             return "LJ_BOND", [pot.epsilon, pot.sigma, pot.cutoff if pot.cutoff is not None else 1e30]
+        if isinstance(pot, _CoulombTruncated):  # FixedPairList[Types]CoulombTruncated: 1-4 pairs (CHEM_POT_COULOMB_BOND)
+            return "COULOMB_BOND", [pot.prefactor, pot.cutoff]
         return pot.kind, pot.params()
 
     def __init__(self, system, flist, potential=None):
         self.system, self.flist = system, flist
         self.potential = potential
         self._typed = {}
+        self.handle = None      # the library list of THIS interaction's kind (the list object may carry several)
         if potential is not None:
             kind, par = self._kp(potential)
-            h = flist._bind(kind, False)
+            h = self.handle = flist._bind(kind, False)
             system.engine.list_set_params(h, par)
 
-    def setPotential(self, *args):
+    def setPotential(self, *args, **kw):
+        # (the reference also spells the arguments out: setPotential(type1=.., type2=.., potential=..), gromacs_topology.py:1408)
+        args = args + tuple(kw[k] for k in ("type1", "type2", "type3", "type4", "potential") if k in kw)
         pot = args[-1]
         types = tuple(int(t) for t in args[:-1])
         kind, par = self._kp(pot)
         if not self.by_types:
             self.potential = pot
-            h = self.flist._bind(kind, False)
+            h = self.handle = self.flist._bind(kind, False)
             self.system.engine.list_set_params(h, par)
             return
-        h = self.flist._bind(kind, True)
+        h = self.handle = self.flist._bind(kind, True)
         self._typed[types] = pot
         self.system.engine.list_set_params(h, par, types=types)
 
@@ -604,6 +619,7 @@ class _FixedListTypesInteraction(_FixedListInteraction):
         self.system, self.flist = system, flist
         self.potential = None
         self._typed = {}
+        self.handle = None
 
 
 class _FixedListLambdaInteraction(_FixedListInteraction):
@@ -635,6 +651,7 @@ interaction = _ns(
     FixedPairListLennardJones=_FixedListInteraction, FixedPairListTypesLennardJones=_FixedListTypesInteraction,
     FixedQuadrupleListDihedralHarmonic=_FixedListInteraction, FixedQuadrupleListTypesDihedralHarmonic=_FixedListTypesInteraction,
     CoulombTruncated=_CoulombTruncated, VerletListCoulombTruncated=_VerletListCoulombTruncated,
+    FixedPairListCoulombTruncated=_FixedListInteraction, FixedPairListTypesCoulombTruncated=_FixedListTypesInteraction,
     TabulatedAngular=_TabulatedAngular, TabulatedDihedral=_TabulatedDihedral,
     FixedQuadrupleListTabulatedDihedral=_FixedListInteraction, FixedQuadrupleListTypesTabulatedDihedral=_FixedListTypesInteraction,
     FixedPairListTabulated=_FixedListInteraction, FixedPairListTypesTabulated=_FixedListTypesInteraction,
@@ -1213,7 +1230,9 @@ class _PotentialEnergy(_Observable):
             return o["epot_lj"]
         if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated)):    # (one tabulated-energy accumulator: plain and mixed tables together)
             return o["epot_tab"]
-        h = i.flist.handle
+        h = getattr(i, "handle", None)      # the interaction's own library list (a list object carries one per kind)
+        if h is None:
+            h = i.flist.handle
         return o["epot_list"][h] if h is not None else 0.0
 
 

@@ -239,7 +239,8 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
                                                      table_dir=os.path.dirname(os.path.abspath(args.top)))
     dihedrals = gromacs_topology.set_dihedral_interactions(espressopp, system, gt, dynamic_types,
                                                            table_dir=os.path.dirname(os.path.abspath(args.top)))
-    pairs14 = gromacs_topology.set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_types, qq_cutoff=args.coulomb_cutoff)   # start_simulation.py:308-309
+    pairs14 = gromacs_topology.set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_types, qq_cutoff=args.coulomb_cutoff,
+                                                     pairs_coulomb=True)   # start_simulation.py:308-309
     if args.max_force > -1:                               # start_simulation.py:320-324, before the thermostat
         integrator.addExtension(espressopp.integrator.CapForce(system, args.max_force))
         log("Cap force to %s" % args.max_force)

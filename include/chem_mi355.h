@@ -58,6 +58,24 @@ extern "C" {
                                       doc/topology.rst:68-75, gromacs_topology.py:935-942 */
 #define CHEM_POT_LJ_BOND       5   /* 1-4 pairs, FixedPairListLennardJones(epsilon, sigma, cutoff): plain LJ inside the cutoff,
                                       gromacs_topology.py:1314-1411 */
+/* 1-4 Coulomb pairs, FixedPairListCoulombTruncated / FixedPairListTypesCoulombTruncated with CoulombTruncated(prefactor, cutoff),
+ * gromacs_topology.py:1391-1409.  The arithmetic is in the external fork, so this rule set is this build's own ([EXT-RECALL],
+ * parity unpinned like chem_nb_coulomb).  Arity 2, plain or by types, params = { prefactor k, cutoff rc }.
+ * For a list entry (i, j) with minimum-image distance r <= rc (inclusive, compared as CHEM_POT_LJ_BOND compares):
+ *     U = k q_i q_j / r,     F_i = k q_i q_j r_ij / r^3,     the energy is not shifted.
+ *   - nothing else is asked of the entry: it need not be on the Verlet list nor be non-excluded, and rc is not bound by
+ *     max_cutoff; the pair is found through its tags like every bonded term (same reach as an LJ 1-4 entry between slabs);
+ *   - charges are the per-particle charges of chem_set_particles at the time of the force evaluation: a reaction (new_q),
+ *     neighbour rule, ATRP flip, dissociation or chem_modify_particle(CHEM_STATE_CHARGE) acts from the next evaluation on
+ *     (the rule of chem_nb_coulomb);
+ *   - by types: parameters of the CURRENT type pair; an entry whose type pair has none contributes nothing;
+ *   - the energy goes to the list's slot of chem_obs.epot_list; chem_get_coulomb keeps meaning the non-bonded term only;
+ *   - chem_list_set_hybrid applies: force and energy times lambda;
+ *   - bond graph, cluster labels and exclusions: exactly what chem_list_add does for an LJ 1-4 list;
+ *   - chem_list_create with arity 3 or 4 is CHEM_ENOTIMPL; chem_list_set_params with np != 2, rc <= 0 or a non-finite value is
+ *     CHEM_EINVAL; prefactor = 0 is allowed (a list that does nothing);
+ *   - harmonic bonds are not evaluated inline while a list of this kind exists. */
+#define CHEM_POT_COULOMB_BOND  6
 #define CHEM_POT_ANG_HARMONIC 10
 #define CHEM_POT_ANG_COSINE   11
 #define CHEM_POT_ANG_TABULATED 12  /* angles func 8: params = { table handle }, grid in radians, f = -dU/dtheta */
