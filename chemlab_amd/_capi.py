@@ -170,6 +170,10 @@ PRODUCT_ONLY = {
     "get_coulomb": (_i, [_P, _pd, _pd]),
     "list_set_hybrid": (_i, [_P, _i, _d, _d]),   # (the CPU oracle has no hybrid lists)
     "list_get_lambda": (_i64, [_P, _i, _pd, _i64]),
+    # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
+    "debug_idle_skipped": (_i64, [_P]),
+    "debug_idle_wrong_skips": (_i64, [_P]),
+    "debug_idle_timeouts": (_i64, [_P]),
 }
 
 

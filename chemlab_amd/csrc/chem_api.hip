@@ -6,6 +6,7 @@
 // The host only synchronises at reaction steps (every `interval` steps) and at the end.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -19,6 +20,7 @@
 
 #include "chem_comm.hpp"
 #include "chem_geom_host.hpp"
+#include "chem_idle_host.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
 #include "chem_tab_host.hpp"
@@ -183,6 +185,29 @@ struct Ctx {
   int opt_tile_split = 0;    // narrow tiles at the end of every tile row (chem_geom_host.hpp plan_tiles): 0 off, nb * 10 + w
   int opt_bucket_cap = 0;    // testing: bucket rows of the fused rebuild narrower than 64 (provokes the mid-run overflow recovery)
   int64_t halts_recovered = 0;
+  // Neighbour launch only on steps that can need a rebuild (single domain, fused rebuild, accumulated criterion; DESIGN.md
+  // section 5, chem_idle_host.hpp).  skip_idle: 0 a launch on every step, 1 the rule, 2 testing -- no launch the host did not
+  // ask for itself, so that every regular rebuild stops the run and is redone.  idle_lag: the host enqueues step s once the
+  // device has published step s - lag (bounded look-ahead); idle_kappa: allowance on the published per-step displacement.
+  // (defaults from the sweep of profiles/skip_idle.txt)
+  int opt_skip_idle = 1, opt_idle_lag = 1; double opt_idle_kappa = 1.25;
+  int64_t idle_skipped = 0, idle_wrong = 0, idle_timeouts = 0;
+  // which steps of the running call went without the launch, from step skip_log_base on: a stop takes the steps enqueued behind
+  // it (they left at once and are redone) out of idle_skipped again; cleared wherever the host has seen the device without a stop
+  std::vector<bool> skip_log; int64_t skip_log_base = 0;
+  void skip_log_add(bool skipped) {
+    const int64_t at = step - skip_log_base;
+    if (at < 0) { skip_log.clear(); skip_log_base = step; }
+    else skip_log.resize((size_t)at, false);
+    skip_log.push_back(skipped);
+    if (skipped) ++idle_skipped;
+  }
+  void skip_log_stop(int64_t halt_step) {      // the run stopped at halt_step: nothing from there on was a step
+    const int64_t at = std::max<int64_t>(halt_step - skip_log_base, 0);
+    for (size_t k = (size_t)at; k < skip_log.size(); ++k) if (skip_log[k]) --idle_skipped;
+    if ((size_t)at < skip_log.size()) skip_log.resize((size_t)at);
+  }
+  void skip_log_confirm() { skip_log.clear(); skip_log_base = step; }
   // slab domain decomposition (chem_comm_init)
   bool dd_on = false; int P = 1, rk = 0;
   std::unique_ptr<Transport> tr;
@@ -202,6 +227,7 @@ struct Ctx {
   virtual int64_t debug_dump_rebuild(long long*, int64_t) { return 0; }
   virtual int64_t debug_force_list(int, int32_t*, int64_t) { return -1; }
   virtual void debug_tiles(int32_t* out) = 0;
+  virtual void debug_acc(double* out) = 0;
   virtual void join_async() {}
 };
 
@@ -345,7 +371,33 @@ template <typename R> struct CtxT : Ctx {
   bool fold_on() const { return dd_merged() && opt_dd_fold; }
   // (allocated here if need be: the first drift of a context runs before its first dd_step_sync, and a launch without the words
   //  would leave that step's displacement out of the accumulated distance)
-  unsigned long long* fold_arg() { if (!(dd_on && fold_on())) return nullptr; ensure_hflag(); return foldmax.p; }
+  // Single domain, fused rebuild, accumulated criterion: the same fold, two sets of words by the parity of the step's decision
+  // (its launch -- k_rebuild_fused or the force kernel -- reads one and clears the other)
+  // (skip_idle 0 is the launch on every step as it was: block maxima, no atomics, nothing published)
+  bool fold_sd() const { return use_fused && !dd_on && opt_criterion == 0 && opt_skip_idle != 0; }
+  unsigned long long* fold_arg() {
+    if (fold_sd()) { ensure_hflag(); return foldmax.p + fused_par * kFoldSlots; }
+    if (!(dd_on && fold_on())) return nullptr;
+    ensure_hflag(); return foldmax.p;
+  }
+  // the published state of the device and the host's generation of it (chem_idle_host.hpp)
+  int hint_gen = 1; int64_t hint_gen_step = 0;      // hint_gen_step: first step enqueued under this generation
+  IdleHint* hint_host() { return reinterpret_cast<IdleHint*>(hflag + 64); }
+  IdleHint* hint_dev() { return reinterpret_cast<IdleHint*>(hflag_dev + 64); }
+  void hint_invalidate() { ++hint_gen; hint_gen_step = step; }
+  IdleHint hint_read() {
+    IdleHint h{}; h.step = -1;
+    if (!hflag) return h;
+    const volatile IdleHint* v = hint_host();
+    const long long s1 = v->step;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    h.acc = v->acc; h.d = v->d; h.gen = v->gen; h.halted = v->halted;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (v->step == s1) h.step = s1;
+    return h;
+  }
+  bool skip_applies() const { return opt_skip_idle && fold_sd() && !want32 && !dbg_on; }
+
   DBuf<int> gtag;                      // slab: index of a tag's ghost copy on this rank (-1: none)
   DBuf<Box<R>> box_dev; Box<R> box_dev_host; bool box_dev_valid = false;   // device copy of the box for the standalone list kernel
   int S = 0;
@@ -425,6 +477,7 @@ template <typename R> struct CtxT : Ctx {
   double pick_list_skin() const {
     return chem::pick_list_skin(L, rc, skin, opt_list_skin, opt_criterion, opt_tiles != 0, opt_fused != 0, dd_on, P, dd_on ? nglob : n);
   }
+  void debug_acc(double* out) override { const DevCtl h = read_ctl(); out[0] = h.acc_ref; out[1] = h.acc_maxdist; }
   void debug_tiles(int32_t* out) override {
     if (geom_dirty) setup_geometry();
     const int ntx = use_tiles ? tile_ntx(box.nc[0], box.xs_nb, box.xs_w) : 0;
@@ -450,7 +503,7 @@ template <typename R> struct CtxT : Ctx {
     setup_fused();
     setup_tile_order();
     HIPCHK(hipStreamSynchronize(stream));
-    geom_dirty = false; resort = true;
+    geom_dirty = false; resort = true; hint_invalidate();
   }
 
   // Fused rebuild kernel: the grid must be co-resident (grid barriers), so it is sized from the
@@ -499,7 +552,7 @@ template <typename R> struct CtxT : Ctx {
     for (std::vector<int>* v : {&o.pos, &o.ord}) { v->resize(2 * (size_t)ntiles); std::copy_n(v->begin(), ntiles, v->begin() + ntiles); }
     tile_pos.upload(o.pos, stream); tile_ord.upload(o.ord, stream);
   }
-  void launch_rebuild_fused() {
+  void launch_rebuild_fused(bool publish = false) {      // publish: a step's decision in run() -- tells the host where the device stands
     FusedArgs<R> a{};
     a.n = n; a.ncell = box.ncell; a.ntiles = ntiles; a.CAP = tile_cap; a.S = S; a.has_excl = has_excl; a.criterion = opt_criterion;
     a.par = fused_par; a.seg_shift = seg_shift; a.tseg_shift = tseg_shift; a.nblk = cdiv(n, kIntPerBlock); a.want32 = want32 ? 1 : 0; a.ntypes = ntypes; a.ablate = dbg_on ? opt_ablate_list : 0; a.coop = opt_coop_overflow;
@@ -515,6 +568,8 @@ template <typename R> struct CtxT : Ctx {
     a.blockmax = blockmax.p; a.ctl = ctl.p; a.gb = gbar.p; a.box = box; a.act = act;
     a.wgst = dbg_on && wgst.p ? wgst.p : nullptr;
     a.bstart = bstart.p; a.bent = bent.p; a.bwork = bwork.p; a.bj = bj.p; a.nbent = (int)std::min<int64_t>(nbent, 1 << 30);
+    a.fold = fold_sd() ? (ensure_hflag(), foldmax.p) : nullptr;
+    a.hint = publish && fold_sd() ? hint_dev() : nullptr; a.gen = hint_gen;
     a.bslots = nullptr; a.bond_pass = 0;
     if (bonds_inline() && !(sizeof(R) == 8 && want32)) {   // (the exact fp64 builder of the int32 rows locates no slots: ensure_list32 rebuilds again)
       if (bslots.n < 2 * (size_t)n) bslots.alloc(2 * (size_t)n + 1024);      // two quads (kBondSlots = 8 words) per particle
@@ -1014,8 +1069,8 @@ template <typename R> struct CtxT : Ctx {
     launch_list_chain();
   }
 
-  void decide_and_rebuild() {
-    if (use_fused) { tbeg(1); launch_rebuild_fused(); tend(); return; }
+  void decide_and_rebuild(bool publish = false) {
+    if (use_fused) { tbeg(1); launch_rebuild_fused(publish); tend(); return; }
     hipLaunchKernelGGL(k_rebuild_decide<R>, dim3(1), dim3(1024), 0, stream, ctl.p, blockmax.p, cdiv(n, kIntPerBlock), 0.5 * skin_eff(), opt_criterion, 3, (const double*)nullptr, 0, (volatile int*)nullptr, 0, 0.5 * skin);
     launch_rebuild_chain();
   }
@@ -1027,8 +1082,9 @@ template <typename R> struct CtxT : Ctx {
     std::memset(hflag, 0, 4096);
     HIPCHK(hipHostGetDevicePointer((void**)&hflag_dev, hflag, 0));
     dd_vals.alloc(64 * kFoldSlots);
-    foldmax.alloc(kFoldSlots);
-    HIPCHK(hipMemsetAsync(foldmax.p, 0, kFoldSlots * sizeof(unsigned long long), stream));
+    foldmax.alloc(2 * kFoldSlots);
+    HIPCHK(hipMemsetAsync(foldmax.p, 0, 2 * kFoldSlots * sizeof(unsigned long long), stream));
+    hint_host()->step = -1;
   }
   void poll_ticket(volatile int* word, int ticket, const char* what) {
     long long spins = 0;
@@ -1161,8 +1217,16 @@ template <typename R> struct CtxT : Ctx {
   }
 
   // forced synchronous rebuild (run() prologue, observe); grows the row stride on overflow
-  void rebuild_now() {
+  // resumed: the step at which the device stopped the run is redone.  DevCtl::force_rebuild then says how the launch counts
+  // (left by the device: 2, a regular decision; 4 where the stopped launch had counted the step already), so that rebuilds,
+  // list_rebuilds and the accumulated distances come out as in a run that never stopped.  An attempt that has not counted the
+  // step (it met a full bucket row before its first barrier) leaves the step's fold words and the accumulated distance of
+  // parity halt_par untouched and clears only the other set: the next attempt reads the same parity again.  The resumed launch
+  // publishes like any step's (the host's look-ahead waits for this step at the next one).
+  void rebuild_now(bool resumed = false, int halt_kind = 0, int halt_par = 0) {
     const double t0 = now_s();
+    hint_invalidate();
+    bool counted = resumed && halt_kind == 3;
     for (int attempt = 0; attempt < 6; ++attempt) {
       if (dd_on) {      // (a slab rebuild the host calls for, not one of the device's decisions: counted on the host)
         set_ctl_field(&DevCtl::force_rebuild, 0); set_ctl_field(&DevCtl::acc_maxdist, 0.0); set_ctl_field(&DevCtl::acc_ref, 0.0);
@@ -1170,8 +1234,18 @@ template <typename R> struct CtxT : Ctx {
         if (attempt == 0) ++dd_direct_rebuilds;
         rebuild_dd();
       }
-      else { set_ctl_field(&DevCtl::force_rebuild, 1); decide_and_rebuild(); }
+      else {
+        if (!resumed) {
+          set_ctl_field(&DevCtl::force_rebuild, 1);
+          // (nothing depends on the maxima of a forced decision: words left behind by a path that does not read them go)
+          if (foldmax.p && !dd_on) HIPCHK(hipMemsetAsync(foldmax.p, 0, 2 * kFoldSlots * sizeof(unsigned long long), stream));
+        }
+        else if (counted) set_ctl_field(&DevCtl::force_rebuild, 4);
+        else fused_par = halt_par;
+        decide_and_rebuild(resumed);
+      }
       DevCtl h = read_ctl();
+      if (resumed && !h.bucket_overflow) counted = true;      // (a launch that got past its first barrier has counted the step)
       if (dd_on) agree_flags(h);
       if (h.halt) set_ctl_field(&DevCtl::halt, 0);       // (a launch that could not finish its lists also stopped the run: this IS the recovery)
       if (h.mig_error) throw ChemError(CHEM_ESTATE, "domain decomposition: particle migration error " + std::to_string(h.mig_error));
@@ -1313,8 +1387,8 @@ template <typename R> struct CtxT : Ctx {
     return nb;
   }
 
-  void compute_forces(bool speculative = false, int subset = 0) {
-    pair_guard = speculative ? (pair_da.gathered ? 2 : 1) : 0;
+  void compute_forces(bool speculative = false, int subset = 0, bool decide = false) {      // decide: single domain, no neighbour launch on this step (guard 3)
+    pair_guard = decide ? 3 : (speculative ? (pair_da.gathered ? 2 : 1) : 0);
     pair_subset = subset;
     const int tpp = pick_tpp();
     const bool timed = timed_step && subset == 0;
@@ -1421,7 +1495,7 @@ template <typename R> struct CtxT : Ctx {
         tr->exchange_with_scalar(halo_msg(), lower, upper, &ctl.p->step_m2, dd_vals.p, stream);
       }
       const int ticket = ++hticket;
-      pair_da = DecideArgs{dd_vals.p, P, (volatile int*)hflag_dev, ticket, dd_par, opt_criterion, 0.5 * skin, fold ? foldmax.p : nullptr};
+      pair_da = DecideArgs{dd_vals.p, P, (volatile int*)hflag_dev, ticket, dd_par, opt_criterion, 0.5 * skin, fold ? foldmax.p : nullptr, nullptr, 0, 0};
       dd_par ^= 1;
       compute_forces(true, 0);     // (guard 2: decision in the prologue of the force kernel)
       pair_da = DecideArgs{};
@@ -1485,10 +1559,35 @@ template <typename R> struct CtxT : Ctx {
     hipLaunchKernelGGL(k_scale_v<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, resc_buf.p + 1, (const DevCtl*)ctl.p);
   }
 
+  // Does step `step` get its neighbour launch?  (single domain, fused rebuild; the rule and its reasons: chem_idle_host.hpp)
+  // The host enqueues far faster than the device runs, so it first lets the device come within idle_lag steps: it spins on the
+  // pinned words, for a bounded time -- nothing on the device ever waits for the host, and a wait that runs out only means one
+  // launch more.
+  static constexpr double kIdleWaitS = 0.05;
+  bool neighbour_launch_wanted() {
+    ensure_hflag();
+    const IdleHost host{hint_gen, resort, want32 || dbg_on};
+    if (host.requested || host.diagnostics) return true;
+    if (opt_skip_idle == 2) return false;
+    IdleHint h = hint_read();
+    if (opt_idle_lag > 0 && step - opt_idle_lag >= hint_gen_step && !idle_hint_fresh(h, hint_gen, step, opt_idle_lag)) {      // (lag 0: no wait, whatever is there)
+      const double t0 = now_s();
+      for (long long spins = 1;; ++spins) {
+        h = hint_read();
+        if (idle_hint_fresh(h, hint_gen, step, opt_idle_lag)) break;
+        if (h.halted == hint_gen) return true;      // the run has stopped: nothing more will be published
+        idle_cpu_pause();
+        if ((spins & 1023) == 0 && now_s() - t0 > kIdleWaitS) { ++idle_timeouts; return true; }
+      }
+    }
+    return idle_launch(h, host, step, 0.5 * skin_eff(), opt_idle_kappa);
+  }
+
   // ---- the hot call -------------------------------------------------------------------
   void run(int64_t nsteps) override {
     if (!(dt > 0)) throw ChemError(CHEM_ESTATE, "dt not set");
     flush_host_state();
+    hint_invalidate();      // (whatever the last call's launches published: the first step of a call gets its neighbour launch)
     const double t0 = now_s();
     if (opt_time_pair) {
       const size_t want = (size_t)std::min<int64_t>(8 * (nsteps / opt_time_pair + 2), 16384);
@@ -1521,6 +1620,8 @@ template <typename R> struct CtxT : Ctx {
     // The device may stop an asynchronous run (fused rebuild: a cell outgrew its bucket row).  Every launch behind that
     // point has left at once; the host learns of it at its next synchronisation -- a reaction / ATRP step or the end of
     // the call --, repairs the set-up (wider rows or the unfused chain: rebuild_now) and re-enters the loop at that step.
+    int resume_kind = 0, resume_par = 0;       // DevCtl::halt and halt_par of that stop
+    int64_t timed_idle_skips = 0;
     auto halted = [&](int64_t& s) -> bool {
       if (!use_fused) return false;
       HIPCHK(hipStreamSynchronize(stream));
@@ -1529,11 +1630,16 @@ template <typename R> struct CtxT : Ctx {
       s = h.halt_step - step0; step = h.halt_step;
       set_ctl_field(&DevCtl::halt, 0);
       resort = true; resume = true; need_int1 = false;
+      resume_kind = h.halt; resume_par = fused_par = h.halt_par & 1;      // (the launches enqueued behind the stop flipped the host's parity and left at once)
+      skip_log_stop(h.halt_step);
+      if (h.halt == 2) ++idle_wrong;
       ++halts_recovered;
       if (g_trace) fprintf(stderr, "[chem trace] run stopped by the device at step %lld (bucket rows of %d, tile capacity %d, list rows of %d): recovering\n", (long long)h.halt_step, bcap, tile_cap, S);
       return true;
     };
     for (int64_t s = 0; s < nsteps; ++s) {
+      // (a stop the device has already told the pinned words about need not wait for the next synchronisation)
+      if (!resume && hflag && skip_applies() && const_cast<const volatile IdleHint*>(hint_host())->halted == hint_gen && halted(s)) { --s; continue; }
       if (need_int1) { launch_integrate<2>(false, false, step, 1); need_int1 = false; }
       timed_step = opt_time_pair && (pair_launch_no++ % opt_time_pair) == 0;
       if (timed_step) timed_extra = 1 + (int)((pair_launch_no / opt_time_pair) % 3);
@@ -1541,9 +1647,18 @@ template <typename R> struct CtxT : Ctx {
       const bool atrp_due = atrp_on && ((step + 1) % atrp.interval == 0);
       const bool last = (s == nsteps - 1);
       force_step_off = 1;      // (hybrid lists: these are the forces of step + 1, whose counter moves behind the integration)
-      if (resume) { resume = false; rebuild_now(); compute_forces(); }   // (positions are drifted, forces of this step were never evaluated)
+      if (resume) { resume = false; skip_log_add(false); rebuild_now(true, resume_kind, resume_par); compute_forces(); }   // (positions are drifted, forces of this step were never evaluated)
       else if (dd_on) dd_step_sync();   // decision, (rebuild,) forces
-      else { decide_and_rebuild(); compute_forces(); }
+      else if (skip_applies() && !neighbour_launch_wanted()) {
+        // the step cannot need a rebuild as far as the host can tell: the force kernel's prologue folds, decides and keeps the books
+        pair_da = DecideArgs{nullptr, 0, nullptr, 0, fused_par, 0, 0.5 * skin, foldmax.p, hint_dev(), hint_gen, step};
+        fused_par ^= 1;
+        compute_forces(false, 0, true);
+        pair_da = DecideArgs{};
+        skip_log_add(true);
+        if (timed_step && timed_extra == 1) ++timed_idle_skips;      // (a decide sample of 0 ms: the neighbour cost per step stays what the timers report)
+      }
+      else { if (skip_applies()) skip_log_add(false); decide_and_rebuild(true); compute_forces(); }
       force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
 
@@ -1552,6 +1667,7 @@ template <typename R> struct CtxT : Ctx {
         ++step;
         if (resc_kind == 1 || resc_kind == 3 || (resc_kind == 2 && step % (int64_t)resc_param == 0)) rescale_velocities();
         if ((react_due || atrp_due || last) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
+        if (react_due || atrp_due || last) skip_log_confirm();
         if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
         if (react_due) react_step();
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
@@ -1567,6 +1683,7 @@ template <typename R> struct CtxT : Ctx {
     check_flags();
     tm.run_wall_s += now_s() - t0;
     tm.steps += nsteps;
+    if (opt_time_pair && !ev_used && timed_idle_skips) { tm.decide_kernel_ms = 0; tm.decide_kernel_launches = timed_idle_skips; }
     if (opt_time_pair && ev_used) {
       // Decomposed path: speculative pair launches that met a pending rebuild leave at once; they are not
       // force evaluations, so samples far below the median are dropped from the average.
@@ -1589,6 +1706,7 @@ template <typename R> struct CtxT : Ctx {
           default: tm.bonded_kernel_ms += t; tm.bonded_kernel_launches++; break;
         }
       }
+      tm.decide_kernel_launches += timed_idle_skips;
     }
   }
 
@@ -1612,7 +1730,7 @@ template <typename R> struct CtxT : Ctx {
   }
   // ---- idioms shared by the routines of the reaction cadence (react_step, diss_step, atrp_step) ----
   bool any_typed_list() const { for (auto& l : top.lists) if (l.by_types) return true; return false; }
-  void request_rebuild() { resort = true; set_ctl_field(&DevCtl::force_rebuild, 1); }
+  void request_rebuild() { resort = true; hint_invalidate(); set_ctl_field(&DevCtl::force_rebuild, 1); }
   // property changes decided on the host (the mirrors already hold them) -> device arrays.  wait = false: the caller
   // keeps `chg` alive and synchronises the stream itself
   DBuf<PropChangeDev> prop_dev;
@@ -2912,6 +3030,9 @@ int chem_set_option(chem_ctx* ctx, const char* name, double value) {
     REQUIRE(chem_comm_unique_id(uid) == 0, CHEM_ECOMM, "cannot create an RCCL unique id");
     CTX.tr.reset(new RcclTransport(1, 0, uid)); CTX.dd_on = true; CTX.P = 1; CTX.rk = 0; CTX.geom_dirty = true;
   }
+  else if (k == "skip_idle") { const int v = (int)value; REQUIRE(v >= 0 && v <= 2, CHEM_EINVAL, "skip_idle must be 0, 1 or 2"); CTX.opt_skip_idle = v; CTX.resort = true; }
+  else if (k == "idle_lag") { const int v = (int)value; REQUIRE(v >= 0 && v <= 64, CHEM_EINVAL, "idle_lag must be 0..64"); CTX.opt_idle_lag = v; }
+  else if (k == "idle_kappa") { REQUIRE(value >= 1.0 && value <= 16.0, CHEM_EINVAL, "idle_kappa must be 1..16"); CTX.opt_idle_kappa = value; }
   else if (k == "count_intra_inter") CTX.opt_intra_inter = value != 0;
   else if (k == "skip_inactive_pairs") { CTX.opt_skip_inactive = value != 0; CTX.pair_dirty = true; }
   else throw ChemError(CHEM_EINVAL, "unknown option " + k);
@@ -2928,6 +3049,11 @@ int64_t chem_debug_dump_rebuild(chem_ctx* ctx, long long* out, int64_t cap) { re
 // ... and the tile geometry in use: out[0..5] = tiles, cells along x, wide tiles per row, width of the narrow ones, tile rows, LDS slots per tile
 int64_t chem_debug_tiles(chem_ctx* ctx, int32_t* out) { try { ctx->c->debug_tiles(out); return 0; } catch (...) { return -2; } }
 int64_t chem_debug_halts(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->halts_recovered : -1; }
+int64_t chem_debug_idle_skipped(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->idle_skipped : -1; }
+int64_t chem_debug_idle_wrong_skips(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->idle_wrong : -1; }
+int64_t chem_debug_idle_timeouts(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->idle_timeouts : -1; }
+// tests (unlisted): out[0] = DevCtl::acc_ref, out[1] = DevCtl::acc_maxdist after the last call
+int64_t chem_debug_acc(chem_ctx* ctx, double* out) { try { ctx->c->debug_acc(out); return 0; } catch (...) { return -2; } }
 int64_t chem_debug_force_list(chem_ctx* ctx, int32_t tag, int32_t* out, int64_t cap) { try { return ctx->c->debug_force_list(tag, out, cap); } catch (...) { return -2; } }
 
 int chem_comm_unique_id(char uid[128]) {

@@ -14,6 +14,7 @@
 #include "../../include/chem_mi355.h"
 #include "../../include/chem_philox.h"
 #include "chem_geom_host.hpp"
+#include "chem_idle_host.hpp"
 
 namespace chem {
 
@@ -47,7 +48,8 @@ struct DevCtl {
   unsigned long long step_max2_bits;  // max |dx|^2 of the current step (bits of a non-negative real)
   double acc_maxdist;                 // accumulated sqrt(max|dx|^2) since the last rebuild
   int need_rebuild;                   // decision of the current step (read by the rebuild chain)
-  int force_rebuild;                  // host request (topology/exclusions changed)
+  int force_rebuild;                  // host request (topology/exclusions changed): 1.  Set when a stopped run is resumed (halt below): 2 = build at
+                                      // this step, the reference rule counts it as the regular decision it was; 4 = build again, everything is counted already
   int nl_overflow;                    // max neighbours seen when a row overflowed (0 = fine)
   int stage_overflow;                 // stencil tile exceeded the LDS capacity
   int cand_count;                     // reaction candidates appended
@@ -75,10 +77,48 @@ struct DevCtl {
   // later launch of the run leaves at once (integrate, forces, bonded, rebuild), so the state stays "drifted, forces of
   // halt_step not evaluated"; the host finds the flag at its next synchronisation, rebuilds with wider rows (or the unfused
   // chain) and resumes at that step.
+  // halt: 1 a full bucket row (nothing of the step counted yet), 2 a rebuild fell due on a step without a neighbour launch
+  // (k_pair_tiles guard 3; nothing counted either), 3 lists the launch could not finish (the step is counted).  halt_par: the
+  // parity of acc_pp the stopped step's decision read.
   int halt;
   int bond_slot_miss;                 // list build: a bonded partner was not among the located excluded partners (internal: the host only enables inline bonds when it cannot happen)
   long long halt_step;
+  int halt_par, pad1;
 };
+
+// ---- one step's decision about the Verlet list, shared by everything that takes it from fold words: the prologue of the force
+// kernel (guard 2: slabs, guard 3: single domain without a neighbour launch) and P0 of k_rebuild_fused ----
+// maximum of nwords bit patterns of non-negative reals, by every wave for itself: lane l takes words l, l + 64, ...
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long mb) {
+  for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = __shfl_xor(mb, o); mb = v > mb ? v : mb; }
+  return mb;
+}
+__device__ __forceinline__ unsigned long long fold_words_max(const unsigned long long* w, int nwords) {
+  unsigned long long mb = 0;
+  for (int q = (int)(threadIdx.x & 63); q < nwords; q += 64) { const unsigned long long v = w[q]; mb = v > mb ? v : mb; }
+  return wave_max_u64(mb);
+}
+// the bookkeeping of a decision, by ONE thread of the launch: accumulated distance (double-buffered by parity: every workgroup
+// of the launch reads [par]), the reference rule on the workload's skin (reported rebuild count; acc_ref and ref_rebuilds are
+// this thread's alone) and the counts.  forced = DevCtl::force_rebuild as every workgroup read it.
+__device__ __forceinline__ void decide_book(DevCtl* ctl, int par, int criterion, double m2, double acc, int need, int forced, double half_skin_ref) {
+  ctl->step_m2 = m2; ctl->acc_pp[par ^ 1] = need ? 0.0 : acc; ctl->acc_maxdist = need ? 0.0 : acc;
+  ctl->need_rebuild = need;
+  if (forced & 4) return;      // a resumed step whose first launch counted it
+  const double accr = criterion ? sqrt(m2) : ctl->acc_ref + sqrt(m2);
+  const bool rn = (accr > half_skin_ref) || (forced & 1);
+  ctl->acc_ref = rn ? 0.0 : accr;
+  if (rn) ctl->ref_rebuilds++;
+  if (need) ctl->rebuild_count++;
+}
+// the same thread tells the host where the device stands (chem_idle_host.hpp; pinned memory, the step last)
+__device__ __forceinline__ void publish_hint(IdleHint* hint, int gen, long long step, double acc, double d) {
+  if (!hint) return;
+  volatile IdleHint* h = hint;
+  h->gen = gen; h->acc = acc; h->d = d;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  h->step = step;
+}
 
 // bonded tables (per-tag CSR, see K4-K6 below; declared here because the list build records the LDS slots of bonded partners)
 constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 16-byte quads)
@@ -246,6 +286,8 @@ __global__ __launch_bounds__(256) void k_integrate(int n, Vec4<R>* __restrict__ 
   // foldmax (decomposed path): kFoldSlots words that collect the block maxima with one atomicMax per block (block b -> word
   // b % kFoldSlots: a few dozen atomics per address, spread over the launch) -- the one-block fold launch between this kernel
   // and the halo exchange is gone; the words travel with the halo, the force kernel's prologue takes the maximum and clears them
+  // (single domain, fused rebuild, option skip_idle: the same fold into one of two sets of words, chosen by the host by the parity
+  //  of the step's decision; the launch that decides -- k_rebuild_fused P0 or k_pair_tiles guard 3 -- reads it and clears the other)
   if (ctl->halt) return;   // (uniform scalar load; see DevCtl::halt)
   // kIntPerBlock particles per 256-thread block: every thread owns kIntPerBlock/256 particles and issues
   // all their loads before the first dependent instruction (more bytes in flight per wave for this
@@ -2215,7 +2257,10 @@ __device__ __noinline__ uint4 bond_record(const TileLDS<R>* T, int p, const Bond
 
 // (fold != nullptr: `gathered` holds n * kFoldSlots bit patterns of squared displacements -- every rank's fold words, see
 //  k_integrate -- instead of n doubles; `fold` = this rank's words, cleared here for the next step)
-struct DecideArgs { const double* gathered; int n; volatile int* host_flag; int ticket, par, criterion; double half_skin_ref; unsigned long long* fold; };
+// guard 3 (single domain, a step without a neighbour launch): `fold` = both parities of the fold words ([par] read, [par ^ 1]
+// cleared for the next step's integrate), `hint` / `gen` / `istep` as in FusedArgs; gathered, n, host_flag and ticket unused.
+struct DecideArgs { const double* gathered; int n; volatile int* host_flag; int ticket, par, criterion; double half_skin_ref; unsigned long long* fold;
+                    IdleHint* hint; int gen; long long istep; };
 
 // (fp64: the 32-byte-per-slot image allows one or two workgroups per CU anyway -- 128 registers instead of 80 and spills)
 // DIAG = true: diagnostic instantiation with per-block phase stamps (`dbg`) and early exits (`ablate`: 1 stop after
@@ -2242,13 +2287,17 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
   if (DIAG && dbg) st0 = wall_clock64();
   if (DIAG && ablate == 4) return;   // diagnostic: dispatch cost only
-  if (guard == 2) {
+  // guard 3 (no neighbour launch on this step): every workgroup folds the integrate kernel's words and decides, workgroup 0
+  // keeps the books and tells the host.  The four loads are issued here and used behind the descriptor's barrier -- one memory
+  // latency for both instead of two in a row on every workgroup's critical path.
+  unsigned long long g3_w = 0; double g3_acc = 0; int g3_forced = 0, g3_halt = 0;
+  static_assert(kFoldSlots == kWave, "guard 3 reads one fold word per lane");
+  if (guard == 3) {
+    g3_halt = ctl->halt; g3_w = da.fold[da.par * kFoldSlots + lane_id()]; g3_acc = ctl->acc_pp[da.par]; g3_forced = ctl->force_rebuild;
+  } else if (guard == 2) {
     double m2;
-    if (da.fold) {      // every wave for itself: lane l takes words l, l + 64, ... of all ranks, then a wave maximum
-      const unsigned long long* gw = reinterpret_cast<const unsigned long long*>(da.gathered);
-      unsigned long long mb = 0;
-      for (int q = lane_id(); q < da.n * kFoldSlots; q += 64) { const unsigned long long v = gw[q]; mb = v > mb ? v : mb; }
-      for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = __shfl_xor(mb, o); mb = v > mb ? v : mb; }
+    if (da.fold) {      // the fold words of all ranks
+      const unsigned long long mb = fold_words_max(reinterpret_cast<const unsigned long long*>(da.gathered), da.n * kFoldSlots);
       m2 = sizeof(R) == 4 ? bits_real_f(mb) : bits_real_d(mb);
       if (blockIdx.x == 0 && threadIdx.x < kFoldSlots) da.fold[threadIdx.x] = 0ull;      // (sent already: the exchange is ahead of this launch in the stream)
     } else {
@@ -2259,35 +2308,48 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
     const int forced = ctl->force_rebuild;
     const int need = (acc > half_skin) || forced;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      ctl->step_m2 = m2; ctl->acc_pp[da.par ^ 1] = need ? 0.0 : acc; ctl->acc_maxdist = need ? 0.0 : acc;
-      {      // the reference rule on the workload's skin (reported rebuild count; these two words are this thread's alone)
-        const double accr = da.criterion ? sqrt(m2) : ctl->acc_ref + sqrt(m2);
-        const bool rn = (accr > da.half_skin_ref) || forced;
-        ctl->acc_ref = rn ? 0.0 : accr;
-        if (rn) ctl->ref_rebuilds++;
-      }
       // (force_rebuild is NOT cleared here: workgroups that start later must read the same value -- the host clears it,
       //  stream-ordered, at the top of the slab rebuild this decision triggers)
-      if (need) ctl->rebuild_count++;
-      ctl->need_rebuild = need;
+      decide_book(ctl, da.par, da.criterion, m2, acc, need, forced ? 1 : 0, da.half_skin_ref);
       da.host_flag[0] = need;
       __threadfence_system();
       da.host_flag[1] = da.ticket;
     }
     if (need) return;
   } else if (guard && ctl->need_rebuild) return;   // speculative launch (decomposed path): the host rebuilds first and launches again
-  if (ctl->halt) return;
+  if (guard != 3 && ctl->halt) return;
   __shared__ TileLDS<R> T;
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   CHEM_DYN_LDS(R);
   if (MODE != 2) for (int k = threadIdx.x; k < ntypes * ntypes; k += BS) spc[k] = pcore[k];
-  if (guard != 2 && blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
+  if (guard < 2 && blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
   const R u_rc2 = sizeof(R) == 4 ? (R)uni.rc2 : (R)uni.drc2, u_lj1 = sizeof(R) == 4 ? (R)uni.lj1 : (R)uni.dlj1,
           u_lj2 = sizeof(R) == 4 ? (R)uni.lj2 : (R)uni.dlj2;
   const int vtile = xcd_remap(blockIdx.x, ntiles);   // ntiles = tiles of THIS launch (all of them, or one of the two subsets below)
   const int tile = vtile < sub_.n1 ? sub_.base1 + vtile : sub_.base2 + (vtile - sub_.n1);
   tile_load_desc<R>(T, desc, tile);
   __syncthreads();
+  if (guard == 3) {
+    // The host left the launch out on a prediction; if a rebuild is due after all, nothing is counted, the run stops here
+    // like behind a full bucket row and the host redoes the step with the launch (nothing but LDS has been written so far).
+    if (g3_halt) return;
+    const unsigned long long mb = wave_max_u64(g3_w);
+    const double m2 = sizeof(R) == 4 ? bits_real_f(mb) : bits_real_d(mb);
+    const double acc = g3_acc + sqrt(m2);
+    const int need = (acc > half_skin) || g3_forced;
+    if (blockIdx.x == 0 && threadIdx.x < kFoldSlots) da.fold[(da.par ^ 1) * kFoldSlots + threadIdx.x] = 0ull;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (need) {
+        if (!g3_forced) ctl->force_rebuild = 2;
+        ctl->halt_step = da.istep; ctl->halt_par = da.par; ctl->halt = 2;
+        if (da.hint) { volatile IdleHint* h = da.hint; h->halted = da.gen; }
+      } else {
+        decide_book(ctl, da.par, 0, m2, acc, 0, 0, da.half_skin_ref);
+        publish_hint(da.hint, da.gen, da.istep, acc, sqrt(m2));
+      }
+    }
+    if (need) return;
+  }
   if (DIAG && ablate == 3) return;   // diagnostic: descriptor load only
   if (DIAG && dbg) st1 = wall_clock64();
   const int nhome = T.geom[4], hbase = T.geom[5];
@@ -2301,7 +2363,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   uint4 bwv = make_uint4(~0u, ~0u, ~0u, ~0u);
   // (uniform.  Single domain: set by the rebuild of THIS step, cleared by the next idle decision; slabs: the host rebuilds, it
   //  asks for the record with bond_mode 3 = mode 2 + record now)
-  const bool bond_rec = bslots && brec && ((bond_mode == 2 && ctl->need_rebuild != 0) || bond_mode == 3);
+  //  (guard 3: a step without a rebuild, and workgroup 0 is writing the word)
+  const bool bond_rec = bslots && brec && ((bond_mode == 2 && guard != 3 && ctl->need_rebuild != 0) || bond_mode == 3);
 #ifndef CHEM_NT_PRE
 #define CHEM_NT_PRE 1
 #endif
@@ -3006,6 +3069,10 @@ template <typename R> struct FusedArgs {
                          //    0: the list build removes the excluded pairs and records their slots
   Box<R> box; ActMask act;
   long long* wgst;   // diagnostics (option debug_stamps=2): 8 wall-clock stamps per workgroup of the last rebuilding launch
+  // accumulated criterion: the step's maxima as k_integrate folded them, both parities ([par] read, [par ^ 1] cleared for the next
+  // step's integrate) -- 64 reads per workgroup where the block maxima are 1954 at a million particles; nullptr: blockmax
+  unsigned long long* fold;
+  IdleHint* hint; int gen;      // pinned host words the bookkeeping thread publishes (step, accumulated distance, displacement) to; may be nullptr
 };
 
 // segment offsets: s_off[k] = base + sum of tot[0..k), s_off[nseg] = grand total (nseg <= 1024)
@@ -3064,26 +3131,24 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
   if (ctl->halt) return;   // a previous launch of this run stopped it (set one launch ago at the earliest: every workgroup sees it)
   // ---- P0: decision, computed redundantly by every workgroup ----
   unsigned long long m = 0;
-  for (int k = t; k < a.nblk; k += BS) { const unsigned long long v = a.blockmax[k]; m = v > m ? v : m; }
-  for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = __shfl_xor(m, o); m = v > m ? v : m; }
-  if (lane == 0) s_m[w] = m;
-  __syncthreads();
-  m = s_m[0];
+  if (a.fold) {
+    m = fold_words_max(a.fold + a.par * kFoldSlots, kFoldSlots);
+    if (b == 0 && t < kFoldSlots) a.fold[(a.par ^ 1) * kFoldSlots + t] = 0ull;
+  } else {
+    for (int k = t; k < a.nblk; k += BS) { const unsigned long long v = a.blockmax[k]; m = v > m ? v : m; }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = __shfl_xor(m, o); m = v > m ? v : m; }
+    if (lane == 0) s_m[w] = m;
+    __syncthreads();
+    m = s_m[0];
 #pragma unroll
-  for (int k = 1; k < BS / 64; ++k) m = s_m[k] > m ? s_m[k] : m;
+    for (int k = 1; k < BS / 64; ++k) m = s_m[k] > m ? s_m[k] : m;
+  }
   const double m2 = sizeof(R) == 4 ? bits_real_f(m) : bits_real_d(m);
   double acc = a.criterion ? sqrt(m2) : ctl->acc_pp[a.par] + sqrt(m2);
   const int forced = ctl->force_rebuild;
   const int need = (acc > a.half_skin) || forced;
-  // reference rule on the workload's skin (bookkeeping of thread (0,0) only: nobody else reads these two words)
-  auto ref_update = [&]() {
-    const double accr = a.criterion ? sqrt(m2) : ctl->acc_ref + sqrt(m2);
-    const bool rn = (accr > a.half_skin_ref) || forced;
-    ctl->acc_ref = rn ? 0.0 : accr;
-    if (rn) ctl->ref_rebuilds++;
-  };
   if (!need) {
-    if (b == 0 && t == 0) { ctl->step_m2 = m2; ctl->acc_pp[a.par ^ 1] = acc; ctl->acc_maxdist = acc; ctl->need_rebuild = 0; ref_update(); }
+    if (b == 0 && t == 0) { decide_book(ctl, a.par, a.criterion, m2, acc, 0, 0, a.half_skin_ref); publish_hint(a.hint, a.gen, a.istep, acc, sqrt(m2)); }
     return;
   }
 
@@ -3104,14 +3169,15 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
     // host redoes this rebuild with the unfused chain (force_rebuild stays set)
     for (int k = b * BS + t; k < a.ncell; k += NB * BS) a.cell_cnt[k] = 0;
     if (b == 0) for (int k = t; k < 1024; k += BS) a.btot[k] = 0;
-    if (b == 0 && t == 0) { ctl->need_rebuild = 1; ctl->force_rebuild = 1; ctl->halt_step = a.istep; ctl->halt = 1; }
+    //  (a regular decision stays one for the reference rule when the host redoes it: DevCtl::force_rebuild)
+    if (b == 0 && t == 0) { ctl->need_rebuild = 1; ctl->force_rebuild = forced ? forced : 2; ctl->halt_step = a.istep; ctl->halt_par = a.par; ctl->halt = 1; if (a.hint) { volatile IdleHint* h = a.hint; h->halted = a.gen; } }
     return;
   }
   // every workgroup has taken its decision: the control block may change now
   if (b == 0 && t == 0) {
-    ctl->step_m2 = m2; ctl->acc_pp[a.par ^ 1] = 0.0; ctl->acc_maxdist = 0.0; ctl->force_rebuild = 0;
-    ctl->rebuild_count++; ctl->need_rebuild = 1;
-    ref_update();
+    ctl->force_rebuild = 0;
+    decide_book(ctl, a.par, a.criterion, m2, acc, 1, forced, a.half_skin_ref);
+    publish_hint(a.hint, a.gen, a.istep, 0.0, sqrt(m2));
   }
 
   // ---- P4: cell_start, canonical order inside every cell + gather + tag -> index map; home count of every tile ----
@@ -3277,7 +3343,7 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
   // the capacity at its next synchronisation and re-enters at this step (chem_api.hip: halted(), rebuild_now()).
   if (t == 0) {
     const volatile DevCtl* vc = ctl;
-    if (vc->stage_overflow | vc->nl_overflow) { ctl->halt_step = a.istep; ctl->halt = 1; }
+    if (vc->stage_overflow | vc->nl_overflow) { ctl->halt_step = a.istep; ctl->halt_par = a.par; ctl->halt = 3; if (b == 0 && a.hint) { volatile IdleHint* h = a.hint; h->halted = a.gen; } }
   }
   if (b == 0 && t == 0) a.gb->stamp[6] = wall_clock64();
   if (wst) { __syncthreads(); if (t == 0) wst[7] |= (long long)(wall_clock64() - wst[0]) << 16; }

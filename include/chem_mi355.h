@@ -465,6 +465,12 @@ int chem_device_sync(chem_ctx* ctx);
 int chem_set_nlist_capacity(chem_ctx* ctx, int max_neighbours);
 /* generic integer knobs, see DESIGN.md ("tpp": lanes per particle in the pair kernel, ...) */
 int chem_set_option(chem_ctx* ctx, const char* name, double value);
+/* counters of "neighbour launch only on steps that can need a rebuild" (options skip_idle, idle_lag, idle_kappa; DESIGN.md
+ * section 5), since the context was created: steps that ran without the neighbour launch; such steps on which a rebuild fell
+ * due after all (the run stopped there and the step was redone); waits for the device's published state that ran out */
+int64_t chem_debug_idle_skipped(chem_ctx* ctx);
+int64_t chem_debug_idle_wrong_skips(chem_ctx* ctx);
+int64_t chem_debug_idle_timeouts(chem_ctx* ctx);
 
 /* ---- multi-GPU (spatial domain decomposition, RCCL halo) ------------------------------ */
 /* storage.DomainDecomposition(system, nodeGrid, cellGrid) under mpirun
