@@ -25,7 +25,7 @@ PREC_F32, PREC_F64 = 32, 64
 
 POT = dict(HARMONIC=1, FENE=2, TABULATED=3, FENE_LJ=4, LJ_BOND=5, COULOMB_BOND=6, DIH_HARMONIC=23, ANG_HARMONIC=10, ANG_COSINE=11, ANG_TABULATED=12, DIH_NCOS=20, DIH_RB=21, DIH_TABULATED=22)
 STATE = dict(POS=1, VEL=2, FORCE=3, TYPE=4, STATE=5, RESID=6, MASS=7, ID=8, IMAGE=9, MOLID=10,
-             POS_UNFOLDED=11, CHARGE=12)
+             POS_UNFOLDED=11, CHARGE=12, LAMBDA=13)
 
 
 class ChemLibraryError(RuntimeError):
@@ -170,6 +170,11 @@ PRODUCT_ONLY = {
     "get_coulomb": (_i, [_P, _pd, _pd]),
     "list_set_hybrid": (_i, [_P, _i, _d, _d]),   # (the CPU oracle has no hybrid lists)
     "list_get_lambda": (_i64, [_P, _i, _pd, _i64]),
+    # per-particle resolution lambda (the CPU oracle has none)
+    "nb_resolution": (_i, [_P, _i, _i, _i, _d]),
+    "resolution_rate": (_i, [_P, _i, _d, _i, _d, _d, _i]),
+    "set_resolution": (_i, [_P, _i64, _pi64, _pd]),
+    "reaction_set_resolution": (_i, [_P, _i, _i, _d]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

@@ -137,6 +137,8 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
     mix = espressopp.interaction.VerletListMixedTabulated(vl)
     cr_observs = {} if cr_observs is None else cr_observs
     has_lj = has_tab = has_mix = False
+    # func 11 / 15: dynamic-resolution pairs, grouped by max_force into one VerletListDynamicResolution* each (:584-611,819-862)
+    dyn_tab, dyn_lj = collections.OrderedDict(), collections.OrderedDict()
 
     def pot_file(name):                                  # table.xvg -> table.pot next to it, converted when missing (:764-769)
         xvg = os.path.join(table_dir, name)
@@ -170,6 +172,33 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
                     mix.setPotential(type1=t1, type2=t2, potential=pot)
                     has_mix = True
                     continue
+                elif param["func"] == 11:
+                    # `[table [max_force]]`: a table scaled by lambda_i lambda_j; without a name table_<n1>_<n2>.xvg
+                    pr = param["params"]
+                    if len(pr) > 2:
+                        raise RuntimeError("nonbond_params %s %s func 11: expected `[table [max_force]]`, got %d parameters" % (n1, n2, len(pr)))
+                    max_force = float(pr[1]) if len(pr) == 2 else -1.0
+                    dyn_tab.setdefault(max_force, collections.OrderedDict())[(t1, t2)] = pr[0] if pr else "table_%s_%s.xvg" % (n1, n2)
+                    continue
+                elif param["func"] == 15:
+                    # `sigma epsilon [max_force]` or `max_force` alone (sigma, epsilon from the atom types by the combination rule)
+                    pr = param["params"]
+                    max_force = -1.0
+                    if len(pr) == 0 or len(pr) > 3:
+                        raise RuntimeError("nonbond_params %s %s func 15: expected `sigma epsilon [max_force]` or `max_force`, got %d parameters" % (n1, n2, len(pr)))
+                    if len(pr) == 1:
+                        max_force = float(pr[0])
+                        a1, a2 = gt.gt.atomtypes[n1], gt.gt.atomtypes[n2]
+                        s1, e1 = convertc6c12(a1["sigma"], a1["epsilon"], cr)
+                        s2, e2 = convertc6c12(a2["sigma"], a2["epsilon"], cr)
+                        sig, eps = combination(s1, e1, s2, e2, cr)
+                    else:
+                        sig, eps = float(pr[0]), float(pr[1])
+                        if len(pr) == 3:
+                            max_force = float(pr[2])
+                    if sig > 0.0:
+                        dyn_lj.setdefault(max_force, collections.OrderedDict())[(t1, t2)] = (sig, eps)
+                    continue
                 else:
                     raise NotImplementedError("nonbond_params func %d is outside the hot-path scope (SURVEY.md 2.1 #3)" % param["func"])
             elif n1 in tables_ and n2 in tables_:
@@ -200,6 +229,20 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
                 for n2 in names[i:]:
                     qq.setPotential(type1=gt.used_atomsym_atomtype[n1], type2=gt.used_atomsym_atomtype[n2], potential=pot_qq)
             system.addInteraction(qq, "coulomb")
+    for bn, (max_force, data) in enumerate(dyn_tab.items()):
+        inter = espressopp.interaction.VerletListDynamicResolutionTabulated(vl, False)
+        for (t1, t2), name in data.items():
+            inter.setPotential(type1=t1, type2=t2, potential=espressopp.interaction.Tabulated(itype=1, filename=pot_file(name), cutoff=tab_cutoff))
+        if max_force != -1:
+            inter.setMaxForce(max_force)
+        system.addInteraction(inter, "tab-dynamic_%d" % bn)
+    for bn, (max_force, data) in enumerate(dyn_lj.items()):
+        inter = espressopp.interaction.VerletListDynamicResolutionLennardJones(vl, False)
+        for (t1, t2), (sig, eps) in data.items():
+            inter.setPotential(type1=t1, type2=t2, potential=espressopp.interaction.LennardJones(epsilon=eps, sigma=sig, cutoff=lj_cutoff))
+        if max_force != -1:
+            inter.setMaxForce(max_force)
+        system.addInteraction(inter, "lj-dynamic_%d" % bn)
     if has_lj:
         system.addInteraction(lj, "lj")
     if has_tab:

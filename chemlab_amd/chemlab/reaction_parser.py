@@ -1,7 +1,7 @@
-"""Reaction .cfg (INI) -> dict, normal (bond-forming / virtual) reactions only.
-Grammar and defaults of /root/reference/src/chemlab/reaction_parser.py:36-66,130-232,235-266
-(SURVEY.md Appendix A).  Dissociation / exchange equations and `ext_*` extensions are out of scope
-and raise NotImplementedError when a reaction actually needs them."""
+"""Reaction .cfg (INI) -> dict: normal (bond-forming / virtual), exchange and dissociation reactions.
+Grammar and defaults of /root/reference/src/chemlab/reaction_parser.py:36-127,130-232,235-266
+(SURVEY.md Appendix A).  What is out of scope (a dissociation without `alpha`, the smooth cutoff, unknown `ext_*`
+extensions) raises NotImplementedError when a reaction actually needs it."""
 import ast
 import collections
 import configparser
@@ -9,6 +9,7 @@ import re
 
 REACTION_NORMAL = "normal"
 REACTION_EXCHANGE = "exchange"
+REACTION_DISSOCIATION = "dissociation"
 
 _RE_REACTANT = re.compile(r"(?P<name>\w+)\((?P<min>\d+),\s*(?P<max>\d+)\)")
 _RE_PRODUCT = re.compile(r"(?P<name>\w+)\((?P<delta>[0-9-]+)\)")
@@ -32,6 +33,21 @@ def parse_equation(text):
         rl[k]["delta"] = p.group("delta")
         rl[k]["new_type"] = p.group("name")
     return rl, REACTION_NORMAL
+
+
+def parse_dissociation_equation(text):
+    """`A(a,b):B(c,d) -> A'(x) + B'(y)` (reaction_parser.py:68-95): the bond A:B breaks; the state windows are half-open,
+    x and y are state increments, A' / B' the types the two particles take once their resolution is back at 1."""
+    reactants, products = (t.strip() for t in text.split("->"))
+    mols = [_RE_REACTANT.match(p.strip()) for p in reactants.split(":")]
+    prods = [_RE_PRODUCT.match(p.strip()) for p in products.split("+")]
+    if len(mols) != 2 or None in mols or len(prods) != 2 or None in prods:
+        raise ValueError("cannot parse dissociation %r" % text)
+    rl = {"type_1": mols[0].groupdict(), "type_2": mols[1].groupdict()}
+    for k, p in zip(("type_1", "type_2"), prods):
+        rl[k]["delta"] = p.group("delta")
+        rl[k]["new_type"] = p.group("name")
+    return rl, REACTION_DISSOCIATION
 
 
 def parse_exchange_equation(text):
@@ -69,8 +85,17 @@ def process_reaction(sec):
     left = eq.split("->")[0]
     if ":" in left and "+" in left:             # A:B + C -> A:C + B  (reaction_parser.py:98-127)
         data["reactant_list"], data["reaction_type"] = parse_exchange_equation(eq)
-    elif ":" in left:                           # A:B -> A + B: dissociation needs BasicDynamicResolution (AdResS), out of scope
-        raise NotImplementedError("dissociation reactions A(a,b):B(c,d) -> A'(x) + B'(y) need the dynamic-resolution machinery (reaction_setup.py:253-356), out of scope")
+    elif ":" in left:                           # A:B -> A + B: dissociation, the products fade in at rate alpha (reaction_setup.py:257-356)
+        if "alpha" not in sec:
+            raise NotImplementedError("dissociation reaction %r: `alpha` is required -- the resolution rate at which the two particles fade back "
+                                      "in (BasicDynamicResolution, reaction_setup.py:303-305); a break without it is not modelled" % eq)
+        try:
+            data["reactant_list"], data["reaction_type"] = parse_dissociation_equation(eq)
+        except ValueError as e:
+            raise NotImplementedError("cannot parse reaction %r: %s" % (eq, e))
+        data["alpha"] = float(sec["alpha"])
+        if "diss_rate" in sec:
+            data["diss_rate"] = float(sec["diss_rate"])
     else:
         try:
             data["reactant_list"], data["reaction_type"] = parse_equation(eq)

@@ -47,6 +47,40 @@ class SetupReactions(object):
                 self.dynamic_types.update((n2t[old], n2t[new]))
         return r
 
+    def _setup_reaction_dissociation(self, cr, fpl):
+        """`A(a,b):B(c,d) -> A'(x) + B'(y)` with `alpha` (reaction_setup.py:257-356): on the break both particles get
+        lambda_adr = 0 and keep their type; BasicDynamicResolution({t1_old: alpha, t2_old: alpha}) ramps them, and its
+        post-process changes type, mass and charge when lambda is back at 1.  The broken bonds are those of the group's list."""
+        e, rl, n2t = self.espp, cr["reactant_list"], self.name2type
+        if cr.get("connectivity_map"):
+            raise RuntimeError("connectivity_map not supported by dissociation reaction")
+        t1_old, t1_new = n2t[rl["type_1"]["name"]], n2t[rl["type_1"]["new_type"]]
+        t2_old, t2_new = n2t[rl["type_2"]["name"]], n2t[rl["type_2"]["new_type"]]
+        r = e.integrator.DissociationReaction(
+            type_1=t1_old, type_2=t2_old, delta_1=int(rl["type_1"]["delta"]), delta_2=int(rl["type_2"]["delta"]),
+            min_state_1=int(rl["type_1"]["min"]), max_state_1=int(rl["type_1"]["max"]),
+            min_state_2=int(rl["type_2"]["min"]), max_state_2=int(rl["type_2"]["max"]),
+            rate=float(cr["rate"]), fpl=fpl, cutoff=float(cr["cutoff"]))
+        if "diss_rate" in cr:
+            r.diss_rate = cr["diss_rate"]
+        r.active = cr.get("active", True)
+        if "min_cutoff" in cr:
+            r.get_reaction_cutoff().min_cutoff = float(cr["min_cutoff"])
+        r.is_virtual = bool(cr["virtual"])
+        self.dynamic_types.update((t1_old, t2_old, t1_new, t2_new))
+        alpha = float(cr["alpha"])
+        dyn_res = e.integrator.BasicDynamicResolution(self.system, {t1_old: alpha, t2_old: alpha})
+        for which, old, new, new_name in (("type_1", t1_old, t1_new, rl["type_1"]["new_type"]), ("type_2", t2_old, t2_new, rl["type_2"]["new_type"])):
+            if old != new:
+                prop = self.topol.gt.atomtypes[new_name]
+                tpp = e.integrator.TopologyParticleProperties(type=new, mass=prop["mass"], lambda_adr=1.0, q=prop["charge"])
+                dyn_res.add_postprocess(e.integrator.PostProcessChangeProperty(old, tpp))
+            r_pp = e.integrator.PostProcessChangeProperty()
+            r_pp.add_change_property(old, e.integrator.TopologyParticleProperties(lambda_adr=0.0))
+            r.add_postprocess(r_pp, which)
+        self.extensions_to_integrator.append(dyn_res)
+        return r
+
     def _setup_reaction_exchange(self, cr, fpl):
         """`A:B + C -> A:C + B` (reaction_setup.py:167-251): a VIRTUAL A + C reaction -- no bond is made or removed, the event
         only changes properties -- that requires A to carry a bonded B in B's state window; A changes type like a normal
@@ -162,7 +196,8 @@ class SetupReactions(object):
             fpl.type_list = set()        # (type pairs, before and after, of the group's reactions: FPLDef.type_list, reaction_setup.py:436,532)
             for cr in group["reaction_list"]:
                 cr["connectivity_map"] = group.get("connectivity_map")      # group level -> reaction level (reaction_setup.py:488)
-                r = self._setup_reaction_exchange(cr, fpl) if cr.get("reaction_type") == "exchange" else self._setup_reaction_normal(cr, fpl)
+                setup = {"exchange": self._setup_reaction_exchange, "dissociation": self._setup_reaction_dissociation}.get(cr.get("reaction_type"), self._setup_reaction_normal)
+                r = setup(cr, fpl)
                 for name, (pp, invoke_on) in group_pp:        # reaction_setup.py:495-505
                     if name not in cr.get("exclude_extensions", []):
                         r.add_postprocess(pp, invoke_on)

@@ -23,6 +23,7 @@
 #include "chem_idle_host.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
+#include "chem_res_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
 
@@ -102,6 +103,18 @@ struct Ctx {
   // Asked wherever charges are kept current; the pair kernel's mode, LDS plan and option limits follow coul_on() alone.
   bool charges_on() const { return coul_on() || top.any_coulomb_bond(); }
   double coul_epot = 0, coul_virial = 0;   // of the last energy evaluation (observe)
+  // Per-particle resolution lambda (chem_nb_resolution, chem_resolution_rate, chem_set_resolution; chem_res_host.hpp): the
+  // stamps by tag and the rates by type live on the host (`res`), marked type pairs in a symmetric bit mask with their caps.
+  // The device copies (stamps, rates, mask, caps) exist only while a type pair is marked (res_pairs_on): lambda moves no force
+  // otherwise.  res_rules: public reaction index -> lambda set on the role-1 / role-2 particle of every event (< 0: none).
+  ResState res; uint32_t res_mask[CHEM_MAX_TYPES] = {}; double res_fmax[CHEM_MAX_TYPES][CHEM_MAX_TYPES] = {}; bool res_dirty = false;
+  std::map<int, std::array<double, 2>> res_rules;
+  bool res_pairs_on() const { for (uint32_t m : res_mask) if (m) return true; return false; }
+  // the force kernel stages one extra word per slot (charge or lambda): LDS plan, kernel choice and option limits follow it
+  bool slot_word_on() const { return coul_on() || res_pairs_on(); }
+  // type changes have to be seen when they happen (re-stamping) and events looked at (res_rules)
+  bool res_tracking() const { return (res.on() && res.any_rate()) || !res_rules.empty(); }
+  virtual void res_push(const std::vector<int32_t>& tags) = 0;      // stamps of these tags -> device (if the copy is alive)
   bool lang = false; double kT = 0, gamma = 0; uint64_t lang_seed = 0; uint32_t lang_tmask = 0;
   bool react_init = false, react_on = false;
   int interval = 0, nearest = 1, max_per_interval = 0; uint64_t react_seed = 0;
@@ -218,6 +231,7 @@ struct Ctx {
   virtual void observe(chem_obs* out) = 0;
   virtual int64_t verlet_pairs(int64_t* out, int64_t cap) = 0;
   virtual void modify_particle(int tag, int what, double value) = 0;
+  virtual int res_apply_completions() = 0;
   virtual void sync() = 0;
   virtual void refresh_timers() {}
   virtual void set_pair_bs(int) {}
@@ -243,7 +257,7 @@ template <typename R> struct CtxT : Ctx {
   // force kernel: fp64 stages 24-byte slots + type bytes (two workgroups per CU instead of one)
   // (with a Coulomb pair registered: + one charge word per slot behind the image, k_pair_tiles MODE 4)
   static size_t pair_lds_bytes(int cap_, bool coul = false) { return coul ? coul_img_bytes<R>(cap_) : (sizeof(R) == 8 ? (size_t)(cap_ + 5) * 25 + 64 : tile_lds_bytes(cap_)); }
-  size_t pair_lds_bytes() const { return pair_lds_bytes(tile_cap, coul_on()); }
+  size_t pair_lds_bytes() const { return pair_lds_bytes(tile_cap, slot_word_on()); }
   // the list build has its own layout of the same block (fp32: SoA groups + type masks + slice boundaries)
   // (fp64 builds use the fp32 list image too -- the force list may be a superset -- and need their own 32-byte-per-slot
   //  image only where the exact int32 rows are built)
@@ -252,7 +266,9 @@ template <typename R> struct CtxT : Ctx {
   size_t scan_lds_bytes() const { return scan_roles_offset(tile_cap, sizeof(V4)) + (size_t)(tile_cap + 1) * sizeof(unsigned int); }
   bool scan_roles_staged() const { return scan_lds_bytes() <= kTileLdsBudget; }      // (otherwise the scan reads the role words from global memory)
   // what a tile of cap_ slots asks of the LDS, over every kernel that stages one (asked before tile_cap is set or grown)
-  static size_t tile_lds_need(int cap_, bool coul) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_, coul)), list_lds_need(cap_, true)); }
+  // (extra: static LDS a force-kernel mode adds beyond what kTileLdsBudget leaves room for -- the staged caps of MODE 5)
+  static size_t tile_lds_need(int cap_, bool coul, size_t extra = 0) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_, coul) + extra), list_lds_need(cap_, true)); }
+  size_t res_lds_extra() const { return res_pairs_on() ? sizeof(R) * kMaxTypes * kMaxTypes : 0; }
   static size_t list_lds_need(int cap_, bool exact_rows) {
     const size_t lb = list_lds_bytes(cap_, kMaxTypes);
     return (sizeof(R) == 4 || exact_rows) ? std::max(tile_lds_bytes(cap_), lb) : lb;
@@ -317,6 +333,7 @@ template <typename R> struct CtxT : Ctx {
   bool bonds_inline() {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
     if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
+    if (res_pairs_on()) return false;      // (nor any lambda)
     if (top.any_hybrid()) return false;      // (the force kernel knows one K, one r0 and no lambda: a hybrid list is never evaluated there)
     // (a 1-4 Coulomb list with parameters is a second slot, so harmonic_only already rules it out; one without parameters does
     //  nothing but would pass that proof -- inline bonds stay off next to any Coulomb term, so ask directly)
@@ -496,7 +513,7 @@ template <typename R> struct CtxT : Ctx {
     HIPCHK(hipMemsetAsync(cell_cnt.p, 0, sizeof(int) * (box.ncell + 1), stream));
     S = row_stride(L, rc + skin_eff(), dd_on ? nglob : n, nl_capacity_user);
     const TilePlan tp = plan_tiles(box.nc[0], box.nc[1], dd_on ? ncz : box.nc[2], dd_on ? nzg : box.nc[2], dd_on ? nglob : n, dd_on, opt_tiles != 0,
-                                   opt_tile_split, [coul = coul_on()](int c) { return tile_lds_need(c, coul); }, kTileLdsBudget);
+                                   opt_tile_split, [coul = slot_word_on(), extra = res_lds_extra()](int c) { return tile_lds_need(c, coul, extra); }, kTileLdsBudget);
     use_tiles = tp.use_tiles; box.xs_nb = tp.xs_nb; box.xs_w = tp.xs_w; ntiles = tp.ntiles;
     if (tp.tile_cap) { tile_cap = tp.tile_cap; if (use_tiles) set_tile_lds_attr(); }      // (a grid without tiles leaves the last capacity as it was)
     alloc_lists();
@@ -598,6 +615,11 @@ template <typename R> struct CtxT : Ctx {
       const int qbytes = (int)pair_lds_bytes();
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+    }
+    if (res_pairs_on()) {      // MODE 5: the image + the lambda words (same layout)
+      const int qbytes = (int)pair_lds_bytes();
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
     }
   }
 
@@ -718,6 +740,7 @@ template <typename R> struct CtxT : Ctx {
     for (auto& r : nb_rules) nt = std::max(nt, r.new_type + 1);
     for (auto& c : atrp_centers) nt = std::max(nt, std::max(c.type, c.new_type) + 1);
     for (int a = 0; a < CHEM_MAX_TYPES; ++a) if (coul_mask[a]) nt = std::max(nt, a + 1);
+    for (const ResRate& r : res.rate) if (r.alpha > 0.0) nt = std::max(nt, r.new_type + 1);
     ntypes = nt;
     std::vector<PairCore<R>> hc((size_t)nt * nt);
     std::vector<PairExt<R>> he((size_t)nt * nt);
@@ -765,7 +788,7 @@ template <typename R> struct CtxT : Ctx {
       }
     }
     if (!opt_skip_inactive || !first) uniform_lj = false;
-    if (coul_on()) { uniform_lj = false; lj_only = false; }
+    if (slot_word_on()) { uniform_lj = false; lj_only = false; }
     all_active = true;   // every pair of types in use carries a potential: the list build skips the per-hit type filter
     for (int a = 0; a < nt; ++a) for (int b = 0; b < nt; ++b) if (!((act.row[a] >> b) & 1u)) all_active = false;
     if (uniform_lj) {
@@ -796,6 +819,68 @@ template <typename R> struct CtxT : Ctx {
   CoulArgs<R> coul_args(size_t nblocks) {
     if (eoutq.n < 2 * nblocks + 8) eoutq.alloc(2 * nblocks + 8);
     return CoulArgs<R>{qtag.p, tag.p, cmask_dev.p, eoutq.p, (R)coul_k, (R)(coul_rc * coul_rc)};
+  }
+
+  // Resolution: stamps by tag (lambda0, s0), rates by type, the mask of marked type pairs and their caps -- allocated only
+  // while a type pair is marked; every rank of a decomposition holds all of them (the set-up calls are the same on every rank).
+  DBuf<double2> rstamp; DBuf<double> ralpha; DBuf<unsigned int> rmask_dev; DBuf<R> rfmax;
+  void upload_res() {
+    res_dirty = false;
+    if (!res_pairs_on()) { HIPCHK(hipStreamSynchronize(stream)); rstamp.free(); ralpha.free(); rmask_dev.free(); rfmax.free(); return; }
+    std::vector<double2> hs((size_t)top.n, double2{1.0, 0.0});
+    if (res.on()) for (size_t t = 0; t < hs.size(); ++t) hs[t] = double2{res.lambda0[t], (double)res.s0[t]};
+    std::vector<double> ha(CHEM_MAX_TYPES);
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) ha[a] = res.rate[a].alpha;
+    std::vector<unsigned int> hm(res_mask, res_mask + CHEM_MAX_TYPES);
+    std::vector<R> hf((size_t)CHEM_MAX_TYPES * CHEM_MAX_TYPES);
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = 0; b < CHEM_MAX_TYPES; ++b) hf[(size_t)a * CHEM_MAX_TYPES + b] = (R)res_fmax[a][b];
+    rstamp.upload(hs, stream); ralpha.upload(ha, stream); rmask_dev.upload(hm, stream); rfmax.upload(hf, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  void res_push(const std::vector<int32_t>& tags) override {
+    if (tags.empty() || res_dirty || !rstamp.p || !device_ready || particles_dirty) { if (!tags.empty()) res_dirty = true; return; }
+    if (tags.size() > 16) { upload_res(); return; }      // (the stamps are not contiguous: beyond a few, one copy of all of them is cheaper)
+    std::vector<double2> stage(tags.size());
+    for (size_t k = 0; k < tags.size(); ++k) { const int32_t t = tags[k]; stage[k] = double2{res.lambda0[t], (double)res.s0[t]}; HIPCHK(hipMemcpyAsync(rstamp.p + t, &stage[k], sizeof(double2), hipMemcpyHostToDevice, stream)); }
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  ResArgs<R> res_args() const { return ResArgs<R>{rstamp.p, ralpha.p, tag.p, rmask_dev.p, rfmax.p, (long long)(step + force_step_off)}; }
+  // Completion (chem_resolution_rate with a property change): every particle whose lambda reached 1 at the current step gets
+  // its new type, mass, charge and state by the route of chem_modify_particle, and a stamp (1, step) under the new type.
+  int res_apply_completions() override {
+    const std::vector<ResCompletion> done = res.completions_at(step);
+    if (done.empty()) return 0;
+    join_async();      // the mirrors are written below
+    std::vector<int32_t> tags;
+    for (const ResCompletion& c : done) {
+      const int32_t t = c.tag;
+      top.type[t] = c.new_type; top.mass[t] = c.new_mass; top.q[t] = c.new_q;
+      modify_particle(t, CHEM_STATE_TYPE, (double)c.new_type); modify_particle(t, CHEM_STATE_MASS, c.new_mass); modify_particle(t, CHEM_STATE_CHARGE, c.new_q);
+      if (c.new_state >= 0) { top.state[t] = c.new_state; modify_particle(t, CHEM_STATE_STATE, (double)c.new_state); }
+      res.stamp(t, 1.0, step); res.seen[t] = c.new_type; tags.push_back(t);
+    }
+    pair_dirty = true; bonded_dirty = true; resort = true;
+    res_push(tags);
+    return (int)done.size();
+  }
+  // Behind the reaction cadence of a step (dissociation, association, ATRP): types that changed are re-stamped, then the
+  // lambda rules of the reactions (chem_reaction_set_resolution) act on this step's events, in arena order.
+  void res_after_reactions() {
+    join_async();      // the event log and the type mirrors of this step are complete
+    res.ensure(top.type);
+    std::vector<int32_t> changed;
+    res.restamp_type_changes(top.type, step, changed);
+    if (!res_rules.empty())
+      for (size_t bk = arena.blocks.size(); bk-- > 0 && arena.blocks[bk].first == step;) {
+        const size_t lo = arena.blocks[bk].second, hi = bk + 1 < arena.blocks.size() ? arena.blocks[bk + 1].second : arena.size();
+        for (size_t k = lo; k < hi; ++k) {
+          const auto it = res_rules.find(public_index(arena.r[k]));
+          if (it == res_rules.end()) continue;
+          if (it->second[0] >= 0.0) { res.stamp(arena.a[k], it->second[0], step); changed.push_back(arena.a[k]); }
+          if (it->second[1] >= 0.0) { res.stamp(arena.b[k], it->second[1], step); changed.push_back(arena.b[k]); }
+        }
+      }
+    res_push(changed);
   }
 
   // ---- per-tag CSR tables built on the device from flat, append-only arrays (md_kernels.hpp "Per-tag CSR tables") ----
@@ -996,6 +1081,7 @@ template <typename R> struct CtxT : Ctx {
     if (labels_dirty) upload_labels();
     if (pair_dirty) upload_pair();
     if (coul_dirty) upload_coul();
+    if (res_dirty) upload_res();
     if (bonded_dirty) upload_bonded();
     if (excl_dirty) upload_excl();
   }
@@ -1175,7 +1261,7 @@ template <typename R> struct CtxT : Ctx {
       if (!ov[0] && !ov[1]) break;
       if (ov[0]) {
         const int want = grown_tile_cap(ov[0]), old_cap = tile_cap;
-        if (want <= tile_cap || tile_lds_need(want, coul_on()) > kTileLdsBudget) break;      // (stays flagged: reported by check_flags / rebuild_now)
+        if (want <= tile_cap || tile_lds_need(want, slot_word_on(), res_lds_extra()) > kTileLdsBudget) break;      // (stays flagged: reported by check_flags / rebuild_now)
         tile_cap = want;
         set_tile_lds_attr();
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&ctl.p->stage_overflow, 0, 1, stream));
@@ -1267,7 +1353,7 @@ template <typename R> struct CtxT : Ctx {
         // fits the LDS, then build again; beyond that the system is too crowded for tiles
         const int want = grown_tile_cap(h.stage_overflow);
         if (use_tiles && want > tile_cap) {
-          if (tile_lds_need(want, coul_on()) <= kTileLdsBudget) {
+          if (tile_lds_need(want, slot_word_on(), res_lds_extra()) <= kTileLdsBudget) {
             if (g_trace) fprintf(stderr, "[chem trace] staged-tile capacity %d -> %d slots\n", tile_cap, want);
             tile_cap = want;
             set_tile_lds_attr(); setup_fused();
@@ -1319,6 +1405,17 @@ template <typename R> struct CtxT : Ctx {
       if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a Coulomb pair registered only tpp = 1 (or 0, automatic) is built");
       if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a Coulomb pair registered only pair_block = 512 is built");
     }
+    const bool resm = res_pairs_on();
+    if (resm) {      // the kernels with the resolution scaling: the same build, and not next to the Coulomb term
+      if (coul) {
+        int a = 0, b = 0;
+        for (a = 0; a < CHEM_MAX_TYPES && !res_mask[a]; ++a) {}
+        for (b = 0; b < CHEM_MAX_TYPES && !((res_mask[a] >> b) & 1u); ++b) {}
+        throw ChemError(CHEM_ENOTIMPL, "resolution-scaled type pair (" + std::to_string(std::min(a, b)) + "," + std::to_string(std::max(a, b)) + ") next to a registered Coulomb pair: the two terms are not served in one context");
+      }
+      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a resolution pair marked only tpp = 1 (or 0, automatic) is built");
+      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a resolution pair marked only pair_block = 512 is built");
+    }
     const bool inline_now = bonds_inline();
     int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;      // (what the LAST rebuild did: both only change where a rebuild is forced)
     if (bond_mode == 2 && dd_on) {      // slabs: the host knows which launch follows a rebuild (mode 3 = mode 2 + record the partner slots now)
@@ -1360,6 +1457,12 @@ template <typename R> struct CtxT : Ctx {
                            nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, ca);
         return ntiles;
       }
+      if (resm) {      // MODE 5: general + resolution scaling, one instantiation per precision and ENERGY
+        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with the resolution scaling");
+        hipLaunchKernelGGL((k_pair_tiles_res<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
+                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, res_args());
+        return ntiles;
+      }
       const int mode = ENERGY ? (cubic_tab ? 3 : 0) : (uniform_lj ? 2 : (lj_only ? 1 : (cubic_tab ? 3 : 0)));
       if (mode == 2) LTT(2); else if (mode == 1) LTT(1); else if (mode == 3) LTT(3); else LTT(0);
 #undef LTT
@@ -1373,6 +1476,12 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL((k_pair_force<R, 4, ENERGY, true, true>), dim3(nbq), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
                          pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, coul_args((size_t)nbq));
       return nbq;
+    }
+    if (resm) {
+      const int nbr = cdiv((long long)n * 4, 256);
+      hipLaunchKernelGGL((k_pair_force_res<R, 4, ENERGY>), dim3(nbr), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
+                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, res_args());
+      return nbr;
     }
     const int nb = cdiv((long long)n * tpp, 256);
 #define LPC(T, CU) hipLaunchKernelGGL((k_pair_force<R, T, ENERGY, CU>), dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, \
@@ -1671,6 +1780,7 @@ template <typename R> struct CtxT : Ctx {
         if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
         if (react_due) react_step();
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
+        if ((react_due || atrp_due) && res_tracking()) res_after_reactions();
         need_int1 = true;
       } else {
         tbeg(2);
@@ -2521,6 +2631,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   if (!t.contiguous) for (int64_t k = 0; k < n; ++k) t.id2tag[t.id[k]] = (int32_t)k;
   c.particles_dirty = c.pair_dirty = c.bonded_dirty = c.excl_dirty = c.labels_dirty = true; c.resort = true;
   c.coul_dirty = true;
+  c.res.clear(); c.res_dirty = true;      // (a new particle set: every lambda is 1 again; rates, marks and reaction rules stay)
   c.step = 0; c.events.clear(); c.arena.clear();
   return 0;
   API_END(ctx)
@@ -2530,7 +2641,17 @@ int chem_modify_particle(chem_ctx* ctx, int64_t id, int what, double value) {
   API_BEGIN
   Ctx& c = CTX; const int t = c.top.tag_of(id);
   REQUIRE(t >= 0, CHEM_EINVAL, "modify_particle: unknown id");
-  if (what == CHEM_STATE_TYPE) { REQUIRE(value >= 0 && value < CHEM_MAX_TYPES, CHEM_EINVAL, "type"); c.top.type[t] = (int)value; c.pair_dirty = true; c.bonded_dirty = true; c.resort = true; }
+  if (what == CHEM_STATE_LAMBDA) {
+    REQUIRE(std::isfinite(value) && value >= 0.0 && value <= 1.0, CHEM_EINVAL, "modify_particle: lambda must lie in [0, 1]");
+    c.res.ensure(c.top.type);
+    c.res.stamp((size_t)t, value, c.step);
+    c.res_push(std::vector<int32_t>{(int32_t)t});
+    return 0;
+  }
+  if (what == CHEM_STATE_TYPE) {
+    REQUIRE(value >= 0 && value < CHEM_MAX_TYPES, CHEM_EINVAL, "type"); c.top.type[t] = (int)value; c.pair_dirty = true; c.bonded_dirty = true; c.resort = true;
+    if (c.res.on()) { std::vector<int32_t> ch; c.res.restamp_type_changes(c.top.type, c.step, ch); c.res_push(ch); }      // (re-stamped under the old type's rate)
+  }
   else if (what == CHEM_STATE_STATE) c.top.state[t] = (int)value;
   else if (what == CHEM_STATE_MASS) { REQUIRE(value > 0, CHEM_EINVAL, "mass"); c.top.mass[t] = value; }
   else if (what == CHEM_STATE_RESID) c.top.res_id[t] = (int)value;
@@ -2589,6 +2710,87 @@ int chem_nb_coulomb(chem_ctx* ctx, int t1, int t2, double prefactor, double rc) 
   // term on or off also changes the LDS footprint the tiles are planned for
   c.pair_dirty = true; c.coul_dirty = true; c.bonded_dirty = true; c.resort = true;
   if (was_on != c.coul_on()) c.geom_dirty = true;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_nb_resolution(chem_ctx* ctx, int t1, int t2, int on, double max_force) {
+  API_BEGIN
+  REQUIRE(t1 >= 0 && t2 >= 0 && t1 < CHEM_MAX_TYPES && t2 < CHEM_MAX_TYPES, CHEM_EINVAL, "nb_resolution: type out of range");
+  REQUIRE(std::isfinite(max_force), CHEM_EINVAL, "nb_resolution: max_force must be finite");
+  Ctx& c = CTX;
+  const bool was_on = c.res_pairs_on(), word_was = c.slot_word_on();
+  if (on) {
+    REQUIRE(c.pp[t1][t2].kind != 0, CHEM_EINVAL, "nb_resolution: type pair (" + std::to_string(t1) + "," + std::to_string(t2) + ") carries no LJ or table potential");
+    c.res_mask[t1] |= 1u << t2; c.res_mask[t2] |= 1u << t1;
+    c.res_fmax[t1][t2] = c.res_fmax[t2][t1] = max_force > 0 ? max_force : 0.0;
+  } else {
+    c.res_mask[t1] &= ~(1u << t2); c.res_mask[t2] &= ~(1u << t1);
+    c.res_fmax[t1][t2] = c.res_fmax[t2][t1] = 0.0;
+  }
+  if (was_on || c.res_pairs_on()) {      // (switching off what was never on changes nothing and costs nothing)
+    c.res_dirty = true; c.pair_dirty = true;
+    if (was_on != c.res_pairs_on()) { c.bonded_dirty = true; c.resort = true; }      // kernel selection, inline bonds
+    if (word_was != c.slot_word_on()) c.geom_dirty = true;      // the LDS footprint the tiles are planned for
+  }
+  return 0;
+  API_END(ctx)
+}
+
+int chem_resolution_rate(chem_ctx* ctx, int type, double alpha, int new_type, double new_mass, double new_q, int new_state) {
+  API_BEGIN
+  REQUIRE(type >= 0 && type < CHEM_MAX_TYPES, CHEM_EINVAL, "resolution_rate: type out of range");
+  REQUIRE(std::isfinite(alpha), CHEM_EINVAL, "resolution_rate: alpha must be finite");
+  REQUIRE(new_type < CHEM_MAX_TYPES, CHEM_EINVAL, "resolution_rate: new type out of range");
+  REQUIRE(!(alpha > 0 && new_type >= 0) || (new_mass > 0 && std::isfinite(new_mass) && std::isfinite(new_q)), CHEM_EINVAL, "resolution_rate: the new mass must be positive and finite, the new charge finite");
+  Ctx& c = CTX;
+  REQUIRE(c.top.n > 0, CHEM_ESTATE, "set particles before resolution_rate");
+  if (!(alpha > 0) && !c.res.on()) return 0;      // removing what was never there
+  c.res.ensure(c.top.type);
+  std::vector<int32_t> changed;
+  c.res.restamp_type_changes(c.top.type, c.step, changed);      // (types that moved while no rate was registered: lambda did not depend on them)
+  ResRate r; r.alpha = alpha; r.new_type = new_type < 0 ? -1 : new_type; r.new_mass = new_mass; r.new_q = new_q; r.new_state = new_state < 0 ? -1 : new_state;
+  c.res.set_rate(type, r, c.step, changed);
+  c.res_dirty = true;      // (rates and stamps: uploaded whole)
+  if (r.alpha > 0 && r.new_type >= 0) c.pair_dirty = true;      // (the type count may grow)
+  return 0;
+  API_END(ctx)
+}
+
+int chem_set_resolution(chem_ctx* ctx, int64_t n, const int64_t* ids, const double* lambda) {
+  API_BEGIN
+  REQUIRE(n >= 0 && (n == 0 || (ids && lambda)), CHEM_EINVAL, "set_resolution: null input");
+  Ctx& c = CTX;
+  std::vector<int32_t> tags((size_t)n);
+  bool all_one = true;
+  for (int64_t k = 0; k < n; ++k) {
+    tags[k] = c.top.tag_of(ids[k]);
+    REQUIRE(tags[k] >= 0, CHEM_EINVAL, "set_resolution: unknown id");
+    REQUIRE(std::isfinite(lambda[k]) && lambda[k] >= 0.0 && lambda[k] <= 1.0, CHEM_EINVAL, "set_resolution: lambda must lie in [0, 1]");
+    all_one = all_one && lambda[k] == 1.0;
+  }
+  if (n == 0 || (all_one && !c.res.on())) return 0;      // (every particle is at 1 already: nothing comes alive)
+  c.res.ensure(c.top.type);
+  for (int64_t k = 0; k < n; ++k) c.res.stamp((size_t)tags[k], lambda[k], c.step);
+  c.res_push(tags);
+  return 0;
+  API_END(ctx)
+}
+
+int chem_reaction_set_resolution(chem_ctx* ctx, int reaction, int role, double lambda) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(reaction >= 0 && reaction < (int)c.pub_map.size(), CHEM_EINVAL, "reaction_set_resolution: unknown reaction index");
+  REQUIRE(role == 1 || role == 2, CHEM_EINVAL, "reaction_set_resolution: role must be 1 or 2");
+  REQUIRE(!(lambda > 1.0) && !std::isnan(lambda), CHEM_EINVAL, "reaction_set_resolution: lambda must lie in [0, 1] (negative: remove the rule)");
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "reaction_set_resolution is not available on the decomposed path (chem_comm_init*)");
+  auto it = c.res_rules.find(reaction);
+  if (lambda < 0.0) {
+    if (it != c.res_rules.end()) { it->second[role - 1] = -1.0; if (it->second[0] < 0.0 && it->second[1] < 0.0) c.res_rules.erase(it); }
+    return 0;
+  }
+  if (it == c.res_rules.end()) it = c.res_rules.emplace(reaction, std::array<double, 2>{-1.0, -1.0}).first;
+  it->second[role - 1] = lambda;
   return 0;
   API_END(ctx)
 }
@@ -2931,7 +3133,24 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
     throw ChemError(CHEM_EINVAL, "run: Coulomb cutoff " + std::to_string(CTX.coul_rc) + " of type pair (" + std::to_string(std::min(a, b)) + "," + std::to_string(std::max(a, b)) +
                                  ") exceeds the list cutoff max_cutoff = " + std::to_string(CTX.rc));
   }
-  CTX.run(nsteps);
+  Ctx& c = CTX;
+  if (!c.res_tracking()) { c.run(nsteps); return 0; }
+  // Resolution ramps with a property change: the call runs in pieces that end where a lambda reaches 1 (the host knows every
+  // stamp, so it knows every such step: chem_res_host.hpp); the change is applied there, and the forces are evaluated again
+  // where the call ends on such a step, so that the forces current at s_full are those of the new properties.  A reaction or
+  // ATRP step may stamp particles (type changes, chem_reaction_set_resolution) and so create completion steps nobody could
+  // know before: while stamps are tracked a piece also ends at every such step, and the next completion is asked afresh.
+  c.res_apply_completions();
+  if (nsteps == 0) c.run(0);
+  for (int64_t left = nsteps; left > 0;) {
+    int64_t stop = c.res.next_completion(c.step);
+    auto sooner = [&](int64_t every) { const int64_t at = (c.step / every + 1) * every; if (stop < 0 || at < stop) stop = at; };
+    if (c.react_on && c.interval > 0) sooner(c.interval);
+    if (c.atrp_on && c.atrp.interval > 0) sooner(c.atrp.interval);
+    const int64_t len = res_next_piece(c.step, left, stop);
+    c.run(len); left -= len;
+    if (c.res_apply_completions() && left == 0) c.run(0);
+  }
   return 0;
   API_END(ctx)
 }
@@ -2942,6 +3161,12 @@ int64_t chem_get_step(chem_ctx* ctx) { return ctx->c->step; }
 int64_t chem_get_state(chem_ctx* ctx, int what, void* out, int64_t cap) {
   API_BEGIN
   REQUIRE(out, CHEM_EINVAL, "null output");
+  if (what == CHEM_STATE_LAMBDA) {      // the fp64 host expression at the current step (replicated by tag: no gather)
+    Ctx& c = CTX;
+    REQUIRE(cap >= c.top.n, CHEM_ENOSPC, "get_state: capacity");
+    for (int64_t t = 0; t < c.top.n; ++t) ((double*)out)[t] = c.res.lambda_at((size_t)t, c.step);
+    return c.top.n;
+  }
   return CTX.get_state(what, out, cap);
   API_END(ctx)
 }
@@ -3070,6 +3295,7 @@ int chem_comm_init(chem_ctx* ctx, int nranks, int rank, const int node_grid[3], 
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init: rank/nranks");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
+  REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on, CHEM_ESTATE, "comm_init: already initialised");
   if (nranks == 1 && !uid) return 0;   // single domain, nothing to do
   REQUIRE(node_grid && node_grid[0] == 1 && node_grid[1] == 1 && node_grid[2] == nranks, CHEM_ENOTIMPL,
@@ -3136,6 +3362,7 @@ int chem_comm_init_ipc(chem_ctx* ctx, int nranks, int rank, const char* shm_name
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks && shm_name, CHEM_EINVAL, "comm_init_ipc: rank/nranks/name");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
+  REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_ipc must precede the first run");
   HIPCHK(hipSetDevice(c.device));
   c.tr.reset(new IpcTransport(nranks, rank, shm_name));
@@ -3149,6 +3376,7 @@ int chem_comm_init_local(chem_ctx* ctx, int nranks, int rank, int hub_id) {
   Ctx& c = CTX;
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init_local: rank/nranks");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
+  REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_local must precede the first run");
   c.tr.reset(new LocalTransport(nranks, rank, hub_id));
   c.dd_on = true; c.P = nranks; c.rk = rank; c.geom_dirty = true;

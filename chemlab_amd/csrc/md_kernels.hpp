@@ -1040,6 +1040,42 @@ __device__ __forceinline__ void coul_term(R kqi, R qj, bool on, R rc2, R r2, R d
   }
 }
 
+// Per-particle resolution lambda (VerletListDynamicResolutionLennardJones / ...Tabulated + BasicDynamicResolution; rule set in
+// include/chem_mi355.h, chem_nb_resolution): the LJ / table force of a MARKED type pair is scaled by w = lambda_i lambda_j and
+// then capped at fmax (> 0), its energy by w.  lambda is a pure function of the by-tag stamp (lambda0, s0), the rate of the
+// particle's current type and the step of the forces (chem_res_host.hpp res_lambda: the same expression, unfused):
+// nothing is updated per step.  mask[ti] bit tj = the pair is marked; fmax[ti * kMaxTypes + tj] its cap (0 = none), staged in LDS
+// beside the pairs' other parameters (res_stage_caps).
+template <typename R> struct ResArgs { const double2* stamp; const double* alpha; const int* tag; const unsigned int* mask; const R* fmax; long long step; };
+__device__ __forceinline__ double res_lambda_dev(const double2* __restrict__ stamp, const double* __restrict__ alpha, long long step, int tg, int ty) {
+#pragma clang fp contract(off)
+  const double2 st = stamp[tg];
+  const double ramp = alpha[ty & (kMaxTypes - 1)] * (double)(step - (long long)st.y);
+  const double l = st.x + ramp;
+  return l < 1.0 ? l : 1.0;
+}
+template <typename R> __device__ __forceinline__ void res_stage_caps(R* sfm, const R* __restrict__ fmax) {      // (caller synchronises)
+  for (int k = threadIdx.x; k < kMaxTypes * kMaxTypes; k += blockDim.x) sfm[k] = fmax[k];
+}
+// one listed pair of a resolution context: li, lj the two lambdas, on = the type pair's mask bit, fcap its force cap.
+// PT(tx, ty, tz, e1, e2, v) accumulates the unscaled term.  An unmarked pair is evaluated as everywhere else; a marked pair
+// with w == 0 is not evaluated at all; the virial share is r.F of the force that was applied.
+template <typename R, bool ENERGY, class PT>
+__device__ __forceinline__ void res_pair(PT&& term, R li, R lj, bool on, R fcap, R dx, R dy, R dz, R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir) {
+  if (!on) { term(fx, fy, fz, e_lj, e_tab, vir); return; }
+  const R w = li * lj;
+  if (w == (R)0) return;
+  R tx = 0, ty = 0, tz = 0; double te1 = 0, te2 = 0, tv = 0;
+  term(tx, ty, tz, te1, te2, tv);
+  tx *= w; ty *= w; tz *= w;
+  if (fcap > (R)0) {
+    const R f2 = tx * tx + ty * ty + tz * tz;
+    if (f2 > fcap * fcap) { const R sc = fcap * rsqrt_r(f2); tx *= sc; ty *= sc; tz *= sc; }
+  }
+  fx += tx; fy += ty; fz += tz;
+  if (ENERGY) { e_lj += (double)w * te1; e_tab += (double)w * te2; vir += (double)(tx * dx + ty * dy + tz * dz); }
+}
+
 // CUBIC: the host selects these instantiations only while a type pair of kind 3 exists, so that the others stay what they were
 template <typename R, bool ENERGY, bool CUBIC = false>
 __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
@@ -1083,15 +1119,20 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
 
 // COUL: plus the truncated Coulomb term, charges read through tag[j] (launched only while a Coulomb pair is registered; these
 // instantiations know both table kinds)
-template <typename R, int TPP, bool ENERGY, bool CUBIC = false, bool COUL = false>
-__global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+// RES: marked type pairs scaled by lambda_i lambda_j and capped (k_pair_force_res, launched only while a type pair is marked;
+// both table kinds); lambda through tag[j] -> stamp, evaluated per neighbour
+// (the body of k_pair_force and of k_pair_force_res, which alone takes the resolution arguments)
+template <typename R, int TPP, bool ENERGY, bool CUBIC, bool COUL, bool RES>
+__device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ nlist, const int* __restrict__ nn, int S,
-                                                    Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                    const Box<R>& box, const PairCore<R>* __restrict__ pcore,
                                                     const PairExt<R>* __restrict__ pext, int ntypes,
                                                     const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
-                                                    double half_skin, DevCtl* ctl, CoulArgs<R> ca = CoulArgs<R>{}) {
+                                                    double half_skin, DevCtl* ctl, const CoulArgs<R>& ca, const ResArgs<R>& ra) {
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   for (int k = threadIdx.x; k < ntypes * ntypes; k += blockDim.x) spc[k] = pcore[k];
+  [[maybe_unused]] const R* sfm = nullptr;
+  if constexpr (RES) { __shared__ R sfm_[kMaxTypes * kMaxTypes]; res_stage_caps<R>(sfm_, ra.fmax); sfm = sfm_; }
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1107,6 +1148,8 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
     const int pbase = ti * ntypes;
     [[maybe_unused]] R kqi = 0; [[maybe_unused]] unsigned int crow = 0;
     if constexpr (COUL) { kqi = ca.k * ca.qtag[ca.tag[i]]; crow = ca.mask[ti]; }
+    [[maybe_unused]] R lami = 1; [[maybe_unused]] unsigned int rrow = 0;
+    if constexpr (RES) { lami = (R)res_lambda_dev(ra.stamp, ra.alpha, ra.step, ra.tag[i], ti); rrow = ra.mask[ti]; }
     // lane `sub` takes 4 consecutive neighbours per trip: one 16-byte index load, then four
     // independent position gathers in flight (rows are padded with the self index)
     for (int k = sub * 4; k < cnt; k += TPP * 4) {
@@ -1118,6 +1161,12 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
         const int ta = ca.tag[jj.x], tb = ca.tag[jj.y], tc = ca.tag[jj.z], td = ca.tag[jj.w];
         qs[0] = ca.qtag[ta]; qs[1] = ca.qtag[tb]; qs[2] = ca.qtag[tc]; qs[3] = ca.qtag[td];
       }
+      [[maybe_unused]] R ls[4] = {1, 1, 1, 1};
+      if constexpr (RES) {
+        const int ta = ra.tag[jj.x], tb = ra.tag[jj.y], tc = ra.tag[jj.z], td = ra.tag[jj.w];
+        ls[0] = (R)res_lambda_dev(ra.stamp, ra.alpha, ra.step, ta, (int)xa.w); ls[1] = (R)res_lambda_dev(ra.stamp, ra.alpha, ra.step, tb, (int)xb.w);
+        ls[2] = (R)res_lambda_dev(ra.stamp, ra.alpha, ra.step, tc, (int)xc.w); ls[3] = (R)res_lambda_dev(ra.stamp, ra.alpha, ra.step, td, (int)xd.w);
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const Vec4<R> xj = xs[u];
@@ -1125,6 +1174,11 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
         R r2 = dx * dx + dy * dy + dz * dz;
         r2 = (k + u < cnt) ? r2 : (R)1e30;     // padding entries (self index) never interact
         const int pidx = pbase + (int)xj.w;
+        if constexpr (RES) {
+          const int tj = (int)xj.w;
+          res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av); },
+                              lami, ls[u], ((rrow >> tj) & 1u) != 0, sfm[ti * kMaxTypes + tj], dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+        } else
         pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
         if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
       }
@@ -1158,6 +1212,24 @@ __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __rest
       }
     }
   }
+}
+template <typename R, int TPP, bool ENERGY, bool CUBIC = false, bool COUL = false>
+__global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                    const int* __restrict__ nlist, const int* __restrict__ nn, int S,
+                                                    Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                    const PairExt<R>* __restrict__ pext, int ntypes,
+                                                    const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                    double half_skin, DevCtl* ctl, CoulArgs<R> ca = CoulArgs<R>{}) {
+  pair_force_body<R, TPP, ENERGY, CUBIC, COUL, false>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, ca, ResArgs<R>{});
+}
+template <typename R, int TPP, bool ENERGY>
+__global__ __launch_bounds__(256) void k_pair_force_res(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                        const int* __restrict__ nlist, const int* __restrict__ nn, int S,
+                                                        Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                        const PairExt<R>* __restrict__ pext, int ntypes,
+                                                        const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                        double half_skin, DevCtl* ctl, ResArgs<R> ra) {
+  pair_force_body<R, TPP, ENERGY, true, false, true>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, CoulArgs<R>{}, ra);
 }
 
 // =======================================================================================
@@ -1336,10 +1408,13 @@ __device__ __forceinline__ void slot_store(Vec4<R>* const sx, const int CAP, int
 }
 // QW (k_pair_tiles MODE 4, not LEAN): one charge word per slot into sq[], tag[g] -> qtag; these loads too are issued before the
 // first LDS write (two dependent latencies instead of one; the dummy slot carries charge 0)
-template <typename R, int BS, bool LEAN = false, bool D3 = false, bool QW = false>
+// RW (k_pair_tiles MODE 5, with QW): the word is the slot's resolution lambda instead, computed here from the by-tag stamp, the
+// slot's type and the step of the forces (ResFill; res_lambda_dev) -- the dummy slot carries lambda 0
+struct ResFill { const double2* stamp; const double* alpha; long long step; };
+template <typename R, int BS, bool LEAN = false, bool D3 = false, bool QW = false, bool RW = false>
 __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx, const int CAP,
                                           const Vec4<R>* __restrict__ x4, int wmode, const int* __restrict__ tagv = nullptr,
-                                          const R* __restrict__ qtag = nullptr, R* const sq = nullptr) {
+                                          const R* __restrict__ qtag = nullptr, R* const sq = nullptr, const ResFill rf = ResFill{}) {
   constexpr int NW = BS / 64, RPW = (NROW + NW - 1) / NW;
   const int t = threadIdx.x;
   const int w = t >> 6, l = t & 63;
@@ -1392,7 +1467,10 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr)
 #pragma unroll
-      for (int c = 0; c < 2; ++c) pq[rr][c] = pk_[rr][c] >= 0 ? qtag[ptg[rr][c]] : (R)0;
+      for (int c = 0; c < 2; ++c) {
+        if constexpr (RW) pq[rr][c] = pk_[rr][c] >= 0 ? (R)res_lambda_dev(rf.stamp, rf.alpha, rf.step, ptg[rr][c], (int)pv[rr][c].w) : (R)0;
+        else pq[rr][c] = pk_[rr][c] >= 0 ? qtag[ptg[rr][c]] : (R)0;
+      }
   }
 #pragma unroll
   for (int rr = 0; rr < RPW; ++rr) {
@@ -1426,7 +1504,8 @@ __device__ __forceinline__ void tile_fill(const TileLDS<R>& T, Vec4<R>* const sx
         p.x = pos_local(p.x, T.cellshx[r][k], T.org[0], T.qs[0]); p.y = pos_local(p.y, T.rowshy[r], T.org[1], T.qs[1]); p.z = pos_local(p.z, T.rowshz[r], T.org[2], T.qs[2]);
         if (wmode) p.w = idx_as_real((g << 5) | (int)p.w, (R)0);
         slot_store<R, D3>(sx, CAP, dst, p);
-        if constexpr (QW) sq[dst] = qtag[tagv[g]];
+        if constexpr (RW) sq[dst] = (R)res_lambda_dev(rf.stamp, rf.alpha, rf.step, tagv[g], (int)p.w);
+        else if constexpr (QW) sq[dst] = qtag[tagv[g]];
       }
     }
   }
@@ -2176,6 +2255,10 @@ struct UniLJ { float rc2, lj1, lj2, pad; double drc2, dlj1, dlj2; };   // all li
 //      4: general as 3, plus the truncated Coulomb term (launched only while a Coulomb pair is registered; TPP 1, 512 threads).
 //         One charge word per slot is staged behind the image (coul_q_offset), read with the slot; the home particle's k*q,
 //         its row of the type-pair mask and rc_qq^2 are registers.  No inline bonds in this mode (the host keeps them off).
+//      5: general as 3, with marked type pairs scaled by lambda_i lambda_j and capped (launched only while a type pair is marked
+//         by chem_nb_resolution; TPP 1, 512 threads, k_pair_tiles_res).  One lambda word per slot is staged where MODE 4 keeps
+//         its charge words (the two terms are not served together), computed in tile_fill; the home particle's lambda and its
+//         row of the resolution mask are registers, the pairs' caps are staged in LDS beside spc[].  No inline bonds.
 // Tiles of one launch: [base1, base1+n1) followed by [base2, ...).  The decomposed path launches the
 // tiles whose stencil stays inside the own layers ("interior": they need no ghost) while the halo
 // exchange is still in flight on the communication stream, and the two boundary tile layers after it.
@@ -2278,8 +2361,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                                                    DecideArgs da, uint4* __restrict__ bslots,
                                                    double bond_K, double bond_r0, int bond_mode, ActMask bact,
                                                    const BondRec<R>* __restrict__ brec,
-                                                   const CoulArgs<R> ca) {
-  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3 || MODE == 4, COUL = MODE == 4;
+                                                   const CoulArgs<R> ca, const ResArgs<R> ra) {
+  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3 || MODE == 4 || MODE == 5, COUL = MODE == 4, RES = MODE == 5;
 #ifndef CHEM_NCH
 #define CHEM_NCH 3
 #endif
@@ -2322,6 +2405,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   CHEM_DYN_LDS(R);
   if (MODE != 2) for (int k = threadIdx.x; k < ntypes * ntypes; k += BS) spc[k] = pcore[k];
+  [[maybe_unused]] const R* sfm = nullptr;
+  if constexpr (RES) { __shared__ R sfm_[kMaxTypes * kMaxTypes]; res_stage_caps<R>(sfm_, ra.fmax); sfm = sfm_; }      // (the barriers behind the descriptor and the staging cover it)
   if (guard < 2 && blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
   const R u_rc2 = sizeof(R) == 4 ? (R)uni.rc2 : (R)uni.drc2, u_lj1 = sizeof(R) == 4 ? (R)uni.lj1 : (R)uni.dlj1,
           u_lj2 = sizeof(R) == 4 ? (R)uni.lj2 : (R)uni.dlj2;
@@ -2384,8 +2469,9 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   };
   if (slice < nhome) locate(slice);
   constexpr bool D3 = sizeof(R) == 8;     // fp64: 24-byte slots + type bytes (see tile_fill)
-  [[maybe_unused]] R* const sq = reinterpret_cast<R*>(chem_dyn_lds + (COUL ? coul_q_offset<R>(CAP) : 0));
+  [[maybe_unused]] R* const sq = reinterpret_cast<R*>(chem_dyn_lds + ((COUL || RES) ? coul_q_offset<R>(CAP) : 0));
   if constexpr (COUL) tile_fill<R, BS, false, D3, true>(T, sx, CAP, x4, 0, ca.tag, ca.qtag, sq);
+  else if constexpr (RES) tile_fill<R, BS, false, D3, true, true>(T, sx, CAP, x4, 0, ra.tag, nullptr, sq, ResFill{ra.stamp, ra.alpha, ra.step});
   else if (!DIAG || ablate != 2) tile_fill<R, BS, false, D3>(T, sx, CAP, x4, 0);
   __syncthreads();
   if (DIAG && ablate == 1) return;   // diagnostic: staging only
@@ -2402,6 +2488,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
       const int pbase = (int)xi.w * ntypes;
       [[maybe_unused]] R kqi = 0; [[maybe_unused]] unsigned int crow = 0;
       if constexpr (COUL) { kqi = ca.k * sq[hslot]; crow = ca.mask[(int)xi.w]; }
+      [[maybe_unused]] R lami = 1; [[maybe_unused]] unsigned int rrow = 0;
+      if constexpr (RES) { lami = sq[hslot]; rrow = ra.mask[(int)xi.w]; }
       // Uniform-LJ fp32 path: (x, y) of one neighbour live in an aligned register pair (the 16-byte LDS read returns
       // x y z w in four consecutive VGPRs), so the differences, their squares and the force accumulation of the x and y
       // components are PACKED fp32 instructions on that pair -- no register shuffling as when the compiler pairs up two
@@ -2453,7 +2541,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
             const unsigned int sl = (wds[2 * h + (u >> 1)] >> ((u & 1) * 16)) & 0xffff;
             if constexpr (D3) { xs[u] = lds_gather3d(sx, sl); if (MODE != 2 || ENERGY) xs[u].w = (R)d3_types<R>(sx, CAP)[sl]; }
             else xs[u] = lds_gather4<R>(sx, sl);
-            if constexpr (COUL) qs[u] = sq[sl];
+            if constexpr (COUL || RES) qs[u] = sq[sl];
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -2467,6 +2555,11 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
               fx += ff * dx; fy += ff * dy; fz += ff * dz;
             } else {
               const int pidx = pbase + (int)xj.w;
+              if constexpr (RES) {
+                const int tj = (int)xj.w;
+                res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av); },
+                                    lami, qs[u], ((rrow >> tj) & 1u) != 0, sfm[(int)xi.w * kMaxTypes + tj], dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+              } else
               pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
               if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
             }
@@ -2495,7 +2588,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
         }
       }
       fx += (R)fxy.x; fy += (R)fxy.y;      // (packed x/y accumulators of the uniform-LJ fp32 path; zero otherwise)
-      if (!COUL && bslots && sub == 0) {
+      if (!COUL && !RES && bslots && sub == 0) {
         // Inline harmonic bonds (FixedPairListHarmonic, gromacs_topology.py:949-961; reaction bonds reaction_setup.py:449-467):
         // the LDS slots of the bonded (= excluded) partners are recorded at every rebuild, the geometry comes from the staged
         // image (tile-local coordinates: 2.4e-7 in the fp32 build, exact in fp64) -- no bonded launch, no second pass over f4.
@@ -2584,9 +2677,9 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
                                                    DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
                                                    double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
                                                    const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
-  static_assert(MODE != 4, "MODE 4 is k_pair_tiles_q");
+  static_assert(MODE != 4 && MODE != 5, "MODE 4 is k_pair_tiles_q, MODE 5 k_pair_tiles_res");
   pair_tiles_body<R, TPP, ENERGY, BS, MODE, DIAG>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, uni, eout, half_skin, ctl, guard, ablate, dbg,
-                                                  sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, brec, CoulArgs<R>{});
+                                                  sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, brec, CoulArgs<R>{}, ResArgs<R>{});
 }
 // MODE 4: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2597,7 +2690,18 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CoulArgs<R> ca) {
   pair_tiles_body<R, 1, ENERGY, 512, 4, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, ca);
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, ca, ResArgs<R>{});
+}
+// MODE 5: one lane per particle, 512 threads; no inline bonds
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_res(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                   const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                   const int* __restrict__ nnh, int S16,
+                                                   const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                   int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                   double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra) {
+  pair_tiles_body<R, 1, ENERGY, 512, 5, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ra);
 }
 
 // =======================================================================================

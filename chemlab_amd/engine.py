@@ -86,6 +86,8 @@ class Engine:
             _ptr(state, C.c_int32), _ptr(res_id, C.c_int32)))
 
     def modify_particle(self, pid, what, value):
+        if what.upper() == "LAMBDA":
+            self._res_entry("set_resolution")
         self._ck(self.api.modify_particle(self.ctx, int(pid), _capi.STATE[what.upper()], float(value)))
 
     def set_exclusions(self, pairs):
@@ -129,6 +131,34 @@ class Engine:
         e, v = C.c_double(0.0), C.c_double(0.0)
         self._ck(fn(self.ctx, C.byref(e), C.byref(v)))
         return e.value, v.value
+
+    # ---- per-particle resolution lambda (include/chem_mi355.h, chem_nb_resolution ff.) ----
+    def _res_entry(self, name):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("resolution: the CPU checker has no per-particle lambda")
+        return fn
+
+    def nb_resolution(self, t1, t2, on=True, max_force=0.0):
+        """Mark (or unmark) the LJ / table of the type pair as scaled by lambda_i lambda_j, capped at max_force (> 0)."""
+        self._ck(self._res_entry("nb_resolution")(self.ctx, int(t1), int(t2), 1 if on else 0, float(max_force)))
+
+    def resolution_rate(self, type_id, alpha, new_type=-1, new_mass=0.0, new_q=0.0, new_state=-1):
+        """BasicDynamicResolution {type: alpha}; with new_type >= 0 the property change when lambda reaches 1.  alpha <= 0
+        removes the entry."""
+        self._ck(self._res_entry("resolution_rate")(self.ctx, int(type_id), float(alpha), int(new_type), float(new_mass), float(new_q), int(new_state)))
+
+    def set_resolution(self, ids, lam):
+        """lambda of the particles `ids` (lambda_adr), stamped at the current step; a scalar is broadcast."""
+        fn = self._res_entry("set_resolution")
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), ids.shape))
+        self._ck(fn(self.ctx, ids.shape[0], _ptr(ids, C.c_int64), _ptr(lam, C.c_double)))
+
+    def reaction_set_resolution(self, reaction, role, lam):
+        """On every event of `reaction` the particle of `role` ('type_1' | 'type_2' | 1 | 2) gets lambda `lam`; negative removes."""
+        ro = {"type_1": 1, "type_2": 2}.get(role, role)
+        self._ck(self._res_entry("reaction_set_resolution")(self.ctx, int(reaction), int(ro), float(lam)))
 
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
@@ -294,12 +324,14 @@ class Engine:
 
     def get_state(self, what):
         w = _capi.STATE[what.upper()]
+        if what.upper() == "LAMBDA":
+            self._res_entry("set_resolution")
         n = self.n
         if what.upper() in ("POS", "VEL", "FORCE", "POS_UNFOLDED"):
             out = np.empty((n, 3), dtype=np.float64)
         elif what.upper() == "IMAGE":
             out = np.empty((n, 3), dtype=np.int32)
-        elif what.upper() in ("MASS", "CHARGE"):
+        elif what.upper() in ("MASS", "CHARGE", "LAMBDA"):
             out = np.empty(n, dtype=np.float64)
         elif what.upper() == "ID":
             out = np.empty(n, dtype=np.int64)

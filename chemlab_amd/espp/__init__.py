@@ -153,6 +153,10 @@ class _DomainDecomposition(object):
         if "v" in pr:
             vel = np.array([list(p) for p in col("v")], dtype=np.float64)
         self.system.engine.set_particles(ids, types, pos, mass, vel=vel, q=q, state=state, res_id=res_id)
+        if "lambda_adr" in pr:          # per-particle resolution (1 unless given): nothing is sent while every value is 1
+            lam = np.array(col("lambda_adr"), dtype=np.float64)
+            if np.any(lam != 1.0):
+                self.system.engine.set_resolution(ids, lam)
         self._uploaded = True
         self._ids = ids
         self._pending = []
@@ -166,11 +170,13 @@ class _DomainDecomposition(object):
         g = lambda w: e.get_state(w)[k]
         # (the CPU checker keeps no charges: an engine without the Coulomb entry points reports 0, as before)
         q = float(g("CHARGE")) if getattr(getattr(e, "api", None), "nb_coulomb", None) is not None else 0.0
-        return _Particle(id=pid, pos=Real3D(*g("POS")), v=Real3D(*g("VEL")), f=Real3D(*g("FORCE")), type=int(g("TYPE")),
+        # (nor a resolution: every particle is at full resolution there)
+        lam = float(g("LAMBDA")) if getattr(getattr(e, "api", None), "set_resolution", None) is not None else 1.0
+        return _Particle(lambda_adr=lam, id=pid, pos=Real3D(*g("POS")), v=Real3D(*g("VEL")), f=Real3D(*g("FORCE")), type=int(g("TYPE")),
                          mass=float(g("MASS")), state=int(g("STATE")), res_id=int(g("RESID")), imageBox=Int3D(*g("IMAGE")), q=q)
 
     def modifyParticle(self, pid, prop, value):
-        self.system.engine.modify_particle(pid, {"type": "TYPE", "state": "STATE", "mass": "MASS", "res_id": "RESID", "q": "CHARGE"}[prop], value)
+        self.system.engine.modify_particle(pid, {"type": "TYPE", "state": "STATE", "mass": "MASS", "res_id": "RESID", "q": "CHARGE", "lambda_adr": "LAMBDA"}[prop], value)
 
 
 def _node_grid(n, *a, **k):
@@ -523,6 +529,45 @@ class _VerletListTabulated(_VerletListInteraction):
         self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
 
 
+class _VerletListDynamicResolution(_VerletListInteraction):
+    """interaction.VerletListDynamicResolutionLennardJones / ...Tabulated(vl, cg_potential) (gromacs_topology.py:584-600,
+    819-862): the pair potential times lambda_i lambda_j, the scaled force capped at max_force (setMaxForce; rule set:
+    include/chem_mi355.h, chem_nb_resolution).  cg_potential = True (weight 1 - lambda_i lambda_j) is not built."""
+
+    def __init__(self, vl, cg_potential=False):
+        if cg_potential:
+            raise NotImplementedError("VerletListDynamicResolution*(cg_potential=True): the coarse-grained weight 1 - lambda_i lambda_j is outside the hot-path scope")
+        _VerletListInteraction.__init__(self, vl)
+        self.max_force = -1.0
+
+    def _send(self, type1, type2, potential):
+        raise NotImplementedError
+
+    def setPotential(self, type1, type2, potential):
+        self._pots[(min(type1, type2), max(type1, type2))] = potential
+        self._send(type1, type2, potential)
+        self.system.engine.nb_resolution(type1, type2, True, max(float(self.max_force), 0.0))
+
+    def setMaxForce(self, max_force):
+        self.max_force = float(max_force)
+        for t1, t2 in self._pots:
+            self.system.engine.nb_resolution(t1, t2, True, max(self.max_force, 0.0))
+
+
+class _VerletListDynamicResolutionLennardJones(_VerletListDynamicResolution):
+    label = "lj_dynres"
+
+    def _send(self, type1, type2, potential):
+        self.system.engine.nb_lj(type1, type2, potential.epsilon, potential.sigma, potential.cutoff, potential.shift == "auto")
+
+
+class _VerletListDynamicResolutionTabulated(_VerletListDynamicResolution):
+    label = "tab_dynres"
+
+    def _send(self, type1, type2, potential):
+        self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
+
+
 class _CoulombTruncated(_Pot):
     """interaction.CoulombTruncated(prefactor, cutoff): U = prefactor q_i q_j / r inside the cutoff, unshifted
     (rule set: include/chem_mi355.h, chem_nb_coulomb)."""
@@ -658,7 +703,8 @@ interaction = _ns(
     FixedTripleListTabulatedAngular=_FixedListInteraction, FixedTripleListTypesTabulatedAngular=_FixedListTypesInteraction,
     FixedPairListLambdaHarmonic=_FixedListLambdaInteraction, FixedPairListLambdaFENE=_FixedListLambdaInteraction,
     FixedPairListLambdaFENELennardJones=_FixedListLambdaInteraction, FixedPairListLambdaTabulated=_FixedListLambdaInteraction,
-    VerletListDynamicResolutionLennardJones=_unsupported("interaction.VerletListDynamicResolutionLennardJones"),
+    VerletListDynamicResolutionLennardJones=_VerletListDynamicResolutionLennardJones,
+    VerletListDynamicResolutionTabulated=_VerletListDynamicResolutionTabulated,
     MixedTabulated=_MixedTabulated, VerletListMixedTabulated=_VerletListMixedTabulated, MultiTabulated=_unsupported("interaction.MultiTabulated"),
 )
 
@@ -808,8 +854,9 @@ class _TopologyParticleProperties(object):
     """integrator.TopologyParticleProperties(type=, mass=, q=, state=, incr_state=) + set_min_max_state(min, max)
     (reaction_setup.py:245-249: the neighbour changes only while its state is in [min, max), and its state is incremented)."""
 
-    def __init__(self, type=None, mass=None, q=None, state=None, incr_state=None, **kw):
+    def __init__(self, type=None, mass=None, q=None, state=None, incr_state=None, lambda_adr=None, **kw):
         self.type, self.mass, self.q, self.state, self.incr_state = type, mass, q, state, incr_state
+        self.lambda_adr = lambda_adr        # honoured on the reactants of a Reaction / DissociationReaction (chem_reaction_set_resolution)
         self.min_state = self.max_state = None
 
     def set_min_max_state(self, min_state, max_state):
@@ -886,8 +933,15 @@ class _PostProcessChangeProperty(object):
     """integrator.PostProcessChangeProperty() and PostProcessChangePropertyByTopologyManager(tm) (reaction_setup.py:225-236):
     both change type / mass / charge of the reactant itself; here they are the same thing (new_type_* of chem_reaction_desc)."""
 
-    def __init__(self, topology_manager=None):
+    def __init__(self, *args):
+        """() | (topology_manager) : the reaction's form, changes added with add_change_property;
+        (type_id, TopologyParticleProperties): BasicDynamicResolution's form (reaction_setup.py:332-333), one change given at once"""
         self.changes = {}
+        if len(args) == 2 and isinstance(args[1], _TopologyParticleProperties):
+            type_id, prop = args
+            self.add_change_property(type_id, prop)
+        elif len(args) > 1:
+            raise TypeError("PostProcessChangeProperty([topology_manager]) or PostProcessChangeProperty(type_id, TopologyParticleProperties)")
 
     def add_change_property(self, type_id, prop):
         self.changes[int(type_id)] = prop
@@ -966,7 +1020,8 @@ class _DissociationReaction(_Reaction):
     rate, fpl, cutoff) + .diss_rate (reaction_setup.py:257-356): breaks bonds of `fpl` that are longer than `cutoff` or,
     with probability diss_rate * dt * interval, any of them (chem_dissociation_add; rule set in include/chem_mi355.h).
     `unexclude` (this shim's own attribute, default True): a broken pair interacts through the pair potential again.
-    The delayed type change of BasicDynamicResolution is not modelled: a PostProcessChangeProperty acts at once."""
+    A PostProcessChangeProperty with a type acts at once; one with TopologyParticleProperties(lambda_adr=...) alone sets the
+    reactant's resolution, and BasicDynamicResolution then carries the delayed type change (reaction_setup.py:319-354)."""
 
     def __init__(self, *a, **kw):
         _Reaction.__init__(self, *a, **kw)
@@ -1022,6 +1077,7 @@ class _ChemicalReaction(object):
                 r._index = e.dissociation_add(r.type_1, r.type_2, r.delta_1, r.delta_2, r.min_state_1, r.max_state_1, r.min_state_2,
                                               r.max_state_2, r.diss_rate, r.cutoff, r.fpl.handle, unexclude=r.unexclude, active=r.active, **kw)
                 r._system = self.system
+                self._lambda_rules(r)
                 continue
             bond_list = -1
             if not r.is_virtual:
@@ -1033,6 +1089,7 @@ class _ChemicalReaction(object):
                                       intramolecular=r.intramolecular, intraresidual=r.intraresidual, is_virtual=r.is_virtual,
                                       active=r.active, **kw)
             r._system = self.system
+            self._lambda_rules(r)
             if isinstance(r, _RestrictReaction):
                 if r.revert:
                     raise NotImplementedError("RestrictReaction.revert (dissociation along a connectivity map) is outside the hot-path scope")
@@ -1045,6 +1102,14 @@ class _ChemicalReaction(object):
                     e.reaction_neighbour_change(r._index, which, old_type, nb_level, int(prop.type), float(prop.mass),
                                                 float(prop.q or 0.0), None if prop.state is None else int(prop.state),
                                                 incr_state=getattr(prop, "incr_state", None), state_window=window)
+
+    def _lambda_rules(self, r):
+        """TopologyParticleProperties(lambda_adr=...) of the reaction's PostProcessChangeProperty: the reactant's resolution"""
+        for which, k in (("type_1", 1), ("type_2", 2)):
+            pp = r._pp.get(which)
+            ch = pp.changes.get(getattr(r, which)) if pp is not None else None
+            if ch is not None and getattr(ch, "lambda_adr", None) is not None:
+                self.system.engine.reaction_set_resolution(r._index, k, float(ch.lambda_adr))
 
     def _connect(self, integrator):
         self._flush()
@@ -1176,6 +1241,40 @@ class _FixedListDynamicResolution(object):
         pass
 
 
+class _BasicDynamicResolution(object):
+    """integrator.BasicDynamicResolution(system, {type: alpha}) + add_postprocess(PostProcessChangeProperty(type, props))
+    (reaction_setup.py:322-354): every particle of such a type with lambda < 1 gains alpha per MD step; when it reaches 1
+    the post-process of its type changes type, mass, charge (and state).  Nothing runs per step here: the engine evaluates
+    lambda from the step counter and the particle's stamp and splits its runs at the completion steps (chem_resolution_rate)."""
+
+    def __init__(self, system, type2alpha=None):
+        self.system = system
+        self.type2alpha = {int(t): float(a) for t, a in (type2alpha or {}).items()}
+        self._pp = []
+
+    def add_postprocess(self, pp):
+        if not isinstance(pp, _PostProcessChangeProperty):
+            raise NotImplementedError("post-process %s of BasicDynamicResolution is outside the hot-path scope" % type(pp).__name__)
+        self._pp.append(pp)
+
+    def _connect(self, integrator):
+        if self.system.storage is not None:
+            self.system.storage.decompose()
+        for t, alpha in sorted(self.type2alpha.items()):
+            ch = None
+            for pp in self._pp:
+                ch = pp.changes.get(t, ch)
+            if ch is None or ch.type is None:
+                self.system.engine.resolution_rate(t, alpha)
+            else:
+                self.system.engine.resolution_rate(t, alpha, new_type=int(ch.type), new_mass=float(ch.mass), new_q=float(ch.q or 0.0),
+                                                   new_state=-1 if ch.state is None else int(ch.state))
+
+    def disconnect(self):
+        for t in sorted(self.type2alpha):
+            self.system.engine.resolution_rate(t, 0.0)
+
+
 integrator = _ns(
     VelocityVerlet=_VelocityVerlet, FixedListDynamicResolution=_FixedListDynamicResolution, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
     Reaction=_Reaction, PostProcessChangeProperty=_PostProcessChangeProperty,
@@ -1187,7 +1286,7 @@ integrator = _ns(
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
     DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
     ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"), FixDistances=_unsupported("integrator.FixDistances"),
-    ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_unsupported("integrator.BasicDynamicResolution"),
+    ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_BasicDynamicResolution,
     PostProcessChangeNeighboursProperty=_PostProcessChangeNeighboursProperty,
     PostProcessRemoveNeighbourBond=_unsupported("integrator.PostProcessRemoveNeighbourBond"),
     PostProcessJoinParticles=_unsupported("integrator.PostProcessJoinParticles"),
@@ -1226,9 +1325,9 @@ class _PotentialEnergy(_Observable):
         if isinstance(i, _VerletListCoulombTruncated):
             return self.system.engine.get_coulomb()[0]
         o = self.system.engine.observe()
-        if isinstance(i, _VerletListLennardJones):
+        if isinstance(i, (_VerletListLennardJones, _VerletListDynamicResolutionLennardJones)):      # (one LJ accumulator: plain and resolution-scaled pairs together)
             return o["epot_lj"]
-        if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated)):    # (one tabulated-energy accumulator: plain and mixed tables together)
+        if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated, _VerletListDynamicResolutionTabulated)):    # (one tabulated-energy accumulator: plain and mixed tables together)
             return o["epot_tab"]
         h = getattr(i, "handle", None)      # the interaction's own library list (a list object carries one per kind)
         if h is None:
@@ -1412,7 +1511,7 @@ class _DumpH5MD(object):
                  store_mass=True, is_single_prec=True, chunk_size=256, **kw):
         self.system, self.filename, self.group = system, filename, group_name
         self.store = dict(species=store_species, res_id=store_res_id, position=store_position, state=store_state, force=store_force,
-                          velocity=store_velocity, mass=store_mass)
+                          velocity=store_velocity, mass=store_mass, lambda_adr=store_lambda)
         self.real = np.float32 if is_single_prec else np.float64
         self.frames = {}            # dataset path -> list of per-frame arrays
         self.steps, self.times = [], []
@@ -1441,6 +1540,8 @@ class _DumpH5MD(object):
             self._add("res_id", e.get_state("RESID").astype(np.int32))
         if self.store["mass"]:
             self._add("mass", e.get_state("MASS").astype(self.real))
+        if self.store["lambda_adr"]:
+            self._add("lambda_adr", e.get_state("LAMBDA").astype(self.real))
         self.frames.setdefault("particles/%s/box/edges/value" % self.group, []).append(np.asarray(list(self.system.bc.boxL), dtype=self.real))
 
     def tree(self):

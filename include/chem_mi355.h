@@ -102,6 +102,7 @@ extern "C" {
 #define CHEM_STATE_MOLID  10   /* int32[n]  lowest particle id of the bonded cluster */
 #define CHEM_STATE_POS_UNFOLDED 11 /* double[n*3] = pos + image*L                  */
 #define CHEM_STATE_CHARGE  12  /* double[n]; also a `what` of chem_modify_particle  */
+#define CHEM_STATE_LAMBDA  13  /* double[n]  resolution lambda at the current step (chem_set_resolution); also a `what` of chem_modify_particle */
 
 typedef struct chem_ctx chem_ctx;
 
@@ -200,7 +201,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
                        const double* pos, const double* vel, const double* mass,
                        const double* q, const int32_t* state, const int32_t* res_id);
 /* storage.modifyParticle(pid, 'type'|'state'|'mass', v)  examples/atrp_lj/hooks.py:63-65 */
-int chem_modify_particle(chem_ctx* ctx, int64_t id, int what /*CHEM_STATE_TYPE|STATE|MASS|RESID|CHARGE*/, double value);
+int chem_modify_particle(chem_ctx* ctx, int64_t id, int what /*CHEM_STATE_TYPE|STATE|MASS|RESID|CHARGE|LAMBDA*/, double value);
 /* DynamicExcludeList(integrator, gt.exclusions)  start_simulation.py:189 */
 int chem_set_exclusions(chem_ctx* ctx, int64_t n, const int64_t* id_pairs);
 
@@ -255,6 +256,64 @@ int chem_nb_coulomb(chem_ctx* ctx, int t1, int t2, double prefactor, double rc);
  * no pair is registered).  Either pointer may be NULL.  chem_obs.epot_lj / epot_tab keep their meaning; chem_obs.virial_nb,
  * the sum over ALL non-bonded pairs, includes the Coulomb part. */
 int chem_get_coulomb(chem_ctx* ctx, double* epot, double* virial);
+
+/* ---- dynamic resolution: per-particle lambda ------------------------------------------ */
+/* interaction.VerletListDynamicResolutionLennardJones / ...Tabulated(vl, cg_potential=False) (gromacs_topology.py:584-600,
+ * 819-862: nonbond_params func 15 / 11), integrator.BasicDynamicResolution(system, {type: alpha}) with
+ * add_postprocess(PostProcessChangeProperty) (reaction_setup.py:257-356) and the particle property lambda_adr.  The arithmetic
+ * is in the external fork, so this rule set is this build's own ([EXT-RECALL], parity unpinned; DESIGN.md "Dynamic resolution").
+ *
+ * Every particle has a resolution lambda in [0, 1], 1 unless set.  Per particle (by tag) the host keeps a stamp (lambda0, s0);
+ * with alpha(t) the rate registered for type t (0 if none) the resolution at step s is
+ *     lambda(s) = min(1.0, lambda0 + alpha(type) * (double)(s - s0))        fp64, in this order, no fused multiply-add.
+ * The forces that are current at step s use lambda(s) (the convention of chem_list_set_hybrid): lambda is a pure function of
+ * the stamp, the type and the step -- no array that is updated per step --, the same on every rank and for run(a); run(b)
+ * as for run(a+b).  A particle is re-stamped with (its current lambda, the current step) when its lambda is set explicitly,
+ * when its type changes by any route (reaction, neighbour rule, ATRP, dissociation, chem_modify_particle, completion below)
+ * and when the rate of its type is changed.  chem_set_particles puts every lambda back to 1.
+ *
+ * chem_nb_resolution marks (on != 0) or unmarks the LJ or table already registered for the symmetric type pair as
+ * resolution-scaled.  For each listed pair of a marked type pair that is not excluded and lies inside that potential's cutoff:
+ *   - w = lambda_i lambda_j; a pair with w == 0 contributes nothing and its potential is not evaluated;
+ *   - F = w F_pot; if max_force > 0 and |F| > max_force, F is rescaled to |F| = max_force (the cap comes after the scaling);
+ *   - the energy share is w U, uncapped, in chem_obs.epot_lj / epot_tab; the virial share is r.F of the force that was applied;
+ *   - unmarked type pairs behave exactly as without this call, whatever lambda their particles have; a context without a
+ *     marked pair launches the kernels it launched before and allocates nothing;
+ *   - marking a type pair that carries no LJ or table is CHEM_EINVAL (the mark would have nothing to scale; a potential that
+ *     is re-sent later keeps its mark; unmarking is always allowed);
+ *   - the Coulomb term is never scaled, and a context does not serve a Coulomb pair and a marked pair together: the next
+ *     force evaluation refuses that with CHEM_ENOTIMPL naming the marked pair;
+ *   - the reference's cg_potential = True variant (weight 1 - w) is not built;
+ *   - while a pair is marked the force kernels are built for option tpp = 1 (or 0) and pair_block = 512 only (CHEM_EINVAL at
+ *     the next evaluation otherwise), and harmonic bonds are not evaluated inline, as for chem_nb_coulomb. */
+int chem_nb_resolution(chem_ctx* ctx, int t1, int t2, int on, double max_force);
+/* BasicDynamicResolution's {type: alpha} entry plus the PostProcessChangeProperty attached to it.  alpha <= 0 removes the
+ * entry.  The rate applies to every particle of that type with lambda < 1.  new_type < 0: no property change; new_state < 0:
+ * the chemical state is kept.  Completion: let s_full be the first step at which the expression above evaluates to >= 1.0.
+ * When the step counter reaches s_full a particle of a type with a registered change gets new_type, new_mass, new_q and
+ * new_state by the route of chem_modify_particle; its lambda stays 1 (stamp (1, s_full) under the new type, so a rate of the
+ * new type does nothing more).  chem_run splits at these steps as it splits at reaction steps -- the host knows every stamp,
+ * so it knows every s_full: no device-side polling, no host round trip per step -- and evaluates the forces again after the
+ * change, so the forces current at s_full (chem_get_state(CHEM_STATE_FORCE), the first half kick of the next step) are those
+ * of the new properties; the half kick that ended the step into s_full was the last with the old ones.  A reaction of the
+ * same step acts first.  On slabs the change goes as far as chem_modify_particle does there.  Call it after
+ * chem_set_particles (CHEM_ESTATE otherwise). */
+int chem_resolution_rate(chem_ctx* ctx, int type, double alpha, int new_type, double new_mass, double new_q, int new_state);
+/* lambda_adr of addParticles / modifyParticle: lambda of the n particles `ids`, stamped at the current step.  A value outside
+ * [0, 1] or non-finite, and an unknown id, are CHEM_EINVAL (nothing is set then).  The same on every rank of a decomposition.
+ * CHEM_STATE_LAMBDA reads lambda at the current step back (chem_get_state: the fp64 host expression) and sets one particle's
+ * (chem_modify_particle). */
+int chem_set_resolution(chem_ctx* ctx, int64_t n, const int64_t* ids, const double* lambda);
+/* TopologyParticleProperties(lambda_adr=...) of the PostProcessChangeProperty of a Reaction / DissociationReaction
+ * (reaction_setup.py:300-330): on every event of `reaction` (an index of chem_reaction_add or chem_dissociation_add) the
+ * particle in `role` (1 | 2) is stamped (lambda, event step), after the reaction's own state and type changes and after the
+ * re-stamping those cause.  A negative lambda removes the rule.  CHEM_EINVAL: unknown index, role other than 1 or 2,
+ * lambda > 1.  Not on the decomposed path (CHEM_ENOTIMPL here after chem_comm_init*, and in chem_comm_init* after this call).
+ * While a rule or a rate exists, a reaction step waits for its own host bookkeeping before the next MD step is enqueued, and
+ * chem_run also ends its pieces at every reaction and ATRP step (a stamp set there may create a completion step).  Rules
+ * are keyed by the reaction index and live as long as the reaction does: reactions are never removed from a context, and
+ * chem_set_particles keeps reactions and rules alike. */
+int chem_reaction_set_resolution(chem_ctx* ctx, int reaction, int role, double lambda);
 
 /* ---- bonded lists -------------------------------------------------------------------- */
 /* FixedPairList/TripleList/QuadrupleList(storage) + FixedXListYyy(system, list, potential)
@@ -404,7 +463,8 @@ int64_t chem_atrp_get_stats(chem_ctx* ctx, chem_atrp_stats* out, int64_t cap);
  *   independence every qualifying bond breaks on its own: no one-event-per-particle resolve, no max_per_interval; a
  *               particle that loses k bonds in one step receives k * delta.
  *   apply       state += delta_{1,2}; where new_type_{1,2} >= 0 type, mass and q change AT ONCE (the delayed change of
- *               the reference's BasicDynamicResolution(alpha) is not modelled; where one particle gets several new
+ *               the reference's BasicDynamicResolution(alpha): new_type = -1 here, chem_reaction_set_resolution(r, role, 0)
+ *               and chem_resolution_rate on the old type with the change; where one particle gets several new
  *               types in one step the last event in list order wins).  The entry leaves `bond_list` (order of the
  *               survivors kept) and the pair leaves the bond graph (unless another pair list still holds it).  mol_id of
  *               the two fragments becomes the lowest particle of each bonded cluster (nothing changes if a still
