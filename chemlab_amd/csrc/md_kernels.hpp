@@ -3961,8 +3961,9 @@ __global__ void k_react_apply(int nc, const Candidate* __restrict__ c, const int
   const Candidate cd = c[k];
   const ReactApply ra = ras.r[cd.r];
   state[cd.a] += ra.delta_1; state[cd.b] += ra.delta_2;
-  if (ra.new_type_1 >= 0) { int i = rtag[cd.a]; if (i >= 0) { x4[i].w = (R)ra.new_type_1; v4[i].w = (R)ra.new_mass_1; } }
-  if (ra.new_type_2 >= 0) { int i = rtag[cd.b]; if (i >= 0) { x4[i].w = (R)ra.new_type_2; v4[i].w = (R)ra.new_mass_2; } }
+  // (the new mass goes with a CHANGE of type: an event that names the type the particle already has leaves its mass alone, as the host mirror and the oracle do)
+  if (ra.new_type_1 >= 0) { int i = rtag[cd.a]; if (i >= 0 && x4[i].w != (R)ra.new_type_1) { x4[i].w = (R)ra.new_type_1; v4[i].w = (R)ra.new_mass_1; } }
+  if (ra.new_type_2 >= 0) { int i = rtag[cd.b]; if (i >= 0 && x4[i].w != (R)ra.new_type_2) { x4[i].w = (R)ra.new_type_2; v4[i].w = (R)ra.new_mass_2; } }
   out[base + __popcll(m & lanemask_lt())] = cd;
 }
 

@@ -96,7 +96,7 @@ extern "C" {
 #define CHEM_STATE_TYPE    4   /* int32[n]                                         */
 #define CHEM_STATE_STATE   5   /* int32[n]  chemical state                         */
 #define CHEM_STATE_RESID   6   /* int32[n]                                         */
-#define CHEM_STATE_MASS    7   /* double[n]                                        */
+#define CHEM_STATE_MASS    7   /* double[n]  the mass the device integrates with: (float)m in the CHEM_PREC_F32 build */
 #define CHEM_STATE_ID      8   /* int64[n]                                         */
 #define CHEM_STATE_IMAGE   9   /* int32[n*3] periodic image counters               */
 #define CHEM_STATE_MOLID  10   /* int32[n]  lowest particle id of the bonded cluster */
@@ -125,7 +125,8 @@ typedef struct chem_reaction_desc {
   int32_t active;
   int32_t bond_list;                  /* handle of the arity-2 list receiving new bonds */
   int32_t new_type_1, new_type_2;     /* -1: unchanged                                */
-  double  new_mass_1, new_mass_2;     /* used when the type changes                   */
+  double  new_mass_1, new_mass_2;     /* used when the type changes: an event that names the type a particle already has
+                                         leaves its mass alone (the charge is set wherever a new type is named)          */
   double  new_q_1, new_q_2;
 } chem_reaction_desc;
 
@@ -426,7 +427,8 @@ int chem_reaction_restrict(chem_ctx* ctx, int reaction, int64_t n, const int64_t
  *   a selected particle matching centre c (first match in insertion order) is flipped with probability
  *               k_activate * ratio_activator   when c.is_activator == 0  ("A" centres: consume activator),
  *               k_deactivate * ratio_deactivator when c.is_activator != 0 ("DA" centres: consume deactivator);
- *   a flip sets type/mass/q to the centre's new property, state += delta_state, and moves
+ *   a flip sets type/mass/q to the centre's new property where new_type differs from the particle's type (a centre that
+ *               names the type the particle already has changes neither its mass nor its charge), state += delta_state, and moves
  *               delta_catalyst / num_particles of catalyst from the consumed pool to the other one (clamped at 0).
  * The arithmetic lives in the external ESPResSo++ fork; this rule set is this build's restatement of the call
  * site's contract ([EXT-RECALL]).  desc == NULL disconnects the extension. */
