@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("CHEM_MI355_LIB") or os.path.join(HERE, "csrc", "libch
 CHEM_MAX_LISTS = 32
 CHEM_MAX_TYPES = 16
 CHEM_MAX_POT_PARAMS = 6
+CHEM_MAX_FIX_SETS = 8
 
 # error codes
 OK, EINVAL, ENOSPC, EDEVICE, ESTATE, ENOTIMPL, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -82,6 +83,10 @@ class AtrpStats(C.Structure):
 class Event(C.Structure):
     _fields_ = [("step", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64),
                 ("reaction", C.c_int32), ("pad", C.c_int32), ("r2", C.c_double)]
+
+
+class FixRecord(C.Structure):
+    _fields_ = [("step", C.c_int64), ("anchor_id", C.c_int64), ("target_id", C.c_int64), ("set", C.c_int32), ("cause", C.c_int32)]
 
 
 class Obs(C.Structure):
@@ -175,6 +180,15 @@ PRODUCT_ONLY = {
     "resolution_rate": (_i, [_P, _i, _d, _i, _d, _d, _i]),
     "set_resolution": (_i, [_P, _i64, _pi64, _pd]),
     "reaction_set_resolution": (_i, [_P, _i, _i, _d]),
+    # fixed distances / by-product release (the CPU oracle has none)
+    "add_particles": (_i, [_P, _i64, _pi64, _pi32, _pd, _pd, _pd, _pd, _pi32, _pi32]),
+    "fix_create": (_i, [_P, _i, _i]),
+    "fix_add": (_i, [_P, _i, _i64, _pi64, _d]),
+    "fix_postprocess": (_i, [_P, _i, _i, _i, _d, _d, _i, _d]),
+    "reaction_release": (_i, [_P, _i, _i, _i, _i]),
+    "fix_count": (_i64, [_P, _i]),
+    "fix_get": (_i64, [_P, _i, _pi64, _pd, _i64]),
+    "fix_log": (_i64, [_P, C.POINTER(FixRecord), _i64]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

@@ -46,6 +46,16 @@ class GromacsTopology(object):
         self._prepare_data()
         return self
 
+    def add_new_atomtype(self, atype_id, atype_name, is_used=False):
+        """A type that the topology file does not know (gromacs_topology.py:172-183; the dummies of ReleaseMolecule).  Not
+        used: it gets no row of the non-bonded matrix, so the used names become a map of their own."""
+        if not is_used and self.used_atomsym_atomtype is self.atomsym_atomtype:
+            self.used_atomsym_atomtype = collections.OrderedDict(self.atomsym_atomtype)
+        self.atomtype_atomsym[atype_id] = atype_name
+        self.atomsym_atomtype[atype_name] = atype_id
+        if is_used:
+            self.used_atomsym_atomtype[atype_name] = atype_id
+
     # molecule replication: ids are 1-based and contiguous (SURVEY Q11)
     def _prepare_data(self):
         gt = self.gt

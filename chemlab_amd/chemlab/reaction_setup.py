@@ -10,6 +10,8 @@ class SetupReactions(object):
         self.dynamic_types = set()
         self.fpls = []
         self.extensions_to_integrator = []
+        self.fix_distances = []            # FixDistances objects of ReleaseMolecule extensions
+        self.use_thermal_group = False     # set by an extension that adds particles the thermostat must leave alone
 
     def _setup_reaction_normal(self, cr, fpl):
         e, rl = self.espp, cr["reactant_list"]
@@ -125,6 +127,8 @@ class SetupReactions(object):
             raise RuntimeError("extension %s is not defined ([ext_%s] missing)" % (name, name))
         if cfg.get("ext_type") == "ATRPActivator":
             return self._setup_atrp_activator(cfg), None
+        if cfg.get("ext_type") == "ReleaseMolecule":
+            return self._setup_release_molecule(cfg)
         if cfg.get("ext_type") != "ChangeNeighboursProperty":
             raise NotImplementedError("reaction extension %s (%s) is outside the hot-path scope (SURVEY f-4)" % (name, cfg.get("ext_type")))
         e, n2t = self.espp, self.name2type
@@ -144,6 +148,65 @@ class SetupReactions(object):
             pp.add_change_property(n2t[old_type], e.integrator.TopologyParticleProperties(**kw), int(nb_level))
             self.dynamic_types.update((n2t[old_type], n2t[new_type]))
         return pp, cfg.get("invoke_on", "both")
+
+    def _setup_release_molecule(self, cfg):
+        """[ext_*] ext_type=ReleaseMolecule (reaction_post_process.py:203-320): every particle of `host_type` gets `replicate`
+        dummy particles of a new type at `eq_length`, held there by FixDistances; a bond of the host (`release_on=bond`,
+        `release_count` per event) or a type change of host or dummy (`release_on=type`) sets a dummy free as `target_type` at
+        lambda 0, BasicDynamicResolution({target: alpha}) fades it in and, where `final_type` differs, changes it once more at
+        lambda 1.  Returns (PostProcessReleaseParticles | None, invoke_on)."""
+        e, topol = self.espp, self.topol
+        host_type, target_type = cfg["host_type"], cfg["target_type"]
+        eq_length, alpha, init_res = float(cfg["eq_length"]), float(cfg["alpha"]), float(cfg["init_res"])
+        final_type = cfg.get("final_type", target_type)
+        if cfg.get("cache_file"):
+            raise NotImplementedError("ReleaseMolecule cache_file is a Python 2 pickle of the reference's own objects: not read or written here")
+        replicate = int(cfg.get("replicate", 1))
+        release_on = cfg.get("release_on", "type")
+        if release_on not in ("bond", "type"):
+            raise RuntimeError("Wrong keyword release_on %s, only: bond or type" % release_on)
+        release_count = int(cfg.get("release_count", 1))
+        invoke_on = cfg.get("invoke_on", "both")        # (the reference reads invoke_on: a `release_host=` key has no effect there, nor here)
+        if invoke_on not in ("type_1", "type_2", "both"):
+            raise RuntimeError("Wrong keyword invoke_on %s, only type_1, type_2, both" % invoke_on)
+        dummy_type_id = max(topol.atomsym_atomtype.values()) + 1
+        topol.add_new_atomtype(dummy_type_id, "DUMMY_%d" % dummy_type_id, False)
+        host_pids = sorted(pid for pid, v in topol.atoms.items() if v["type"] == host_type)
+        target_type_id = topol.atomsym_atomtype[target_type]
+        target_properties = topol.gt.atomtypes[target_type]
+        eng = self.system.engine
+        ids, pos = eng.get_state("ID"), eng.get_state("POS")
+        row = {int(pid): k for k, pid in enumerate(ids.tolist())}
+        particle_list, fix_list = [], []
+        dummy_idx = max(topol.atoms) + 1
+        for host_pid in host_pids:
+            hp = pos[row[host_pid]]
+            for _ in range(replicate):
+                fix_list.append((host_pid, dummy_idx, eq_length))
+                particle_list.append([dummy_idx, dummy_type_id, e.Real3D(hp[0] + eq_length, hp[1], hp[2]), target_properties["mass"], dummy_idx,
+                                      init_res, target_properties.get("state", 0)])
+                dummy_idx += 1
+        self.system.storage.addParticles(particle_list, "id", "type", "pos", "mass", "res_id", "lambda_adr", "state")
+        self.system.storage.decompose()
+        release_pp = None
+        if release_on == "type":
+            fd = e.integrator.FixDistances(self.system, fix_list, topol.atomsym_atomtype[host_type], dummy_type_id)
+        else:
+            fd = e.integrator.FixDistances(self.system, fix_list)
+            release_pp = e.integrator.PostProcessReleaseParticles(fd, release_count)
+        self.fix_distances.append(fd)
+        fxd_pp = e.integrator.PostProcessChangeProperty()
+        fxd_pp.add_change_property(dummy_type_id, e.integrator.TopologyParticleProperties(type=target_type_id, mass=target_properties["mass"], lambda_adr=0.0))
+        fd.add_postprocess(fxd_pp)
+        self.system.integrator.addExtension(fd)
+        dyn_res = e.integrator.BasicDynamicResolution(self.system, {target_type_id: alpha})
+        if target_type != final_type:
+            fp = topol.gt.atomtypes[final_type]
+            tpp = e.integrator.TopologyParticleProperties(type=topol.atomsym_atomtype[final_type], mass=fp["mass"], q=fp["charge"], state=fp.get("state", 0), lambda_adr=1.0)
+            dyn_res.add_postprocess(e.integrator.PostProcessChangeProperty(target_type_id, tpp))
+        self.system.integrator.addExtension(dyn_res)
+        self.use_thermal_group = True        # the dummies must not be thermalised
+        return release_pp, invoke_on
 
     def _setup_atrp_activator(self, cfg):
         """[ext_*] ext_type=ATRPActivator -> integrator extension (reaction_post_process.py:380-426):
@@ -182,7 +245,7 @@ class SetupReactions(object):
             group_ext = [(name, self._setup_extension(name)) for name in group["extensions"]]
             # integrator extensions (ATRPActivator) go to the driver, post-processes to the group's reactions (reaction_setup.py:470-483)
             self.extensions_to_integrator.extend(x for _, (x, inv) in group_ext if inv is None)
-            group_pp = [(name, v) for name, v in group_ext if v[1] is not None]
+            group_pp = [(name, v) for name, v in group_ext if v[1] is not None and v[0] is not None]      # (ReleaseMolecule on a type change: nothing to attach)
             # --t_hybrid_bond N (reaction_setup.py:444-467): the group's bonds start at lambda = 0; the driver registers the list
             # with integrator.FixedListDynamicResolution, which brings them to full strength over N steps
             hybrid = getattr(self.args, "t_hybrid_bond", 0) > 0 if self.args is not None else False

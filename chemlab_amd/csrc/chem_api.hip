@@ -24,6 +24,7 @@
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
 #include "chem_res_host.hpp"
+#include "chem_fix_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
 
@@ -115,6 +116,19 @@ struct Ctx {
   // type changes have to be seen when they happen (re-stamping) and events looked at (res_rules)
   bool res_tracking() const { return (res.on() && res.any_rate()) || !res_rules.empty(); }
   virtual void res_push(const std::vector<int32_t>& tags) = 0;      // stamps of these tags -> device (if the copy is alive)
+  // Fixed distances (chem_fix_create ff.; chem_fix_host.hpp): sets, entries, release rules and the log live on the host; the
+  // device holds the flat entry array only while a live entry exists (fix_dirty: rewritten at the next flush_host_state).
+  FixState fix; bool fix_dirty = false;
+  bool ran = false;      // chem_run has been called since chem_set_particles (chem_add_particles is refused then)
+  // releases have to be looked for at every reaction / ATRP step: a rule, or a typed set, with entries to act on
+  bool fix_tracking() const {
+    if (!fix.any()) return false;
+    if (!fix.rules.empty()) return true;
+    for (const FixSet& s : fix.sets) if (!s.ent.empty() && (s.anchor_type >= 0 || s.target_type >= 0)) return true;
+    return false;
+  }
+  virtual int fix_after_reactions(bool events) = 0;       // release by reaction (this step's events) and by type; the number released
+  virtual void add_particles_prepare() = 0;                // positions and velocities back into pos0 / vel0 (tag order)
   bool lang = false; double kT = 0, gamma = 0; uint64_t lang_seed = 0; uint32_t lang_tmask = 0;
   bool react_init = false, react_on = false;
   int interval = 0, nearest = 1, max_per_interval = 0; uint64_t react_seed = 0;
@@ -741,6 +755,7 @@ template <typename R> struct CtxT : Ctx {
     for (auto& c : atrp_centers) nt = std::max(nt, std::max(c.type, c.new_type) + 1);
     for (int a = 0; a < CHEM_MAX_TYPES; ++a) if (coul_mask[a]) nt = std::max(nt, a + 1);
     for (const ResRate& r : res.rate) if (r.alpha > 0.0) nt = std::max(nt, r.new_type + 1);
+    for (const FixSet& fs : fix.sets) for (const FixPost& fp : fs.post) nt = std::max(nt, fp.new_type + 1);
     ntypes = nt;
     std::vector<PairCore<R>> hc((size_t)nt * nt);
     std::vector<PairExt<R>> he((size_t)nt * nt);
@@ -881,6 +896,90 @@ template <typename R> struct CtxT : Ctx {
         }
       }
     res_push(changed);
+  }
+
+  // ---- fixed distances (chem_fix_add; rule set: include/chem_mi355.h, host routines: chem_fix_host.hpp) ----
+  // The flat entry array is rewritten by the host at an add or a release only (both sit behind a synchronisation); it is freed
+  // with the last entry, and a context without entries launches exactly what it launched before.
+  DBuf<FixEnt<R>> fix_dev; int fix_n = 0;
+  void upload_fix() {
+    fix_dirty = false;
+    const std::vector<FixEntry> all = fix.device_order();
+    HIPCHK(hipStreamSynchronize(stream));
+    fix_n = (int)all.size();
+    if (all.empty()) { fix_dev.free(); return; }
+    std::vector<FixEnt<R>> h(all.size());
+    for (size_t k = 0; k < all.size(); ++k) { h[k] = FixEnt<R>{}; h[k].a = all[k].anchor; h[k].t = all[k].target; h[k].d = (R)all[k].dist; }
+    fix_dev.upload(h, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  void launch_fix() {
+    if (fix_n <= 0) return;
+    FixGeom<R> g{};
+    for (int d = 0; d < 3; ++d) { g.L[d] = (R)L[d]; g.invL[d] = (R)(1.0 / L[d]); }
+    hipLaunchKernelGGL((k_fix_distances<R>), dim3(cdiv(fix_n, 256)), dim3(256), 0, stream, fix_n, fix_dev.p, rtag.p, nglob, x4.p, v4.p, g, pos_scale(), (const DevCtl*)ctl.p);
+  }
+  // What a release does to its target: the post-process of the set that matches the target's current type, by the route of
+  // the other host-decided property changes (mirrors, k_apply_props, charges), then the lambda stamp; the lists are rebuilt.
+  int fix_apply_releases(const std::vector<FixRecord>& rel) {
+    if (rel.empty()) return 0;
+    const bool on_device = device_ready && !particles_dirty;      // (otherwise the mirrors alone: everything is uploaded later)
+    std::vector<HostTopology::PropChange> chg;
+    std::vector<std::pair<int32_t, double>> stamps;
+    for (const FixRecord& r : rel) {
+      const int32_t t = r.target;
+      const FixPost* p = fix.post_for(r.set, top.type[t]);
+      if (!p) continue;
+      if (p->new_type >= 0) { top.type[t] = p->new_type; top.mass[t] = p->new_mass; top.q[t] = p->new_q; }
+      if (p->new_state >= 0 && (!on_device || !state_mirror_stale)) top.state[t] = p->new_state;
+      if (p->new_type >= 0 || p->new_state >= 0) chg.push_back(HostTopology::PropChange{t, top.type[t], p->new_state >= 0 ? 1 : 0, p->new_state >= 0 ? p->new_state : 0, top.mass[t], top.q[t]});
+      if (p->lambda >= 0.0) stamps.emplace_back(t, p->lambda);
+    }
+    if (on_device) apply_prop_changes(chg);
+    std::vector<int32_t> changed;
+    if (res.on() || !stamps.empty()) {
+      res.ensure(top.type);
+      res.restamp_type_changes(top.type, step, changed);      // (re-stamped under the old type's rate first)
+      for (const auto& s : stamps) { res.stamp((size_t)s.first, s.second, step); changed.push_back(s.first); }
+      res_push(changed);
+    }
+    fix_dirty = true;
+    if (!on_device) return (int)rel.size();
+    if (!chg.empty() && any_typed_list()) upload_bonded(false);
+    upload_fix();
+    request_rebuild();      // the target's displacement was never tracked, and its new type pair may bring it onto the lists
+    return (int)rel.size();
+  }
+  int fix_after_reactions(bool events) override {
+    int nrel = 0;
+    join_async();      // the event log and the type mirrors of this step are complete
+    if (events && !fix.rules.empty()) {
+      // this step's association events that formed a bond, in the order chem_get_events reports them: (min id, max id)
+      struct Ev { int32_t a, b; int r; };
+      std::vector<Ev> evs;
+      for (size_t bk = arena.blocks.size(); bk-- > 0 && arena.blocks[bk].first == step;) {
+        const size_t lo = arena.blocks[bk].second, hi = bk + 1 < arena.blocks.size() ? arena.blocks[bk + 1].second : arena.size();
+        for (size_t k = lo; k < hi; ++k) if (arena.r[k] >= 0 && !reactions[arena.r[k]].is_virtual) evs.push_back(Ev{arena.a[k], arena.b[k], public_index(arena.r[k])});
+      }
+      std::sort(evs.begin(), evs.end(), [](const Ev& p, const Ev& q) { return std::make_pair(std::min(p.a, p.b), std::max(p.a, p.b)) < std::make_pair(std::min(q.a, q.b), std::max(q.a, q.b)); });
+      std::vector<FixReactant> rc;
+      for (const Ev& e : evs) { rc.push_back(FixReactant{e.r, 1, e.a}); rc.push_back(FixReactant{e.r, 2, e.b}); }
+      nrel += fix_apply_releases(fix.release_by_reaction(rc, step));
+    }
+    nrel += fix_apply_releases(fix.release_by_type(top.type, step));
+    return nrel;
+  }
+  // chem_add_particles after the first upload: the particle data goes back to the staging arrays (unfolded positions, so that
+  // the images are counted again), everything per-tag is uploaded afresh with the larger set
+  void add_particles_prepare() override {
+    if (particles_dirty) return;
+    const int64_t n0 = top.n;
+    std::vector<double> p((size_t)3 * n0), v((size_t)3 * n0);
+    get_state(CHEM_STATE_POS_UNFOLDED, p.data(), 3 * n0);
+    get_state(CHEM_STATE_VEL, v.data(), 3 * n0);
+    refresh_state_mirror();
+    pos0 = std::move(p); vel0 = std::move(v);
+    particles_dirty = true;
   }
 
   // ---- per-tag CSR tables built on the device from flat, append-only arrays (md_kernels.hpp "Per-tag CSR tables") ----
@@ -1082,6 +1181,7 @@ template <typename R> struct CtxT : Ctx {
     if (pair_dirty) upload_pair();
     if (coul_dirty) upload_coul();
     if (res_dirty) upload_res();
+    if (fix_dirty) upload_fix();
     if (bonded_dirty) upload_bonded();
     if (excl_dirty) upload_excl();
   }
@@ -1749,7 +1849,7 @@ template <typename R> struct CtxT : Ctx {
     for (int64_t s = 0; s < nsteps; ++s) {
       // (a stop the device has already told the pinned words about need not wait for the next synchronisation)
       if (!resume && hflag && skip_applies() && const_cast<const volatile IdleHint*>(hint_host())->halted == hint_gen && halted(s)) { --s; continue; }
-      if (need_int1) { launch_integrate<2>(false, false, step, 1); need_int1 = false; }
+      if (need_int1) { launch_integrate<2>(false, false, step, 1); launch_fix(); need_int1 = false; }
       timed_step = opt_time_pair && (pair_launch_no++ % opt_time_pair) == 0;
       if (timed_step) timed_extra = 1 + (int)((pair_launch_no / opt_time_pair) % 3);
       const bool react_due = react_on && interval > 0 && ((step + 1) % interval == 0);
@@ -1781,11 +1881,13 @@ template <typename R> struct CtxT : Ctx {
         if (react_due) react_step();
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
         if ((react_due || atrp_due) && res_tracking()) res_after_reactions();
+        if ((react_due || atrp_due) && fix_tracking()) fix_after_reactions(react_due);
         need_int1 = true;
       } else {
         tbeg(2);
         launch_integrate<3>(lang, false, step, 1);
         tend();
+        launch_fix();
         ++step;
       }
       timed_step = false;
@@ -2633,7 +2735,138 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   c.coul_dirty = true;
   c.res.clear(); c.res_dirty = true;      // (a new particle set: every lambda is 1 again; rates, marks and reaction rules stay)
   c.step = 0; c.events.clear(); c.arena.clear();
+  // (fixed distances: entries and log go with the tags; sets, post-processes and release rules stay)
+  for (FixSet& fs : c.fix.sets) { fs.ent.clear(); fs.next_seq = 0; }
+  c.fix.targets.clear(); c.fix.anchors.clear(); c.fix.log.clear(); c.fix_dirty = true; c.ran = false;
   return 0;
+  API_END(ctx)
+}
+
+int chem_add_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_t* type, const double* pos, const double* vel,
+                       const double* mass, const double* q, const int32_t* state, const int32_t* res_id) {
+  API_BEGIN
+  Ctx& c = CTX; HostTopology& t = c.top;
+  REQUIRE(t.n > 0, CHEM_ESTATE, "add_particles: set particles first");
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "add_particles is not available on the decomposed path");
+  REQUIRE(c.step == 0 && !c.ran, CHEM_ESTATE, "add_particles: only at step 0 and before the first chem_run");
+  REQUIRE(n > 0 && id && type && pos && mass, CHEM_EINVAL, "add_particles: null or empty input");
+  REQUIRE(t.n + n < (1ll << 27), CHEM_EINVAL, "add_particles: too many particles for one context");
+  std::vector<int64_t> order(n);
+  for (int64_t i = 0; i < n; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return id[a] < id[b]; });
+  const int64_t n0 = t.n, top_id = t.id[n0 - 1];
+  REQUIRE(id[order[0]] > top_id, CHEM_EINVAL, "add_particles: every new id must be greater than the largest present id (" + std::to_string(top_id) + ")");
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t s = order[k];
+    REQUIRE(k == 0 || id[s] != id[order[k - 1]], CHEM_EINVAL, "add_particles: duplicate particle id");
+    REQUIRE(type[s] >= 0 && type[s] < CHEM_MAX_TYPES, CHEM_EINVAL, "add_particles: particle type out of range [0," + std::to_string(CHEM_MAX_TYPES) + "): CHEM_MAX_TYPES is the limit");
+    REQUIRE(mass[s] > 0, CHEM_EINVAL, "add_particles: particle mass must be positive");
+    for (int d = 0; d < 3; ++d) REQUIRE(std::isfinite(pos[3 * s + d]), CHEM_EINVAL, "add_particles: position");
+  }
+  c.add_particles_prepare();      // (nothing has failed so far; particle data back in pos0 / vel0 if it was on the device)
+  const int64_t n1 = n0 + n;
+  t.id.resize(n1); t.type.resize(n1); t.state.resize(n1); t.res_id.resize(n1); t.mol_id.resize(n1); t.mass.resize(n1); t.q.resize(n1);
+  t.graph.resize(n1); t.excl.resize(n1);
+  c.pos0.resize(3 * n1); c.vel0.resize(3 * n1, 0.0);
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t s = order[k], g = n0 + k;
+    t.id[g] = id[s]; if (id[s] != t.id0 + g) t.contiguous = false;
+    t.type[g] = type[s]; t.mass[g] = mass[s]; t.q[g] = q ? q[s] : 0.0;
+    t.state[g] = state ? state[s] : 0; t.res_id[g] = res_id ? res_id[s] : (int32_t)id[s]; t.mol_id[g] = (int32_t)g;
+    for (int d = 0; d < 3; ++d) { c.pos0[3 * g + d] = pos[3 * s + d]; c.vel0[3 * g + d] = vel ? vel[3 * s + d] : 0.0; }
+  }
+  t.n = n1;
+  if (!t.contiguous) { t.id2tag.clear(); for (int64_t k = 0; k < n1; ++k) t.id2tag[t.id[k]] = (int32_t)k; }
+  if (c.res.on()) { c.res.lambda0.resize(n1, 1.0); c.res.s0.resize(n1, 0); c.res.seen.resize(n1); for (int64_t g = n0; g < n1; ++g) c.res.seen[g] = t.type[g]; }
+  c.particles_dirty = c.pair_dirty = c.bonded_dirty = c.excl_dirty = c.labels_dirty = true; c.resort = true;
+  c.coul_dirty = true; c.res_dirty = true; c.fix_dirty = true; c.geom_dirty = true;
+  if (!c.restrict_map.empty()) c.restrict_dirty = true;      // (per-tag CSR)
+  return 0;
+  API_END(ctx)
+}
+
+int chem_fix_create(chem_ctx* ctx, int anchor_type, int target_type) {
+  API_BEGIN
+  REQUIRE(anchor_type >= -1 && anchor_type < CHEM_MAX_TYPES && target_type >= -1 && target_type < CHEM_MAX_TYPES, CHEM_EINVAL, "fix_create: type");
+  const int h = CTX.fix.create(anchor_type, target_type);
+  REQUIRE(h >= 0, CHEM_ENOSPC, "fix_create: a context holds at most " + std::to_string(CHEM_MAX_FIX_SETS) + " sets (CHEM_MAX_FIX_SETS)");
+  return h;
+  API_END(ctx)
+}
+
+int chem_fix_add(chem_ctx* ctx, int set, int64_t n, const int64_t* ids, double dist) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "fixed distances are not available on the decomposed path (anchor and target may sit on different ranks)");
+  REQUIRE(c.top.n > 0, CHEM_ESTATE, "fix_add: set particles first");
+  REQUIRE(n >= 0 && (ids || n == 0), CHEM_EINVAL, "fix_add: null input");
+  std::vector<int32_t> tags((size_t)(2 * n));
+  for (int64_t k = 0; k < 2 * n; ++k) tags[k] = (int32_t)c.top.tag_of(ids[k]);
+  std::string why;
+  const int rc = c.fix.add(set, n, tags.data(), dist, c.top.n, why);
+  if (rc < 0) throw ChemError(rc, "fix_add: " + why);
+  if (n) c.fix_dirty = true;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_fix_postprocess(chem_ctx* ctx, int set, int old_type, int new_type, double new_mass, double new_q, int new_state, double lambda) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(set >= 0 && set < (int)c.fix.sets.size(), CHEM_EINVAL, "fix_postprocess: unknown set");
+  REQUIRE(old_type >= 0 && old_type < CHEM_MAX_TYPES && new_type < CHEM_MAX_TYPES, CHEM_EINVAL, "fix_postprocess: type");
+  REQUIRE(new_type < 0 || (new_mass > 0 && std::isfinite(new_mass) && std::isfinite(new_q)), CHEM_EINVAL, "fix_postprocess: the new mass must be positive");
+  REQUIRE(!(lambda > 1.0) && !std::isnan(lambda), CHEM_EINVAL, "fix_postprocess: lambda must lie in [0, 1] (negative: left alone)");
+  c.fix.set_post(set, FixPost{old_type, new_type < 0 ? -1 : new_type, new_mass, new_q, new_state < 0 ? -1 : new_state, lambda < 0.0 ? -1.0 : lambda});
+  c.pair_dirty = true;      // (the type count of the pair tables covers new_type)
+  return 0;
+  API_END(ctx)
+}
+
+int chem_reaction_release(chem_ctx* ctx, int reaction, int role, int set, int count) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "fixed distances are not available on the decomposed path");
+  REQUIRE(c.assoc_row(reaction) >= 0, CHEM_EINVAL, "reaction_release: not an index of chem_reaction_add");
+  REQUIRE(role == 1 || role == 2, CHEM_EINVAL, "reaction_release: role must be 1 or 2");
+  REQUIRE(set >= 0 && set < (int)c.fix.sets.size(), CHEM_EINVAL, "reaction_release: unknown set");
+  REQUIRE(count >= 1, CHEM_EINVAL, "reaction_release: count");
+  c.fix.rules.push_back(FixRule{reaction, role, set, count});
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_fix_count(chem_ctx* ctx, int set) {
+  API_BEGIN
+  REQUIRE(set >= 0 && set < (int)CTX.fix.sets.size(), CHEM_EINVAL, "fix_count: unknown set");
+  return (int64_t)CTX.fix.sets[set].ent.size();
+  API_END(ctx)
+}
+
+int64_t chem_fix_get(chem_ctx* ctx, int set, int64_t* ids, double* dist, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(set >= 0 && set < (int)c.fix.sets.size(), CHEM_EINVAL, "fix_get: unknown set");
+  const std::vector<FixEntry>& e = c.fix.sets[set].ent;
+  const int64_t m = (int64_t)e.size();
+  if (!ids && !dist) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "fix_get: capacity");
+  for (int64_t k = 0; k < m; ++k) {
+    if (ids) { ids[2 * k] = c.top.id[e[k].anchor]; ids[2 * k + 1] = c.top.id[e[k].target]; }
+    if (dist) dist[k] = e[k].dist;
+  }
+  return m;
+  API_END(ctx)
+}
+
+int64_t chem_fix_log(chem_ctx* ctx, chem_fix_record* out, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  const int64_t m = (int64_t)c.fix.log.size();
+  if (!out) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "fix_log: capacity");
+  for (int64_t k = 0; k < m; ++k) { const FixRecord& r = c.fix.log[k]; out[k] = chem_fix_record{r.step, c.top.id[r.anchor], c.top.id[r.target], r.set, r.cause}; }
+  return m;
   API_END(ctx)
 }
 
@@ -3134,13 +3367,19 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
                                  ") exceeds the list cutoff max_cutoff = " + std::to_string(CTX.rc));
   }
   Ctx& c = CTX;
-  if (!c.res_tracking()) { c.run(nsteps); return 0; }
+  c.ran = true;
+  // fixed distances: a type that chem_modify_particle changed since the last call releases entries of a typed set here
+  const bool fix_live = c.fix.any();
+  if (fix_live) { c.join_async(); c.fix_after_reactions(false); }
+  if (!c.res_tracking() && !c.fix_tracking()) { c.run(nsteps); return 0; }
   // Resolution ramps with a property change: the call runs in pieces that end where a lambda reaches 1 (the host knows every
   // stamp, so it knows every such step: chem_res_host.hpp); the change is applied there, and the forces are evaluated again
   // where the call ends on such a step, so that the forces current at s_full are those of the new properties.  A reaction or
   // ATRP step may stamp particles (type changes, chem_reaction_set_resolution) and so create completion steps nobody could
   // know before: while stamps are tracked a piece also ends at every such step, and the next completion is asked afresh.
-  c.res_apply_completions();
+  // (a completion changes a type: the release by type of the fixed-distance sets follows it)
+  auto completions = [&]() -> int { int k = c.res_apply_completions(); if (k && c.fix.any()) k += c.fix_after_reactions(false); return k; };
+  completions();
   if (nsteps == 0) c.run(0);
   for (int64_t left = nsteps; left > 0;) {
     int64_t stop = c.res.next_completion(c.step);
@@ -3149,7 +3388,7 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
     if (c.atrp_on && c.atrp.interval > 0) sooner(c.atrp.interval);
     const int64_t len = res_next_piece(c.step, left, stop);
     c.run(len); left -= len;
-    if (c.res_apply_completions() && left == 0) c.run(0);
+    if (completions() && left == 0) c.run(0);
   }
   return 0;
   API_END(ctx)
@@ -3296,6 +3535,7 @@ int chem_comm_init(chem_ctx* ctx, int nranks, int rank, const int node_grid[3], 
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init: rank/nranks");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on, CHEM_ESTATE, "comm_init: already initialised");
   if (nranks == 1 && !uid) return 0;   // single domain, nothing to do
   REQUIRE(node_grid && node_grid[0] == 1 && node_grid[1] == 1 && node_grid[2] == nranks, CHEM_ENOTIMPL,
@@ -3363,6 +3603,7 @@ int chem_comm_init_ipc(chem_ctx* ctx, int nranks, int rank, const char* shm_name
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks && shm_name, CHEM_EINVAL, "comm_init_ipc: rank/nranks/name");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_ipc must precede the first run");
   HIPCHK(hipSetDevice(c.device));
   c.tr.reset(new IpcTransport(nranks, rank, shm_name));
@@ -3377,6 +3618,7 @@ int chem_comm_init_local(chem_ctx* ctx, int nranks, int rank, int hub_id) {
   REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, CHEM_EINVAL, "comm_init_local: rank/nranks");
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_local must precede the first run");
   c.tr.reset(new LocalTransport(nranks, rank, hub_id));
   c.dd_on = true; c.P = nranks; c.rk = rank; c.geom_dirty = true;

@@ -354,6 +354,47 @@ __global__ __launch_bounds__(256) void k_integrate(int n, Vec4<R>* __restrict__ 
   }
 }
 
+// ---- fixed distances (chem_fix_add; rule set in include/chem_mi355.h) -----------------------------------------------
+// Behind every launch of k_integrate that drifts, while a live entry exists.  One lane per entry; anchor and target are found
+// through rtag, so the array survives every resort.  Two 16-byte loads per particle (x4, v4), one 16-byte store each of the
+// target's x4 and v4 (w = type / mass kept).  Entries of one anchor are consecutive (FixState::device_order): the anchor
+// loads of neighbouring lanes hit one line.  The move is a displacement through pos_add, like the drift.
+template <typename R> struct FixEnt;
+template <> struct FixEnt<float> { int a, t; float d; int pad; };
+template <> struct FixEnt<double> { int a, t; double d; };
+template <typename R> struct FixGeom { R L[3], invL[3]; };      // (fp64 build only; the fp32 build wraps in fixed point)
+__device__ __forceinline__ float fix_delta(float a, float b, float qs, float, float) {
+  int dq = (int)((unsigned)qbits(a) - (unsigned)qbits(b));
+  if (dq >= kQHalf || dq < -kQHalf) dq = (int)((unsigned)dq + 0x80000000u);
+  return (float)dq * qs;
+}
+__device__ __forceinline__ double fix_delta(double a, double b, double, double L, double invL) { const double x = a - b; return x - L * rint(x * invL); }
+template <typename R>
+__global__ __launch_bounds__(256) void k_fix_distances(int ne, const FixEnt<R>* __restrict__ ent, const int* __restrict__ rtag, int ntag,
+                                                        Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4, FixGeom<R> g, PosScale<R> ps,
+                                                        const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;   // (the drift in front of this launch left at once, too)
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ne) return;
+  const FixEnt<R> e = ent[k];
+  if ((unsigned)e.a >= (unsigned)ntag || (unsigned)e.t >= (unsigned)ntag) return;
+  const int ia = rtag[e.a], it = rtag[e.t];
+  if (ia < 0 || it < 0) return;
+  const Vec4<R> xa = x4[ia], va = v4[ia];
+  Vec4<R> xt = x4[it], vt = v4[it];
+  const R rx = fix_delta(xt.x, xa.x, ps.s[0], g.L[0], g.invL[0]), ry = fix_delta(xt.y, xa.y, ps.s[1], g.L[1], g.invL[1]),
+          rz = fix_delta(xt.z, xa.z, ps.s[2], g.L[2], g.invL[2]);
+  const R r2 = rx * rx + ry * ry + rz * rz;
+  R dx = e.d, dy = (R)0, dz = (R)0;      // |u| = 0: u = (1, 0, 0)
+  if (r2 > (R)0) {
+    const R s = e.d / sqrt_r(r2);
+    dx = s * rx - rx; dy = s * ry - ry; dz = s * rz - rz;
+  }
+  xt.x = pos_add(xt.x, dx, ps.inv[0]); xt.y = pos_add(xt.y, dy, ps.inv[1]); xt.z = pos_add(xt.z, dz, ps.inv[2]);
+  vt.x = va.x; vt.y = va.y; vt.z = va.z;
+  x4[it] = xt; v4[it] = vt;
+}
+
 // one block: fold the step's per-block max displacement into the accumulated distance and
 // decide whether the Verlet list must be rebuilt (VelocityVerlet::run).
 // phase 3: both (single GPU); phase 1: fold only -> ctl->step_m2 (then max over ranks);

@@ -160,6 +160,69 @@ class Engine:
         ro = {"type_1": 1, "type_2": 2}.get(role, role)
         self._ck(self._res_entry("reaction_set_resolution")(self.ctx, int(reaction), int(ro), float(lam)))
 
+    # ---- fixed distances / by-product release (include/chem_mi355.h, chem_fix_create ff.) ----
+    def _fix_entry(self, name):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("FixDistances: the CPU checker has no fixed distances")
+        return fn
+
+    def add_particles(self, ids, types, pos, mass, vel=None, q=None, state=None, res_id=None):
+        """Append particles (ids above the largest present one) at step 0, before the first run; lists, exclusions,
+        stamps and reactions are kept."""
+        fn = self._fix_entry("add_particles")
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n = ids.shape[0]
+        types = np.ascontiguousarray(types, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(n, 3)
+        mass = np.ascontiguousarray(np.broadcast_to(np.asarray(mass, dtype=np.float64), (n,)))
+        vel = None if vel is None else np.ascontiguousarray(vel, dtype=np.float64).reshape(n, 3)
+        q = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
+        state = None if state is None else np.ascontiguousarray(state, dtype=np.int32)
+        res_id = None if res_id is None else np.ascontiguousarray(res_id, dtype=np.int32)
+        self._ck(fn(self.ctx, n, _ptr(ids, C.c_int64), _ptr(types, C.c_int32), _ptr(pos, C.c_double), _ptr(vel, C.c_double),
+                    _ptr(mass, C.c_double), _ptr(q, C.c_double), _ptr(state, C.c_int32), _ptr(res_id, C.c_int32)))
+
+    def fix_create(self, anchor_type=-1, target_type=-1):
+        """A new set of fixed distances; with types, an entry leaves when its anchor or target no longer has that type."""
+        return self._ck(self._fix_entry("fix_create")(self.ctx, int(anchor_type), int(target_type)))
+
+    def fix_add(self, h, pairs, dist):
+        """Entries (anchor id, target id) at distance `dist`."""
+        p = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        self._ck(self._fix_entry("fix_add")(self.ctx, int(h), p.shape[0], _ptr(p, C.c_int64), float(dist)))
+
+    def fix_postprocess(self, h, old_type, new_type=-1, new_mass=0.0, new_q=0.0, new_state=-1, lam=-1.0):
+        """What becomes of a released target of type old_type; lam in [0, 1] stamps its resolution, negative leaves it."""
+        self._ck(self._fix_entry("fix_postprocess")(self.ctx, int(h), int(old_type), int(new_type), float(new_mass), float(new_q), int(new_state), float(lam)))
+
+    def reaction_release(self, reaction, role, h, count=1):
+        """PostProcessReleaseParticles(fd, count) on role 'type_1' | 'type_2' | 'both' of `reaction`."""
+        for ro in {"type_1": (1,), "type_2": (2,), "both": (1, 2), 1: (1,), 2: (2,)}[role]:
+            self._ck(self._fix_entry("reaction_release")(self.ctx, int(reaction), ro, int(h), int(count)))
+
+    def fix_count(self, h):
+        return self._ck(self._fix_entry("fix_count")(self.ctx, int(h)))
+
+    def fix_get(self, h):
+        """(pairs (n, 2) int64, dist (n,)) of the live entries in insertion order."""
+        fn = self._fix_entry("fix_get")
+        n = self._ck(fn(self.ctx, int(h), None, None, 0))
+        ids, d = np.empty((n, 2), dtype=np.int64), np.empty(n, dtype=np.float64)
+        if n:
+            self._ck(fn(self.ctx, int(h), _ptr(ids, C.c_int64), _ptr(d, C.c_double), n))
+        return ids, d
+
+    def fix_log(self):
+        """Release records (step, set, anchor_id, target_id, cause) ordered by (step, set, insertion index)."""
+        fn = self._fix_entry("fix_log")
+        n = self._ck(fn(self.ctx, None, 0))
+        buf = (_capi.FixRecord * max(n, 1))()
+        if n:
+            self._ck(fn(self.ctx, buf, n))
+        dt = np.dtype([("step", "i8"), ("anchor_id", "i8"), ("target_id", "i8"), ("set", "i4"), ("cause", "i4")])
+        return np.frombuffer(buf, dtype=dt, count=n).copy()
+
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
         if kind == _capi.POT["COULOMB_BOND"] and getattr(self.api, "nb_coulomb", None) is None:

@@ -129,8 +129,29 @@ class _DomainDecomposition(object):
         system.engine.set_box(list(system.bc.boxL))
 
     def addParticles(self, plist, *props):
+        if self._uploaded:          # the particle set is on the engine: the new ones are appended (chem_add_particles)
+            self._append(list(plist), list(props))
+            return
         self._props = list(props)
         self._pending.extend(plist)
+
+    def _append(self, plist, pr):
+        """addParticles after the upload (the dummies of ReleaseMolecule, reaction_post_process.py:262): ids above every
+        present one; lists, exclusions, lambda stamps and reactions of the engine are kept."""
+        if not plist:
+            return
+        col = lambda name, default=None: [p[pr.index(name)] for p in plist] if name in pr else default
+        n = len(plist)
+        ids = np.array(col("id"), dtype=np.int64)
+        vel = np.array([list(p) for p in col("v")], dtype=np.float64) if "v" in pr else None
+        self.system.engine.add_particles(ids, np.array(col("type", [0] * n), dtype=np.int32), np.array([list(p) for p in col("pos")], dtype=np.float64),
+                                         np.array(col("mass", [1.0] * n), dtype=np.float64), vel=vel, q=np.array(col("q", [0.0] * n), dtype=np.float64),
+                                         state=np.array(col("state", [0] * n), dtype=np.int32), res_id=np.array(col("res_id", list(ids)), dtype=np.int32))
+        if "lambda_adr" in pr:
+            lam = np.array(col("lambda_adr"), dtype=np.float64)
+            if np.any(lam != 1.0):
+                self.system.engine.set_resolution(ids, lam)
+        self._ids = np.concatenate([self._ids, ids])
 
     def addParticle(self, pid, pos):
         self._props = ["id", "pos"]
@@ -967,6 +988,7 @@ class _Reaction(object):
         self.active = True
         self._pp = {}
         self._nb_pp = []
+        self._release = []
         self._constraints = []
         self._index = None
         self._system = None
@@ -989,6 +1011,9 @@ class _Reaction(object):
     def add_postprocess(self, pp, which="type_1"):
         if isinstance(pp, _PostProcessChangeNeighboursProperty):
             self._nb_pp.append((pp, which))
+            return
+        if isinstance(pp, _PostProcessReleaseParticles):
+            self._release.append((pp, which))
             return
         if not isinstance(pp, _PostProcessChangeProperty):
             raise NotImplementedError("post-process %s is outside the hot-path scope" % type(pp).__name__)
@@ -1094,6 +1119,10 @@ class _ChemicalReaction(object):
                 if r.revert:
                     raise NotImplementedError("RestrictReaction.revert (dissociation along a connectivity map) is outside the hot-path scope")
                 e.reaction_restrict(r._index, r._connections)
+            for rel, which in r._release:         # PostProcessReleaseParticles(fd, count): the FixDistances extension is connected first
+                if rel.fd.handle is None:
+                    raise RuntimeError("PostProcessReleaseParticles: add its FixDistances to the integrator before the reactions")
+                e.reaction_release(r._index, which, rel.fd.handle, rel.count)
             for cons, which in r._constraints:
                 e.reaction_constraint(r._index, which, cons.type_id, cons.min_state, cons.max_state)
             for pp, which in r._nb_pp:
@@ -1275,7 +1304,80 @@ class _BasicDynamicResolution(object):
             self.system.engine.resolution_rate(t, 0.0)
 
 
+class _FixDistances(object):
+    """integrator.FixDistances(system, fix_list[, anchor_type, target_type]) + add_triplet, add_postprocess(
+    PostProcessChangeProperty), get_all_triplets (reaction_post_process.py:269-289): every (anchor, target, distance) keeps
+    the target at that distance from its anchor on every MD step, on the device (chem_fix_create / chem_fix_add); with types,
+    an entry leaves when its anchor or target no longer has that type.  The post-process says what a released target becomes."""
+
+    def __init__(self, system, fix_list=None, anchor_type=None, target_type=None):
+        self.system = system
+        self._list = [(int(a), int(t), float(d)) for a, t, d in (fix_list or [])]
+        self.anchor_type = -1 if anchor_type is None else int(anchor_type)
+        self.target_type = -1 if target_type is None else int(target_type)
+        self._pp = []
+        self.handle = None
+
+    def add_triplet(self, anchor, target, dist):
+        if self.handle is None:
+            self._list.append((int(anchor), int(target), float(dist)))
+        else:
+            self.system.engine.fix_add(self.handle, [(int(anchor), int(target))], float(dist))
+
+    def add_postprocess(self, pp):
+        if not isinstance(pp, _PostProcessChangeProperty):
+            raise NotImplementedError("post-process %s of FixDistances is outside the hot-path scope" % type(pp).__name__)
+        self._pp.append(pp)
+        if self.handle is not None:
+            self._send_postprocess(pp)
+
+    def _send_postprocess(self, pp):
+        for old, ch in sorted(pp.changes.items()):
+            self.system.engine.fix_postprocess(self.handle, old, new_type=-1 if ch.type is None else int(ch.type),
+                                               new_mass=float(ch.mass) if ch.mass is not None else 0.0, new_q=float(ch.q or 0.0),
+                                               new_state=-1 if ch.state is None else int(ch.state),
+                                               lam=-1.0 if getattr(ch, "lambda_adr", None) is None else float(ch.lambda_adr))
+
+    def _connect(self, integrator):
+        if self.handle is not None:
+            return
+        if self.system.storage is not None:
+            self.system.storage.decompose()
+        e = self.system.engine
+        self.handle = e.fix_create(self.anchor_type, self.target_type)
+        k = 0
+        while k < len(self._list):          # one call per run of equal distances, insertion order kept
+            m = k
+            while m < len(self._list) and self._list[m][2] == self._list[k][2]:
+                m += 1
+            e.fix_add(self.handle, [(a, t) for a, t, _ in self._list[k:m]], self._list[k][2])
+            k = m
+        for pp in self._pp:
+            self._send_postprocess(pp)
+
+    def get_all_triplets(self):
+        if self.handle is None:
+            return list(self._list)
+        ids, dist = self.system.engine.fix_get(self.handle)
+        return [(int(a), int(t), float(d)) for (a, t), d in zip(ids.tolist(), dist.tolist())]
+
+    def totalSize(self):
+        return len(self._list) if self.handle is None else int(self.system.engine.fix_count(self.handle))
+
+
+class _PostProcessReleaseParticles(object):
+    """integrator.PostProcessReleaseParticles(fd, count) (reaction_post_process.py:278): attached to a Reaction with
+    add_postprocess(pp, 'type_1' | 'type_2' | 'both'), every bond-forming event releases up to `count` entries of `fd` whose
+    anchor is that reactant (chem_reaction_release)."""
+
+    def __init__(self, fd, count=1):
+        if not isinstance(fd, _FixDistances):
+            raise TypeError("PostProcessReleaseParticles(FixDistances, count)")
+        self.fd, self.count = fd, int(count)
+
+
 integrator = _ns(
+    FixDistances=_FixDistances, PostProcessReleaseParticles=_PostProcessReleaseParticles,
     VelocityVerlet=_VelocityVerlet, FixedListDynamicResolution=_FixedListDynamicResolution, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
     Reaction=_Reaction, PostProcessChangeProperty=_PostProcessChangeProperty,
     PostProcessChangePropertyByTopologyManager=_PostProcessChangeProperty, ReactionConstraintNeighbourState=_ReactionConstraintNeighbourState,
@@ -1285,7 +1387,7 @@ integrator = _ns(
     Isokinetic=_Isokinetic, LangevinBarostat=_unsupported("integrator.LangevinBarostat"),
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
     DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
-    ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"), FixDistances=_unsupported("integrator.FixDistances"),
+    ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"),
     ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_BasicDynamicResolution,
     PostProcessChangeNeighboursProperty=_PostProcessChangeNeighboursProperty,
     PostProcessRemoveNeighbourBond=_unsupported("integrator.PostProcessRemoveNeighbourBond"),
@@ -1303,8 +1405,37 @@ class _Observable(object):
 
 
 class _Temperature(_Observable):
+    """analysis.Temperature(system) + add_type(type_id) (start_simulation.py:453-456): with types, the temperature of the
+    particles of those types alone, 3 degrees of freedom each; without, the engine's own."""
+
+    def __init__(self, system, *a):
+        _Observable.__init__(self, system, *a)
+        self._types = []
+
+    def add_type(self, type_id):
+        if type_id is not None and int(type_id) not in self._types:
+            self._types.append(int(type_id))
+
     def compute(self):
-        return self.system.engine.observe()["temperature"]
+        e = self.system.engine
+        if not self._types:
+            return e.observe()["temperature"]
+        sel = np.isin(e.get_state("TYPE"), self._types)
+        if not sel.any():
+            return 0.0
+        v, m = e.get_state("VEL")[sel], e.get_state("MASS")[sel]
+        return float((m[:, None] * v * v).sum() / (3.0 * sel.sum()))
+
+
+class _NumFixDistances(_Observable):
+    """analysis.NumFixDistances(system, fd) (start_simulation.py:561-563): the number of live entries."""
+
+    def __init__(self, system, fd):
+        _Observable.__init__(self, system)
+        self.fd = fd
+
+    def compute(self):
+        return self.fd.totalSize()
 
 
 class _KineticEnergy(_Observable):
@@ -1450,7 +1581,7 @@ class _SystemMonitor(object):
 
 analysis = _ns(
     Temperature=_Temperature, KineticEnergy=_KineticEnergy, PotentialEnergy=_PotentialEnergy, NPart=_NPart, MaxPID=_MaxPID,
-    NFixedPairListEntries=_NFixedPairListEntries, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
+    NFixedPairListEntries=_NFixedPairListEntries, NumFixDistances=_NumFixDistances, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
     Pressure=_unsupported("analysis.Pressure"), PressureTensor=_unsupported("analysis.PressureTensor"),

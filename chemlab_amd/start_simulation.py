@@ -215,6 +215,7 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     hooks = dict(file_hooks, **(hooks or {}))
     ar, chem_fpls, cr_interval, dynamic_types, integrator_extensions = None, [], None, set(), []
     reaction_index = {}
+    sc = None
     if args.reactions is not None and os.path.exists(args.reactions):
         rc = reaction_parser.parse_config(args.reactions)
         sc = reaction_setup.SetupReactions(espressopp, system, verletlist, gt, topology_manager, rc, args)
@@ -244,11 +245,19 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     if args.max_force > -1:                               # start_simulation.py:320-324, before the thermostat
         integrator.addExtension(espressopp.integrator.CapForce(system, args.max_force))
         log("Cap force to %s" % args.max_force)
+    # thermal groups (start_simulation.py:312-318): --thermal_groups, else --table_groups; used only where the reaction set-up
+    # asks for them (an extension that added dummy particles)
+    group_names = args.thermal_groups or args.table_groups
+    thermal_groups = [gt.atomsym_atomtype.get(x) for x in group_names.split(",")] if group_names else []
+    use_thermal_group = sc is not None and sc.use_thermal_group
     # thermostat (start_simulation.py:329-354)
     temperature = args.temperature * kb
     if args.thermostat == "lv":
         th = espressopp.integrator.LangevinThermostat(system)
         th.temperature, th.gamma = temperature, args.thermostat_gamma
+        if use_thermal_group:                             # start_simulation.py:334-336
+            log("Running thermostat on thermal groups: %s" % thermal_groups)
+            th.add_valid_types(thermal_groups)
         integrator.addExtension(th)
     elif args.thermostat == "vr":                         # start_simulation.py:337-340
         th = espressopp.integrator.StochasticVelocityRescaling(system)
@@ -291,7 +300,11 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     # observables (start_simulation.py:447-569)
     energy_file = "%s_energy_%s.csv" % (args.output_prefix, rng_seed)
     mon = espressopp.analysis.SystemMonitor(system, integrator, espressopp.analysis.SystemMonitorOutputCSV(energy_file))
-    mon.add_observable("T", espressopp.analysis.Temperature(system))
+    temp_comp = espressopp.analysis.Temperature(system)
+    if use_thermal_group:                                 # start_simulation.py:454-456
+        for t_id in thermal_groups:
+            temp_comp.add_type(t_id)
+    mon.add_observable("T", temp_comp)
     mon.add_observable("Ekin", espressopp.analysis.KineticEnergy(system))
     for k in range(system.getNumberOfInteractions()):
         mon.add_observable(system.getNameOfInteraction(k), espressopp.analysis.PotentialEnergy(system, system.getInteraction(k)), False)
@@ -300,6 +313,9 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     if args.t_hybrid_bond > 0:                            # start_simulation.py:495-498
         for i, (gname, fpl, _) in enumerate(chem_fpls):
             mon.add_observable("res_fpl_%d" % i, espressopp.analysis.ResolutionFixedPairList(system, fpl))
+    if args.count_fix_distances and sc is not None:       # start_simulation.py:561-563
+        for fd_idx, fd in enumerate(sc.fix_distances):
+            mon.add_observable("fd_%d" % fd_idx, espressopp.analysis.NumFixDistances(system, fd))
     for (cr_type, cr_total, _), obs in sorted(cr_observs.items(), key=lambda kv: kv[0][:2]):
         # computed with every energy row: that is also what moves the mixed (func 10) tables along with the conversion
         mon.add_observable("cr_%s_%s" % (cr_type, cr_total), obs)
@@ -393,6 +409,13 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     for ext in integrator_extensions:
         if hasattr(ext, "save_stats"):
             ext.save_stats()                                  # ATRPActivator.stats_filename (reaction_post_process.py:390-396)
+    if sc is not None and sc.fix_distances:                   # start_simulation.py:1019-1025: the triplets that are still held
+        import pickle
+        all_fix_distances = []
+        for fd in sc.fix_distances:
+            all_fix_distances.extend(fd.get_all_triplets())
+        with rank.wopen("%s_%s_all_fix_distances.pck" % (args.output_prefix, rng_seed), "wb") as f:
+            pickle.dump(all_fix_distances, f)
     npart = espressopp.analysis.NPart(system).compute()
     with rank.wopen("%s_%s_benchmark.csv" % (args.output_prefix, rng_seed), "a+") as f:
         f.write("%d %d %s %s\n" % (1, npart, total_time, integrator_loop))

@@ -316,6 +316,81 @@ int chem_set_resolution(chem_ctx* ctx, int64_t n, const int64_t* ids, const doub
  * chem_set_particles keeps reactions and rules alike. */
 int chem_reaction_set_resolution(chem_ctx* ctx, int reaction, int role, double lambda);
 
+/* ---- fixed distances: by-product release (FixDistances, ReleaseMolecule) --------------- */
+/* integrator.FixDistances(system, fix_list[, anchor_type, target_type]) + add_postprocess(PostProcessChangeProperty),
+ * integrator.PostProcessReleaseParticles(fd, count) on a Reaction, analysis.NumFixDistances, and storage.addParticles after
+ * the first upload -- reaction_post_process.py:203-320 (ext_type=ReleaseMolecule): dummy particles ride at a fixed distance
+ * from a host particle until a reaction of the host, or a type change, sets them free as a small molecule that fades in
+ * through the resolution lambda.  The arithmetic of FixDistances is in the external fork, so this rule set is this build's own
+ * ([EXT-RECALL], parity unpinned; DESIGN.md "Fixed distances").
+ *
+ * A set holds entries (anchor a, target t, distance d) in insertion order.
+ * Per step: behind every drift (the first half kick + drift of velocity Verlet), exactly once per drift and before anything
+ * reads the new positions (rebuild decision, forces), for every live entry:
+ *     u = minimum image of x_t - x_a, both after the drift (the target drifts like any particle, with the velocity it carries);
+ *     u = (1, 0, 0) if |u| = 0, else u / |u|;
+ *     x_t <- x_a + d u, applied as the displacement (d u - (x_t - x_a)) through the drift's own position update (fixed-point
+ *            add in the CHEM_PREC_F32 build), so folding, image counters and CHEM_STATE_POS_UNFOLDED go on as for any particle;
+ *     v_t <- v_a, the anchor's half-step velocity at that moment.
+ * Nothing else is special about a target: it takes the second half kick with its own force and mass, counts in ekin,
+ * temperature and momentum, and is thermalised or not according to chem_thermostat_langevin_types.  The constraint's move
+ * does not enter the displacement maximum of the rebuild criterion.  After a run that the device stopped and the host resumed
+ * the positions of that step are drifted and constrained already: the rule is not applied again there.
+ * Release: the entry is removed; the post-process of its set whose old_type is the target's current type (if any) is applied
+ * by the route of chem_modify_particle (type, mass, charge, state, and the stamp (lambda, release step) as
+ * chem_reaction_set_resolution sets one); the lists are rebuilt before the next force evaluation.  From the next drift on the
+ * target is an ordinary particle; it keeps the velocity it had.
+ *   by a reaction  (chem_reaction_release) in the reaction step, after the step's bonds and type changes: for every
+ *       bond-forming event of a reaction with a release rule, events in the order chem_get_events reports them, role 1 before
+ *       role 2, rules in the order they were added: up to `count` live entries of the rule's set whose anchor is that reactant,
+ *       lowest insertion index first; fewer if fewer remain.  Cause 1.
+ *   by type  (sets created with types; -1 asks nothing of that side): an entry leaves when type(anchor) != anchor_type or
+ *       type(target) != target_type.  Types change only at host-visible points, so the check runs behind the release by
+ *       reaction, behind the ATRP step, behind the resolution completions and at the start of chem_run (chem_modify_particle):
+ *       indistinguishable from a check on every step.  The record carries the current step.  Cause 2.
+ * While a release rule or a typed set with entries exists, chem_run ends its pieces at every reaction and ATRP step, and a
+ * reaction step waits for its own host bookkeeping (as for chem_reaction_set_resolution).
+ * Not on the decomposed path (anchor and target may sit on different ranks): chem_fix_add after chem_comm_init*, and
+ * chem_comm_init* with entries present, are CHEM_ENOTIMPL. */
+#define CHEM_MAX_FIX_SETS 8
+typedef struct chem_fix_record {
+  int64_t step;
+  int64_t anchor_id, target_id;
+  int32_t set;
+  int32_t cause;            /* 1 = reaction, 2 = type condition */
+} chem_fix_record;
+/* storage.addParticles after the particle set exists: appends n particles.  Every new id must be greater than the largest
+ * present id (CHEM_EINVAL otherwise; ids within the call in any order, no duplicates): id order stays tag order and existing
+ * tags do not move.  Allowed only while chem_get_step() == 0 and before the first chem_run (CHEM_ESTATE later, and before
+ * chem_set_particles).  Exclusions, bonded lists, the bond graph, lambda stamps (new particles: lambda 1), reactions and rates
+ * are kept -- chem_set_particles would clear them.  A type at or above CHEM_MAX_TYPES is CHEM_EINVAL naming the limit.  Pointer
+ * conventions of chem_set_particles.  Not after chem_comm_init* (CHEM_ENOTIMPL). */
+int chem_add_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_t* type, const double* pos, const double* vel,
+                       const double* mass, const double* q, const int32_t* state, const int32_t* res_id);
+/* FixDistances(system, fix_list, anchor_type, target_type): a new, empty set; (-1, -1): no type condition.  Returns the handle;
+ * more than CHEM_MAX_FIX_SETS sets: CHEM_ENOSPC. */
+int chem_fix_create(chem_ctx* ctx, int anchor_type, int target_type);
+/* fd.add_triplet(anchor, target, dist): ids = n (anchor, target) pairs.  CHEM_EINVAL (nothing is added then): dist not positive
+ * and finite, an unknown id, anchor == target, a target that already is the target of a live entry of any set, a target that
+ * is an anchor, an anchor that is a target.  An anchor may carry any number of entries.  Allowed between chem_run calls. */
+int chem_fix_add(chem_ctx* ctx, int set, int64_t n, const int64_t* ids, double dist);
+/* fd.add_postprocess(PostProcessChangeProperty): what becomes of a released target whose type is old_type at the release.
+ * new_type < 0: no property change; new_state < 0: the chemical state is kept (conventions of chem_resolution_rate);
+ * lambda in [0, 1]: stamp (lambda, release step); lambda < 0: the resolution is left alone; lambda > 1: CHEM_EINVAL.  A second
+ * call for one old_type replaces the first. */
+int chem_fix_postprocess(chem_ctx* ctx, int set, int old_type, int new_type, double new_mass, double new_q, int new_state, double lambda);
+/* reaction.add_postprocess(PostProcessReleaseParticles(fd, count), 'type_1' | 'type_2'): role 1 | 2 ('both': two calls) of the
+ * association reaction `reaction` (index of chem_reaction_add) releases `count` >= 1 entries of `set` per event. */
+int chem_reaction_release(chem_ctx* ctx, int reaction, int role, int set, int count);
+/* analysis.NumFixDistances: the number of live entries */
+int64_t chem_fix_count(chem_ctx* ctx, int set);
+/* fd.get_all_triplets(): the live entries in insertion order, ids[2k] = anchor, ids[2k+1] = target, dist[k]; either pointer
+ * may be NULL.  Returns the count (ids == dist == NULL: the count alone). */
+int64_t chem_fix_get(chem_ctx* ctx, int set, int64_t* ids, double* dist, int64_t cap);
+/* the release records since the context was created, ordered by (step, set, insertion index); out == NULL: the count.
+ * (chem_set_particles empties every set and the log -- tags are new --; sets, post-processes and release rules stay.) */
+int64_t chem_fix_log(chem_ctx* ctx, chem_fix_record* out, int64_t cap);
+
 /* ---- bonded lists -------------------------------------------------------------------- */
 /* FixedPairList/TripleList/QuadrupleList(storage) + FixedXListYyy(system, list, potential)
  * gromacs_topology.py:949-961,1086-1096,1206-1224; reaction_setup.py:444-467.
