@@ -180,6 +180,7 @@ PRODUCT_ONLY = {
     "resolution_rate": (_i, [_P, _i, _d, _i, _d, _d, _i]),
     "set_resolution": (_i, [_P, _i64, _pi64, _pd]),
     "reaction_set_resolution": (_i, [_P, _i, _i, _d]),
+    "nb_cap": (_i, [_P, _i, _i, _d]),   # capped pair potentials (the CPU oracle has no cap radius)
     # fixed distances / by-product release (the CPU oracle has none)
     "add_particles": (_i, [_P, _i64, _pi64, _pi32, _pd, _pd, _pd, _pd, _pi32, _pi32]),
     "fix_create": (_i, [_P, _i, _i]),

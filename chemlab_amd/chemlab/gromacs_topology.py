@@ -146,7 +146,8 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
     tab = espressopp.interaction.VerletListTabulated(vl)
     mix = espressopp.interaction.VerletListMixedTabulated(vl)
     cr_observs = {} if cr_observs is None else cr_observs
-    has_lj = has_tab = has_mix = False
+    tab_cap = espressopp.interaction.VerletListTabulatedCapped(vl)      # func 13 (:513, 684-695)
+    has_lj = has_tab = has_mix = has_tab_cap = False
     # func 11 / 15: dynamic-resolution pairs, grouped by max_force into one VerletListDynamicResolution* each (:584-611,819-862)
     dyn_tab, dyn_lj = collections.OrderedDict(), collections.OrderedDict()
 
@@ -161,7 +162,7 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
         for n2 in names[i:]:
             t1, t2 = gt.used_atomsym_atomtype[n1], gt.used_atomsym_atomtype[n2]
             param = gt.gt.nonbond_params.get(tuple(sorted((n1, n2))))
-            table_name, sig, eps = None, -1.0, -1.0
+            table_name, table_cap, sig, eps = None, None, -1.0, -1.0
             if param:
                 if param["func"] == 1:
                     sig, eps = float(param["params"][0]), float(param["params"][1])
@@ -209,6 +210,15 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
                     if sig > 0.0:
                         dyn_lj.setdefault(max_force, collections.OrderedDict())[(t1, t2)] = (sig, eps)
                     continue
+                elif param["func"] == 13:
+                    # `table caprad`: the table evaluated at r = caprad inside caprad (:619-621), on the type pairs that react
+                    pr = param["params"]
+                    if len(pr) != 2:
+                        raise RuntimeError("nonbond_params %s %s func 13: expected `table caprad`, got %d parameters" % (n1, n2, len(pr)))
+                    table_name, table_cap = pr[0], float(pr[1])
+                elif param["func"] == 16:
+                    raise NotImplementedError("nonbond_params %s %s func 16: LennardJonesEnergyCapped is not built -- what its force does inside the cap radius "
+                                              "is not pinned down and no example input uses it (func 13, TabulatedCapped, is)" % (n1, n2))
                 else:
                     raise NotImplementedError("nonbond_params func %d is outside the hot-path scope (SURVEY.md 2.1 #3)" % param["func"])
             elif n1 in tables_ and n2 in tables_:
@@ -223,6 +233,10 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
                 pot = xvg.replace(".xvg", "") + ".pot"
                 if not os.path.exists(pot):
                     tables.convert_table(xvg, pot)
+                if table_cap is not None:
+                    tab_cap.setPotential(type1=t1, type2=t2, potential=espressopp.interaction.TabulatedCapped(itype=1, filename=pot, cutoff=tab_cutoff, caprad=table_cap))
+                    has_tab_cap = True
+                    continue
                 tab.setPotential(type1=t1, type2=t2, potential=espressopp.interaction.Tabulated(itype=1, filename=pot, cutoff=tab_cutoff))
                 has_tab = True
             elif sig > 0.0:
@@ -257,6 +271,8 @@ def set_nonbonded_interactions(espressopp, system, gt, vl, lj_cutoff, tab_cutoff
         system.addInteraction(lj, "lj")
     if has_tab:
         system.addInteraction(tab, "lj-tab")
+    if has_tab_cap:
+        system.addInteraction(tab_cap, "lj-tab_cap")
     if has_mix:
         system.addInteraction(mix, "lj-mix_tab")
     return lj if has_lj else None, tab if has_tab else None

@@ -111,6 +111,10 @@ struct Ctx {
   ResState res; uint32_t res_mask[CHEM_MAX_TYPES] = {}; double res_fmax[CHEM_MAX_TYPES][CHEM_MAX_TYPES] = {}; bool res_dirty = false;
   std::map<int, std::array<double, 2>> res_rules;
   bool res_pairs_on() const { for (uint32_t m : res_mask) if (m) return true; return false; }
+  // Capped pairs (chem_nb_cap): the cap radius of every capped type pair, symmetric, 0 = none.  The device copy (the squares, in
+  // the kernels' precision) exists only while a type pair is capped (caps_on); the capped force kernels are launched only then.
+  double cap_rad[CHEM_MAX_TYPES][CHEM_MAX_TYPES] = {}; bool cap_dirty = false;
+  bool caps_on() const { for (const auto& row : cap_rad) for (double c : row) if (c > 0) return true; return false; }
   // the force kernel stages one extra word per slot (charge or lambda): LDS plan, kernel choice and option limits follow it
   bool slot_word_on() const { return coul_on() || res_pairs_on(); }
   // type changes have to be seen when they happen (re-stamping) and events looked at (res_rules)
@@ -280,9 +284,10 @@ template <typename R> struct CtxT : Ctx {
   size_t scan_lds_bytes() const { return scan_roles_offset(tile_cap, sizeof(V4)) + (size_t)(tile_cap + 1) * sizeof(unsigned int); }
   bool scan_roles_staged() const { return scan_lds_bytes() <= kTileLdsBudget; }      // (otherwise the scan reads the role words from global memory)
   // what a tile of cap_ slots asks of the LDS, over every kernel that stages one (asked before tile_cap is set or grown)
-  // (extra: static LDS a force-kernel mode adds beyond what kTileLdsBudget leaves room for -- the staged caps of MODE 5)
+  // (extra: static LDS a force-kernel mode adds beyond what kTileLdsBudget leaves room for -- the staged force caps of MODE 5,
+  //  the staged cap radii of MODE 6, both in MODE 7)
   static size_t tile_lds_need(int cap_, bool coul, size_t extra = 0) { return std::max(std::max(tile_lds_bytes(cap_), pair_lds_bytes(cap_, coul) + extra), list_lds_need(cap_, true)); }
-  size_t res_lds_extra() const { return res_pairs_on() ? sizeof(R) * kMaxTypes * kMaxTypes : 0; }
+  size_t res_lds_extra() const { return ((res_pairs_on() ? 1 : 0) + (caps_on() ? 1 : 0)) * sizeof(R) * kMaxTypes * kMaxTypes; }
   static size_t list_lds_need(int cap_, bool exact_rows) {
     const size_t lb = list_lds_bytes(cap_, kMaxTypes);
     return (sizeof(R) == 4 || exact_rows) ? std::max(tile_lds_bytes(cap_), lb) : lb;
@@ -348,6 +353,7 @@ template <typename R> struct CtxT : Ctx {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
     if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
     if (res_pairs_on()) return false;      // (nor any lambda)
+    if (caps_on()) return false;      // (nor any cap radius)
     if (top.any_hybrid()) return false;      // (the force kernel knows one K, one r0 and no lambda: a hybrid list is never evaluated there)
     // (a 1-4 Coulomb list with parameters is a second slot, so harmonic_only already rules it out; one without parameters does
     //  nothing but would pass that proof -- inline bonds stay off next to any Coulomb term, so ask directly)
@@ -635,6 +641,16 @@ template <typename R> struct CtxT : Ctx {
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
     }
+    if (caps_on()) {      // MODE 6: the image alone; MODE 7: the image + the lambda words
+      const int qbytes = (int)pair_lds_bytes();
+      if (res_pairs_on()) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_rescap<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_rescap<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+      } else {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_cap<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_cap<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
+      }
+    }
   }
 
   void alloc_lists() {
@@ -803,7 +819,12 @@ template <typename R> struct CtxT : Ctx {
       }
     }
     if (!opt_skip_inactive || !first) uniform_lj = false;
-    if (slot_word_on()) { uniform_lj = false; lj_only = false; }
+    if (slot_word_on() || caps_on()) { uniform_lj = false; lj_only = false; }
+    // a re-sent potential keeps its cap: the radius must still lie inside the cutoff it has now
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = a; b < CHEM_MAX_TYPES; ++b)
+      if (cap_rad[a][b] > 0 && pp[a][b].kind != 0 && !(cap_rad[a][b] < pp[a][b].rc))
+        throw ChemError(CHEM_EINVAL, "capped type pair (" + std::to_string(a) + "," + std::to_string(b) + "): cap radius " + std::to_string(cap_rad[a][b]) +
+                                     " is not inside the cutoff " + std::to_string(pp[a][b].rc) + " of the potential the pair carries now");
     all_active = true;   // every pair of types in use carries a potential: the list build skips the per-hit type filter
     for (int a = 0; a < nt; ++a) for (int b = 0; b < nt; ++b) if (!((act.row[a] >> b) & 1u)) all_active = false;
     if (uniform_lj) {
@@ -859,6 +880,18 @@ template <typename R> struct CtxT : Ctx {
     for (size_t k = 0; k < tags.size(); ++k) { const int32_t t = tags[k]; stage[k] = double2{res.lambda0[t], (double)res.s0[t]}; HIPCHK(hipMemcpyAsync(rstamp.p + t, &stage[k], sizeof(double2), hipMemcpyHostToDevice, stream)); }
     HIPCHK(hipStreamSynchronize(stream));
   }
+  // Capped pairs: the squared cap radii by type pair -- allocated only while a type pair is capped; type-pair data, the same on
+  // every rank of a decomposition.
+  DBuf<R> capc2;
+  void upload_cap() {
+    cap_dirty = false;
+    if (!caps_on()) { HIPCHK(hipStreamSynchronize(stream)); capc2.free(); return; }
+    std::vector<R> hc((size_t)CHEM_MAX_TYPES * CHEM_MAX_TYPES);
+    for (int a = 0; a < CHEM_MAX_TYPES; ++a) for (int b = 0; b < CHEM_MAX_TYPES; ++b) hc[(size_t)a * CHEM_MAX_TYPES + b] = (R)(cap_rad[a][b] * cap_rad[a][b]);
+    capc2.upload(hc, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  CapArgs<R> cap_args() const { return CapArgs<R>{capc2.p}; }
   ResArgs<R> res_args() const { return ResArgs<R>{rstamp.p, ralpha.p, tag.p, rmask_dev.p, rfmax.p, (long long)(step + force_step_off)}; }
   // Completion (chem_resolution_rate with a property change): every particle whose lambda reached 1 at the current step gets
   // its new type, mass, charge and state by the route of chem_modify_particle, and a stamp (1, step) under the new type.
@@ -1181,6 +1214,7 @@ template <typename R> struct CtxT : Ctx {
     if (pair_dirty) upload_pair();
     if (coul_dirty) upload_coul();
     if (res_dirty) upload_res();
+    if (cap_dirty) upload_cap();
     if (fix_dirty) upload_fix();
     if (bonded_dirty) upload_bonded();
     if (excl_dirty) upload_excl();
@@ -1516,6 +1550,16 @@ template <typename R> struct CtxT : Ctx {
       if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a resolution pair marked only tpp = 1 (or 0, automatic) is built");
       if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a resolution pair marked only pair_block = 512 is built");
     }
+    const bool capm = caps_on();
+    if (capm) {      // the kernels with the cap radii: the same build again, and not next to the Coulomb term
+      if (coul) {
+        int a = 0, b = 0;
+        for (int k = CHEM_MAX_TYPES * CHEM_MAX_TYPES; k-- > 0;) if (cap_rad[k / CHEM_MAX_TYPES][k % CHEM_MAX_TYPES] > 0 && k / CHEM_MAX_TYPES <= k % CHEM_MAX_TYPES) { a = k / CHEM_MAX_TYPES; b = k % CHEM_MAX_TYPES; }      // (the first capped pair)
+        throw ChemError(CHEM_ENOTIMPL, "capped type pair (" + std::to_string(a) + "," + std::to_string(b) + ") next to a registered Coulomb pair: the two terms are not served in one context");
+      }
+      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a capped pair registered only tpp = 1 (or 0, automatic) is built");
+      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a capped pair registered only pair_block = 512 is built");
+    }
     const bool inline_now = bonds_inline();
     int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;      // (what the LAST rebuild did: both only change where a rebuild is forced)
     if (bond_mode == 2 && dd_on) {      // slabs: the host knows which launch follows a rebuild (mode 3 = mode 2 + record the partner slots now)
@@ -1559,8 +1603,19 @@ template <typename R> struct CtxT : Ctx {
       }
       if (resm) {      // MODE 5: general + resolution scaling, one instantiation per precision and ENERGY
         if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with the resolution scaling");
+        if (capm) {      // MODE 7: ... + capped type pairs
+          hipLaunchKernelGGL((k_pair_tiles_rescap<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
+                             nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, res_args(), cap_args());
+          return ntiles;
+        }
         hipLaunchKernelGGL((k_pair_tiles_res<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
                            nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, res_args());
+        return ntiles;
+      }
+      if (capm) {      // MODE 6: general + capped type pairs, one instantiation per precision and ENERGY
+        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with capped pairs");
+        hipLaunchKernelGGL((k_pair_tiles_cap<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
+                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, cap_args());
         return ntiles;
       }
       const int mode = ENERGY ? (cubic_tab ? 3 : 0) : (uniform_lj ? 2 : (lj_only ? 1 : (cubic_tab ? 3 : 0)));
@@ -1576,6 +1631,18 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL((k_pair_force<R, 4, ENERGY, true, true>), dim3(nbq), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
                          pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, coul_args((size_t)nbq));
       return nbq;
+    }
+    if (resm && capm) {
+      const int nbr = cdiv((long long)n * 4, 256);
+      hipLaunchKernelGGL((k_pair_force_rescap<R, 4, ENERGY>), dim3(nbr), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
+                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, res_args(), cap_args());
+      return nbr;
+    }
+    if (capm) {
+      const int nbc = cdiv((long long)n * 4, 256);
+      hipLaunchKernelGGL((k_pair_force_cap<R, 4, ENERGY>), dim3(nbc), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
+                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, cap_args());
+      return nbc;
     }
     if (resm) {
       const int nbr = cdiv((long long)n * 4, 256);
@@ -2955,6 +3022,7 @@ int chem_nb_resolution(chem_ctx* ctx, int t1, int t2, int on, double max_force) 
   const bool was_on = c.res_pairs_on(), word_was = c.slot_word_on();
   if (on) {
     REQUIRE(c.pp[t1][t2].kind != 0, CHEM_EINVAL, "nb_resolution: type pair (" + std::to_string(t1) + "," + std::to_string(t2) + ") carries no LJ or table potential");
+    REQUIRE(!(c.cap_rad[t1][t2] > 0), CHEM_EINVAL, "nb_resolution: type pair (" + std::to_string(t1) + "," + std::to_string(t2) + ") is capped (chem_nb_cap): a pair is capped or resolution-scaled, not both");
     c.res_mask[t1] |= 1u << t2; c.res_mask[t2] |= 1u << t1;
     c.res_fmax[t1][t2] = c.res_fmax[t2][t1] = max_force > 0 ? max_force : 0.0;
   } else {
@@ -2965,6 +3033,29 @@ int chem_nb_resolution(chem_ctx* ctx, int t1, int t2, int on, double max_force) 
     c.res_dirty = true; c.pair_dirty = true;
     if (was_on != c.res_pairs_on()) { c.bonded_dirty = true; c.resort = true; }      // kernel selection, inline bonds
     if (word_was != c.slot_word_on()) c.geom_dirty = true;      // the LDS footprint the tiles are planned for
+  }
+  return 0;
+  API_END(ctx)
+}
+
+int chem_nb_cap(chem_ctx* ctx, int t1, int t2, double caprad) {
+  API_BEGIN
+  REQUIRE(t1 >= 0 && t2 >= 0 && t1 < CHEM_MAX_TYPES && t2 < CHEM_MAX_TYPES, CHEM_EINVAL, "nb_cap: type out of range");
+  REQUIRE(std::isfinite(caprad), CHEM_EINVAL, "nb_cap: caprad must be finite");
+  Ctx& c = CTX;
+  const bool was_on = c.caps_on();
+  const std::string pair = "(" + std::to_string(t1) + "," + std::to_string(t2) + ")";
+  if (caprad > 0) {
+    REQUIRE(c.pp[t1][t2].kind != 0, CHEM_EINVAL, "nb_cap: type pair " + pair + " carries no LJ or table potential");
+    REQUIRE(caprad < c.pp[t1][t2].rc, CHEM_EINVAL, "nb_cap: caprad " + std::to_string(caprad) + " of type pair " + pair + " must lie inside its cutoff " + std::to_string(c.pp[t1][t2].rc));
+    REQUIRE(!((c.res_mask[t1] >> t2) & 1u), CHEM_EINVAL, "nb_cap: type pair " + pair + " is resolution-marked: a pair is capped or resolution-scaled, not both");
+    c.cap_rad[t1][t2] = c.cap_rad[t2][t1] = caprad;
+  } else {
+    c.cap_rad[t1][t2] = c.cap_rad[t2][t1] = 0.0;
+  }
+  if (was_on || c.caps_on()) {      // (removing what was never there changes nothing and costs nothing)
+    c.cap_dirty = true; c.pair_dirty = true;
+    if (was_on != c.caps_on()) { c.bonded_dirty = true; c.resort = true; c.geom_dirty = true; }      // kernel selection, inline bonds, the LDS footprint the tiles are planned for
   }
   return 0;
   API_END(ctx)

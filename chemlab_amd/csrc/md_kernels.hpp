@@ -1117,12 +1117,28 @@ __device__ __forceinline__ void res_pair(PT&& term, R li, R lj, bool on, R fcap,
   if (ENERGY) { e_lj += (double)w * te1; e_tab += (double)w * te2; vir += (double)(tx * dx + ty * dy + tz * dz); }
 }
 
+// Capped pairs (VerletListTabulatedCapped / VerletListLennardJonesCapped; rule set in include/chem_mi355.h, chem_nb_cap): inside
+// the cap radius c of its type pair a pair is evaluated at r_e = c instead of r -- force magnitude f(c) along r_ij, energy U(c),
+// virial share f(c) r.  c2[ti * kMaxTypes + tj] = c^2 (0 = the pair is not capped), staged in LDS beside the pairs' other
+// parameters (cap_stage_radii); the decision is taken on the squares.
+template <typename R> struct CapArgs { const R* c2; };
+template <typename R> __device__ __forceinline__ void cap_stage_radii(R* sc2, const R* __restrict__ c2) {      // (caller synchronises)
+  for (int k = threadIdx.x; k < kMaxTypes * kMaxTypes; k += blockDim.x) sc2[k] = c2[k];
+}
+
 // CUBIC: the host selects these instantiations only while a type pair of kind 3 exists, so that the others stay what they were
-template <typename R, bool ENERGY, bool CUBIC = false>
+// CAPPED (with c2 = the type pair's squared cap radius): likewise only while a type pair is capped.  r2 is clamped to c2 before
+// the branch on the kind; every kind then scales its f(r_e) / r_e by r_e / r (0 at r = 0: the one guard, the direction is undefined there)
+template <typename R, bool ENERGY, bool CUBIC = false, bool CAPPED = false>
 __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
                                           const Vec4<R>* __restrict__ tab, R r2, R dx, R dy, R dz,
-                                          R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir) {
+                                          R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir, R c2 = (R)0) {
   if (r2 <= pc.rc2) {
+    [[maybe_unused]] R sc = (R)1;      // r_e / r
+    const R rt2 = r2;                   // the pair's own r^2 (virial share: r.F of the applied force)
+    if constexpr (CAPPED) {
+      if (r2 < c2) { sc = r2 > (R)0 ? sqrt_r(c2) * rsqrt_r(r2) : (R)0; r2 = c2; }
+    }
     if (CUBIC && pc.kind == (R)3) {
       const PairExt<R> px = pext[pidx];
       const R r = sqrt_r(r2);
@@ -1133,14 +1149,16 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
       if (k > px.nrow - 2) k = px.nrow - 2;
       const R w = t - (R)k;
       const Vec4<R> cf = tab[px.toff + 2 * k];      // force coefficients; the energy row behind it is read with ENERGY only
-      const R ff = (cf.x + w * (cf.y + w * (cf.z + w * cf.w))) / r;
+      R ff = (cf.x + w * (cf.y + w * (cf.z + w * cf.w))) / r;
+      if constexpr (CAPPED) ff *= sc;
       fx += ff * dx; fy += ff * dy; fz += ff * dz;
-      if (ENERGY) { const Vec4<R> ce = tab[px.toff + 2 * k + 1]; e_tab += (double)(ce.x + w * (ce.y + w * (ce.z + w * ce.w))); vir += (double)(ff * r2); }
+      if (ENERGY) { const Vec4<R> ce = tab[px.toff + 2 * k + 1]; e_tab += (double)(ce.x + w * (ce.y + w * (ce.z + w * ce.w))); vir += (double)(ff * rt2); }
     } else if (pc.kind == (R)1) {
       const R r2i = rcp_r(r2), r6i = r2i * r2i * r2i;
-      const R ff = r6i * (pc.lj1 * r6i - pc.lj2) * r2i;
+      R ff = r6i * (pc.lj1 * r6i - pc.lj2) * r2i;
+      if constexpr (CAPPED) ff *= sc;
       fx += ff * dx; fy += ff * dy; fz += ff * dz;
-      if (ENERGY) { const PairExt<R> px = pext[pidx]; e_lj += (double)(r6i * (px.e1 * r6i - px.e2) + px.shift); vir += (double)(ff * r2); }
+      if (ENERGY) { const PairExt<R> px = pext[pidx]; e_lj += (double)(r6i * (px.e1 * r6i - px.e2) + px.shift); vir += (double)(ff * rt2); }
     } else {
       const PairExt<R> px = pext[pidx];
       const R r = sqrt_r(r2);
@@ -1151,9 +1169,10 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
       if (k > px.nrow - 2) k = px.nrow - 2;
       const R wgt = t - (R)k;
       const Vec4<R> row = tab[px.toff + k];  // (f_k, df_k, e_k, de_k)
-      const R ff = (row.x + wgt * row.y) / r;
+      R ff = (row.x + wgt * row.y) / r;
+      if constexpr (CAPPED) ff *= sc;
       fx += ff * dx; fy += ff * dy; fz += ff * dz;
-      if (ENERGY) { e_tab += (double)(row.z + wgt * row.w); vir += (double)(ff * r2); }
+      if (ENERGY) { e_tab += (double)(row.z + wgt * row.w); vir += (double)(ff * rt2); }
     }
   }
 }
@@ -1163,17 +1182,21 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
 // RES: marked type pairs scaled by lambda_i lambda_j and capped (k_pair_force_res, launched only while a type pair is marked;
 // both table kinds); lambda through tag[j] -> stamp, evaluated per neighbour
 // (the body of k_pair_force and of k_pair_force_res, which alone takes the resolution arguments)
-template <typename R, int TPP, bool ENERGY, bool CUBIC, bool COUL, bool RES>
+// CAPPED: type pairs with a cap radius (k_pair_force_cap, k_pair_force_rescap, launched only while a type pair is capped)
+template <typename R, int TPP, bool ENERGY, bool CUBIC, bool COUL, bool RES, bool CAPPED = false>
 __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ nlist, const int* __restrict__ nn, int S,
                                                     const Box<R>& box, const PairCore<R>* __restrict__ pcore,
                                                     const PairExt<R>* __restrict__ pext, int ntypes,
                                                     const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
-                                                    double half_skin, DevCtl* ctl, const CoulArgs<R>& ca, const ResArgs<R>& ra) {
+                                                    double half_skin, DevCtl* ctl, const CoulArgs<R>& ca, const ResArgs<R>& ra,
+                                                    const CapArgs<R>& cp = CapArgs<R>{}) {
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   for (int k = threadIdx.x; k < ntypes * ntypes; k += blockDim.x) spc[k] = pcore[k];
   [[maybe_unused]] const R* sfm = nullptr;
   if constexpr (RES) { __shared__ R sfm_[kMaxTypes * kMaxTypes]; res_stage_caps<R>(sfm_, ra.fmax); sfm = sfm_; }
+  [[maybe_unused]] const R* sc2 = nullptr;
+  if constexpr (CAPPED) { __shared__ R sc2_[kMaxTypes * kMaxTypes]; cap_stage_radii<R>(sc2_, cp.c2); sc2 = sc2_; }
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1215,12 +1238,14 @@ __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict
         R r2 = dx * dx + dy * dy + dz * dz;
         r2 = (k + u < cnt) ? r2 : (R)1e30;     // padding entries (self index) never interact
         const int pidx = pbase + (int)xj.w;
+        [[maybe_unused]] R c2 = (R)0;
+        if constexpr (CAPPED) c2 = sc2[ti * kMaxTypes + (int)xj.w];
         if constexpr (RES) {
           const int tj = (int)xj.w;
-          res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av); },
+          res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
                               lami, ls[u], ((rrow >> tj) & 1u) != 0, sfm[ti * kMaxTypes + tj], dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
         } else
-        pair_term<R, ENERGY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+        pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir, c2);
         if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
       }
     }
@@ -1271,6 +1296,26 @@ __global__ __launch_bounds__(256) void k_pair_force_res(int n, const Vec4<R>* __
                                                         const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                         double half_skin, DevCtl* ctl, ResArgs<R> ra) {
   pair_force_body<R, TPP, ENERGY, true, false, true>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, CoulArgs<R>{}, ra);
+}
+// capped general and capped resolution builds (both table kinds): entry points of their own, so that the argument blocks of
+// k_pair_force and k_pair_force_res stay what they are
+template <typename R, int TPP, bool ENERGY>
+__global__ __launch_bounds__(256) void k_pair_force_cap(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                        const int* __restrict__ nlist, const int* __restrict__ nn, int S,
+                                                        Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                        const PairExt<R>* __restrict__ pext, int ntypes,
+                                                        const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                        double half_skin, DevCtl* ctl, CapArgs<R> cp) {
+  pair_force_body<R, TPP, ENERGY, true, false, false, true>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, CoulArgs<R>{}, ResArgs<R>{}, cp);
+}
+template <typename R, int TPP, bool ENERGY>
+__global__ __launch_bounds__(256) void k_pair_force_rescap(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                           const int* __restrict__ nlist, const int* __restrict__ nn, int S,
+                                                           Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                           const PairExt<R>* __restrict__ pext, int ntypes,
+                                                           const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                           double half_skin, DevCtl* ctl, ResArgs<R> ra, CapArgs<R> cp) {
+  pair_force_body<R, TPP, ENERGY, true, false, true, true>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, CoulArgs<R>{}, ra, cp);
 }
 
 // =======================================================================================
@@ -2257,17 +2302,17 @@ __global__ __launch_bounds__(1024) void k_tile_scan(int ntiles, TileLDS<R>* __re
 }
 
 // ---- pair forces on tiles --------------------------------------------------------------
-template <typename R, bool ENERGY, bool LJONLY, bool CUBIC = false>
+template <typename R, bool ENERGY, bool LJONLY, bool CUBIC = false, bool CAPPED = false>
 __device__ __forceinline__ void pair_accum(const PairCore<R> pc, const PairExt<R>* __restrict__ pext, int pidx,
                                            const Vec4<R>* __restrict__ tab, R r2, R dx, R dy, R dz,
-                                           R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir) {
+                                           R& fx, R& fy, R& fz, double& e_lj, double& e_tab, double& vir, R c2 = (R)0) {
   if (LJONLY && !ENERGY) {
     const R r2i = rcp_r(r2), r6i = r2i * r2i * r2i;
     R ff = r6i * (pc.lj1 * r6i - pc.lj2) * r2i;
     ff = (r2 <= pc.rc2) ? ff * pc.kind : (R)0;   // kind (1 for LJ) keeps the read a single ds_read_b128 (b96 costs 2x the LDS cycles)
     fx += ff * dx; fy += ff * dy; fz += ff * dz;
   } else {
-    pair_term<R, ENERGY, CUBIC>(pc, pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+    pair_term<R, ENERGY, CUBIC, CAPPED>(pc, pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir, c2);
   }
 }
 
@@ -2300,6 +2345,9 @@ struct UniLJ { float rc2, lj1, lj2, pad; double drc2, dlj1, dlj2; };   // all li
 //         by chem_nb_resolution; TPP 1, 512 threads, k_pair_tiles_res).  One lambda word per slot is staged where MODE 4 keeps
 //         its charge words (the two terms are not served together), computed in tile_fill; the home particle's lambda and its
 //         row of the resolution mask are registers, the pairs' caps are staged in LDS beside spc[].  No inline bonds.
+//      6: general as 3, with capped type pairs (launched only while a type pair is capped by chem_nb_cap; TPP 1, 512 threads,
+//         k_pair_tiles_cap).  The squared cap radii are staged in LDS beside spc[]; no word per slot.  No inline bonds.
+//      7: 5 and 6 together (k_pair_tiles_rescap): marked type pairs and capped type pairs in one context, never the same pair.
 // Tiles of one launch: [base1, base1+n1) followed by [base2, ...).  The decomposed path launches the
 // tiles whose stencil stays inside the own layers ("interior": they need no ghost) while the halo
 // exchange is still in flight on the communication stream, and the two boundary tile layers after it.
@@ -2402,8 +2450,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                                                    DecideArgs da, uint4* __restrict__ bslots,
                                                    double bond_K, double bond_r0, int bond_mode, ActMask bact,
                                                    const BondRec<R>* __restrict__ brec,
-                                                   const CoulArgs<R> ca, const ResArgs<R> ra) {
-  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE == 3 || MODE == 4 || MODE == 5, COUL = MODE == 4, RES = MODE == 5;
+                                                   const CoulArgs<R> ca, const ResArgs<R> ra, const CapArgs<R> cp = CapArgs<R>{}) {
+  constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE >= 3, COUL = MODE == 4, RES = MODE == 5 || MODE == 7, CAPPED = MODE == 6 || MODE == 7;
 #ifndef CHEM_NCH
 #define CHEM_NCH 3
 #endif
@@ -2448,6 +2496,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   if (MODE != 2) for (int k = threadIdx.x; k < ntypes * ntypes; k += BS) spc[k] = pcore[k];
   [[maybe_unused]] const R* sfm = nullptr;
   if constexpr (RES) { __shared__ R sfm_[kMaxTypes * kMaxTypes]; res_stage_caps<R>(sfm_, ra.fmax); sfm = sfm_; }      // (the barriers behind the descriptor and the staging cover it)
+  [[maybe_unused]] const R* sc2 = nullptr;
+  if constexpr (CAPPED) { __shared__ R sc2_[kMaxTypes * kMaxTypes]; cap_stage_radii<R>(sc2_, cp.c2); sc2 = sc2_; }      // (likewise)
   if (guard < 2 && blockIdx.x == 0 && threadIdx.x == 0 && ctl->acc_maxdist > half_skin) ctl->skin_violation = 1;
   const R u_rc2 = sizeof(R) == 4 ? (R)uni.rc2 : (R)uni.drc2, u_lj1 = sizeof(R) == 4 ? (R)uni.lj1 : (R)uni.dlj1,
           u_lj2 = sizeof(R) == 4 ? (R)uni.lj2 : (R)uni.dlj2;
@@ -2596,12 +2646,14 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
               fx += ff * dx; fy += ff * dy; fz += ff * dz;
             } else {
               const int pidx = pbase + (int)xj.w;
+              [[maybe_unused]] R c2 = (R)0;
+              if constexpr (CAPPED) c2 = sc2[(int)xi.w * kMaxTypes + (int)xj.w];
               if constexpr (RES) {
                 const int tj = (int)xj.w;
-                res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av); },
+                res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
                                     lami, qs[u], ((rrow >> tj) & 1u) != 0, sfm[(int)xi.w * kMaxTypes + tj], dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
               } else
-              pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir);
+              pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir, c2);
               if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
             }
           }
@@ -2629,7 +2681,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
         }
       }
       fx += (R)fxy.x; fy += (R)fxy.y;      // (packed x/y accumulators of the uniform-LJ fp32 path; zero otherwise)
-      if (!COUL && !RES && bslots && sub == 0) {
+      if (!COUL && !RES && !CAPPED && bslots && sub == 0) {
         // Inline harmonic bonds (FixedPairListHarmonic, gromacs_topology.py:949-961; reaction bonds reaction_setup.py:449-467):
         // the LDS slots of the bonded (= excluded) partners are recorded at every rebuild, the geometry comes from the staged
         // image (tile-local coordinates: 2.4e-7 in the fp32 build, exact in fp64) -- no bonded launch, no second pass over f4.
@@ -2718,7 +2770,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
                                                    DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
                                                    double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
                                                    const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
-  static_assert(MODE != 4 && MODE != 5, "MODE 4 is k_pair_tiles_q, MODE 5 k_pair_tiles_res");
+  static_assert(MODE < 4, "MODE 4 is k_pair_tiles_q, MODE 5 k_pair_tiles_res, MODE 6 k_pair_tiles_cap, MODE 7 k_pair_tiles_rescap");
   pair_tiles_body<R, TPP, ENERGY, BS, MODE, DIAG>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, uni, eout, half_skin, ctl, guard, ablate, dbg,
                                                   sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, brec, CoulArgs<R>{}, ResArgs<R>{});
 }
@@ -2743,6 +2795,28 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra) {
   pair_tiles_body<R, 1, ENERGY, 512, 5, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
                                                sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ra);
+}
+// MODE 6: one lane per particle, 512 threads; no inline bonds
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_cap(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                   const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                   const int* __restrict__ nnh, int S16,
+                                                   const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                   int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                   double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CapArgs<R> cp) {
+  pair_tiles_body<R, 1, ENERGY, 512, 6, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ResArgs<R>{}, cp);
+}
+// MODE 7: one lane per particle, 512 threads; no inline bonds
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_rescap(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                   const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                   const int* __restrict__ nnh, int S16,
+                                                   const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                   int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                   double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra, CapArgs<R> cp) {
+  pair_tiles_body<R, 1, ENERGY, 512, 7, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ra, cp);
 }
 
 // =======================================================================================

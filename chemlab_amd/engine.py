@@ -160,6 +160,14 @@ class Engine:
         ro = {"type_1": 1, "type_2": 2}.get(role, role)
         self._ck(self._res_entry("reaction_set_resolution")(self.ctx, int(reaction), int(ro), float(lam)))
 
+    def nb_cap(self, t1, t2, caprad):
+        """Cap the LJ / table of the type pair at the radius caprad: inside it the pair is evaluated at r = caprad
+        (include/chem_mi355.h, chem_nb_cap); caprad <= 0 removes the cap."""
+        fn = getattr(self.api, "nb_cap", None)
+        if fn is None:
+            raise NotImplementedError("capped pair potentials: the CPU checker has no cap radius")
+        self._ck(fn(self.ctx, int(t1), int(t2), float(caprad)))
+
     # ---- fixed distances / by-product release (include/chem_mi355.h, chem_fix_create ff.) ----
     def _fix_entry(self, name):
         fn = getattr(self.api, name, None)

@@ -589,6 +589,57 @@ class _VerletListDynamicResolutionTabulated(_VerletListDynamicResolution):
         self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
 
 
+class _LennardJonesCapped(_LennardJones):
+    """interaction.LennardJonesCapped(epsilon, sigma, cutoff, caprad, shift): LJ evaluated at r = caprad inside caprad
+    (rule set: include/chem_mi355.h, chem_nb_cap)."""
+
+    def __init__(self, epsilon=1.0, sigma=1.0, cutoff=2.5, caprad=0.0, shift="auto"):
+        _LennardJones.__init__(self, epsilon, sigma, cutoff, shift)
+        self.caprad = caprad
+
+
+class _TabulatedCapped(_Tabulated):
+    """interaction.TabulatedCapped(itype, filename, cutoff, caprad) (gromacs_topology.py:684-695, nonbond_params func 13):
+    the table evaluated at r = caprad inside caprad (rule set: include/chem_mi355.h, chem_nb_cap)."""
+
+    def __init__(self, itype=1, filename=None, cutoff=None, caprad=0.0):
+        _Tabulated.__init__(self, itype, filename, cutoff)
+        self.caprad = caprad
+
+
+class _VerletListCapped(_VerletListInteraction):
+    """interaction.VerletListLennardJonesCapped / VerletListTabulatedCapped(vl): the potential is sent as for the uncapped
+    interaction, then its cap radius.  The energy is the engine's LJ / tabulated accumulator, shared with the uncapped pairs."""
+    energy_key = None
+
+    def _send(self, type1, type2, potential):
+        raise NotImplementedError
+
+    def setPotential(self, type1, type2, potential):
+        self._pots[(min(type1, type2), max(type1, type2))] = potential
+        self._send(type1, type2, potential)
+        self.system.engine.nb_cap(type1, type2, float(potential.caprad))
+
+    def computeEnergy(self):
+        return self.system.engine.observe()[self.energy_key]
+
+
+class _VerletListLennardJonesCapped(_VerletListCapped):
+    label = "lj_cap"
+    energy_key = "epot_lj"
+
+    def _send(self, type1, type2, potential):
+        self.system.engine.nb_lj(type1, type2, potential.epsilon, potential.sigma, potential.cutoff, potential.shift == "auto")
+
+
+class _VerletListTabulatedCapped(_VerletListCapped):
+    label = "tab_cap"
+    energy_key = "epot_tab"
+
+    def _send(self, type1, type2, potential):
+        self.system.engine.nb_table(type1, type2, potential.r0, potential.dr, potential.e, potential.f, potential.cutoff, **_interp_kw(potential))
+
+
 class _CoulombTruncated(_Pot):
     """interaction.CoulombTruncated(prefactor, cutoff): U = prefactor q_i q_j / r inside the cutoff, unshifted
     (rule set: include/chem_mi355.h, chem_nb_coulomb)."""
@@ -727,6 +778,11 @@ interaction = _ns(
     VerletListDynamicResolutionLennardJones=_VerletListDynamicResolutionLennardJones,
     VerletListDynamicResolutionTabulated=_VerletListDynamicResolutionTabulated,
     MixedTabulated=_MixedTabulated, VerletListMixedTabulated=_VerletListMixedTabulated, MultiTabulated=_unsupported("interaction.MultiTabulated"),
+    LennardJonesCapped=_LennardJonesCapped, VerletListLennardJonesCapped=_VerletListLennardJonesCapped,
+    TabulatedCapped=_TabulatedCapped, VerletListTabulatedCapped=_VerletListTabulatedCapped,
+    # (nonbond_params func 16: what the force does inside the cap of the energy-capped variant is not pinned down, and no example uses it)
+    LennardJonesEnergyCapped=_unsupported("interaction.LennardJonesEnergyCapped"),
+    VerletListLennardJonesEnergyCapped=_unsupported("interaction.VerletListLennardJonesEnergyCapped"),
 )
 
 
@@ -1456,9 +1512,9 @@ class _PotentialEnergy(_Observable):
         if isinstance(i, _VerletListCoulombTruncated):
             return self.system.engine.get_coulomb()[0]
         o = self.system.engine.observe()
-        if isinstance(i, (_VerletListLennardJones, _VerletListDynamicResolutionLennardJones)):      # (one LJ accumulator: plain and resolution-scaled pairs together)
+        if isinstance(i, (_VerletListLennardJones, _VerletListDynamicResolutionLennardJones, _VerletListLennardJonesCapped)):      # (one LJ accumulator: plain and resolution-scaled pairs together)
             return o["epot_lj"]
-        if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated, _VerletListDynamicResolutionTabulated)):    # (one tabulated-energy accumulator: plain and mixed tables together)
+        if isinstance(i, (_VerletListTabulated, _VerletListMixedTabulated, _VerletListDynamicResolutionTabulated, _VerletListTabulatedCapped)):    # (one tabulated-energy accumulator: plain and mixed tables together)
             return o["epot_tab"]
         h = getattr(i, "handle", None)      # the interaction's own library list (a list object carries one per kind)
         if h is None:

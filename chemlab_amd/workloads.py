@@ -238,7 +238,9 @@ def apply(spec, eng, thermostat=True, reactions=True):
         eng.nb_coulomb(*cq)
     for rs in spec.get("resolution", []):       # (t1, t2, max_force): the pair's LJ / table scaled by lambda_i lambda_j, capped (0: no cap)
         eng.nb_resolution(rs[0], rs[1], True, rs[2] if len(rs) > 2 else 0.0)
-    for rr in spec.get("res_rates", []):        # (type, alpha[, new_type, new_mass, new_q, new_state]) or a dict of resolution_rate's arguments
+    for cp in spec.get("caps", []):             # (t1, t2, caprad): inside caprad the pair's LJ / table is evaluated at r = caprad
+        eng.nb_cap(*cp)
+    for rr in spec.get("res_rates", []):       # (type, alpha[, new_type, new_mass, new_q, new_state]) or a dict of resolution_rate's arguments
         eng.resolution_rate(**rr) if isinstance(rr, dict) else eng.resolution_rate(*rr)
     if spec.get("lam") is not None:             # lambda per particle, in the order of spec["ids"]
         eng.set_resolution(spec["ids"], spec["lam"])

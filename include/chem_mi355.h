@@ -316,6 +316,42 @@ int chem_set_resolution(chem_ctx* ctx, int64_t n, const int64_t* ids, const doub
  * chem_set_particles keeps reactions and rules alike. */
 int chem_reaction_set_resolution(chem_ctx* ctx, int reaction, int role, double lambda);
 
+/* ---- capped pair potentials ------------------------------------------------------------ */
+/* interaction.TabulatedCapped(itype, filename, cutoff, caprad) via VerletListTabulatedCapped, and LennardJonesCapped(epsilon,
+ * sigma, cutoff, caprad, shift) via VerletListLennardJonesCapped (gromacs_topology.py:619-621, 684-695, 895-897: nonbond_params
+ * func 13, label lj-tab_cap; put on the type pairs that react, so that two reactive beads can approach to the reaction cutoff
+ * without the steep core throwing them apart).  The arithmetic is in the external fork, so this rule set is this build's own
+ * ([EXT-RECALL], parity unpinned; DESIGN.md "Capped pairs").
+ *
+ * chem_nb_cap marks the LJ or table already registered for the symmetric type pair as capped at c = caprad; caprad <= 0
+ * removes the mark.  A potential that is re-sent later keeps its mark.  For every listed, non-excluded pair of a capped type
+ * pair with r^2 <= rc^2 (rc: that potential's cutoff):
+ *   - r_e = c if r^2 < c^2, else r: the decision is taken on the squares;
+ *   - F_i = (f(r_e) / r) r_ij, with f the potential's force magnitude: the interpolated force column for a table of any
+ *     itype, f(r) = 24 eps (2 (sigma/r)^12 - (sigma/r)^6) / r for LJ.  Inside the cap the force keeps the magnitude f(c) and
+ *     the direction of r_ij;
+ *   - the energy share is U(r_e), plus the LJ shift where the pair has one: constant inside the cap, in chem_obs.epot_tab /
+ *     epot_lj; the virial share is r.F of the force that was applied, f(c) r inside the cap;
+ *   - at r = 0 the force is exactly zero and finite (no NaN, no Inf), the energy is U(c);
+ *   - force and energy are continuous at r = c, so two precisions (or two ranks) that disagree on which side of c a pair lies
+ *     agree on what it contributes to within their rounding: no pair has to be set aside at the cap radius when results are
+ *     compared, unlike at the cutoff, where the force jumps;
+ *   - inside the cap the energy does not integrate the force (U is constant, F is not zero): a trajectory with overlapping
+ *     capped pairs does not conserve the total energy in NVE;
+ *   - uncapped type pairs behave exactly as without this call; a context without a capped pair launches the kernels it
+ *     launched before and allocates nothing;
+ *   - a type change by any route (reaction, neighbour rule, chem_modify_particle, resolution completion) moves a pair between
+ *     capped and uncapped type pairs from the next force evaluation on.
+ * CHEM_EINVAL: the type pair carries no LJ or table; caprad is non-finite; caprad >= rc of that potential (if a re-sent
+ * potential's rc no longer exceeds the radius, the next chem_run refuses with CHEM_EINVAL naming the pair); the type pair is
+ * also resolution-marked -- chem_nb_resolution on a capped pair is refused likewise.  Capped pairs and resolution-marked
+ * pairs on DIFFERENT type pairs are served together.  A context does not serve a Coulomb pair and a capped pair together:
+ * the next force evaluation refuses that with CHEM_ENOTIMPL naming the capped pair.  While a pair is capped the force
+ * kernels are built for option tpp = 1 (or 0) and pair_block = 512 only (CHEM_EINVAL at the next evaluation otherwise), and
+ * harmonic bonds are not evaluated inline, as for chem_nb_coulomb.  Caps are type-pair data: the same call on every rank of a
+ * decomposition. */
+int chem_nb_cap(chem_ctx* ctx, int t1, int t2, double caprad);
+
 /* ---- fixed distances: by-product release (FixDistances, ReleaseMolecule) --------------- */
 /* integrator.FixDistances(system, fix_list[, anchor_type, target_type]) + add_postprocess(PostProcessChangeProperty),
  * integrator.PostProcessReleaseParticles(fd, count) on a Reaction, analysis.NumFixDistances, and storage.addParticles after
