@@ -197,6 +197,7 @@ struct Ctx {
   int opt_ablate_list = 0;  // diagnostics (with debug_stamps): parts of the list build left out, see tools/rebuild_stamps.py
                             // (1 tables + staging only, 3 no peel, 5 exclusions ignored, 4 home particles behind the first pass of 512 skipped: the lists are incomplete)
   int opt_coop_overflow = 1; // list build: the home particles behind a tile's last full pass of 512 are swept by nine lanes each (dev_nlist_tile_f32)
+  int opt_row_order = 1;    // fused rebuild: a tile's force-list rows stored by length, the shortest in the last pass (chem_roworder_host.hpp); 0 = natural order
   int opt_tiles = 1;        // LDS-tiled list/force kernels when the cell grid allows
   int opt_fused = 1;        // rebuild chain as one persistent launch with grid barriers (single domain, tiles)
   int pair_guard = 0;       // 256 while the force kernels are launched speculatively (decomposed path)
@@ -258,6 +259,7 @@ struct Ctx {
   virtual void debug_enable(int) {}
   virtual int64_t debug_dump_rebuild(long long*, int64_t) { return 0; }
   virtual int64_t debug_force_list(int, int32_t*, int64_t) { return -1; }
+  virtual int64_t debug_row_order(int, int32_t*, int64_t) { return -1; }
   virtual void debug_tiles(int32_t* out) = 0;
   virtual void debug_acc(double* out) = 0;
   virtual void join_async() {}
@@ -368,6 +370,15 @@ template <typename R> struct CtxT : Ctx {
   int fused_grid = 0, fused_grid_diag = 0, fused_par = 0, seg_shift = 0, tseg_shift = 0; bool use_fused = false;
   DBuf<int> nlist, nn, nnh;
   DBuf<unsigned short> nl16;
+  // row order (option row_order): the staging regions of the fused rebuild's workgroups.  (Which home a stored row belongs to
+  // is written into nnh by every list build, so the option may change between two builds.)
+  DBuf<unsigned short> stage16; DBuf<int> stage_cnt; int stage_cap = 0;
+  bool row_on() const { return row_order_on(opt_row_order, use_fused, use_tiles, dd_on, S); }
+  void ensure_row_order() {
+    if (!row_on()) return;
+    stage_cap = row_stage_cap(n, box.ncell, HX * HY * HZ, tile_cap);
+    stage16.alloc((size_t)fused_grid * stage_cap * S); stage_cnt.alloc((size_t)fused_grid * stage_cap);
+  }
   DBuf<TileLDS<R>> tdesc;
   DBuf<long long> dbgbuf, wgst; bool dbg_on = false;
   Candidate* pin_ev = nullptr; size_t pin_ev_cap = 0;   // pinned host staging for reaction events
@@ -580,6 +591,7 @@ template <typename R> struct CtxT : Ctx {
     if (!gbar.p) { gbar.alloc(1); HIPCHK(hipMemsetAsync(gbar.p, 0, sizeof(GridBar), stream)); }
     HIPCHK(hipMemsetAsync(seg_tot.p, 0, sizeof(int) * 1024, stream));
     use_fused = true;
+    ensure_row_order();
   }
   DBuf<int> tile_pos, tile_ord;
   void setup_tile_order() {
@@ -603,6 +615,11 @@ template <typename R> struct CtxT : Ctx {
     a.tile_pos = opt_lpt ? tile_pos.p : nullptr; a.tile_ord = opt_lpt ? tile_ord.p : nullptr;
     a.desc = tdesc.p; a.excl_start = excl_start.p; a.excl_list = excl_list.p; a.nl16 = nl16.p; a.nnh = nnh.p; a.nlist = nlist.p; a.nn = nn.p;
     a.blockmax = blockmax.p; a.ctl = ctl.p; a.gb = gbar.p; a.box = box; a.act = act;
+    if (row_on()) {
+      ensure_row_order();
+      a.stage16 = stage16.p; a.stage_cnt = stage_cnt.p; a.stage_cap = stage_cap;
+      a.row_P = std::max(pair_bs / std::max(pick_tpp(), 1), 64);
+    }
     a.wgst = dbg_on && wgst.p ? wgst.p : nullptr;
     a.bstart = bstart.p; a.bent = bent.p; a.bwork = bwork.p; a.bj = bj.p; a.nbent = (int)std::min<int64_t>(nbent, 1 << 30);
     a.fold = fold_sd() ? (ensure_hflag(), foldmax.p) : nullptr;
@@ -663,6 +680,7 @@ template <typename R> struct CtxT : Ctx {
     // behind upload_particles' size allows for (57 particles in 2197 tiles: observe() wrote past the end, tests/test_gpu_geometry.py)
     eout.alloc(3 * std::max((size_t)cdiv((long long)ac * 64, 256), (size_t)ntiles) + 8);
     tm.nlist_capacity = S;
+    ensure_row_order();
   }
 
   void upload_particles() {
@@ -2638,8 +2656,17 @@ template <typename R> struct CtxT : Ctx {
       for (int sg = 0; sg < NHSEG; ++sg) {
         const int cnt = T.hoff[sg + 1] - T.hoff[sg];
         if (p < T.hstart[sg] || p >= T.hstart[sg] + cnt) continue;
-        const int q = T.hoff[sg] + (p - T.hstart[sg]), nhome = T.geom[4], hbase = T.geom[5];
+        int q = T.hoff[sg] + (p - T.hstart[sg]);
+        const int nhome = T.geom[4], hbase = T.geom[5];
+        {      // row order: the position that holds this home's row
+          std::vector<int> hw((size_t)nhome);
+          HIPCHK(hipMemcpy(hw.data(), nnh.p + hbase, sizeof(int) * (size_t)nhome, hipMemcpyDeviceToHost));
+          const auto it = std::find_if(hw.begin(), hw.end(), [q](int w) { return row_word_home(w) == q; });
+          if (it == hw.end()) return -1;
+          q = (int)(it - hw.begin());
+        }
         int n16 = 0; HIPCHK(hipMemcpy(&n16, nnh.p + hbase + q, sizeof(int), hipMemcpyDeviceToHost));
+        n16 = row_word_count(n16);
         int64_t m = 0;
         for (int c = 0; c * 8 < n16; ++c) {
           unsigned short ch[8];
@@ -2658,6 +2685,20 @@ template <typename R> struct CtxT : Ctx {
       }
     }
     return -1;
+  }
+  // diagnostic / tests: the stored order of one tile's force-list rows -- out[0 .. nh) = entries of the row at every position,
+  // out[nh .. 2 nh) = the home (index in the tile's cell-run order) it belongs to; returns nh, -1 without tiles
+  int64_t debug_row_order(int tile, int32_t* out, int64_t cap) override {
+    if (!use_tiles || !device_ready || tile < 0 || tile >= ntiles) return -1;
+    HIPCHK(hipStreamSynchronize(stream));
+    std::vector<TileLDS<R>> hd(1);
+    HIPCHK(hipMemcpy(hd.data(), tdesc.p + tile, sizeof(TileLDS<R>), hipMemcpyDeviceToHost));
+    const int nh = hd[0].geom[4], hbase = hd[0].geom[5];
+    if (!out) return nh;
+    if (cap < 2 * (int64_t)nh) throw ChemError(CHEM_ENOSPC, "debug_row_order: capacity");
+    if (nh > 0) HIPCHK(hipMemcpy(out, nnh.p + hbase, sizeof(int) * (size_t)nh, hipMemcpyDeviceToHost));
+    for (int k = 0; k < nh; ++k) { const int w = out[k]; out[k] = row_word_count(w); out[nh + k] = row_word_home(w); }
+    return nh;
   }
   int64_t debug_dump_rebuild(long long* out, int64_t cap) override {
     if (!dbg_on || !use_fused) return 0;
@@ -2678,7 +2719,7 @@ template <typename R> struct CtxT : Ctx {
     if (!device_ready || particles_dirty) return;
     std::vector<int> hn; (use_tiles ? nnh : nn).download(hn, acap(), stream);
     long long tot = 0;
-    if (use_tiles) { for (int k = 0; k < n; ++k) tot += hn[k]; } else { for (int k = G; k < G + n; ++k) tot += hn[k]; }
+    if (use_tiles) { for (int k = 0; k < n; ++k) tot += row_word_count(hn[k]); } else { for (int k = G; k < G + n; ++k) tot += hn[k]; }
     tm.nlist_entries = tot; tm.nlist_capacity = S;
   }
 
@@ -3562,6 +3603,7 @@ int chem_set_option(chem_ctx* ctx, const char* name, double value) {
   else if (k == "dd_fold") CTX.opt_dd_fold = value != 0;
   else if (k == "dd_fastx") { CTX.opt_dd_fastx = value != 0; CTX.resort = true; }
   else if (k == "coop_overflow") { CTX.opt_coop_overflow = value != 0 ? 1 : 0; CTX.resort = true; }
+  else if (k == "row_order") { CTX.opt_row_order = value != 0 ? 1 : 0; CTX.resort = true; }
   else if (k == "lpt_tiles") { CTX.opt_lpt = value != 0; CTX.resort = true; }
   else if (k == "tiles") { CTX.opt_tiles = value != 0; CTX.geom_dirty = true; }
   else if (k == "fused_rebuild") { CTX.opt_fused = value != 0; CTX.geom_dirty = true; }
@@ -3609,6 +3651,8 @@ int64_t chem_debug_idle_wrong_skips(chem_ctx* ctx) { return ctx && ctx->c ? ctx-
 int64_t chem_debug_idle_timeouts(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->idle_timeouts : -1; }
 // tests (unlisted): out[0] = DevCtl::acc_ref, out[1] = DevCtl::acc_maxdist after the last call
 int64_t chem_debug_acc(chem_ctx* ctx, double* out) { try { ctx->c->debug_acc(out); return 0; } catch (...) { return -2; } }
+// ... the stored order of a tile's force-list rows (option row_order): counts by position, then the home of every position; returns the tile's home count
+int64_t chem_debug_row_order(chem_ctx* ctx, int32_t tile, int32_t* out, int64_t cap) { try { return ctx->c->debug_row_order(tile, out, cap); } catch (...) { return -2; } }
 int64_t chem_debug_force_list(chem_ctx* ctx, int32_t tag, int32_t* out, int64_t cap) { try { return ctx->c->debug_force_list(tag, out, cap); } catch (...) { return -2; } }
 
 int chem_comm_unique_id(char uid[128]) {

@@ -15,6 +15,7 @@
 #include "../../include/chem_philox.h"
 #include "chem_geom_host.hpp"
 #include "chem_idle_host.hpp"
+#include "chem_roworder_host.hpp"
 
 namespace chem {
 
@@ -1723,6 +1724,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 //               the force kernel every step.  Layout is tile-major and transposed: the 8-slot chunk c
 //               of home particle q of a tile lives at  base + (c*nhome + q)*8,  so that consecutive
 //               lanes (= consecutive home particles) read consecutive 16-byte words.
+//               nnh holds one word per stored row: its entries in the lower half, in the upper half the home particle (index
+//               in the tile's cell-run order) the row belongs to -- the natural order here, q itself; the fused rebuild may
+//               store a tile's rows in another order (dev_row_order, chem_roworder_host.hpp).
 //   nlist/nn  : int32 global indices of ALL non-excluded pairs within rc+skin (the Verlet list the
 //               reaction scan and diagnostics traverse) -- only when `nlist` is non-null.
 // One lane per home particle walks the nine x-runs of its 27-cell stencil in the staged LDS image:
@@ -1734,9 +1738,12 @@ template <typename R, int BS>
 __device__ __forceinline__ void dev_nlist_tile(const TileLDS<R>& T, Vec4<R>* const sx, const int* tag, const R rl2,
                                                const int* excl_start, const int* excl_list, const int has_excl, const ActMask& act,
                                                unsigned short* nl16, const int S16, int* nnh, int* nlist, const int S, int* nn, DevCtl* ctl,
-                                               const Box<R>* bx = nullptr, const int* rtag = nullptr, const Vec4<R>* x4 = nullptr, const R rl2_rows_ = (R)-1) {
+                                               const Box<R>* bx = nullptr, const int* rtag = nullptr, const Vec4<R>* x4 = nullptr, const R rl2_rows_ = (R)-1,
+                                               const int hbase_out = -1) {
+    // (hbase_out >= 0: the rows and counts go to that row base of nl16 / nnh instead of the tile's own -- the staging region of
+    //  the row order, see dev_row_order)
     const R rl2_rows = rl2_rows_ > (R)0 ? rl2_rows_ : rl2;   // int32 Verlet rows: the workload's rc+skin (see dev_nlist_tile_f32)
-    const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4], hbase = T.geom[5];
+    const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4], hbase = hbase_out >= 0 ? hbase_out : T.geom[5];
     unsigned short* reg16 = nl16 + (size_t)hbase * S16;
     for (int q = threadIdx.x; q < nhome; q += BS) {
       int sgi = 0;
@@ -1850,7 +1857,7 @@ __device__ __forceinline__ void dev_nlist_tile(const TileLDS<R>& T, Vec4<R>* con
       // pad the last chunk with the far-away dummy slot (chunks are read whole)
       const int real16 = cnt16;
       if (real16 <= S16) while (cnt16 & 7) push((unsigned int)total);
-      nnh[hbase + q] = real16 < S16 ? real16 : S16;
+      nnh[hbase + q] = row_word(real16 < S16 ? real16 : S16, q);
       if (real16 > S16) atomicMax(&ctl->nl_overflow, real16);
       if (row32) {
         const int c32 = cnt < S ? cnt : S;
@@ -1878,8 +1885,9 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
                                                    unsigned short* nl16, const int S16, int* nnh, int* nlist, const int S, int* nn, DevCtl* ctl,
                                                    const Box<RS>* bx, const int* rtag, const Vec4<RS>* x4, const int ablate = 0, const float rl2_rows_ = -1.f,
                                                    uint4* bslots = nullptr, const int* gtag = nullptr, const int real0 = 0, const int real1 = 0x7fffffff,
-                                                   const int coop_on = 0) {
-  // (gtag, real0, real1: slab decomposition -- index of a tag's GHOST copy on this rank, range of the real particles)
+                                                   const int coop_on = 0, const int hbase_out = -1) {
+  // (gtag, real0, real1: slab decomposition -- index of a tag's GHOST copy on this rank, range of the real particles;
+  //  hbase_out >= 0: row base of the rows and counts in nl16 / nnh instead of the tile's own, see dev_row_order)
   const float rl2_rows = rl2_rows_ > 0.f ? rl2_rows_ : rl2;   // int32 Verlet rows: the workload's rc+skin (the 16-bit force list may use a wider list skin)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1888,7 +1896,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
   const CHEM_LDS float* img = (const CHEM_LDS float*)l3;
   const CHEM_LDS unsigned int* tmask = (const CHEM_LDS unsigned int*)(l3 + L.tmask_off);
   const CHEM_LDS unsigned short* bnd = (const CHEM_LDS unsigned short*)(l3 + L.bnd_off);
-  const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4], hbase = T.geom[5];
+  const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4], hbase = hbase_out >= 0 ? hbase_out : T.geom[5];
   const bool nowin = T.geom[7] != 0;
   unsigned short* reg16 = nl16 + (size_t)hbase * S16;
   const float clen0 = (float)T.clen[0], clen1 = (float)T.clen[1], clen2 = (float)T.clen[2], subinv = (float)T.subinv;
@@ -2141,7 +2149,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     // pad the last chunk with the far-away dummy slot (chunks are read whole)
     const int real16 = cnt16;
     if (real16 <= S16) while (cnt16 & 7) push((unsigned int)total);
-    nnh[hbase + q] = ablate >= 2 ? (real16 < 0 ? 1 : 0) : (real16 < S16 ? real16 : S16);   // (diagnostic builds of the list leave no usable chunks)
+    nnh[hbase + q] = row_word(ablate >= 2 ? (real16 < 0 ? 1 : 0) : (real16 < S16 ? real16 : S16), q);   // (diagnostic builds of the list leave no usable chunks)
     if (real16 > S16) atomicMax(&ctl->nl_overflow, real16);
     if (row32) {
       const int c32 = cnt < S ? cnt : S;
@@ -2174,7 +2182,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     if (it < npass) {
       q = it * BS + (int)threadIdx.x;
       if (q >= nhome) q = -1;
-      if (ablate == 4 && q >= BS) { nnh[hbase + q] = 0; q = -1; }      // (diagnostic: what the sweeps behind the first pass cost)
+      if (ablate == 4 && q >= BS) { nnh[hbase + q] = row_word(0, q); q = -1; }      // (diagnostic: what the sweeps behind the first pass cost)
     } else if (it - npass < ncr) {
       qf = -1;
       const int q0 = nfull + 7 * wv + kRound * (it - npass), qc = q0 + hl;
@@ -2225,7 +2233,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
         if (row == 8) {      // e = the home's row count: pad the last chunk with the far-away dummy slot, as the one-lane sweep does
           const int real16 = e;
           if (real16 <= S16) for (; e & 7; ++e) regq[(size_t)(e >> 3) * nhome * 8 + (e & 7)] = (unsigned short)total;
-          nnh[hbase + qc] = real16 < S16 ? real16 : S16;
+          nnh[hbase + qc] = row_word(real16 < S16 ? real16 : S16, qc);
           if (real16 > S16) atomicMax(&ctl->nl_overflow, real16);
         }
       }
@@ -2544,15 +2552,19 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
 #ifndef CHEM_NT_PRE
 #define CHEM_NT_PRE 1
 #endif
+  // (row order, chem_roworder_host.hpp: position q of the tile's list holds the row of the home named in the upper half of
+  //  its count word; the count and the chunks go by position, the particle and its slot by the home)
   auto locate = [&](int q) {
+    const int cw = nnh[hbase + q];
+    const int qn = row_word_home(cw);
     int sgi = 0;
 #pragma unroll
-    for (int k = 1; k < NHSEG; ++k) sgi += (q >= T.hoff[k]) ? 1 : 0;
-    const int inrun = q - T.hoff[sgi];
+    for (int k = 1; k < NHSEG; ++k) sgi += (qn >= T.hoff[k]) ? 1 : 0;
+    const int inrun = qn - T.hoff[sgi];
     p = T.hstart[sgi] + inrun; qq = q;
     const int hr = (sgi / HY + 1) * SY + (sgi % HY + 1);
     hslot = T.rowoff[hr] + T.celloff[hr][1] + inrun;      // the home particle's own slot in the staged tile
-    cnt = nnh[hbase + q];
+    cnt = row_word_count(cw);
     if (bslots && !bond_rec) bwv = bslots[2 * (size_t)p];   // (inline bonds: first quad, issued with the list chunks, consumed after the pair loop)
 #pragma unroll
     for (int c = 0; c < NCH; ++c)                           // the tile's region is always allocated: safe before cnt is known
@@ -3086,6 +3098,55 @@ __device__ __forceinline__ int block_scan_excl(int v, int* total) {
   return off + incl - v;
 }
 
+// ---- row order of ONE tile's force list (option row_order; the rule and its reasons: chem_roworder_host.hpp).  The sweep has
+// written the tile's rows and counts into the workgroup's staging region (st16 / stcnt, the tile's own layout: chunk c of home
+// i at (c nhome + i) 8); here the rows are ranked by (chunks, natural index) -- a counting sort: per wave-pass of 64 homes and
+// class the ballot gives the count and every lane's place among its equals, an exclusive scan over (class, wave-pass) the
+// rest -- and copied to their positions in nl16, with their count words (entries, home).  Entry for entry the rows of the sweep.  `wc`: LDS scratch
+// of kRowClasses * (kRowStageMax / 64) words (the sweep's image: free behind the barrier).  P: rows per pass of the force kernel.
+template <int BS>
+__device__ __forceinline__ void dev_row_order(const int nhome, const int hbase, const int S16, const int P, const unsigned short* st16, int* stcnt,
+                                              unsigned short* nl16, int* nnh, int* wc) {
+  const int t = threadIdx.x, lane = lane_id();
+  const int NC = S16 / 8 + 1, NWP = (nhome + 63) >> 6;      // classes (cnt <= S16), wave-passes
+  __syncthreads();      // the sweep is over: its rows and counts are visible to the workgroup, its image is free
+  for (int i0 = (t & ~63); i0 < nhome; i0 += BS) {      // (wave-uniform)
+    const int i = i0 + lane;
+    const int cnt = i < nhome ? row_word_count(stcnt[i]) : 0;
+    const int k = i < nhome ? row_chunks(cnt) : -1;
+    int pre = 0;
+    for (int c = 0; c < NC; ++c) {
+      const unsigned long long m = __ballot(k == c);
+      if (k == c) pre = __popcll(m & lanemask_lt());
+      if (lane == 0) wc[c * NWP + (i0 >> 6)] = __popcll(m);
+    }
+    if (i < nhome) stcnt[i] = row_word(cnt, pre);      // (own word: the place among the equals of the wave-pass takes the home's half)
+  }
+  __syncthreads();
+  {
+    const int nwc = NC * NWP;
+    int carry = 0;
+    for (int base = 0; base < nwc; base += BS) {
+      const int k = base + t;
+      const int v = k < nwc ? wc[k] : 0;
+      int tot;
+      const int ex = block_scan_excl<BS>(v, &tot);
+      if (k < nwc) wc[k] = carry + ex;
+      carry += tot;
+    }
+    __syncthreads();
+  }
+  uint4* const reg = reinterpret_cast<uint4*>(nl16 + (size_t)hbase * S16);
+  for (int i = t; i < nhome; i += BS) {
+    const int v = stcnt[i], cnt = row_word_count(v), k = row_chunks(cnt);
+    const int pos = row_position(wc[k * NWP + (i >> 6)] + row_word_home(v), nhome, P);
+    nnh[hbase + pos] = row_word(cnt, i);
+    const uint4* src = reinterpret_cast<const uint4*>(st16) + i;
+    // (one chunk at a time: four in flight cost the kernel 68 bytes of scratch per lane more, a real call 52)
+    for (int c = 0; c < k; ++c) reg[(size_t)c * nhome + pos] = src[(size_t)c * nhome];
+  }
+}
+
 // ---- bonded work list: rebuilt together with the Verlet list (the particle order only changes
 // there).  bwork = compact list of the particles that own bonded entries (i, e0, e1), bj = the
 // entries' partner tags already resolved to particle indices.  The per-step kernel runs over the
@@ -3280,6 +3341,9 @@ template <typename R> struct FusedArgs {
   int* tile_pos;         // where the descriptor of tile t goes: inside every XCD's range the full-size tiles first, the short edge
                          // tiles last, so that the one-shot force launch (workgroup v reads desc[xcd_remap(v)]) ends on short blocks
   unsigned short* nl16; int *nnh, *nlist, *nn;
+  // row order (dev_row_order; stage16 == nullptr: off, the natural order): staging region of every workgroup, rows of
+  // stage_cap homes and their count words; rows per pass of the force kernel
+  unsigned short* stage16; int* stage_cnt; int stage_cap, row_P;
   unsigned long long* blockmax; DevCtl* ctl; GridBar* gb;
   const int* bstart; const BondedEntry* bent; int4 *bwork, *bj; int nbent;
   uint4* bslots;         // inline bonds (non-null: the bonded partners' LDS slots are recorded, eight words per particle)
@@ -3492,21 +3556,27 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
         int* dst = reinterpret_cast<int*>(&a.desc[pos_r ? pos_r[tile] : tile]);
         for (int k = t; k < (int)(sizeof(TileLDS<R>) / 4); k += BS) dst[k] = src[k];
       }
+      const bool ordered = a.stage16 && T.geom[4] <= a.stage_cap && !(f32list && ablate == 1);
+      const int sbase = ordered ? b * a.stage_cap : -1;      // row base of this workgroup's staging region
       if (f32list) {
         const ListLDS L = list_lds_layout(a.CAP, a.ntypes);
         list_stage_f32<R, BS>(T, chem_dyn_lds, L, a.CAP, a.x4o, a.act, a.ntypes);
         __syncthreads();
-        if (ablate == 1) { for (int q = t; q < T.geom[4]; q += BS) a.nnh[T.geom[5] + q] = 0; }
+        if (ablate == 1) { for (int q = t; q < T.geom[4]; q += BS) a.nnh[T.geom[5] + q] = row_word(0, q); }
         else
-        dev_nlist_tile_f32<R, BS>(T, chem_dyn_lds, L, a.tago, (float)a.rl2, a.excl_start, a.excl_list, a.bond_pass ? 0 : a.has_excl, a.nl16, a.S, a.nnh,
-                               (DIAG && a.want32) ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, ablate, (float)a.rl2_rows,
-                               a.bond_pass ? (uint4*)nullptr : a.bslots, nullptr, 0, 0x7fffffff, a.coop);
+        dev_nlist_tile_f32<R, BS>(T, chem_dyn_lds, L, a.tago, (float)a.rl2, a.excl_start, a.excl_list, a.bond_pass ? 0 : a.has_excl, ordered ? a.stage16 : a.nl16, a.S,
+                               ordered ? a.stage_cnt : a.nnh, (DIAG && a.want32) ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, ablate, (float)a.rl2_rows,
+                               a.bond_pass ? (uint4*)nullptr : a.bslots, nullptr, 0, 0x7fffffff, a.coop, sbase);
       } else {
         tile_fill<R, BS, true>(T, sx, a.CAP, a.x4o, 1);
         __syncthreads();
-        dev_nlist_tile<R, BS>(T, sx, a.tago, a.rl2, a.excl_start, a.excl_list, a.has_excl, a.act, a.nl16, a.S, a.nnh,
-                              a.want32 ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, a.rl2_rows);
+        dev_nlist_tile<R, BS>(T, sx, a.tago, a.rl2, a.excl_start, a.excl_list, a.has_excl, a.act, ordered ? a.stage16 : a.nl16, a.S, ordered ? a.stage_cnt : a.nnh,
+                              a.want32 ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, a.rl2_rows, sbase);
       }
+      // row order: the sweep went into this workgroup's staging region, the rows reach their places now.  A tile beyond the
+      // staging region (or a diagnostic build without rows) has been written in place, in the natural order.
+      if (ordered) dev_row_order<BS>(T.geom[4], T.geom[5], a.S, a.row_P, a.stage16 + (size_t)sbase * a.S, a.stage_cnt + sbase, a.nl16, a.nnh,
+                                     reinterpret_cast<int*>(chem_dyn_lds));
     }
     WGST(6);
     if (wst && t == 0) wst[7] = ndone;

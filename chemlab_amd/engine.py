@@ -443,6 +443,20 @@ class Engine:
             raise ChemError(int(m), "force list not available (no LDS tiles)")
         return buf[:m].copy()
 
+    def debug_row_order(self, tile):
+        """Diagnostic (tests): stored order of the force-list rows of tile descriptor `tile` (option row_order):
+        (entries of the row at every position, home -- index in the tile's cell-run order -- of every position)."""
+        lib = self.api.lib
+        lib.chem_debug_row_order.restype = C.c_int64
+        nh = lib.chem_debug_row_order(C.c_void_p(self.ctx), C.c_int32(int(tile)), None, C.c_int64(0))
+        if nh < 0:
+            raise ChemError(int(nh), "row order not available (no LDS tiles)")
+        buf = np.zeros(2 * max(int(nh), 1), dtype=np.int32)
+        m = lib.chem_debug_row_order(C.c_void_p(self.ctx), C.c_int32(int(tile)), buf.ctypes.data_as(C.c_void_p), C.c_int64(buf.size))
+        if m != nh:
+            raise ChemError(int(m), "row order read-back failed")
+        return buf[:nh].copy(), buf[nh:2 * nh].copy()
+
     def observe(self):
         o = _capi.Obs()
         self._ck(self.api.observe(self.ctx, C.byref(o)))
