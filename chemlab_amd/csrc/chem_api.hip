@@ -325,6 +325,7 @@ template <typename R> struct CtxT : Ctx {
   // fused rebuild (single domain, tiles): segment scans + grid barrier state
   DBuf<int> cell_loc, seg_tot, tile_n, tile_loc, tseg_tot, cell_n, bucket; int bcap = 0; DBuf<GridBar> gbar;
   DBuf<int> tile_cnt, tile_off;   // reaction scan on tiles: candidates per tile, their offsets
+  DBuf<int> tile_need;            // ... and the candidates every tile found, whether its region held them or not
   DBuf<unsigned int> scan_role;   // ... and the role bits of every particle slot (k_react_roles)
   DBuf<int4> bwork, bj; int nb_owner = 0; bool bwork_dirty = true;   // bonded work list (see dev_bonded_prep)
   // Inline bonds: all bonded terms are 2-body bonds of ONE harmonic parameter set and the exclusion set is exactly the bond
@@ -2066,8 +2067,10 @@ template <typename R> struct CtxT : Ctx {
     Trace trc("react");
     upload_restrictions();
     const bool any_cons = upload_constraint_bits();
-    launch_reaction_scan(ConnTable{restricted_mask ? conn_start.p : nullptr, conn_partner.p, conn_mask.p, any_cons ? cons_ok.p : nullptr});
-    const DevCtl h = read_ctl();
+    const ConnTable conn{restricted_mask ? conn_start.p : nullptr, conn_partner.p, conn_mask.p, any_cons ? cons_ok.p : nullptr};
+    launch_reaction_scan(conn);
+    DevCtl h = read_ctl();
+    if (h.cand_overflow && use_tiles && rescan_crowded_tiles(conn)) h = read_ctl();
     trc.lap("scan");
     if (h.cand_overflow) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow");
     const int nc = dd_on ? gather_candidates(h.cand_count) : h.cand_count;
@@ -2129,12 +2132,13 @@ template <typename R> struct CtxT : Ctx {
     Candidate* cdst = dd_on ? cand_loc.p : cand.p;
     if (use_tiles) {
       const int region_cap = std::max(1, cand_cap / std::max(ntiles, 1));
-      tile_cnt.alloc(ntiles + 1); tile_off.alloc(ntiles + 1);
+      tile_cnt.alloc(ntiles + 1); tile_off.alloc(ntiles + 1); tile_need.alloc(ntiles + 1);
       if (scan_role.n < (size_t)acap()) scan_role.alloc((size_t)acap() + 1024);
       hipLaunchKernelGGL(k_react_roles<R>, dim3(std::min(cdiv(acap(), 256), 4096)), dim3(256), 0, stream, acap(), nglob, x4.p, tag.p, state.p, rs_dev.p, scan_role.p);
       hipLaunchKernelGGL((k_react_scan_tiles<R, 512>), dim3(ntiles), dim3(512), scan_roles_staged() ? scan_lds_bytes() : tile_lds_bytes(), stream, ntiles, tile_cap, x4.p, tag.p, tdesc.p, state.p,
                          res_id.p, mol_id.p, boxd, rs_dev.p, evout.p, region_cap, tile_cnt.p, ctl.p, (R)(0.5 * skin_eff()),
-                         has_excl ? (const int*)excl_start.p : (const int*)nullptr, (const int*)excl_list.p, conn, (const unsigned int*)scan_role.p, scan_roles_staged() ? 1 : 0);
+                         has_excl ? (const int*)excl_start.p : (const int*)nullptr, (const int*)excl_list.p, conn, (const unsigned int*)scan_role.p, scan_roles_staged() ? 1 : 0,
+                         (const int*)nullptr, tile_need.p);
       hipLaunchKernelGGL(k_cand_offsets, dim3(1), dim3(1024), 0, stream, ntiles, tile_cnt.p, tile_off.p, ctl.p);
       hipLaunchKernelGGL(k_cand_gather, dim3(std::min(ntiles, 2048)), dim3(256), 0, stream, ntiles, evout.p, region_cap, tile_cnt.p, tile_off.p, cdst, cand_cap, ctl.p);
     } else {
@@ -2142,6 +2146,26 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL(k_react_scan<R>, dim3(cdiv((long long)n * 8, 256)), dim3(256), 0, stream, G, n, x4.p, tag.p, nlist.p, nn.p, S, state.p,
                          res_id.p, mol_id.p, boxd, rs_dev.p, cdst, cand_cap, ctl.p, conn);
     }
+  }
+
+  // The regions of the tile scan hold cand_cap / ntiles records each, a share of the MEAN density: a cluster in a dilute box
+  // fills the regions of its few tiles while the candidate array is almost empty.  The scan counted on (tile_need), so when
+  // the total fits cand_cap -- the documented capacity -- the tiles are scanned once more, each writing at its exclusive
+  // offset straight into the candidate array (no gather).  Taken only after an overflow; a step whose regions sufficed
+  // launches what it always launched.  Returns false when the candidates really exceed cand_cap (the flag stays set).
+  bool rescan_crowded_tiles(const ConnTable conn) {
+    std::vector<int> need;
+    tile_need.download(need, (size_t)ntiles, stream);
+    long long tot = 0;
+    for (int v : need) tot += v;
+    if (tot > cand_cap) return false;
+    set_ctl_field(&DevCtl::cand_overflow, 0);
+    hipLaunchKernelGGL(k_cand_offsets, dim3(1), dim3(1024), 0, stream, ntiles, tile_need.p, tile_off.p, ctl.p);
+    hipLaunchKernelGGL((k_react_scan_tiles<R, 512>), dim3(ntiles), dim3(512), scan_roles_staged() ? scan_lds_bytes() : tile_lds_bytes(), stream, ntiles, tile_cap, x4.p, tag.p, tdesc.p, state.p,
+                       res_id.p, mol_id.p, boxd, rs_dev.p, dd_on ? cand_loc.p : cand.p, 0, tile_cnt.p, ctl.p, (R)(0.5 * skin_eff()),
+                       has_excl ? (const int*)excl_start.p : (const int*)nullptr, (const int*)excl_list.p, conn, (const unsigned int*)scan_role.p, scan_roles_staged() ? 1 : 0,
+                       (const int*)tile_off.p, tile_need.p);
+    return true;
   }
 
   // A boundary pair is seen by two ranks (real-ghost on each); the scan emits it only where the
@@ -2152,15 +2176,22 @@ template <typename R> struct CtxT : Ctx {
     const std::vector<int> cnts = allgather_counts(nc);
     int mx = 0, tot = 0;
     for (int v : cnts) { mx = std::max(mx, v); tot += v; }
-    if ((long long)mx * P > cand_cap || tot > cand_cap) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow (gathered)");
+    if (tot > cand_cap) throw ChemError(CHEM_ENOSPC, "reaction candidate buffer overflow (gathered)");
     if (mx > 0) {
-      // padded all-gather into evout (scratch here), then compaction into cand in rank order
-      HIPCHK(hipMemcpyAsync(evout.p + (size_t)rk * mx, cand_loc.p, sizeof(Candidate) * nc, hipMemcpyDeviceToDevice, stream));
-      tr->allgather(evout.p + (size_t)rk * mx, evout.p, sizeof(Candidate) * mx, stream);
-      int off = 0;
-      for (int r = 0; r < P; ++r) {
-        if (cnts[r]) HIPCHK(hipMemcpyAsync(cand.p + off, evout.p + (size_t)r * mx, sizeof(Candidate) * cnts[r], hipMemcpyDeviceToDevice, stream));
-        off += cnts[r];
+      // padded all-gather into evout (scratch here, cand_cap records), then compaction into cand in rank order.  The padding
+      // is P times the largest share: where that exceeds the scratch (a cluster inside one slab) the shares travel in pieces
+      // of cand_cap / P records; otherwise in one piece
+      const int piece = std::min(mx, cand_cap / P);
+      for (int base = 0; base < mx; base += piece) {
+        const int mine = std::max(0, std::min(piece, nc - base));
+        if (mine) HIPCHK(hipMemcpyAsync(evout.p + (size_t)rk * piece, cand_loc.p + base, sizeof(Candidate) * mine, hipMemcpyDeviceToDevice, stream));
+        tr->allgather(evout.p + (size_t)rk * piece, evout.p, sizeof(Candidate) * piece, stream);
+        int off = 0;
+        for (int r = 0; r < P; ++r) {
+          const int m = std::max(0, std::min(piece, cnts[r] - base));
+          if (m) HIPCHK(hipMemcpyAsync(cand.p + off + base, evout.p + (size_t)r * piece, sizeof(Candidate) * m, hipMemcpyDeviceToDevice, stream));
+          off += cnts[r];
+        }
       }
     }
     return tot;

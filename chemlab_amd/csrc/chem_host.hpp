@@ -215,26 +215,32 @@ struct HostTopology {
   void graph_add(int32_t a, int32_t b) { sorted_insert(graph[a], b); sorted_insert(graph[b], a); }
 
   // relabel the bonded cluster containing a (a-b already linked).  Labels: res_id takes
-  // min(res_id[a],res_id[b]) (reaction.cfg: "the residue id will be transfered"), mol_id the
-  // lowest tag of the cluster.  `touched` collects tags whose labels changed.
+  // min(res_id[a],res_id[b]) as they are when this bond's turn comes (reaction.cfg: "the residue id
+  // will be transfered"; the rule of chem_reaction_init), mol_id the lowest tag of the cluster.  That
+  // minimum is taken over the WHOLE cluster: the bonds of a step are linked before the first
+  // relabelling, so the cluster may reach beyond the clusters a and b came from.
+  // `touched` collects tags whose labels changed.
   std::vector<uint32_t> visit_stamp;   // flood-fill marks (epoch stamped, no per-call allocation)
   uint32_t visit_epoch = 0;
   std::vector<int32_t> flood_stack;
 
   void merge_cluster(int32_t a, int32_t b, bool relabel_res, std::vector<int32_t>& touched) {
     const int32_t new_res = std::min(res_id[a], res_id[b]);
-    const int32_t new_mol = std::min(mol_id[a], mol_id[b]);
+    int32_t new_mol = std::min(mol_id[a], mol_id[b]);
     if (visit_stamp.size() != (size_t)n) { visit_stamp.assign((size_t)n, 0); visit_epoch = 0; }
     if (++visit_epoch == 0) { std::fill(visit_stamp.begin(), visit_stamp.end(), 0); visit_epoch = 1; }
     flood_stack.clear(); flood_stack.push_back(a);
     visit_stamp[a] = visit_epoch;
-    while (!flood_stack.empty()) {
-      int32_t p = flood_stack.back(); flood_stack.pop_back();
+    for (size_t h = 0; h < flood_stack.size(); ++h) {      // the flood fill leaves the members of the cluster in flood_stack
+      const int32_t p = flood_stack[h];
+      new_mol = std::min(new_mol, mol_id[p]);
+      for (int32_t nb : graph[p]) if (visit_stamp[nb] != visit_epoch) { visit_stamp[nb] = visit_epoch; flood_stack.push_back(nb); }
+    }
+    for (int32_t p : flood_stack) {
       bool ch = false;
       if (relabel_res && res_id[p] != new_res) { res_id[p] = new_res; ch = true; }
       if (mol_id[p] != new_mol) { mol_id[p] = new_mol; ch = true; }
       if (ch) touched.push_back(p);
-      for (int32_t nb : graph[p]) if (visit_stamp[nb] != visit_epoch) { visit_stamp[nb] = visit_epoch; flood_stack.push_back(nb); }
     }
   }
 

@@ -3905,7 +3905,11 @@ __global__ __launch_bounds__(BS, 4) void k_react_scan_tiles(int ntiles, int CAP,
                                                             const ReactSet* __restrict__ rs_g, Candidate* __restrict__ region, int region_cap,
                                                             int* __restrict__ tile_count, DevCtl* ctl, R slack,
                                                             const int* __restrict__ excl_start, const int* __restrict__ excl_list, ConnTable conn,
-                                                            const unsigned int* __restrict__ role, int roles_staged) {      // (roles_staged 0: the image leaves no room behind it -- role words from global memory)
+                                                            const unsigned int* __restrict__ role, int roles_staged,      // (roles_staged 0: the image leaves no room behind it -- role words from global memory)
+                                                            const int* __restrict__ direct_off, int* __restrict__ tile_need) {
+  // tile_need[tile]: the candidates the tile found, however many fitted its region.  Second pass of a step in which a region was
+  // too small (direct_off != nullptr; rescan_crowded_tiles): `region` is the candidate array itself, the tile writes its
+  // tile_need[tile] records at direct_off[tile], the exclusive scan of tile_need.
   __shared__ TileLDS<R> T;
   __shared__ ReactSet rs;
   __shared__ int s_cnt;
@@ -3932,7 +3936,8 @@ __global__ __launch_bounds__(BS, 4) void k_react_scan_tiles(int ntiles, int CAP,
     const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4];
     if (roles_staged && threadIdx.x == 0 && total < CAP) sr[total] = 0u;      // (the far-away dummy slot: no role)
     __syncthreads();
-    Candidate* out = region + (size_t)tile * region_cap;
+    Candidate* out = direct_off ? region + direct_off[tile] : region + (size_t)tile * region_cap;
+    const int cap = direct_off ? tile_need[tile] : region_cap;
     for (int q = threadIdx.x; q < nhome; q += BS) {
       int sgi = 0;
 #pragma unroll
@@ -4021,7 +4026,7 @@ __global__ __launch_bounds__(BS, 4) void k_react_scan_tiles(int ntiles, int CAP,
             chem_philox::reaction_draw(rs.seed, rs.step, (uint32_t)tgi, (uint32_t)tgj, (uint32_t)k, rr);
             if (R_.prob < 1.0 && !(chem_philox::u01(rr[0]) < R_.prob)) continue;
             const int idx = atomicAdd(&s_cnt, 1);
-            if (idx < region_cap) out[idx] = fwd ? Candidate{tgi, tgj, k, rr[1], d2} : Candidate{tgj, tgi, k, rr[1], d2};   // tgi < tgj: forward role assignment wins
+            if (idx < cap) out[idx] = fwd ? Candidate{tgi, tgj, k, rr[1], d2} : Candidate{tgj, tgi, k, rr[1], d2};   // tgi < tgj: forward role assignment wins
             else ctl->cand_overflow = 1;
           }
           }
@@ -4029,7 +4034,7 @@ __global__ __launch_bounds__(BS, 4) void k_react_scan_tiles(int ntiles, int CAP,
       }
     }
     __syncthreads();
-    if (threadIdx.x == 0) tile_count[tile] = s_cnt < region_cap ? s_cnt : region_cap;
+    if (threadIdx.x == 0) { tile_count[tile] = s_cnt < cap ? s_cnt : cap; if (!direct_off) tile_need[tile] = s_cnt; }
   }
 }
 

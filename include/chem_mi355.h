@@ -497,7 +497,18 @@ int chem_cap_force(chem_ctx* ctx, double max_force);
 
 /* ---- reactions ----------------------------------------------------------------------- */
 /* integrator.ChemicalReaction(system, vl, storage, tm, interval) + .nearest_mode
- * + .max_per_interval  reaction_setup.py:416-427 */
+ * + .max_per_interval  reaction_setup.py:416-427
+ * Capacity: a reaction step holds at most max(8 * N, 1024) candidates (N particles of the whole system; a candidate is a pair
+ * and a reaction that passed every filter and its acceptance draw, before the one-event-per-particle resolve).  A step that
+ * finds more fails chem_run with CHEM_ENOSPC "reaction candidate buffer overflow" and applies nothing; fewer events are never
+ * reported instead.  The limit is on the total alone: where in the box the candidates sit does not matter (one rank of a
+ * decomposition: the candidates it finds, and the gathered total).
+ * Labels: a bond-forming event joins two bonded clusters.  All bonds of the step are put into the bond graph first; then,
+ * for the step's bonds (a, b) in (min id, max id) order, every particle of the cluster that now holds a and b gets
+ * res_id = min(res_id[a], res_id[b]) as these two are at that moment (the residue id is transferred from the bond's own ends:
+ * where several bonds of one step join one cluster, the first of them decides, and that need not be the lowest res_id in the
+ * cluster) and mol_id = the lowest particle of the cluster (CHEM_STATE_MOLID).  The next reaction step's intramolecular /
+ * intraresidual filters read these. */
 int chem_reaction_init(chem_ctx* ctx, int interval, int nearest, int max_per_interval, uint64_t seed);
 /* ar.add_reaction(Reaction(...))  reaction_setup.py:81-92,506; returns the reaction index */
 int chem_reaction_add(chem_ctx* ctx, const chem_reaction_desc* d);

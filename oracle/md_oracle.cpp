@@ -551,17 +551,20 @@ static void exclude(Orc& o, int32_t a, int32_t b) {
 }
 
 // relabel the bonded cluster containing `start` with the minimum res_id / tag it holds
-static void merge_cluster(Orc& o, int32_t a, int32_t b) {
-  int32_t new_res = std::min(o.res_id[a], o.res_id[b]);
+static void merge_cluster(Orc& o, int32_t a, int32_t b, bool relabel_res = true) {
+  const int32_t new_res = std::min(o.res_id[a], o.res_id[b]);   // the residue id is transferred from this bond's two ends, as they are now
   int32_t new_mol = std::min(o.mol_id[a], o.mol_id[b]);
-  // flood fill from a over the bond graph (a-b is already in the graph)
-  std::vector<int32_t> stack{a};
+  // flood fill from a over the bond graph (a-b is already in the graph, and so are the other bonds of this step: the
+  // cluster may reach beyond the clusters a and b came from, so the lowest tag is taken over all of it)
+  std::vector<int32_t> stack{a}, members;
   std::set<int32_t> vis{a};
   while (!stack.empty()) {
     int32_t p = stack.back(); stack.pop_back();
-    o.res_id[p] = new_res; o.mol_id[p] = new_mol;
+    members.push_back(p);
+    new_mol = std::min(new_mol, o.mol_id[p]);
     for (int32_t nb : o.graph[p]) if (vis.insert(nb).second) stack.push_back(nb);
   }
+  for (int32_t p : members) { if (relabel_res) o.res_id[p] = new_res; o.mol_id[p] = new_mol; }
 }
 
 // try to place (t[0..arity)) into the first list of that arity whose registered type tuples match
@@ -888,11 +891,7 @@ int orc_list_add(void* c, int list, int64_t n, const int64_t* ids) {
   }
   // bonds feed the topology graph (TopologyManager.observe_tuple + initialize_topology)
   for (auto& e : nb) { o.graph[e.first].insert(e.second); o.graph[e.second].insert(e.first); }
-  for (auto& e : nb) {
-    int32_t new_mol = std::min(o.mol_id[e.first], o.mol_id[e.second]);
-    std::vector<int32_t> st{e.first}; std::set<int32_t> vis{e.first};
-    while (!st.empty()) { int32_t p = st.back(); st.pop_back(); o.mol_id[p] = new_mol; for (int32_t q : o.graph[p]) if (vis.insert(q).second) st.push_back(q); }
-  }
+  for (auto& e : nb) merge_cluster(o, e.first, e.second, false);
   return 0;
 }
 

@@ -40,14 +40,15 @@ def model(n, types, res, init_bonds, reg, batches):
         new = [(a, b) for a, b in batch if add_bond(a, b)]
         for a, b in new:
             graph[a].add(b); graph[b].add(a)
-        for a, b in new:                                   # labels: flood the merged cluster, in event order
-            nr, nm = min(res[a], res[b]), min(mol[a], mol[b])
-            stack, seen = [a], {a}
+        for a, b in new:                                   # labels: flood the merged cluster (all bonds of the batch are in the graph), in event order;
+            stack, seen = [a], {a}                         # the residue id comes from the bond's two ends, mol is the lowest of the WHOLE cluster
             while stack:
-                p = stack.pop(); res[p] = nr; mol[p] = nm
-                for q in graph[p]:
+                for q in graph[stack.pop()]:
                     if q not in seen:
                         seen.add(q); stack.append(q)
+            nr, nm = min(res[a], res[b]), min(mol[p] for p in seen)
+            for p in seen:
+                res[p] = nr; mol[p] = nm
         for a, b in new:
             excl[a].add(b); excl[b].add(a)
             cands = [(x, a, b) for x in sorted(graph[a]) if x != b] + [(a, b, m) for m in sorted(graph[b]) if m != a]
