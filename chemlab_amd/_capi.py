@@ -89,6 +89,15 @@ class FixRecord(C.Structure):
     _fields_ = [("step", C.c_int64), ("anchor_id", C.c_int64), ("target_id", C.c_int64), ("set", C.c_int32), ("cause", C.c_int32)]
 
 
+class NbRemove(C.Structure):
+    _fields_ = [("reaction", C.c_int32), ("invoke_on", C.c_int32), ("anchor_type", C.c_int32), ("nb_level", C.c_int32),
+                ("type_1", C.c_int32), ("type_2", C.c_int32), ("unexclude", C.c_int32), ("pad", C.c_int32)]
+
+
+class BondRecord(C.Structure):
+    _fields_ = [("step", C.c_int64), ("id_near", C.c_int64), ("id_far", C.c_int64), ("list", C.c_int32), ("reaction", C.c_int32)]
+
+
 class Obs(C.Structure):
     _fields_ = [("step", C.c_int64), ("npart", C.c_int64), ("ekin", C.c_double),
                 ("temperature", C.c_double), ("epot_lj", C.c_double), ("epot_tab", C.c_double),
@@ -190,6 +199,11 @@ PRODUCT_ONLY = {
     "fix_count": (_i64, [_P, _i]),
     "fix_get": (_i64, [_P, _i, _pi64, _pd, _i64]),
     "fix_log": (_i64, [_P, C.POINTER(FixRecord), _i64]),
+    # reverse reactions: bond removal and join by a reaction (the CPU oracle has neither)
+    "reaction_remove_bond": (_i, [_P, C.POINTER(NbRemove)]),
+    "reaction_removed": (_i64, [_P, C.POINTER(BondRecord), _i64]),
+    "reaction_join": (_i, [_P, _i, _i, _i, _d]),
+    "fix_joins": (_i64, [_P, C.POINTER(FixRecord), _i64]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

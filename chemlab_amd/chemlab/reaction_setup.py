@@ -129,6 +129,12 @@ class SetupReactions(object):
             return self._setup_atrp_activator(cfg), None
         if cfg.get("ext_type") == "ReleaseMolecule":
             return self._setup_release_molecule(cfg)
+        if cfg.get("ext_type") in ("JoinMolecule", "RemoveNeighboursBonds"):
+            # The engine is asked first, before anything of the section is parsed: the CPU checker has no reverse reactions
+            # and answers with NotImplementedError naming the extension, whatever keys the section holds.
+            if not self.system.engine.supports("reaction_join" if cfg["ext_type"] == "JoinMolecule" else "reaction_remove_bond"):
+                raise NotImplementedError("reaction extension %s (%s): the CPU checker has no reverse reactions" % (name, cfg["ext_type"]))
+            return self._setup_join_molecule(cfg) if cfg["ext_type"] == "JoinMolecule" else self._setup_remove_neighbour_bonds(cfg)
         if cfg.get("ext_type") != "ChangeNeighboursProperty":
             raise NotImplementedError("reaction extension %s (%s) is outside the hot-path scope (SURVEY f-4)" % (name, cfg.get("ext_type")))
         e, n2t = self.espp, self.name2type
@@ -208,6 +214,51 @@ class SetupReactions(object):
         self.use_thermal_group = True        # the dummies must not be thermalised
         return release_pp, invoke_on
 
+    def _setup_remove_neighbour_bonds(self, cfg):
+        """[ext_*] ext_type=RemoveNeighboursBonds (reaction_post_process.py:117-137): `bonds_to_remove=ANCHOR->T1:T2:level,...`;
+        on every event the bonds T1 - T2 found `level` bonds from a reactant of type ANCHOR leave the lists."""
+        e, n2t = self.espp, self.name2type
+        pp = e.integrator.PostProcessRemoveNeighbourBond(self.tm)
+        invoke_on = cfg.get("invoke_on", "both")
+        for item in cfg["bonds_to_remove"].split(","):
+            anchor, pair = item.split("->")
+            t1, t2, nb_level = pair.split(":")
+            pp.add_bond_to_remove(n2t[anchor.strip()], int(nb_level), n2t[t1.strip()], n2t[t2.strip()])
+            self.dynamic_types.update((n2t[anchor.strip()], n2t[t1.strip()], n2t[t2.strip()]))
+        return pp, invoke_on
+
+    def _setup_join_molecule(self, cfg):
+        """[ext_*] ext_type=JoinMolecule (reaction_post_process.py:322-362), the reverse of ReleaseMolecule: a new dummy type;
+        an EMPTY FixDistances set with the type condition (host_type, dummy) whose post-process turns a released dummy into
+        `target_type` at lambda = init_res; on every event the type_1 reactant takes the type_2 reactant as a dummy at
+        eq_length (PostProcessJoinParticles), and the type_2 reactant of type `final_type` becomes the dummy type at
+        lambda = init_res.  Returns two post-processes.  (The change to the dummy type names the mass of final_type: a
+        particle keeps its mass when it becomes a dummy, which the reference says by naming none.)"""
+        e, topol = self.espp, self.topol
+        host_type_id = topol.atomsym_atomtype[cfg["host_type"]]
+        target_type = cfg["target_type"]
+        target_type_id = topol.atomsym_atomtype[target_type]
+        target_properties = topol.gt.atomtypes[target_type]
+        eq_length, init_res = float(cfg["eq_length"]), float(cfg["init_res"])
+        final_type = cfg.get("final_type", target_type)
+        final_type_id = topol.atomsym_atomtype[final_type]
+        dummy_type_id = max(topol.atomsym_atomtype.values()) + 1
+        topol.add_new_atomtype(dummy_type_id, "DUMMY_%d" % dummy_type_id, False)
+        fd = e.integrator.FixDistances(self.system, [], host_type_id, dummy_type_id)
+        fxd_pp = e.integrator.PostProcessChangeProperty()
+        fxd_pp.add_change_property(dummy_type_id, e.integrator.TopologyParticleProperties(
+            type=target_type_id, mass=target_properties["mass"], state=target_properties.get("state", 0), lambda_adr=init_res))
+        fd.add_postprocess(fxd_pp)
+        self.system.integrator.addExtension(fd)
+        self.fix_distances.append(fd)
+        join_pp = e.integrator.PostProcessJoinParticles(fd, eq_length)
+        dummy_pp = e.integrator.PostProcessChangeProperty()
+        dummy_pp.add_change_property(final_type_id, e.integrator.TopologyParticleProperties(
+            type=dummy_type_id, mass=topol.gt.atomtypes[final_type]["mass"], lambda_adr=init_res, state=target_properties.get("state", 0)))
+        self.dynamic_types.update((host_type_id, target_type_id, final_type_id, dummy_type_id))
+        self.use_thermal_group = True        # the dummies must not be thermalised
+        return [(join_pp, "type_1"), (dummy_pp, "type_2")]
+
     def _setup_atrp_activator(self, cfg):
         """[ext_*] ext_type=ATRPActivator -> integrator extension (reaction_post_process.py:380-426):
         options=`TYPE(state,A|DA)->NEWTYPE(delta);...`, flag DA marks the centres that react with the deactivator."""
@@ -242,7 +293,10 @@ class SetupReactions(object):
         if g["max_per_interval"] > 0:
             ar.max_per_interval = g["max_per_interval"]
         for gname, group in self.cfg["reactions"].items():
-            group_ext = [(name, self._setup_extension(name)) for name in group["extensions"]]
+            group_ext = []
+            for name in group["extensions"]:        # (an extension may bring several post-processes: JoinMolecule brings two)
+                made = self._setup_extension(name)
+                group_ext.extend((name, v) for v in (made if isinstance(made, list) else [made]))
             # integrator extensions (ATRPActivator) go to the driver, post-processes to the group's reactions (reaction_setup.py:470-483)
             self.extensions_to_integrator.extend(x for _, (x, inv) in group_ext if inv is None)
             group_pp = [(name, v) for name, v in group_ext if v[1] is not None and v[0] is not None]      # (ReleaseMolecule on a type change: nothing to attach)

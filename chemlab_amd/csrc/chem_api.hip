@@ -144,6 +144,12 @@ struct Ctx {
   int assoc_row(int pub) const { return pub >= 0 && pub < (int)pub_map.size() && pub_map[pub] >= 0 ? pub_map[pub] : -1; }
   int public_index(int arena_r) const { return arena_r >= 0 ? assoc_pub[arena_r] : diss_pub[~arena_r]; }
   std::vector<chem_nb_change> nb_rules;   // PostProcessChangeNeighboursProperty (chem_reaction_neighbour_change)
+  // Reverse reactions: PostProcessRemoveNeighbourBond (chem_reaction_remove_bond; rules keyed by the row of `reactions`, the log
+  // by tags and the public index) and PostProcessJoinParticles (chem_reaction_join: fix.joins).  Both act in reverse_step().
+  std::vector<NbRemoveRule> rm_rules;
+  struct RemovedRec { int64_t step; int32_t near, far, list, reaction; };
+  std::vector<RemovedRec> removed_log;
+  bool reverse_on() const { return !rm_rules.empty() || !fix.joins.empty(); }
   // RestrictReaction.define_connection (chem_reaction_restrict): (tag lo, tag hi) -> reaction bits; CSR rebuilt when it changed
   std::map<std::pair<int32_t, int32_t>, uint32_t> restrict_map; uint32_t restricted_mask = 0; bool restrict_dirty = false;
   std::vector<NbCons> constraints;   // ReactionConstraintNeighbourState (chem_reaction_constraint)
@@ -1964,7 +1970,8 @@ template <typename R> struct CtxT : Ctx {
         if ((react_due || atrp_due || last) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
         if (react_due || atrp_due || last) skip_log_confirm();
         if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
-        if (react_due) react_step();
+        if (react_due) react_step();      // (takes the type snapshot of the removal rules where it finds events)
+        if (react_due && react_had_events && reverse_on()) reverse_step();      // bond removals, then joins: behind the events and the neighbour changes
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
         if ((react_due || atrp_due) && res_tracking()) res_after_reactions();
         if ((react_due || atrp_due) && fix_tracking()) fix_after_reactions(react_due);
@@ -2056,6 +2063,7 @@ template <typename R> struct CtxT : Ctx {
   // they call (tables, event order, trim) are in chem_react_host.hpp ----
   void react_step() {
     tm.reaction_steps++;
+    react_had_events = false;
     if (reactions.empty()) return;
     // the host runs ahead of the device by up to `interval` steps: drain that backlog first so that
     // reaction_wall_s measures the reaction step, not the MD steps queued before it
@@ -2078,6 +2086,8 @@ template <typename R> struct CtxT : Ctx {
     int* status = resolve_candidates(nc, trc);
     trim_to_max_per_interval(nc, status);
     const EventSpan hev = apply_and_download_events(nc, status, ras, trc);
+    react_had_events = hev.size() > 0;
+    if (react_had_events && !rm_rules.empty()) reverse_snapshot();      // the types the removal rules judge by: before any association event reaches the mirrors
     commit_events(hev, trc);
     trc.lap("end");
     tm.reaction_wall_s += now_s() - t0;
@@ -2431,6 +2441,74 @@ template <typename R> struct CtxT : Ctx {
   // synchronous full path of a set-up change: both CSR tables from scratch, labels, forced rebuild.  O(all bonds) per step
   // that breaks something; a step that breaks nothing costs the scan and one read-back.
   DBuf<Candidate> diss_rec; DBuf<int> diss_count;
+  // behind HostTopology::remove_bonds (diss_step, reverse_step): the synchronous full path of a set-up change
+  void rebuild_tables_after_removal() {
+    excl_deg.clear();      // (the exclusion log shrank: degrees are counted afresh)
+    upload_excl(true);
+    upload_bonded(true);      // (re-proves bonds_excluded: a break that keeps its exclusion ends the inline-bond mode; typed slots against the new types)
+    mol_id.upload(top.mol_id, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    request_rebuild();
+  }
+
+  // ---- reverse reactions (rule sets: include/chem_mi355.h, chem_reaction_remove_bond / chem_reaction_join; host selection:
+  // chem_react_host.hpp select_removals, chem_fix_host.hpp join_by_reaction) ----
+  // A reaction step without events pays nothing for the rules: the snapshot is taken, and reverse_step() is called, only
+  // where react_step() found events (react_had_events).
+  std::vector<int32_t> type0;      // types at the start of this step's association phase
+  bool react_had_events = false;
+  void reverse_snapshot() {
+    join_async();      // mirrors replayed up to the last step's events (this step's are not in the arena yet); diss_step keeps them current itself
+    type0 = top.type;
+  }
+  DBuf<FixEnt<R>> place_dev;
+  void reverse_step() {
+    HIPCHK(hipStreamSynchronize(stream));
+    const double t0 = now_s();
+    join_async();      // this step's block is in the arena, its bonds are in the graph and the lists, the mirrors hold the new types
+    std::vector<AssocEvent> evs;
+    for (size_t bk = arena.blocks.size(); bk-- > 0 && arena.blocks[bk].first == step;) {
+      const size_t lo = arena.blocks[bk].second, hi = bk + 1 < arena.blocks.size() ? arena.blocks[bk + 1].second : arena.size();
+      for (size_t k = lo; k < hi; ++k) if (arena.r[k] >= 0) evs.push_back(AssocEvent{arena.a[k], arena.b[k], arena.r[k]});
+    }
+    if (evs.empty()) return;
+    std::sort(evs.begin(), evs.end(), [](const AssocEvent& p, const AssocEvent& q) { return event_key(p) < event_key(q); });
+    Trace trc("reverse");
+    if (!rm_rules.empty()) {
+      const std::vector<RemovedBond> rem = select_removals(top, type0, reactions, rm_rules, evs);
+      std::vector<int> rrow;
+      const std::vector<HostTopology::BrokenBond> broken = removals_by_list(top, rem, &rrow);
+      if (!broken.empty()) {
+        for (size_t k = 0; k < broken.size(); ++k) removed_log.push_back(RemovedRec{step, broken[k].a, broken[k].b, broken[k].list, public_index(rrow[k])});
+        std::vector<int32_t> touched;
+        top.remove_bonds(broken, touched);
+        if (g_trace) fprintf(stderr, "[chem trace] removed bonds %zu\n", broken.size());
+        trc.lap("host removal");
+        rebuild_tables_after_removal();
+        trc.lap("table rebuild");
+      }
+    }
+    if (!fix.joins.empty()) {
+      std::vector<FixState::JoinEvent> jev;
+      for (const AssocEvent& e : evs) jev.push_back(FixState::JoinEvent{public_index(e.reaction), e.a, e.b});
+      const std::vector<FixEntry> added = fix.join_by_reaction(jev, step, top.n);
+      if (!added.empty()) {
+        std::vector<FixEnt<R>> h(added.size());
+        for (size_t k = 0; k < added.size(); ++k) { h[k] = FixEnt<R>{}; h[k].a = added[k].anchor; h[k].t = added[k].target; h[k].d = (R)added[k].dist; }
+        place_dev.upload(h, stream);
+        FixGeom<R> g{};
+        for (int d = 0; d < 3; ++d) { g.L[d] = (R)L[d]; g.invL[d] = (R)(1.0 / L[d]); }
+        hipLaunchKernelGGL((k_fix_place<R>), dim3(cdiv((long long)added.size(), 256)), dim3(256), 0, stream, (int)added.size(), place_dev.p, rtag.p, nglob, x4.p, v4.p, g, pos_scale());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        upload_fix();
+        request_rebuild();      // the target jumped: the rebuild bins it where it is now
+        trc.lap("joins");
+      }
+    }
+    tm.reaction_wall_s += now_s() - t0;
+  }
+
   void diss_step() {
     bool any = false;
     for (auto& d : dissociations) any |= d.active != 0;
@@ -2490,15 +2568,10 @@ template <typename R> struct CtxT : Ctx {
     arena.mirror_pos = arena.size();
     std::vector<int32_t> touched;
     top.remove_bonds(broken, touched);
-    excl_deg.clear();      // (the exclusion log shrank: degrees are counted afresh)
     HIPCHK(hipStreamSynchronize(stream));
     if (g_trace) fprintf(stderr, "[chem trace] broken bonds %zu\n", rec.size());
     trc.lap("host removal");
-    upload_excl(true);
-    upload_bonded(true);      // (re-proves bonds_excluded: a break that keeps its exclusion ends the inline-bond mode; typed slots against the new types)
-    mol_id.upload(top.mol_id, stream);
-    HIPCHK(hipStreamSynchronize(stream));
-    request_rebuild();
+    rebuild_tables_after_removal();
     trc.lap("table rebuild");
     tm.reaction_wall_s += now_s() - t0;
   }
@@ -2876,7 +2949,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   c.step = 0; c.events.clear(); c.arena.clear();
   // (fixed distances: entries and log go with the tags; sets, post-processes and release rules stay)
   for (FixSet& fs : c.fix.sets) { fs.ent.clear(); fs.next_seq = 0; }
-  c.fix.targets.clear(); c.fix.anchors.clear(); c.fix.log.clear(); c.fix_dirty = true; c.ran = false;
+  c.fix.targets.clear(); c.fix.anchors.clear(); c.fix.log.clear(); c.fix.join_log.clear(); c.removed_log.clear(); c.fix_dirty = true; c.ran = false;
   return 0;
   API_END(ctx)
 }
@@ -2972,6 +3045,56 @@ int chem_reaction_release(chem_ctx* ctx, int reaction, int role, int set, int co
   REQUIRE(count >= 1, CHEM_EINVAL, "reaction_release: count");
   c.fix.rules.push_back(FixRule{reaction, role, set, count});
   return 0;
+  API_END(ctx)
+}
+
+int chem_reaction_join(chem_ctx* ctx, int reaction, int role, int set, double dist) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "fixed distances are not available on the decomposed path");
+  REQUIRE(c.assoc_row(reaction) >= 0, CHEM_EINVAL, "reaction_join: not an index of chem_reaction_add");
+  REQUIRE(role == 1 || role == 2, CHEM_EINVAL, "reaction_join: role must be 1 or 2");
+  REQUIRE(set >= 0 && set < (int)c.fix.sets.size(), CHEM_EINVAL, "reaction_join: unknown set");
+  REQUIRE(dist > 0.0 && std::isfinite(dist), CHEM_EINVAL, "reaction_join: the distance must be positive and finite");
+  c.fix.joins.push_back(FixJoinRule{reaction, role, set, dist});
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_fix_joins(chem_ctx* ctx, chem_fix_record* out, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  const int64_t m = (int64_t)c.fix.join_log.size();
+  if (!out) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "fix_joins: capacity");
+  for (int64_t k = 0; k < m; ++k) { const FixRecord& r = c.fix.join_log[k]; out[k] = chem_fix_record{r.step, c.top.id[r.anchor], c.top.id[r.target], r.set, r.cause}; }
+  return m;
+  API_END(ctx)
+}
+
+int chem_reaction_remove_bond(chem_ctx* ctx, const chem_nb_remove* r) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "bond removal by a reaction is not available on the decomposed path");
+  REQUIRE(r, CHEM_EINVAL, "reaction_remove_bond: null rule");
+  const int row = c.assoc_row(r->reaction);
+  REQUIRE(row >= 0, CHEM_EINVAL, "reaction_remove_bond: not an index of chem_reaction_add");
+  REQUIRE(r->invoke_on >= 1 && r->invoke_on <= 3, CHEM_EINVAL, "reaction_remove_bond: invoke_on must be 1, 2 or 3");
+  REQUIRE(r->nb_level >= 1, CHEM_EINVAL, "reaction_remove_bond: nb_level must be at least 1");
+  for (int t : {r->anchor_type, r->type_1, r->type_2}) REQUIRE(t >= 0 && t < CHEM_MAX_TYPES, CHEM_EINVAL, "reaction_remove_bond: type");
+  c.rm_rules.push_back(NbRemoveRule{row, r->invoke_on, r->anchor_type, r->nb_level, r->type_1, r->type_2, r->unexclude != 0 ? 1 : 0});
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_reaction_removed(chem_ctx* ctx, chem_bond_record* out, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  const int64_t m = (int64_t)c.removed_log.size();
+  if (!out) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "reaction_removed: capacity");
+  for (int64_t k = 0; k < m; ++k) { const Ctx::RemovedRec& r = c.removed_log[k]; out[k] = chem_bond_record{r.step, c.top.id[r.near], c.top.id[r.far], r.list, r.reaction}; }
+  return m;
   API_END(ctx)
 }
 
@@ -3534,7 +3657,7 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
   // fixed distances: a type that chem_modify_particle changed since the last call releases entries of a typed set here
   const bool fix_live = c.fix.any();
   if (fix_live) { c.join_async(); c.fix_after_reactions(false); }
-  if (!c.res_tracking() && !c.fix_tracking()) { c.run(nsteps); return 0; }
+  if (!c.res_tracking() && !c.fix_tracking() && c.fix.joins.empty()) { c.run(nsteps); return 0; }
   // Resolution ramps with a property change: the call runs in pieces that end where a lambda reaches 1 (the host knows every
   // stamp, so it knows every such step: chem_res_host.hpp); the change is applied there, and the forces are evaluated again
   // where the call ends on such a step, so that the forces current at s_full are those of the new properties.  A reaction or
@@ -3702,6 +3825,7 @@ int chem_comm_init(chem_ctx* ctx, int nranks, int rank, const int node_grid[3], 
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on, CHEM_ESTATE, "comm_init: already initialised");
   if (nranks == 1 && !uid) return 0;   // single domain, nothing to do
   REQUIRE(node_grid && node_grid[0] == 1 && node_grid[1] == 1 && node_grid[2] == nranks, CHEM_ENOTIMPL,
@@ -3770,6 +3894,7 @@ int chem_comm_init_ipc(chem_ctx* ctx, int nranks, int rank, const char* shm_name
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_ipc must precede the first run");
   HIPCHK(hipSetDevice(c.device));
   c.tr.reset(new IpcTransport(nranks, rank, shm_name));
@@ -3785,6 +3910,7 @@ int chem_comm_init_local(chem_ctx* ctx, int nranks, int rank, int hub_id) {
   REQUIRE(c.dissociations.empty(), CHEM_ENOTIMPL, "dissociation reactions are registered: they are not available on the decomposed path");
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
+  REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_local must precede the first run");
   c.tr.reset(new LocalTransport(nranks, rank, hub_id));
   c.dd_on = true; c.P = nranks; c.rk = rank; c.geom_dirty = true;

@@ -19,13 +19,14 @@
 namespace chem {
 
 constexpr int kFixMaxSets = CHEM_MAX_FIX_SETS;
-constexpr int kFixCauseReaction = 1, kFixCauseType = 2;
+constexpr int kFixCauseReaction = 1, kFixCauseType = 2, kFixCauseJoined = 3, kFixCauseRefused = 4;
 
 struct FixEntry { int32_t anchor, target; double dist; int64_t seq; };
 // what becomes of a released target of type old_type (chem_fix_postprocess): new_type < 0 no property change, new_state < 0
 // state kept, lambda < 0 resolution left alone
 struct FixPost { int old_type, new_type; double new_mass, new_q; int new_state; double lambda; };
 struct FixRule { int reaction, role, set, count; };      // chem_reaction_release: public reaction index, role 1 | 2
+struct FixJoinRule { int reaction, role, set; double dist; };      // chem_reaction_join: public reaction index, anchor role 1 | 2
 struct FixRecord { int64_t step; int32_t set, anchor, target, cause; int64_t seq; };
 struct FixSet {
   int anchor_type = -1, target_type = -1;
@@ -41,6 +42,8 @@ struct FixState {
   std::vector<FixSet> sets;
   std::vector<FixRule> rules;
   std::vector<FixRecord> log;
+  std::vector<FixJoinRule> joins;
+  std::vector<FixRecord> join_log;                     // chem_fix_joins: cause 3 = joined, 4 = refused, in visit order
   std::unordered_set<int32_t> targets;                 // tags that are the target of a live entry
   std::unordered_map<int32_t, int> anchors;            // tag -> number of live entries it anchors
   bool any() const { for (const FixSet& s : sets) if (!s.ent.empty()) return true; return false; }
@@ -150,6 +153,24 @@ struct FixState {
     }
     if (!hit) return {};
     return release_marked(mark, step, kFixCauseType);
+  }
+  // Join by a reaction (chem_reaction_join): per event (canonical order), per rule of its reaction in the order the rules were
+  // added, the reactant in the rule's role becomes the anchor and the other one the target of a new entry of the rule's set.
+  // A pair chem_fix_add would refuse adds nothing and is logged with cause 4.  Returns the new entries in visit order.
+  struct JoinEvent { int reaction; int32_t a, b; };      // a: role 1, b: role 2
+  std::vector<FixEntry> join_by_reaction(const std::vector<JoinEvent>& events, int64_t step, int64_t ntags) {
+    std::vector<FixEntry> added;
+    std::string why;
+    for (const JoinEvent& e : events)
+      for (const FixJoinRule& rl : joins) {
+        if (rl.reaction != e.reaction) continue;
+        const int32_t pair[2] = {rl.role == 1 ? e.a : e.b, rl.role == 1 ? e.b : e.a};
+        const bool ok = add(rl.set, 1, pair, rl.dist, ntags, why) == 0;
+        const int64_t seq = ok ? sets[rl.set].ent.back().seq : -1;
+        join_log.push_back(FixRecord{step, (int32_t)rl.set, pair[0], pair[1], ok ? kFixCauseJoined : kFixCauseRefused, seq});
+        if (ok) added.push_back(sets[rl.set].ent.back());
+      }
+    return added;
   }
   // the flat device order: every live entry, entries of one anchor consecutive (stable by anchor tag: sets and insertion
   // order decide among equals)

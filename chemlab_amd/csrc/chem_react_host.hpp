@@ -94,6 +94,59 @@ template <class Rec> bool trim_accepted(const std::vector<Rec>& rec, std::vector
   return true;
 }
 
+// PostProcessRemoveNeighbourBond (chem_reaction_remove_bond; rule set: include/chem_mi355.h): which bonds the visits of one
+// reaction step remove.  `reaction` of a rule and of an event is the row of the association table.  The selection reads the
+// bond graph as it stands (this step's new bonds linked, nothing of this step removed yet) and `type0`, the types at the start
+// of the step's association phase; it changes nothing.  Events come in canonical order; per event role 1 before role 2, rules
+// in the order they were added; within one visit the bonds (p, q) by (tag p, tag q).  A bond found twice is reported for the
+// first visit only.
+struct NbRemoveRule { int reaction, invoke_on, anchor_type, nb_level, type_1, type_2, unexclude; };
+struct AssocEvent { int32_t a, b; int reaction; };
+struct RemovedBond { int32_t near, far; int reaction, unexclude; };
+inline std::vector<RemovedBond> select_removals(const HostTopology& top, const std::vector<int32_t>& type0, const std::vector<chem_reaction_desc>& reactions,
+                                                const std::vector<NbRemoveRule>& rules, const std::vector<AssocEvent>& events) {
+  std::vector<RemovedBond> out;
+  TupleSet found;
+  std::unordered_map<int32_t, int> dist;
+  std::vector<int32_t> frontier, next;
+  for (const AssocEvent& e : events)
+    for (int role = 1; role <= 2; ++role)
+      for (const NbRemoveRule& rl : rules) {
+        if (rl.reaction != e.reaction || !(rl.invoke_on & role)) continue;
+        if ((role == 1 ? reactions[e.reaction].type_1 : reactions[e.reaction].type_2) != rl.anchor_type) continue;
+        const int32_t anchor = role == 1 ? e.a : e.b;
+        // breadth-first levels 0 .. nb_level; `frontier` ends as level nb_level - 1
+        dist.clear(); dist[anchor] = 0; frontier.assign(1, anchor);
+        for (int lvl = 1; lvl <= rl.nb_level; ++lvl) {
+          next.clear();
+          for (int32_t p : frontier) for (int32_t nb : top.graph[p]) if (dist.emplace(nb, lvl).second) next.push_back(nb);
+          if (lvl < rl.nb_level) frontier.swap(next);
+        }
+        std::sort(frontier.begin(), frontier.end());
+        for (int32_t p : frontier)
+          for (int32_t q : top.graph[p]) {
+            if (dist[q] != rl.nb_level) continue;
+            const int tp = type0[p], tq = type0[q];
+            if (!((tp == rl.type_1 && tq == rl.type_2) || (tp == rl.type_2 && tq == rl.type_1))) continue;
+            if (!found.insert(HostTopology::pair_key(p, q))) continue;
+            out.push_back(RemovedBond{p, q, e.reaction, rl.unexclude});
+          }
+      }
+  return out;
+}
+// One removed bond per arity-2 list that holds it, lists in handle order: the batch HostTopology::remove_bonds takes and the
+// records of chem_reaction_removed.
+inline std::vector<HostTopology::BrokenBond> removals_by_list(const HostTopology& top, const std::vector<RemovedBond>& rem, std::vector<int>* reaction_of = nullptr) {
+  std::vector<HostTopology::BrokenBond> bb;
+  for (const RemovedBond& r : rem)
+    for (size_t li = 0; li < top.lists.size(); ++li) {
+      if (top.lists[li].arity != 2 || !top.lists[li].seen.contains(HostTopology::pair_key(r.near, r.far))) continue;
+      bb.push_back(HostTopology::BrokenBond{r.near, r.far, (int32_t)li, r.unexclude});
+      if (reaction_of) reaction_of->push_back(r.reaction);
+    }
+  return bb;
+}
+
 // One firing of the ATRPActivator (rule set: include/chem_mi355.h, chem_atrp_desc): pool draw (Philox stream keyed
 // (seed, step, tag)), the num_particles smallest keys in (key, tag) order, then the acceptance loop with the catalyst
 // bookkeeping.  Updates the type/mass/charge/state mirrors of `top` and the two ratios of `atrp`; the caller pushes

@@ -370,14 +370,10 @@ __device__ __forceinline__ float fix_delta(float a, float b, float qs, float, fl
   return (float)dq * qs;
 }
 __device__ __forceinline__ double fix_delta(double a, double b, double, double L, double invL) { const double x = a - b; return x - L * rint(x * invL); }
+// one entry: the target goes to x_a + d u / |u|, u the minimum image of x_t - x_a ((1, 0, 0) for |u| = 0), and takes the anchor's velocity
 template <typename R>
-__global__ __launch_bounds__(256) void k_fix_distances(int ne, const FixEnt<R>* __restrict__ ent, const int* __restrict__ rtag, int ntag,
-                                                        Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4, FixGeom<R> g, PosScale<R> ps,
-                                                        const DevCtl* __restrict__ ctl) {
-  if (ctl->halt) return;   // (the drift in front of this launch left at once, too)
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= ne) return;
-  const FixEnt<R> e = ent[k];
+__device__ __forceinline__ void fix_apply_entry(const FixEnt<R> e, const int* __restrict__ rtag, int ntag, Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4,
+                                                const FixGeom<R>& g, const PosScale<R>& ps) {
   if ((unsigned)e.a >= (unsigned)ntag || (unsigned)e.t >= (unsigned)ntag) return;
   const int ia = rtag[e.a], it = rtag[e.t];
   if (ia < 0 || it < 0) return;
@@ -394,6 +390,25 @@ __global__ __launch_bounds__(256) void k_fix_distances(int ne, const FixEnt<R>* 
   xt.x = pos_add(xt.x, dx, ps.inv[0]); xt.y = pos_add(xt.y, dy, ps.inv[1]); xt.z = pos_add(xt.z, dz, ps.inv[2]);
   vt.x = va.x; vt.y = va.y; vt.z = va.z;
   x4[it] = xt; v4[it] = vt;
+}
+template <typename R>
+__global__ __launch_bounds__(256) void k_fix_distances(int ne, const FixEnt<R>* __restrict__ ent, const int* __restrict__ rtag, int ntag,
+                                                        Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4, FixGeom<R> g, PosScale<R> ps,
+                                                        const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;   // (the drift in front of this launch left at once, too)
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ne) return;
+  fix_apply_entry<R>(ent[k], rtag, ntag, x4, v4, g, ps);
+}
+// Placement of the entries a reaction step has just joined (chem_reaction_join): the same move, once, at the reaction step and
+// over the new entries only (targets are distinct, and no target is an anchor: the lanes write disjoint particles).  The host
+// launches it behind a synchronised reaction step, in front of the forced rebuild, which then bins the target where it is.
+template <typename R>
+__global__ __launch_bounds__(256) void k_fix_place(int ne, const FixEnt<R>* __restrict__ ent, const int* __restrict__ rtag, int ntag,
+                                                    Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4, FixGeom<R> g, PosScale<R> ps) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ne) return;
+  fix_apply_entry<R>(ent[k], rtag, ntag, x4, v4, g, ps);
 }
 
 // one block: fold the step's per-block max displacement into the accumulated distance and

@@ -231,6 +231,51 @@ class Engine:
         dt = np.dtype([("step", "i8"), ("anchor_id", "i8"), ("target_id", "i8"), ("set", "i4"), ("cause", "i4")])
         return np.frombuffer(buf, dtype=dt, count=n).copy()
 
+    def supports(self, name):
+        """Whether this engine's library exports the entry point `name` (without the prefix), e.g. 'reaction_join': the CPU
+        checker lacks what only the product has."""
+        return getattr(self.api, name, None) is not None
+
+    # ---- reverse reactions (include/chem_mi355.h, chem_reaction_remove_bond / chem_reaction_join) ----
+    def _reverse_entry(self, name, what):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("%s: the CPU checker has no reverse reactions" % what)
+        return fn
+
+    def reaction_remove_bond(self, reaction, invoke_on, anchor_type, nb_level, type_1, type_2, unexclude=False):
+        """PostProcessRemoveNeighbourBond.add_bond_to_remove(anchor_type, nb_level, type_1, type_2) on the events of `reaction`:
+        invoke_on 'type_1' | 'type_2' | 'both'."""
+        fn = self._reverse_entry("reaction_remove_bond", "RemoveNeighboursBonds")
+        io = {"type_1": 1, "type_2": 2, "both": 3}.get(invoke_on, invoke_on)
+        r = _capi.NbRemove(int(reaction), int(io), int(anchor_type), int(nb_level), int(type_1), int(type_2), 1 if unexclude else 0, 0)
+        self._ck(fn(self.ctx, C.byref(r)))
+
+    def reaction_removed(self):
+        """Removal records (step, id_near, id_far, list, reaction): one per (bond, list), by step, then visit order."""
+        fn = self._reverse_entry("reaction_removed", "RemoveNeighboursBonds")
+        n = self._ck(fn(self.ctx, None, 0))
+        buf = (_capi.BondRecord * max(n, 1))()
+        if n:
+            self._ck(fn(self.ctx, buf, n))
+        dt = np.dtype([("step", "i8"), ("id_near", "i8"), ("id_far", "i8"), ("list", "i4"), ("reaction", "i4")])
+        return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+    def reaction_join(self, reaction, role, h, dist):
+        """PostProcessJoinParticles(fd, dist): the reactant in `role` ('type_1' | 'type_2') anchors the other one in set `h`."""
+        fn = self._reverse_entry("reaction_join", "JoinMolecule")
+        self._ck(fn(self.ctx, int(reaction), {"type_1": 1, "type_2": 2}.get(role, role), int(h), float(dist)))
+
+    def fix_joins(self):
+        """Join records (step, anchor_id, target_id, set, cause): cause 3 = joined, 4 = refused, in visit order."""
+        fn = self._reverse_entry("fix_joins", "JoinMolecule")
+        n = self._ck(fn(self.ctx, None, 0))
+        buf = (_capi.FixRecord * max(n, 1))()
+        if n:
+            self._ck(fn(self.ctx, buf, n))
+        dt = np.dtype([("step", "i8"), ("anchor_id", "i8"), ("target_id", "i8"), ("set", "i4"), ("cause", "i4")])
+        return np.frombuffer(buf, dtype=dt, count=n).copy()
+
     def list_create(self, arity, kind, by_types=False):
         kind = _capi.POT[kind] if isinstance(kind, str) else kind
         if kind == _capi.POT["COULOMB_BOND"] and getattr(self.api, "nb_coulomb", None) is None:

@@ -1045,6 +1045,8 @@ class _Reaction(object):
         self._pp = {}
         self._nb_pp = []
         self._release = []
+        self._remove = []
+        self._join = []
         self._constraints = []
         self._index = None
         self._system = None
@@ -1070,6 +1072,12 @@ class _Reaction(object):
             return
         if isinstance(pp, _PostProcessReleaseParticles):
             self._release.append((pp, which))
+            return
+        if isinstance(pp, _PostProcessRemoveNeighbourBond):
+            self._remove.append((pp, which))
+            return
+        if isinstance(pp, _PostProcessJoinParticles):
+            self._join.append((pp, which))
             return
         if not isinstance(pp, _PostProcessChangeProperty):
             raise NotImplementedError("post-process %s is outside the hot-path scope" % type(pp).__name__)
@@ -1187,6 +1195,15 @@ class _ChemicalReaction(object):
                     e.reaction_neighbour_change(r._index, which, old_type, nb_level, int(prop.type), float(prop.mass),
                                                 float(prop.q or 0.0), None if prop.state is None else int(prop.state),
                                                 incr_state=getattr(prop, "incr_state", None), state_window=window)
+            # the reverse direction (chem_reaction_remove_bond, chem_reaction_join): behind the neighbour changes, as the engine orders them
+            for pp, which in r._remove:
+                for anchor_type, nb_level, t1, t2 in pp.rules:
+                    e.reaction_remove_bond(r._index, which, anchor_type, nb_level, t1, t2, pp.unexclude)
+            for pp, which in r._join:
+                if pp.fd.handle is None:
+                    raise RuntimeError("PostProcessJoinParticles: add its FixDistances to the integrator before the reactions")
+                for role in {"type_1": ("type_1",), "type_2": ("type_2",), "both": ("type_1", "type_2")}[which]:
+                    e.reaction_join(r._index, role, pp.fd.handle, pp.eq_length)
 
     def _lambda_rules(self, r):
         """TopologyParticleProperties(lambda_adr=...) of the reaction's PostProcessChangeProperty: the reactant's resolution"""
@@ -1432,6 +1449,38 @@ class _PostProcessReleaseParticles(object):
         self.fd, self.count = fd, int(count)
 
 
+class _PostProcessRemoveNeighbourBond(object):
+    """integrator.PostProcessRemoveNeighbourBond(topology_manager).add_bond_to_remove(anchor_type, nb_level, type_1, type_2)
+    (reaction_post_process.py:117-137), attached to a Reaction with add_postprocess(pp, 'type_1' | 'type_2' | 'both'): the bonds
+    type_1 - type_2 found nb_level bonds from a reactant of type anchor_type are taken out (chem_reaction_remove_bond).
+    `unexclude` (this shim's own attribute, default True, as DissociationReaction's): the freed pair interacts through the pair
+    potential again.  The argument defaults to None and a call without it is refused: the reference's constructor takes the
+    topology manager, and a bare call is how callers ask whether the post-process exists at all."""
+
+    def __init__(self, topology_manager=None):
+        if topology_manager is None:
+            raise NotImplementedError("integrator.PostProcessRemoveNeighbourBond needs the topology manager")
+        self.rules = []     # (anchor_type, nb_level, type_1, type_2) in insertion order
+        self.unexclude = True
+
+    def add_bond_to_remove(self, anchor_type, nb_level, type_1, type_2):
+        self.rules.append((int(anchor_type), int(nb_level), int(type_1), int(type_2)))
+
+
+class _PostProcessJoinParticles(object):
+    """integrator.PostProcessJoinParticles(fd, eq_length) (reaction_post_process.py:351), attached to a Reaction with
+    add_postprocess(pp, 'type_1'): on every event that reactant becomes the anchor and the other one the target of a new
+    entry of `fd` at eq_length (chem_reaction_join).  Both arguments default to None and a call without them is refused, as
+    for PostProcessRemoveNeighbourBond."""
+
+    def __init__(self, fd=None, eq_length=None):
+        if fd is None or eq_length is None:
+            raise NotImplementedError("integrator.PostProcessJoinParticles needs a FixDistances and a length")
+        if not isinstance(fd, _FixDistances):
+            raise TypeError("PostProcessJoinParticles(FixDistances, eq_length)")
+        self.fd, self.eq_length = fd, float(eq_length)
+
+
 integrator = _ns(
     FixDistances=_FixDistances, PostProcessReleaseParticles=_PostProcessReleaseParticles,
     VelocityVerlet=_VelocityVerlet, FixedListDynamicResolution=_FixedListDynamicResolution, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
@@ -1446,8 +1495,7 @@ integrator = _ns(
     ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"),
     ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_BasicDynamicResolution,
     PostProcessChangeNeighboursProperty=_PostProcessChangeNeighboursProperty,
-    PostProcessRemoveNeighbourBond=_unsupported("integrator.PostProcessRemoveNeighbourBond"),
-    PostProcessJoinParticles=_unsupported("integrator.PostProcessJoinParticles"),
+    PostProcessRemoveNeighbourBond=_PostProcessRemoveNeighbourBond, PostProcessJoinParticles=_PostProcessJoinParticles,
 )
 
 

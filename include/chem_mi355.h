@@ -393,7 +393,7 @@ typedef struct chem_fix_record {
   int64_t step;
   int64_t anchor_id, target_id;
   int32_t set;
-  int32_t cause;            /* 1 = reaction, 2 = type condition */
+  int32_t cause;            /* chem_fix_log: 1 = reaction, 2 = type condition; chem_fix_joins: 3 = joined, 4 = refused */
 } chem_fix_record;
 /* storage.addParticles after the particle set exists: appends n particles.  Every new id must be greater than the largest
  * present id (CHEM_EINVAL otherwise; ids within the call in any order, no duplicates): id order stays tag order and existing
@@ -426,6 +426,67 @@ int64_t chem_fix_get(chem_ctx* ctx, int set, int64_t* ids, double* dist, int64_t
 /* the release records since the context was created, ordered by (step, set, insertion index); out == NULL: the count.
  * (chem_set_particles empties every set and the log -- tags are new --; sets, post-processes and release rules stay.) */
 int64_t chem_fix_log(chem_ctx* ctx, chem_fix_record* out, int64_t cap);
+
+/* ---- reverse reactions: bond removal and join by a reaction (RemoveNeighboursBonds, JoinMolecule) ---------------- */
+/* integrator.PostProcessRemoveNeighbourBond(tm).add_bond_to_remove(anchor_type, nb_level, t1, t2) and
+ * integrator.PostProcessJoinParticles(fd, eq_length), each with reaction.add_postprocess(pp, invoke_on) --
+ * reaction_post_process.py:117-137, 322-362 (ext_type=RemoveNeighboursBonds / JoinMolecule; examples/dacron/rev_with_water:
+ * the hydrolysis  C(0,1):E(0,1) + W(0,2) -> A(1):Z(1) + E(1)  takes the ester bond out again and attaches the consumed water
+ * to the regenerated acid group as a dummy, ready to be released by the next condensation).  The arithmetic of both is in the
+ * external fork, so these rule sets are this build's own ([EXT-RECALL], parity unpinned; DESIGN.md "Reverse reactions").
+ * Both act on the events of association reactions (chem_reaction_add, virtual ones included) in the reaction step, in this
+ * order: association events, neighbour changes (chem_reaction_neighbour_change), REMOVALS, JOINS, ATRP step, lambda rules
+ * (chem_reaction_set_resolution), release by reaction, release by type.
+ *
+ * chem_reaction_remove_bond
+ *   order       events of `reaction` in canonical order (min id, max id); role 1 before role 2; rules in the order they were
+ *               added; within one visit the bonds by (id p, id q).
+ *   roles       a role is visited only if invoke_on (1 | 2 | 3 = both) includes it and the reaction's own type for that role
+ *               (chem_reaction_desc.type_1 / type_2: the reactant's type before the event) equals anchor_type.
+ *   bonds       from the anchor, every bond (p, q) of the bond graph as it stands after this step's new bonds (and before any
+ *               removal of this step) with graph distance d(anchor, p) = nb_level - 1 and d(anchor, q) = nb_level; it is
+ *               removed when the unordered pair {type p, type q} equals {type_1, type_2}, with the types at the START of this
+ *               step's association phase: after the dissociation block, before any association event, role change or
+ *               neighbour change of the step (an E that the same step turns into something else still matches C:E).
+ *   effect      what the `apply` of a dissociation (chem_dissociation_desc) does to a broken pair, except that the pair leaves
+ *               EVERY arity-2 list that holds it (order of the survivors kept): it leaves the bond graph, mol_id of the
+ *               fragments is recomputed, res_id stays, unexclude != 0 lifts the 1-2 exclusion, triples and quadruples that
+ *               hold p, q as consecutive members go; the 1-3 / 1-4 exclusions those once caused stay (the same known limit).
+ *               No state or type changes: those are the reaction's own.
+ *   duplicates  a bond found by two visits is removed once and recorded for the first.
+ *   log         chem_reaction_removed: one record per (bond, list), ordered by step, then by visit order, then by list handle;
+ *               id_near = p, id_far = q; `reaction` is the public index.  out == NULL: the count.  chem_set_particles empties it.
+ *   afterwards  the lists are rebuilt before the next force evaluation (the table rebuild of a dissociation step).
+ * CHEM_EINVAL: rule == NULL, not an index of chem_reaction_add, invoke_on outside 1..3, nb_level < 1, a type outside
+ * [0, CHEM_MAX_TYPES).  A context without a rule launches exactly what it launched before. */
+typedef struct chem_nb_remove {
+  int32_t reaction, invoke_on, anchor_type, nb_level;
+  int32_t type_1, type_2, unexclude, pad;
+} chem_nb_remove;
+typedef struct chem_bond_record {
+  int64_t step;
+  int64_t id_near, id_far;
+  int32_t list, reaction;
+} chem_bond_record;
+int chem_reaction_remove_bond(chem_ctx* ctx, const chem_nb_remove* rule);
+int64_t chem_reaction_removed(chem_ctx* ctx, chem_bond_record* out, int64_t cap);
+/* chem_reaction_join: on every event of `reaction` the reactant in `role` (1 | 2) becomes the anchor and the other reactant
+ * the target of a new entry (anchor, target, dist) of `set`; insertion order continues.
+ *   order       events in canonical order, rules in the order they were added.
+ *   refusals    a pair chem_fix_add would refuse (a target that already is a target or an anchor, an anchor that is a target)
+ *               adds nothing and is recorded with cause 4.
+ *   placement   at once, on the device, over this step's new entries only, by the arithmetic of the per-step rule above:
+ *               u = minimum image of x_t - x_a, (1, 0, 0) for |u| = 0; x_t <- x_a + d u / |u| through the drift's position
+ *               update; v_t <- v_a.  The lists are then rebuilt before the next force evaluation: the rebuild bins the target
+ *               where it is, and the jump never meets the displacement criterion.
+ *   afterwards  the release by reaction and the type check of the same step see the entry: a set created with types judges it
+ *               with the types the step has just given.
+ *   log         chem_fix_joins: cause 3 = joined, 4 = refused, in visit order.  chem_fix_log keeps its meaning (releases only).
+ * While a join rule exists chem_run ends its pieces at every reaction step, as for release rules.
+ * CHEM_EINVAL: not an index of chem_reaction_add, role other than 1 or 2, unknown set, dist not positive and finite.
+ * Neither call is available on the decomposed path: CHEM_ENOTIMPL after chem_comm_init*, and in chem_comm_init* after either. */
+int chem_reaction_join(chem_ctx* ctx, int reaction, int role, int set, double dist);
+int64_t chem_fix_joins(chem_ctx* ctx, chem_fix_record* out, int64_t cap);
 
 /* ---- bonded lists -------------------------------------------------------------------- */
 /* FixedPairList/TripleList/QuadrupleList(storage) + FixedXListYyy(system, list, potential)
