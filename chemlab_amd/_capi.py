@@ -105,6 +105,11 @@ class Obs(C.Structure):
                 ("momentum", C.c_double * 3), ("virial_nb", C.c_double)]
 
 
+class Pressure(C.Structure):
+    _fields_ = [("pressure", C.c_double), ("volume", C.c_double), ("mv2", C.c_double), ("virial_nb", C.c_double),
+                ("virial_list", C.c_double * CHEM_MAX_LISTS), ("virial", C.c_double)]
+
+
 class Timers(C.Structure):
     _fields_ = [("run_wall_s", C.c_double), ("steps", C.c_int64), ("rebuilds", C.c_int64),
                 ("reaction_steps", C.c_int64), ("nlist_entries", C.c_int64),
@@ -204,6 +209,10 @@ PRODUCT_ONLY = {
     "reaction_removed": (_i64, [_P, C.POINTER(BondRecord), _i64]),
     "reaction_join": (_i, [_P, _i, _i, _i, _d]),
     "fix_joins": (_i64, [_P, C.POINTER(FixRecord), _i64]),
+    # pressure observable, Berendsen barostat, current box (the CPU oracle has a fixed box and no virial of the lists)
+    "get_pressure": (_i, [_P, C.POINTER(Pressure)]),
+    "barostat_berendsen": (_i, [_P, _d, _d]),
+    "get_box": (_i, [_P, _pd]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

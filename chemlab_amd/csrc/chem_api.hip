@@ -93,6 +93,16 @@ struct Ctx {
   double L[3] = {0, 0, 0}, rc = 0, skin = 0, dt = 0, cap_force = 0;
   int resc_kind = 0; double resc_kT = 0, resc_param = 0;   // Berendsen (1) / Isokinetic (2) velocity rescaling, StochasticVelocityRescaling (3)
   uint64_t svr_seed = 0;
+  // Berendsen barostat (chem_barostat_berendsen; chem_baro_host.hpp): on while baro_tau > 0.  baro_keep: the forces in f4 are
+  // those evaluated before the last scaling of a finished run, in the particle order of that evaluation -- the next chem_run
+  // starts from them (what a longer run would have done) unless something re-sorted the particles or touched the system since.
+  double baro_p0 = 0, baro_tau = 0; bool baro_keep = false;
+  // what the scalings since the last list build (since the last rebuild of the reference rule) have been charged as displacement:
+  // taken off the half skin every decision compares with (the same as adding it to the accumulated distance on the device)
+  double baro_charge = 0, baro_charge_ref = 0; int baro_seen_builds = -1, baro_seen_ref = -1;
+  double half_skin_eff() const { return std::max(0.5 * skin_eff() - baro_charge, 0.0); }
+  double half_skin_ref() const { return std::max(0.5 * skin - baro_charge_ref, 0.0); }
+  bool baro_on() const { return baro_tau > 0; }
   HostTopology top;
   std::vector<double> pos0, vel0;  // staged particle data (tag order) until first upload
   int ntypes = 1;
@@ -254,6 +264,7 @@ struct Ctx {
   virtual void run(int64_t nsteps) = 0;
   virtual int64_t get_state(int what, void* out, int64_t cap) = 0;
   virtual void observe(chem_obs* out) = 0;
+  virtual void pressure(chem_pressure* out) = 0;
   virtual int64_t verlet_pairs(int64_t* out, int64_t cap) = 0;
   virtual void modify_particle(int tag, int what, double value) = 0;
   virtual int res_apply_completions() = 0;
@@ -451,7 +462,7 @@ template <typename R> struct CtxT : Ctx {
     if (v->step == s1) h.step = s1;
     return h;
   }
-  bool skip_applies() const { return opt_skip_idle && fold_sd() && !want32 && !dbg_on; }
+  bool skip_applies() const { return opt_skip_idle && fold_sd() && !want32 && !dbg_on && !baro_on(); }
 
   DBuf<int> gtag;                      // slab: index of a tag's ghost copy on this rank (-1: none)
   DBuf<Box<R>> box_dev; Box<R> box_dev_host; bool box_dev_valid = false;   // device copy of the box for the standalone list kernel
@@ -499,6 +510,7 @@ template <typename R> struct CtxT : Ctx {
     for (auto e : ev) (void)hipEventDestroy(e);
     if (pin_ev) (void)hipHostFree(pin_ev);
     if (hflag) (void)hipHostFree(hflag);
+    if (baro_pin) (void)hipHostFree(baro_pin);
     if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); (void)hipEventDestroy(ev_fold); (void)hipEventDestroy(ev_halo); }
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -544,6 +556,7 @@ template <typename R> struct CtxT : Ctx {
     skin_list = pick_list_skin();
     setup_geometry_once();
     if (skin_list > 0 && !use_fused && !dd_on) { skin_list = 0.0; setup_geometry_once(); }   // the wider skin only pays on the fused tile path
+    baro_replan_pending = false;
   }
   void setup_geometry_once() {
     setup_box();
@@ -612,8 +625,8 @@ template <typename R> struct CtxT : Ctx {
     FusedArgs<R> a{};
     a.n = n; a.ncell = box.ncell; a.ntiles = ntiles; a.CAP = tile_cap; a.S = S; a.has_excl = has_excl; a.criterion = opt_criterion;
     a.par = fused_par; a.seg_shift = seg_shift; a.tseg_shift = tseg_shift; a.nblk = cdiv(n, kIntPerBlock); a.want32 = want32 ? 1 : 0; a.ntypes = ntypes; a.ablate = dbg_on ? opt_ablate_list : 0; a.coop = opt_coop_overflow;
-    a.half_skin = 0.5 * skin_eff(); a.rl2 = (R)((rc + skin_eff()) * (rc + skin_eff()));
-    a.half_skin_ref = 0.5 * skin; a.rl2_rows = (R)((rc + skin) * (rc + skin));
+    a.half_skin = half_skin_eff(); a.rl2 = (R)((rc + skin_eff()) * (rc + skin_eff()));
+    a.half_skin_ref = half_skin_ref(); a.rl2_rows = (R)((rc + skin) * (rc + skin));
     a.istep = step;
     a.x4 = x4.p; a.v4 = v4.p; a.x4o = x4o.p; a.v4o = v4o.p; a.x0 = opt_criterion ? x0.p : nullptr;      // (reference positions: only the displacement criterion reads them -- 16 MB of writes per rebuild otherwise)
     a.tag = tag.p; a.tago = tago.p; a.rtag = rtag.p; a.img4 = img4.p; a.img4o = img4o.p;
@@ -1316,7 +1329,7 @@ template <typename R> struct CtxT : Ctx {
 
   void decide_and_rebuild(bool publish = false) {
     if (use_fused) { tbeg(1); launch_rebuild_fused(publish); tend(); return; }
-    hipLaunchKernelGGL(k_rebuild_decide<R>, dim3(1), dim3(1024), 0, stream, ctl.p, blockmax.p, cdiv(n, kIntPerBlock), 0.5 * skin_eff(), opt_criterion, 3, (const double*)nullptr, 0, (volatile int*)nullptr, 0, 0.5 * skin);
+    hipLaunchKernelGGL(k_rebuild_decide<R>, dim3(1), dim3(1024), 0, stream, ctl.p, blockmax.p, cdiv(n, kIntPerBlock), half_skin_eff(), opt_criterion, 3, (const double*)nullptr, 0, (volatile int*)nullptr, 0, half_skin_ref());
     launch_rebuild_chain();
   }
 
@@ -1471,6 +1484,7 @@ template <typename R> struct CtxT : Ctx {
   void rebuild_now(bool resumed = false, int halt_kind = 0, int halt_par = 0) {
     const double t0 = now_s();
     hint_invalidate();
+    baro_keep = false;      // (a list build re-sorts the particles, not f4)
     bool counted = resumed && halt_kind == 3;
     for (int attempt = 0; attempt < 6; ++attempt) {
       if (dd_on) {      // (a slab rebuild the host calls for, not one of the device's decisions: counted on the host)
@@ -1558,7 +1572,7 @@ template <typename R> struct CtxT : Ctx {
   }
 
   template <bool ENERGY> int launch_pair(V4* fdst, int tpp) {
-    const double hs = 0.5 * skin_eff();
+    const double hs = half_skin_eff();
     const bool coul = coul_on();
     if (coul) {      // the kernels with the Coulomb term are built for one lane per particle and 512-thread blocks
       if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a Coulomb pair registered only tpp = 1 (or 0, automatic) is built");
@@ -1860,6 +1874,99 @@ template <typename R> struct CtxT : Ctx {
     hipLaunchKernelGGL(k_scale_v<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, resc_buf.p + 1, (const DevCtl*)ctl.p);
   }
 
+  // ---- pressure (chem_get_pressure) and Berendsen barostat (chem_barostat_berendsen); the rules: chem_baro_host.hpp ----
+  DBuf<double> vlist, vpart, baro_buf;   // bonded virial per list / per block; k_baro_mu's results
+  double* baro_pin = nullptr;            // pinned host words the step's (P, mu, mu^3, ...) are copied into
+  int launch_bonded_virial(bool per_list = true) {      // returns the number of block partials in vpart; per_list: the sums by list too
+    const int nbv = cdiv(n, 256);
+    if (vpart.n < (size_t)nbv) vpart.alloc((size_t)nbv + 64);
+    if (per_list) { vlist.alloc(CHEM_MAX_LISTS); HIPCHK(hipMemsetAsync(vlist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream)); }
+    hipLaunchKernelGGL((k_bonded_virial<R>), dim3(nbv), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, per_list ? vlist.p : (double*)nullptr, vpart.p,
+                       ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+    return nbv;
+  }
+  void pressure(chem_pressure* out) override {
+    chem_obs ob;
+    observe(&ob);      // kinetic sum and non-bonded virial (summed over the ranks of a decomposition)
+    std::memset(out, 0, sizeof(*out));
+    std::vector<double> hv(CHEM_MAX_LISTS, 0.0);
+    if (nbent > 0 && n > 0) { launch_bonded_virial(); vlist.download(hv, CHEM_MAX_LISTS, stream); }
+    if (dd_on && P > 1) {
+      HIPCHK(hipMemcpyAsync(redbuf.p, hv.data(), sizeof(double) * CHEM_MAX_LISTS, hipMemcpyHostToDevice, stream));
+      tr->allreduce_sum_f64(redbuf.p, CHEM_MAX_LISTS, stream);
+      HIPCHK(hipMemcpyAsync(hv.data(), redbuf.p, sizeof(double) * CHEM_MAX_LISTS, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    out->volume = L[0] * L[1] * L[2]; out->mv2 = 2.0 * ob.ekin; out->virial_nb = ob.virial_nb;
+    double w = ob.virial_nb;
+    for (size_t l = 0; l < top.lists.size(); ++l) { out->virial_list[l] = hv[l]; w += hv[l]; }
+    out->virial = w;
+    out->pressure = baro_pressure(out->mv2, w, out->volume);
+  }
+  // the box lengths alone changed (same cell grid, same plan): everything the kernels take by value
+  void refresh_box_lengths() {
+    for (int d = 0; d < 3; ++d) {
+      box.L[d] = (R)L[d]; box.invL[d] = (R)(1.0 / L[d]);
+      box.cell_inv[d] = (R)((box.nc[0] > 0 ? box.nc[d] : 1) / L[d]);
+      boxd.L[d] = L[d]; boxd.invL[d] = 1.0 / L[d];
+      box.qs[d] = boxd.qs[d] = q_scale(d); box.qh[d] = boxd.qh[d] = 0.5 * L[d];
+      box.qsf[d] = (R)q_scale(d); box.qinvf[d] = (R)(1.0 / q_scale(d));
+    }
+  }
+  bool baro_replan_pending = false;      // geom_dirty was raised by a scaling, not by the caller: the forces in f4 stay valid
+  // One barostat action, behind the second half kick (and the velocity rescaling) of the step that has just been counted:
+  // P from the positions and velocities of this step and the virial of its force evaluation (the energy instantiation over the
+  // same lists: a second pair pass), mu on the device, the fp64 positions scaled there; the host reads mu, moves the box and
+  // asks for the rebuild behind the next drift.  One host synchronisation of its own (on the fused path the run loop's look at the
+  // control block in front of it, for a stop by the device, is a second; the rebuild that follows has its own).
+  void baro_step() {
+    const int nb = launch_pair<true>(x4o.p, pick_tpp());      // (scratch force buffer: f4 keeps the step's forces)
+    const int nbv = nbent > 0 ? launch_bonded_virial(false) : 0;
+    const int nkb = cdiv(n, 256);
+    hipLaunchKernelGGL(k_kinetic<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, ekout.p);
+    baro_buf.alloc(8);
+    const bool cq = coul_on();
+    hipLaunchKernelGGL(k_baro_mu, dim3(1), dim3(256), 0, stream, (const double*)ekout.p, nkb, (const double*)eout.p, nb, cq ? (const double*)eoutq.p : (const double*)nullptr, cq ? nb : 0,
+                       (const double*)vpart.p, nbv, L[0] * L[1] * L[2], dt, baro_tau, baro_p0, baro_buf.p);
+    if constexpr (!kFixed) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x4.p, (const double*)(baro_buf.p + 1), (const DevCtl*)ctl.p);
+    if (!baro_pin) HIPCHK(hipHostMalloc((void**)&baro_pin, 8 * sizeof(double), hipHostMallocDefault));
+    double* h = baro_pin;
+    HIPCHK(hipMemcpyAsync(h, baro_buf.p, 6 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!baro_mu3_ok(h[2])) {
+      char msg[256];
+      snprintf(msg, sizeof(msg), "Berendsen barostat: mu^3 = %.6g <= 0 at step %lld (P = %.6g, P0 = %.6g, dt/tau = %.6g): the box cannot be scaled; use a larger tau",
+               h[2], (long long)step, h[0], baro_p0, dt / baro_tau);
+      throw ChemError(CHEM_ESTATE, msg);
+    }
+    const double mu = h[1];
+    for (int d = 0; d < 3; ++d) L[d] *= mu;
+    // The box lengths reach every kernel by value from here on; what the device keeps in absolute length follows mu: the
+    // reference positions of the displacement criterion (fp64 build) and the length fields of the tile descriptors.
+    refresh_box_lengths();
+    if constexpr (!kFixed) if (opt_criterion) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x0.p, (const double*)(baro_buf.p + 1), (const DevCtl*)ctl.p);
+    if (use_tiles) hipLaunchKernelGGL((k_baro_tile_desc<R>), dim3(std::min(ntiles, 2048)), dim3(128), 0, stream, ntiles, tile_cap, (const int*)cell_start.p, box, tdesc.p, ctl.p,
+                                      (const int*)cell_sub.p, (use_fused && opt_lpt) ? (const int*)tile_pos.p : (const int*)nullptr);
+    // The lists stay.  A scaling changes a listed separation by at most |mu - 1| (rc + skin_eff): half of that per particle
+    // (baro_list_charge), plus |mu - 1| skin_eff / 2 for the displacement already accumulated, which scales too, is charged
+    // as displacement -- taken off the half skin of every later decision, under both criteria, until the device has built lists
+    // again (its counters say so).  Where the charge and the distance accumulated so far already exceed the half skin, the
+    // lists are built behind the next drift whatever the device decides.
+    const DevCtl hc = read_ctl();
+    if (hc.rebuild_count != baro_seen_builds) { baro_charge = 0; baro_seen_builds = hc.rebuild_count; }
+    if (hc.ref_rebuilds != baro_seen_ref) { baro_charge_ref = 0; baro_seen_ref = hc.ref_rebuilds; }
+    const double c = baro_list_charge(mu, rc, skin_eff()) + 0.5 * std::fabs(mu - 1.0) * skin_eff();
+    baro_charge += c; baro_charge_ref += c;
+    if (hc.acc_maxdist + baro_charge > 0.5 * skin_eff()) { resort = true; hint_invalidate(); }
+    // If the new box asks for another cell grid than the one in force (either direction), the geometry is planned again in
+    // front of the list build that follows the next drift; until then the tables of the old plan stay (the reaction work of
+    // this step reads them: same particles, same tiles).
+    if (baro_replan(L, rc + skin_eff(), box.nc)) {
+      if (g_trace) fprintf(stderr, "[chem trace] barostat: box %.6f %.6f %.6f asks for another cell grid at step %lld\n", L[0], L[1], L[2], (long long)step);
+      geom_dirty = true; baro_replan_pending = true; resort = true; hint_invalidate();
+    }
+  }
+
   // Does step `step` get its neighbour launch?  (single domain, fused rebuild; the rule and its reasons: chem_idle_host.hpp)
   // The host enqueues far faster than the device runs, so it first lets the device come within idle_lag steps: it spins on the
   // pinned words, for a bounded time -- nothing on the device ever waits for the host, and a wait that runs out only means one
@@ -1887,6 +1994,11 @@ template <typename R> struct CtxT : Ctx {
   // ---- the hot call -------------------------------------------------------------------
   void run(int64_t nsteps) override {
     if (!(dt > 0)) throw ChemError(CHEM_ESTATE, "dt not set");
+    if (baro_on() && dd_on) throw ChemError(CHEM_ENOTIMPL, "Berendsen barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
+    // barostat: the forces of the last run's final step (evaluated before its scaling) are the ones this run starts from,
+    // provided nothing has touched the system or re-sorted the particles since
+    const bool keep_forces = baro_on() && baro_keep && !(particles_dirty || (geom_dirty && !baro_replan_pending) || labels_dirty || pair_dirty || coul_dirty || res_dirty || cap_dirty || fix_dirty || bonded_dirty || excl_dirty);
+    baro_keep = false;
     flush_host_state();
     hint_invalidate();      // (whatever the last call's launches published: the first step of a call gets its neighbour launch)
     const double t0 = now_s();
@@ -1912,9 +2024,11 @@ template <typename R> struct CtxT : Ctx {
     }
     if (react_on && !reactions.empty()) reserve_reaction_tables();
     force_step_off = 0;
-    if (resort) rebuild_now();
-    compute_forces();
-    if (lang) launch_integrate<0>(true, true, step, 0);  // thermalize: f += friction + noise, stored
+    if (!keep_forces) {
+      if (resort) rebuild_now();
+      compute_forces();
+      if (lang) launch_integrate<0>(true, true, step, 0);  // thermalize: f += friction + noise, stored
+    }
     bool need_int1 = true;
     const int64_t step0 = step;
     bool resume = false;       // re-entering the step at which the device stopped the run (DevCtl::halt)
@@ -1950,6 +2064,7 @@ template <typename R> struct CtxT : Ctx {
       force_step_off = 1;      // (hybrid lists: these are the forces of step + 1, whose counter moves behind the integration)
       if (resume) { resume = false; skip_log_add(false); rebuild_now(true, resume_kind, resume_par); compute_forces(); }   // (positions are drifted, forces of this step were never evaluated)
       else if (dd_on) dd_step_sync();   // decision, (rebuild,) forces
+      else if (baro_on() && resort) { if (geom_dirty) setup_geometry(); rebuild_now(); compute_forces(); }      // the scalings used the skin up, or the box asks for another plan
       else if (skip_applies() && !neighbour_launch_wanted()) {
         // the step cannot need a rebuild as far as the host can tell: the force kernel's prologue folds, decides and keeps the books
         pair_da = DecideArgs{nullptr, 0, nullptr, 0, fused_par, 0, 0.5 * skin, foldmax.p, hint_dev(), hint_gen, step};
@@ -1963,11 +2078,12 @@ template <typename R> struct CtxT : Ctx {
       force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
 
-      if (last || react_due || atrp_due || !opt_fuse || resc_kind) {
+      if (last || react_due || atrp_due || !opt_fuse || resc_kind || baro_on()) {
         launch_integrate<1>(lang, lang, step, 1);
         ++step;
         if (resc_kind == 1 || resc_kind == 3 || (resc_kind == 2 && step % (int64_t)resc_param == 0)) rescale_velocities();
-        if ((react_due || atrp_due || last) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
+        if ((react_due || atrp_due || last || baro_on()) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
+        if (baro_on()) baro_step();      // aftIntV: behind the velocity rescaling, in front of the reaction work
         if (react_due || atrp_due || last) skip_log_confirm();
         if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
         if (react_due) react_step();      // (takes the type snapshot of the removal rules where it finds events)
@@ -1986,6 +2102,7 @@ template <typename R> struct CtxT : Ctx {
       timed_step = false;
     }
     check_flags();
+    baro_keep = baro_on();
     tm.run_wall_s += now_s() - t0;
     tm.steps += nsteps;
     if (opt_time_pair && !ev_used && timed_idle_skips) { tm.decide_kernel_ms = 0; tm.decide_kernel_launches = timed_idle_skips; }
@@ -3320,6 +3437,31 @@ int chem_get_coulomb(chem_ctx* ctx, double* epot, double* virial) {
   CTX.observe(&o);
   if (epot) *epot = CTX.coul_epot;
   if (virial) *virial = CTX.coul_virial;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_get_pressure(chem_ctx* ctx, chem_pressure* out) { API_BEGIN REQUIRE(out, CHEM_EINVAL, "null output"); CTX.pressure(out); return 0; API_END(ctx) }
+
+int chem_barostat_berendsen(chem_ctx* ctx, double pressure, double tau) {
+  API_BEGIN
+  Ctx& c = CTX;
+  if (!(tau > 0)) {      // off: nothing of it stays (lists that scalings have aged are built again first)
+    if (c.baro_charge > 0 || c.baro_charge_ref > 0) c.resort = true;
+    c.baro_tau = 0; c.baro_p0 = 0; c.baro_keep = false; c.baro_charge = c.baro_charge_ref = 0; c.baro_seen_builds = c.baro_seen_ref = -1;
+    return 0;
+  }
+  REQUIRE(std::isfinite(pressure) && std::isfinite(tau), CHEM_EINVAL, "Berendsen barostat: pressure and tau must be finite");
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "Berendsen barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
+  c.baro_p0 = pressure; c.baro_tau = tau;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_get_box(chem_ctx* ctx, double L[3]) {
+  API_BEGIN
+  REQUIRE(L, CHEM_EINVAL, "null output");
+  for (int d = 0; d < 3; ++d) L[d] = CTX.L[d];
   return 0;
   API_END(ctx)
 }

@@ -16,6 +16,7 @@
 #include "chem_geom_host.hpp"
 #include "chem_idle_host.hpp"
 #include "chem_roworder_host.hpp"
+#include "chem_baro_host.hpp"
 
 namespace chem {
 
@@ -3709,6 +3710,109 @@ __global__ __launch_bounds__(256) void k_scale_v(int i0, int n, Vec4<R>* __restr
   Vec4<R> v = v4[i];
   v.x *= s; v.y *= s; v.z *= s;
   v4[i] = v;
+}
+
+// =======================================================================================
+// K12 pressure and Berendsen barostat (analysis.Pressure, integrator.BerendsenBarostat; chem_baro_host.hpp)
+// =======================================================================================
+// sum of `nblk` values part[stride * k + off] by one block of 256, in an order that depends on nothing but nblk
+__device__ __forceinline__ double baro_block_sum(const double* __restrict__ part, int nblk, int stride, int off, double* red) {
+  double s = 0;
+  for (int k = threadIdx.x; k < nblk; k += blockDim.x) s += part[(size_t)stride * k + off];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  __syncthreads();
+  if (lane_id() == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+// Bonded virial: walks the bstart / bent / bpar entries of k_bonded<R, true>.  Member 0 of a pair entry contributes r_ij . F_ij
+// once (as the energy does), so the sum is right on slabs, where the partner may be a ghost.  The force law is bonded_term's
+// own (hybrid lambda and 1-4 Coulomb charges included: qtag is read for Coulomb entries only, hy.par for hybrid slots only).
+// Triples and quadruples depend on angles alone: their virial vanishes identically and is left at zero.
+// vlist[l] += the share of list l (atomics: an observable; nullptr: not wanted); part[block] = the block's sum over all lists, reduced in a fixed
+// order (what the barostat reads: the same bits for the same state).
+template <typename R>
+__global__ __launch_bounds__(256) void k_bonded_virial(int i0, int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                       const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                       const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ vlist, double* __restrict__ part,
+                                                       DevCtl* ctl, BTab bt, HybridArgs hy, const R* __restrict__ qtag) {
+  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+  double w = 0;
+  if (i < i0 + n) {
+    const int tg = tag[i];
+    const int e0 = bstart[tg], e1 = bstart[tg + 1];
+    for (int e = e0; e < e1; ++e) {
+      const BondedEntry be = bent[e];
+      const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+      const BondedParam& bp = bpar[slot];
+      if (bp.arity == 4) ++e;      // (quadruples occupy two consecutive entries)
+      if (bp.arity != 2 || me != 0) continue;
+      const int j0 = rtag[be.t0], j1 = rtag[be.t1];
+      if ((j0 | j1) < 0) { ctl->bonded_missing = 1; continue; }
+      double q0 = 0, q1 = 0;
+      if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
+      D3 f = {0, 0, 0};
+      bonded_term<R, false, false, true, true>(bp, 0, j0, j1, 0, 0, x4, box, f, nullptr, ctl, bt, hybrid_lambda(hy, bp, slot, be.t2), q0, q1);
+      const D3 d = minimgD(box, posD<R>(x4[j0], box) - posD<R>(x4[j1], box));
+      const double t = dot3(d, f);
+      if (vlist) atomicAdd(&vlist[bp.list], t);      // (the per-step launch of the barostat reads part[] alone)
+      w += t;
+    }
+  }
+  __shared__ double red[4];
+  for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o);
+  if (lane_id() == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+// One block folds the partials of the step -- k_kinetic (Ekin at [4k]), the energy instantiation of the pair kernel (r.F at
+// [3k + 2]; Coulomb term at [2k + 1]) and k_bonded_virial -- into P and mu.  out: [0] P, [1] mu, [2] mu^3, [3] sum m v^2,
+// [4] non-bonded virial, [5] bonded virial.  mu = 1 where mu^3 <= 0: the host reads [2] and stops the run.
+__global__ __launch_bounds__(256) void k_baro_mu(const double* __restrict__ ekpart, int nk, const double* __restrict__ epart, int ne, const double* __restrict__ qpart, int nq,
+                                                 const double* __restrict__ bpart, int nbv, double volume, double dt, double tau, double p0, double* __restrict__ out) {
+  __shared__ double red[4];
+  const double ek = baro_block_sum(ekpart, nk, 4, 0, red);
+  const double wnb = baro_block_sum(epart, ne, 3, 2, red) + baro_block_sum(qpart, nq, 2, 1, red);
+  const double wb = baro_block_sum(bpart, nbv, 1, 0, red);
+  if (threadIdx.x == 0) {
+    const double mv2 = 2.0 * ek;
+    const double p = baro_pressure(mv2, wnb + wb, volume);
+    const double mu3 = baro_mu3(dt, tau, p0, p);
+    out[0] = p; out[1] = baro_mu3_ok(mu3) ? baro_mu(mu3) : 1.0; out[2] = mu3; out[3] = mv2; out[4] = wnb; out[5] = wb;
+  }
+}
+// After a scaling the tile descriptors of the last list build keep their lengths in the old unit: periodic shifts, the
+// reference point and the cell edges of the staged coordinates, the fixed-point scale.  This kernel computes the tables of every
+// tile again from the unchanged cell_start and the NEW box (tile_tables, the routine of the list build) and copies those
+// fields alone into the descriptor in force -- the slot tables, the home runs and the list base (geom[5]) stay what the list
+// was built with.  pos: the descriptor's place where the fused rebuild stores them in launch order (nullptr: by tile).
+template <typename R>
+__global__ __launch_bounds__(128) void k_baro_tile_desc(int ntiles, int CAP, const int* __restrict__ cell_start, Box<R> box,
+                                                        TileLDS<R>* __restrict__ desc, DevCtl* ctl, const int* __restrict__ cell_sub,
+                                                        const int* __restrict__ pos) {
+  if (ctl->halt) return;
+  __shared__ TileLDS<R> T;
+  constexpr int a0 = (int)(offsetof(TileLDS<R>, cellshx) / 4), a1 = (int)(offsetof(TileLDS<R>, hstart) / 4);
+  constexpr int b0 = (int)(offsetof(TileLDS<R>, org) / 4), b1 = (int)(sizeof(TileLDS<R>) / 4);
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();
+    tile_tables<R>(T, CAP, tile, cell_start, box, ctl, cell_sub);
+    const int* src = reinterpret_cast<const int*>(&T);
+    int* dst = reinterpret_cast<int*>(&desc[pos ? pos[tile] : tile]);
+    for (int k = a0 + (int)threadIdx.x; k < a1; k += blockDim.x) dst[k] = src[k];
+    for (int k = b0 + (int)threadIdx.x; k < b1; k += blockDim.x) dst[k] = src[k];
+  }
+}
+// x <- mu x about the origin.  Only the fp64 build keeps lengths in its position words; the fp32 build's are box fractions and
+// follow the box lengths the host hands to the next launches.
+__global__ __launch_bounds__(256) void k_baro_scale_x(int n, double4* __restrict__ x4, const double* __restrict__ mu, const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double s = *mu;
+  double4 x = x4[i];
+  x.x *= s; x.y *= s; x.z *= s;
+  x4[i] = x;
 }
 
 // =======================================================================================

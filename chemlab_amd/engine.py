@@ -62,7 +62,6 @@ class Engine:
     def set_box(self, L):
         L = np.ascontiguousarray(L, dtype=np.float64)
         self._ck(self.api.set_box(self.ctx, _ptr(L, C.c_double)))
-        self.box = L.copy()
 
     def set_cutoff(self, max_cutoff, skin):
         self._ck(self.api.set_cutoff(self.ctx, float(max_cutoff), float(skin)))
@@ -509,6 +508,33 @@ class Engine:
         return dict(step=o.step, npart=o.npart, ekin=o.ekin, temperature=o.temperature,
                     epot_lj=o.epot_lj, epot_tab=o.epot_tab, epot_list=list(o.epot_list)[:nl],
                     list_size=list(o.list_size)[:nl], momentum=list(o.momentum), virial_nb=o.virial_nb)
+
+    # ---- pressure, Berendsen barostat, current box (include/chem_mi355.h "pressure and barostat") ----
+    def pressure(self):
+        """P = (sum m v^2 + W) / (3 V) at the current state, with its parts: volume, mv2, virial_nb, virial_list, virial."""
+        fn = getattr(self.api, "get_pressure", None)
+        if fn is None:
+            raise NotImplementedError("Pressure: the CPU checker has no virial of the bonded lists")
+        p = _capi.Pressure()
+        self._ck(fn(self.ctx, C.byref(p)))
+        return dict(pressure=p.pressure, volume=p.volume, mv2=p.mv2, virial_nb=p.virial_nb,
+                    virial_list=list(p.virial_list)[:len(self._lists)], virial=p.virial)
+
+    def barostat_berendsen(self, pressure, tau):
+        """Isotropic Berendsen barostat on every step; tau <= 0 switches it off."""
+        fn = getattr(self.api, "barostat_berendsen", None)
+        if fn is None:
+            raise NotImplementedError("BerendsenBarostat: the CPU checker has no barostat (its box is fixed)")
+        self._ck(fn(self.ctx, float(pressure), float(tau)))
+
+    def box(self):
+        """The current box edges (they move while a barostat is on)."""
+        fn = getattr(self.api, "get_box", None)
+        if fn is None:
+            raise NotImplementedError("box: the CPU checker has no read-back of the box (it is fixed: what set_box was given)")
+        L = np.zeros(3)
+        self._ck(fn(self.ctx, _ptr(L, C.c_double)))
+        return L
 
     def timers(self):
         t = _capi.Timers()

@@ -108,7 +108,18 @@ class _RNG(object):
 class _OrthorhombicBC(object):
     def __init__(self, rng, boxL):
         self.rng = rng
-        self.boxL = Real3D(*[float(b) for b in boxL])
+        self._boxL = Real3D(*[float(b) for b in boxL])
+        self._engine = None      # set by the storage: from then on the box is the engine's (a barostat moves it)
+
+    @property
+    def boxL(self):
+        """The box as it is now: read from the engine at every access, so that every writer prints the current one."""
+        if self._engine is not None:
+            try:
+                self._boxL = Real3D(*[float(b) for b in self._engine.box()])
+            except NotImplementedError:      # the CPU checker: the box it was given
+                pass
+        return self._boxL
 
 
 class _Particle(object):
@@ -127,6 +138,7 @@ class _DomainDecomposition(object):
         self._props = None
         self._uploaded = False
         system.engine.set_box(list(system.bc.boxL))
+        system.bc._engine = system.engine
 
     def addParticles(self, plist, *props):
         if self._uploaded:          # the particle set is on the engine: the new ones are appended (chem_add_particles)
@@ -881,6 +893,41 @@ class _BerendsenThermostat(object):
         self.system.engine.thermostat_rescale(None, 1.0, 1.0)
 
 
+class _BerendsenBarostat(object):
+    """integrator.BerendsenBarostat(system, pressure): .tau, .pressure (start_simulation.py:356-376): isotropic, on every step
+    (include/chem_mi355.h chem_barostat_berendsen).  Attributes set after addExtension reach the engine at once."""
+
+    def __init__(self, system, pressure=1.0):
+        # (the driver hands the analysis.Pressure observable here and sets the target through .pressure afterwards)
+        p0 = float(pressure) if isinstance(pressure, (int, float)) else 1.0
+        self.__dict__.update(system=system, _pressure=p0, _tau=1.0, _connected=False)
+
+    def _push(self):
+        if self._connected:
+            self.system.engine.barostat_berendsen(self._pressure, self._tau)
+
+    pressure = property(lambda self: self._pressure)
+    tau = property(lambda self: self._tau)
+
+    @pressure.setter
+    def pressure(self, v):
+        self.__dict__["_pressure"] = float(v)
+        self._push()
+
+    @tau.setter
+    def tau(self, v):
+        self.__dict__["_tau"] = float(v)
+        self._push()
+
+    def _connect(self, integrator):
+        self.__dict__["_connected"] = True
+        self._push()
+
+    def disconnect(self):
+        self.__dict__["_connected"] = False
+        self.system.engine.barostat_berendsen(0.0, 0.0)
+
+
 class _Isokinetic(object):
     """integrator.Isokinetic(system): .temperature, .coupling = rescale every `coupling` steps (start_simulation.py:345-348)."""
 
@@ -1488,7 +1535,7 @@ integrator = _ns(
     PostProcessChangePropertyByTopologyManager=_PostProcessChangeProperty, ReactionConstraintNeighbourState=_ReactionConstraintNeighbourState,
     TopologyParticleProperties=_TopologyParticleProperties, TopologyManager=_TopologyManager, ExtAnalyze=_ExtAnalyze,
     StochasticVelocityRescaling=_StochasticVelocityRescaling,
-    BerendsenThermostat=_BerendsenThermostat, BerendsenBarostat=_unsupported("integrator.BerendsenBarostat"),
+    BerendsenThermostat=_BerendsenThermostat, BerendsenBarostat=_BerendsenBarostat,
     Isokinetic=_Isokinetic, LangevinBarostat=_unsupported("integrator.LangevinBarostat"),
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
     DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
@@ -1548,6 +1595,28 @@ class _KineticEnergy(_Observable):
 
     def compute(self):
         return self.system.engine.observe()["ekin"]
+
+
+class _Pressure(_Observable):
+    """analysis.Pressure(system).compute(): (sum m v^2 + W) / (3 V) in the engine's units (start_simulation.py:466-469;
+    include/chem_mi355.h chem_get_pressure)."""
+
+    def __init__(self, system):
+        _Observable.__init__(self, system)
+
+    def compute(self):
+        return self.system.engine.pressure()["pressure"]
+
+
+class _BoxSize(_Observable):
+    """The `L` column that goes with `P` (start_simulation.py:466-469): the x edge of the current box.  The reference's
+    class is in the external fork; what it reports for a box that is not cubic is unpinned."""
+
+    def __init__(self, system):
+        _Observable.__init__(self, system)
+
+    def compute(self):
+        return float(self.system.bc.boxL[0])
 
 
 class _PotentialEnergy(_Observable):
@@ -1688,7 +1757,7 @@ analysis = _ns(
     NFixedPairListEntries=_NFixedPairListEntries, NumFixDistances=_NumFixDistances, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
-    Pressure=_unsupported("analysis.Pressure"), PressureTensor=_unsupported("analysis.PressureTensor"),
+    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_unsupported("analysis.PressureTensor"),
 )
 
 esutil = _ns(RNG=_RNG)

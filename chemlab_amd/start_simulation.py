@@ -133,7 +133,7 @@ def write_final_outputs(args, system, gt, conf, bonded, angles, dihedrals, chem_
     topology_manager.save_res_topology(prefix + "_res_topology.dat")
     topology_manager.save_residues(prefix + "_residue_list.dat")
     pos, _ = _conf_positions(system, conf, unfolded=False)
-    outputs.write_gro(prefix + "_confout.gro", conf, pos, conf.box)
+    outputs.write_gro(prefix + "_confout.gro", conf, pos, list(system.bc.boxL))      # the box as it is now (a barostat moves it)
     espressopp.io.DumpGRO(system, system.integrator, filename=prefix + "_whole_confout.gro").dump()
     if ar is not None:
         ar.save_reaction_counters(prefix + "_reaction_counters")
@@ -166,8 +166,9 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     parser = app_args._args()
     args = parser.parse_args(argv)
     parser.save_to_file("%sparams.out" % args.output_prefix, args)
-    if args.pressure is not None:
-        raise NotImplementedError("barostats are outside the MI355X hot-path scope")
+    if args.pressure is not None and args.pressure > 0.0 and args.barostat == "lv":
+        raise NotImplementedError("--pressure with --barostat lv (the default): espressopp.integrator.LangevinBarostat is outside the MI355X "
+                                  "hot-path scope; use --barostat br (BerendsenBarostat)")
     kb, mass_factor = args.kb, args.mass_factor
     lj_cutoff, cg_cutoff = args.lj_cutoff, args.cg_cutoff
     max_cutoff = max(lj_cutoff, cg_cutoff)            # as the reference, without coulomb_cutoff: a larger one is refused at run()
@@ -273,6 +274,18 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
         integrator.addExtension(th)
     elif args.thermostat != "no":
         raise Exception("Wrong thermostat keyword: `%s`" % args.thermostat)   # start_simulation.py:351-352
+    # pressure coupling (start_simulation.py:356-376)
+    pressure_comp = espressopp.analysis.Pressure(system)
+    if args.pressure is not None and args.pressure > 0.0:
+        pressure = args.pressure * 0.060221374            # bar -> kJ/mol/nm^3
+        if args.barostat != "br":                         # ("lv" was refused above)
+            raise Exception("Wrong barostat keyword: `%s`" % args.barostat)
+        log("Barostat: Berendsen with P=%s and tau=%s" % (pressure, args.barostat_tau))
+        barostat = espressopp.integrator.BerendsenBarostat(system, pressure_comp)
+        barostat.tau = args.barostat_tau
+        barostat.pressure = pressure
+        integrator.addExtension(barostat)
+        args.store_pressure = True
     # topology manager wiring (start_simulation.py:378-441): spawned angles land in the dynamic Types list
     for name, (fl, inter) in list(bonded.items()):
         dynamic_exclusion_list.observe_tuple(fl)
@@ -306,6 +319,9 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
             temp_comp.add_type(t_id)
     mon.add_observable("T", temp_comp)
     mon.add_observable("Ekin", espressopp.analysis.KineticEnergy(system))
+    if args.store_pressure:                               # start_simulation.py:466-469
+        mon.add_observable("P", pressure_comp)
+        mon.add_observable("L", espressopp.analysis.BoxSize(system))
     for k in range(system.getNumberOfInteractions()):
         mon.add_observable(system.getNameOfInteraction(k), espressopp.analysis.PotentialEnergy(system, system.getInteraction(k)), False)
     for i, (gname, fpl, _) in enumerate(chem_fpls):
@@ -322,7 +338,8 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     integrator.addExtension(espressopp.integrator.ExtAnalyze(mon, cad["energy_collect"]))
     # trajectory + topology writer (start_simulation.py:571-657): H5MD tree, see espp._DumpH5MD for the on-disk form
     traj_file = espressopp.io.DumpH5MD(
-        system, "%s_%s_traj.h5" % (args.output_prefix, rng_seed), group_name="atoms", static_box=True,
+        system, "%s_%s_traj.h5" % (args.output_prefix, rng_seed), group_name="atoms",
+        static_box=False if args.pressure else True,      # start_simulation.py:578: the box of an NPT run is per frame
         store_species=args.store_species, store_res_id=args.store_res_id, store_charge=args.store_charge, store_position=args.store_position,
         store_state=args.store_state, store_lambda=args.store_lambda, store_force=args.store_force, store_velocity=args.store_velocity,
         store_mass=args.store_mass, is_single_prec=args.store_single_precision, chunk_size=256)
@@ -370,7 +387,7 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
                 integrator.addExtension(ext)
             reactions_enabled = True
             pos, vel = _conf_positions(system, conf, unfolded=True)      # start_simulation.py:741-745
-            outputs.write_gro("%s_%s_before_reaction_confout.gro" % (args.output_prefix, args.rng_seed), conf, pos, conf.box, velocities=vel)
+            outputs.write_gro("%s_%s_before_reaction_confout.gro" % (args.output_prefix, args.rng_seed), conf, pos, list(system.bc.boxL), velocities=vel)
             if "hook_init_reaction" in hooks and not hooks["hook_init_reaction"](system, integrator, ar, gt, args):
                 raise RuntimeError("hook_init_reaction return False")
             if not save_traj_topology:                                                             # start_simulation.py:750-757

@@ -556,6 +556,56 @@ int chem_thermostat_svr(chem_ctx* ctx, double kT, double coupling, uint64_t seed
  * on top, uncapped (extension order).  max_force <= 0 switches it off. */
 int chem_cap_force(chem_ctx* ctx, double max_force);
 
+/* ---- pressure and barostat (NPT) ------------------------------------------------------- */
+/* analysis.Pressure(system).compute() and integrator.BerendsenBarostat(system, pressure) with .tau / .pressure --
+ * start_simulation.py:356-376, 466-469.  The arithmetic is in the external fork, so this rule set is this build's own
+ * ([EXT-RECALL], parity unpinned; DESIGN.md "Pressure and barostat").
+ *
+ * Pressure:  P = (sum_i m_i v_i^2 + W) / (3 V),  V = Lx Ly Lz, in the engine's units, over all particles (dummies included).
+ * W = sum r.F over every registered interaction:
+ *   - non-bonded: exactly chem_obs.virial_nb (LJ, tables, Coulomb, capped and lambda-weighted terms, each with the force that
+ *     was applied);
+ *   - pair lists: r_ij . F_ij of every entry, one list at a time (harmonic, FENE, FENE+LJ, tabulated, 1-4 LJ, 1-4 Coulomb),
+ *     a hybrid list's entries times their lambda; member 0 of an entry contributes it once, so it is right on slabs;
+ *   - triple and quadruple lists depend on angles only: their virial vanishes identically under uniform scaling and is
+ *     reported as exactly 0 (it is not evaluated).
+ * Not in W: thermostat friction and noise, the clipping of chem_cap_force, the chem_fix_* constraint.
+ * Same preconditions as chem_observe; works on slabs (the sums join the all-reduce). */
+typedef struct chem_pressure {
+  double pressure;
+  double volume;
+  double mv2;                          /* sum_i m_i v_i^2 */
+  double virial_nb;                    /* == chem_obs.virial_nb */
+  double virial_list[CHEM_MAX_LISTS];
+  double virial;                       /* W = virial_nb + sum of virial_list */
+} chem_pressure;
+int chem_get_pressure(chem_ctx* ctx, chem_pressure* out);
+/* Berendsen barostat, isotropic, on every step at the reference's aftIntV point: after the second half kick of step s and
+ * after a velocity-rescale thermostat (if any), before the reaction, dissociation or ATRP work of that step.
+ *     mu = [1 - (dt / tau) (P0 - P)]^(1/3),   P from x(t+dt), v(t+dt) and the virial of the step's own force evaluation;
+ *     L <- mu L,  x <- mu x about the origin for every particle (dummies and the unfolded image bookkeeping scale too:
+ *     CHEM_STATE_POS_UNFOLDED = pos + image * L).
+ * Velocities and forces are not touched: the next half kick uses the forces evaluated before the scaling, also when it is the
+ * first of the next chem_run (run(a); run(b) is run(a + b)), unless the system was changed or observed in between in a way
+ * that re-sorts the particles (then the forces are evaluated again at the scaled positions).
+ * mu^3 <= 0 stops chem_run with CHEM_ESTATE "Berendsen barostat: ..."; there is no clamp.  tau <= 0 switches it off: the
+ * context then enqueues exactly the launches it enqueued before.  While it is on: the host waits for the device on every step (to read mu from
+ * pinned memory, the box travels to the kernels by value; on the fused path also to look for a stop by the device; and in a
+ * list build that the scalings ask for), the fused integrate and the skip_idle shortcut are off, the virial comes from a second
+ * pair pass (the energy instantiation, over the lists the step's forces used).  The lists outlive a scaling: every scaling is
+ * charged |mu - 1| (rc + skin_eff) / 2 (+ |mu - 1| skin_eff / 2 for the distance already accumulated) as displacement wherever
+ * the rebuild criterion accumulates, under both rebuild_criterion values, and what the device keeps in absolute length
+ * (reference positions, tile descriptors) follows mu.  After a scaling
+ * cell_grid(L, rc + skin_eff) is compared with the grid in force; if they differ, in either direction, the geometry is planned
+ * again in front of a list build behind the next drift, so the cell counts are always those a fresh context would plan at that box (this can switch
+ * between the tile path and the per-cell lists in the middle of a run).  Reaction cutoffs and fixed distances are absolute
+ * lengths and do not scale.  The three box edges are multiplied by the same mu: their ratios hold to one rounding per step.
+ * Not on the decomposed path, a gap of that path: the call is CHEM_ENOTIMPL after chem_comm_init*, and chem_run refuses a
+ * context that was decomposed after the call. */
+int chem_barostat_berendsen(chem_ctx* ctx, double pressure, double tau);
+/* system.bc.boxL: the current box edges */
+int chem_get_box(chem_ctx* ctx, double L[3]);
+
 /* ---- reactions ----------------------------------------------------------------------- */
 /* integrator.ChemicalReaction(system, vl, storage, tm, interval) + .nearest_mode
  * + .max_per_interval  reaction_setup.py:416-427

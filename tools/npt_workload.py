@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""The price of the barostat per step ("Pressure and barostat"; profiles/npt_kernels.txt): the C3 set-up
+of tools/bench_configs.py -- 128k beads of a tabulated polymer melt with harmonic bonds and angles -- with the barostat off
+(--tau 0: the launches every context enqueued before) or on (--tau T: a second pair pass for the virial, k_bonded_virial,
+k_baro_mu, the refresh of the tile descriptors and the host's waits per step; the lists live on across the scalings).
+
+    python3 tools/npt_workload.py [--tau T] [--dp D] [--steps K] [--warmup W] [--prec 32|64] [--chains N] [--time_pair N]
+
+The target pressure is the melt's own pressure after the warm-up plus --dp, so that the box moves but slowly.  The rule has no
+compressibility factor, so tau carries it: this stiff melt needs --tau of 100 or more (profiles/npt_kernels.txt uses 500; with
+--tau 5 the box oscillates with growing amplitude and the run stops with the barostat's mu^3 <= 0 error after five steps).
+Prints one JSON line: particles, steps, steps per second, the box edge before and after, per-kernel times (time_pair_kernel)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from chemlab_amd import workloads as W          # noqa: E402
+from chemlab_amd.engine import Engine           # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tau", type=float, default=0.0)
+    ap.add_argument("--dp", type=float, default=0.5)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--prec", type=int, default=32)
+    ap.add_argument("--chains", type=int, default=4000)
+    ap.add_argument("--time_pair", type=int, default=0)
+    a = ap.parse_args()
+    spec = W.polymer_melt(n_chains=a.chains, chain_len=32, seed=3)
+    g = Engine(device=0, precision=a.prec)
+    W.apply(spec, g)
+    g.run(a.warmup)
+    out = dict(particles=int(spec["n"]), tau=a.tau, steps=a.steps, precision=a.prec)
+    has_box = hasattr(g.api, "get_box")          # (a library from before the feature: the off state only)
+    if a.tau > 0:
+        p = g.pressure()
+        out.update(pressure_start=p["pressure"], p0=p["pressure"] + a.dp)
+        g.barostat_berendsen(p["pressure"] + a.dp, a.tau)
+    if has_box:
+        out["box_start"] = float(g.box()[0])
+    if a.time_pair:
+        g.set_option("time_pair_kernel", a.time_pair)
+    g.sync()
+    t0 = time.perf_counter()
+    g.run(a.steps)
+    g.sync()
+    dt = time.perf_counter() - t0
+    t = g.timers()
+    out.update(steps_per_s=a.steps / dt, rebuilds=int(t["rebuilds"]), list_rebuilds=int(t["list_rebuilds"]))
+    if has_box:
+        out["box_end"] = float(g.box()[0])
+    if a.time_pair:
+        for k in ("pair", "rebuild", "decide", "integrate", "bonded"):
+            n = t["%s_kernel_launches" % k]
+            out["%s_us" % k] = 1e3 * t["%s_kernel_ms" % k] / n if n else None
+    g.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
