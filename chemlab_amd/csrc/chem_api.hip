@@ -2452,6 +2452,21 @@ template <typename R> struct CtxT : Ctx {
       for (int role = 1; role <= 2; ++role)
         for (auto& rl : nb_rules) if (rl.reaction == e.r && (rl.invoke_on & role)) top.neighbour_change(role == 1 ? e.a : e.b, rl, chg);
     if (chg.empty()) return false;
+    // k_apply_props takes one lane per record: a particle that several visits changed (chained rules, two events around one
+    // neighbour) gets ONE record, with what the last visit left in the mirrors (every record holds absolute values; the state
+    // mirror is right wherever a record of the particle set it)
+    {
+      std::unordered_map<int32_t, size_t> at;
+      size_t w = 0;
+      for (const HostTopology::PropChange& c : chg) {
+        auto it = at.find(c.tag);
+        if (it == at.end()) { at.emplace(c.tag, w); chg[w++] = c; continue; }
+        HostTopology::PropChange& m = chg[it->second];
+        m.type = c.type; m.mass = c.mass; m.q = c.q;
+        if (c.set_state) { m.set_state = 1; m.state = c.state; }
+      }
+      chg.resize(w);
+    }
     apply_prop_changes(chg);
     if (!reads_state) state_mirror_stale = true;      // (rules that set a state moved the device copy, not a refreshed mirror)
     return true;

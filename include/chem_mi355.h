@@ -136,7 +136,9 @@ typedef struct chem_event {
   int64_t step;
   int64_t id_a, id_b;     /* particle taking role type_1 / type_2 */
   int32_t reaction;
-  int32_t pad;            /* with option "count_intra_inter": 1 = both particles were in one bonded cluster before the event */
+  int32_t pad;            /* with option "count_intra_inter": 1 = both particles had one mol_id before this step's bonds (the
+                             cluster labels as the step's scan read them: no bond of the same step counts); 0 without the option.
+                             Served on every path, slabs included: the labels are replicated on every rank. */
   double  r2;             /* fp64 squared distance at decision time */
 } chem_event;
 
@@ -624,7 +626,19 @@ int chem_reaction_init(chem_ctx* ctx, int interval, int nearest, int max_per_int
 /* ar.add_reaction(Reaction(...))  reaction_setup.py:81-92,506; returns the reaction index */
 int chem_reaction_add(chem_ctx* ctx, const chem_reaction_desc* d);
 /* topology_manager.register_tuple/triplet/quadruplet(list, t1, t2[, t3[, t4]])
- * start_simulation.py:395-440: new bonds spawn entries of `list` when the type tuple matches */
+ * start_simulation.py:395-440: new bonds spawn entries of `list` when the type tuple matches.
+ *   when         in the reaction step, after ALL bonds of the step are in the bond graph; the step's bonds (a, b) = (role 1,
+ *                role 2) are taken in canonical order (min id, max id).
+ *   types        those right after the step's events (a type the same event changed decides the match) and before any
+ *                neighbour change of the step (chem_reaction_neighbour_change does not).
+ *   candidates   per bond, neighbours walked in ascending tag: triples (n, a, b) for n bonded to a, then (a, b, m) for m bonded
+ *                to b; then quadruples, per n bonded to a: (n', n, a, b) for n' bonded to n, then (n, a, b, m) for m bonded to
+ *                b; then (a, b, m, m') for m bonded to b, m' bonded to m.  A particle appears once in a tuple.
+ *   which list   the first list of the tuple's arity, in handle order, that has a registered type tuple (in registration
+ *                order) equal to the tuple's types read forward or reversed; the forward match is preferred and the tuple is
+ *                stored in the matching orientation.  No later list is tried, also where that list holds the tuple already.
+ *   duplicates   a list holds a tuple once, whatever its orientation: two adjacent bonds of one step give one angle.
+ *   exclusion    the (first, last) pair of a tuple is excluded only when the tuple was inserted. */
 int chem_topology_register(chem_ctx* ctx, int arity, int list, const int32_t* types);
 /* integrator.PostProcessChangeNeighboursProperty(tm).add_change_property(old_type, TopologyParticleProperties, nb_level),
  * attached to the reactions of a group by `extensions=` (reaction_post_process.py:76-115, reaction_setup.py:128-165;
@@ -632,7 +646,9 @@ int chem_topology_register(chem_ctx* ctx, int arity, int list, const int32_t* ty
  * been applied and the new bonds are in the graph, every particle exactly `nb_level` bonds away from a reactant of an
  * event of `reaction` (invoke_on 1: the type_1 role, 2: the type_2 role, 3: both) whose type is `old_type` gets
  * new_type / new_mass / new_q and, if set_state != 0, chemical state new_state.  Events are visited in canonical order
- * (min id, max id), role 1 before role 2, rules in the order they were added. */
+ * (min id, max id), role 1 before role 2, rules in the order they were added.  The graph distance is exact (a particle
+ * reachable at two distances counts at the shorter one); the particles of one visit are taken in ascending tag; a later
+ * visit sees the types and states an earlier one left.  new_mass and new_q are set also where new_type == old_type. */
 typedef struct chem_nb_change {
   int32_t reaction, invoke_on, old_type, nb_level;
   int32_t new_type, set_state, new_state, pad;   /* set_state 0: keep the state, 1: state = new_state, 2: state += new_state (incr_state) */
@@ -643,7 +659,15 @@ int chem_reaction_neighbour_change(chem_ctx* ctx, const chem_nb_change* rule);
 /* reaction.add_constraint(ReactionConstraintNeighbourState(type, min_state, max_state), 'type_1' | 'type_2')
  * reaction_setup.py:203-204 (exchange reactions `A:B + C -> A:C + B`, which the reference sets up as a virtual A + C reaction
  * that requires A to carry a B): a candidate pair is accepted only if the particle in role `role` (1 | 2) has a bonded
- * neighbour of type nb_type whose chemical state is in [min_state, max_state).  One constraint per reaction and role. */
+ * neighbour of type nb_type whose chemical state is in [min_state, max_state).
+ *   one per reaction   a reaction carries ONE constraint: a second call for the same reaction replaces the first, whatever
+ *                      its role.
+ *   what is read       bond graph, types and states as they are at the start of that step's association scan (after the
+ *                      step's dissociation block; the events, neighbour changes and ATRP firings of earlier steps included).
+ *   who is judged      the particle that holds `role` after the role assignment of the scan: the forward assignment (lower
+ *                      tag = type_1) first, the reversed one only where the forward one does not fit.  A pair that fits
+ *                      both assignments (equal types, both in both windows) is judged by the forward one alone: it is NOT
+ *                      tried reversed when the constraint fails. */
 int chem_reaction_constraint(chem_ctx* ctx, int reaction, int role, int nb_type, int min_state, int max_state);
 /* integrator.RestrictReaction(...).define_connection(b1, b2)  reaction_setup.py:75-78,115-128 (group option
  * `connectivity_map`: a file of id pairs): reaction `reaction` only accepts candidate pairs whose unordered id pair was

@@ -1051,6 +1051,7 @@ int64_t orc_get_state(void* c, int what, void* out, int64_t cap) {
       case CHEM_STATE_RESID: i32[i] = o.res_id[i]; break;
       case CHEM_STATE_MOLID: i32[i] = (int32_t)o.id[o.mol_id[i]]; break;
       case CHEM_STATE_MASS: d[i] = o.mass[i]; break;
+      case CHEM_STATE_CHARGE: d[i] = o.q[i]; break;
       case CHEM_STATE_ID: i64[i] = o.id[i]; break;
       case CHEM_STATE_IMAGE: for (int k = 0; k < 3; ++k) i32[3 * i + k] = o.img[3 * i + k]; break;
       default: FAIL(CHEM_EINVAL, "get_state: what");

@@ -1,6 +1,7 @@
 """The association reaction step on the device against tests/react_ref.py (plain numpy, no oracle): every zoo member through
 every scan path -- LDS tiles, the per-cell list, the brute-force list, one slab that is its own neighbour, two and three slabs --
-in both precisions.  The members are frozen (no pair potential, K = 0 reaction bonds) with coordinates on a 2^-10 grid in
+in both precisions.  The members are frozen (no pair potential; K = 0 reaction bonds, or masses of 2^80 where a member carries
+bonded forces for test_forces_through_the_incremental_tables) with coordinates on a 2^-10 grid in
 power-of-two boxes, so fp64 and the fp32 build's fixed-point codec hold the same positions and every r2 is compared to the bit;
 the closing pairs (member 8) move without forces and are compared at the positions read back from the engine.
 tests/test_react_ref.py asserts the members' own conditions (matching rounds, ties, pairs on the cutoffs, candidate counts)."""
@@ -9,8 +10,9 @@ import pytest
 import react_ref as RR
 from chemlab_amd import workloads as W
 from chemlab_amd.engine import ChemError
+from test_gpu_bonded import TOL_E, TOL_F
 from test_gpu_parity import _HUB, _run_ranks
-from test_react_ref import _run_engine, check_against_reference, check_closing
+from test_react_ref import FORCE_MEMBERS, _run_engine, check_against_reference, check_closing, check_forces, run_with_forces
 
 pytestmark = pytest.mark.gpu
 
@@ -38,8 +40,9 @@ def _on_path(make_gpu, prec, path, body):
 @pytest.mark.parametrize("path", list(PATHS))
 @pytest.mark.parametrize("name", list(RR.ZOO))
 def test_reaction_step_matches_reference(make_gpu, name, path, prec):
-    """Events (step, id_a, id_b, reaction, r2 bits), bond list, STATE, TYPE, MASS, MOLID, RESID and exclusions after every
-    reaction step equal the reference's; every path and both precisions therefore equal each other."""
+    """Events (step, id_a, id_b, reaction, r2 bits), pad, bond list, spawned lists, STATE, TYPE, MASS, CHARGE, MOLID, RESID,
+    exclusions and ATRP stats rows after every reaction step (after every step where the member runs the ATRP activator) equal
+    the reference's; every path and both precisions therefore equal each other."""
     spec, _ = RR.member(name)
     for got in _on_path(make_gpu, prec, path, lambda g: _run_engine(g, spec)):
         check_against_reference(name, got)
@@ -51,6 +54,20 @@ def test_reaction_step_brute_force_list(make_gpu, name, prec):
     """A 4^3 box: 2.2 cells per axis, the brute-force list; the scan is k_react_scan on that list."""
     spec, _ = RR.member(name)
     check_against_reference(name, _run_engine(make_gpu(prec), spec))
+
+
+@pytest.mark.parametrize("prec", [64, 32])
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("name", FORCE_MEMBERS)
+def test_forces_through_the_incremental_tables(make_gpu, name, path, prec):
+    """`spawn` and `nbchange_typed` have bonded parameters and masses of 2^80: after every reaction step FORCE and chem_obs.epot_list
+    equal the autograd reference on the reference's own lists and types, within the tolerances of tests/test_gpu_bonded.py, relative
+    to the largest force component of the particle's cell.  The tuples and exclusions of a step and the slots re-resolved after a
+    retyping reach the device through the incremental table uploads only.  Nothing moves: POS after the last step is the input to
+    the bit."""
+    spec, ref = RR.member(name)
+    for out, pos in _on_path(make_gpu, prec, path, lambda g: run_with_forces(g, spec)):
+        check_forces(spec, ref, out, pos, TOL_F[prec], TOL_E[prec], "%s fp%d" % (path, prec))
 
 
 @pytest.mark.parametrize("prec", [64, 32])

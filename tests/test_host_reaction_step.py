@@ -1,7 +1,7 @@
 """CPU-only tests of the host algorithms of the reaction step (chemlab_amd/csrc/chem_react_host.hpp: sort_bond_events,
 trim_accepted, build_restrict_csr, constraint_bits, atrp_select -- what CtxT::react_step and CtxT::atrp_step call between
-their device launches).  Each is compared with a brute-force Python model; the ATRP selection, whose draws are Philox
-streams Python cannot reproduce, is checked through its invariants (the GPU-vs-oracle ATRP tests are its parity check).
+their device launches).  Each is compared with a brute-force Python model; the ATRP selection is checked through its
+invariants and against the model of tests/react_ref.py (atrp_model, which restates the Philox draw).
 The harness is compiled with g++ from tests/host/.
 
 sort_bond_events: the events of one step touch disjoint particles, so 4500 of them need 9000 tags; that case draws from
@@ -12,6 +12,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from react_ref import atrp_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -212,5 +214,15 @@ def test_atrp_select(harness, select_all, num, delta):
         if t not in seen:
             assert mirrors[t] == (types[t], states[t])
     assert int(st[8]) == 1
+    # the brute-force model of tests/react_ref.py (Philox restated in Python): the same row, the same flips in the same order
+    ty, sta, mass, q = np.array(types), np.array(states), np.ones(n), np.zeros(n)
+    A = dict(num_particles=num, select_from_all=select_all, ratio_activator=ra, ratio_deactivator=rd, delta_catalyst=delta, k_activate=0.9, k_deactivate=0.8,
+             seed=12345, centers=[dict(type_id=0, state=0, is_activator=0, new_type=1, delta_state=1, new_mass=2.5, new_q=0.25),
+                                  dict(type_id=1, state=1, is_activator=1, new_type=0, delta_state=-1, new_mass=1.0, new_q=0.0)])
+    row, flips = atrp_model(ty, sta, mass, q, A, 70)
+    assert (row["step"], row["candidates"], row["selected"], row["activated"], row["deactivated"]) == (step, ncand, selected, act, deact)
+    assert (row["ratio_activator"], row["ratio_deactivator"]) == (ra1, rd1)
+    assert flips == [tuple(int(x) for x in l.split()[:2]) + (int(l.split()[3]),) + tuple(float(x) for x in l.split()[4:]) for l in out[3:3 + nchg]]
+    assert mirrors == list(zip(ty.tolist(), sta.tolist()))
     # another step draws another selection
     assert run(harness, atrp_script(n, types, states, num, select_all, ra, rd, delta, 80))[3:] != out[3:]
