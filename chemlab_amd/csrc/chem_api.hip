@@ -17,10 +17,12 @@
 #include <mutex>
 #include <exception>
 #include <tuple>
+#include <type_traits>
 
 #include "chem_comm.hpp"
 #include "chem_geom_host.hpp"
 #include "chem_idle_host.hpp"
+#include "chem_launch_host.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
 #include "chem_res_host.hpp"
@@ -281,6 +283,50 @@ struct Ctx {
   virtual void debug_acc(double* out) = 0;
   virtual void join_async() {}
 };
+
+// ---- from a plan of chem_launch_host.hpp to an instantiation ---------------------------------------------------------------
+template <int V> using Int = std::integral_constant<int, V>;
+// a run-time value as a compile-time one: f(Int<V>) for the V among Vs that v equals; false where none does (or f says so)
+template <int... Vs, class F> bool pick_among(int v, F&& f) { return ((v == Vs && f(Int<Vs>{})) || ...); }
+
+// f(kernel, Int<MODE>) for the tile kernel of a variant.  What this can name is the header's built set (and what the header
+// lists as carried along is instantiated), so set_tile_lds_attr has prepared whatever launch_pair can launch.
+template <typename R, class F> void with_tile_kernel(const PairVariant& v, F&& f) {
+  const bool found = variant_built(v) && pick_among<0, 1>(v.energy, [&](auto E_) {
+    constexpr bool E = decltype(E_)::value != 0;
+    switch (v.mode) {
+      case 4: f(&k_pair_tiles_q<R, E>, Int<4>{}); return true;
+      case 5: f(&k_pair_tiles_res<R, E>, Int<5>{}); return true;
+      case 6: f(&k_pair_tiles_cap<R, E>, Int<6>{}); return true;
+      case 7: f(&k_pair_tiles_rescap<R, E>, Int<7>{}); return true;
+    }
+    return pick_among<0, 1, 2, 3>(v.mode, [&](auto M_) { return pick_among<1, 2, 4, 8>(v.tpp, [&](auto T_) {
+      return pick_among<256, 512, 1024>(v.block, [&](auto B_) { return pick_among<0, 1>(v.diag, [&](auto D_) {
+        constexpr int M = decltype(M_)::value, T = decltype(T_)::value, B = decltype(B_)::value;
+        constexpr bool D = decltype(D_)::value != 0;
+        if constexpr (tile_variant_built(M, T, B, E, D)) { f(&k_pair_tiles<R, T, E, B, M, D>, M_); return true; }
+        else { if constexpr (tile_variant_unlaunched(M, T, B, E, D)) (void)&k_pair_tiles<R, T, E, B, M, D>; return false; }
+      }); });
+    }); });
+  });
+  if (!found) throw ChemError(CHEM_ESTATE, "internal: no pair-force kernel is built for the planned variant");
+}
+// ... and for the row kernel of a variant
+template <typename R, class F> void with_row_kernel(const PairVariant& v, F&& f) {
+  const bool found = variant_built(v) && pick_among<0, 1>(v.energy, [&](auto E_) {
+    constexpr bool E = decltype(E_)::value != 0;
+    switch (v.mode) {
+      case 4: f(&k_pair_force<R, 4, E, true, true>, Int<4>{}); return true;
+      case 5: f(&k_pair_force_res<R, 4, E>, Int<5>{}); return true;
+      case 6: f(&k_pair_force_cap<R, 4, E>, Int<6>{}); return true;
+      case 7: f(&k_pair_force_rescap<R, 4, E>, Int<7>{}); return true;
+    }
+    return pick_among<1, 2, 4, 8, 16, 32, 64>(v.tpp, [&](auto T_) { return pick_among<0, 1>(v.cubic, [&](auto C_) {
+      f(&k_pair_force<R, decltype(T_)::value, E, decltype(C_)::value != 0>, Int<0>{}); return true;
+    }); });
+  });
+  if (!found) throw ChemError(CHEM_ESTATE, "internal: no pair-force kernel is built for the planned variant");
+}
 
 template <typename R> struct CtxT : Ctx {
   using V4 = Vec4<R>;
@@ -657,37 +703,16 @@ template <typename R> struct CtxT : Ctx {
   }
 
   void set_tile_lds_attr() {
-    const int bytes = (int)tile_lds_bytes();
-#define SETA(K) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nlist_tiles<R, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)list_lds_need()));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_react_scan_tiles<R, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(scan_roles_staged() ? scan_lds_bytes() : tile_lds_bytes())));
-#define SETB(T, E, M) SETA((k_pair_tiles<R, T, E, 256, M>)); SETA((k_pair_tiles<R, T, E, 512, M>)); SETA((k_pair_tiles<R, T, E, 1024, M>)); \
-                      if (T == 1 && !E) SETA((k_pair_tiles<R, 1, false, 512, M, true>))
-#define SETT(E, M) SETB(1, E, M); SETB(2, E, M); SETB(4, E, M); SETB(8, E, M)
-    SETT(false, 2); SETT(false, 1); SETT(false, 0); SETT(true, 0); SETT(false, 3); SETT(true, 3);
-#undef SETT
-#undef SETB
-#undef SETA
-    if (coul_on()) {      // MODE 4 (one lane per particle, 512 threads): the image + the charge words
-      const int qbytes = (int)pair_lds_bytes();
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_q<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-    }
-    if (res_pairs_on()) {      // MODE 5: the image + the lambda words (same layout)
-      const int qbytes = (int)pair_lds_bytes();
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_res<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-    }
-    if (caps_on()) {      // MODE 6: the image alone; MODE 7: the image + the lambda words
-      const int qbytes = (int)pair_lds_bytes();
-      if (res_pairs_on()) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_rescap<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_rescap<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-      } else {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_cap<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_tiles_cap<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qbytes));
-      }
-    }
+    // every force kernel a plan can name (chem_launch_host.hpp); MODE 4..7 while their feature is on: the image + the charge
+    // words (4), + the lambda words (5, 7: same layout), the image alone (6)
+    const bool on47[4] = {coul_on(), res_pairs_on(), caps_on() && !res_pairs_on(), caps_on() && res_pairs_on()};
+    for_each_tile_variant([&](const PairVariant& v) {
+      if (v.mode >= 4 && !on47[v.mode - 4]) return;
+      const int bytes = (int)(v.mode >= 4 ? pair_lds_bytes() : tile_lds_bytes());
+      with_tile_kernel<R>(v, [&](auto kern, auto) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)); });
+    });
   }
 
   void alloc_lists() {
@@ -1565,40 +1590,17 @@ template <typename R> struct CtxT : Ctx {
   }
 
   // ---- forces -------------------------------------------------------------------------
-  int pick_tpp() const {
-    if (opt_tpp > 0) return use_tiles ? std::min(opt_tpp, 8) : opt_tpp;
-    if (use_tiles) return 1;   // one lane per home particle at every size (measured 10k..1M particles after the ds_read_b128 fix: 125k particles 17.4 us against 20.6 with two lanes)
-    return n >= 100000 ? 4 : (n >= 8000 ? 8 : 16);
-  }
+  int pick_tpp() const { return chem::pick_tpp(use_tiles, n, opt_tpp); }
 
-  template <bool ENERGY> int launch_pair(V4* fdst, int tpp) {
+  // the pair forces into fdst (ENERGY: and the energy words into eout); the kernel is chem_launch_host.hpp's choice
+  template <bool ENERGY> int launch_pair(V4* fdst) {
     const double hs = half_skin_eff();
-    const bool coul = coul_on();
-    if (coul) {      // the kernels with the Coulomb term are built for one lane per particle and 512-thread blocks
-      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a Coulomb pair registered only tpp = 1 (or 0, automatic) is built");
-      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a Coulomb pair registered only pair_block = 512 is built");
-    }
-    const bool resm = res_pairs_on();
-    if (resm) {      // the kernels with the resolution scaling: the same build, and not next to the Coulomb term
-      if (coul) {
-        int a = 0, b = 0;
-        for (a = 0; a < CHEM_MAX_TYPES && !res_mask[a]; ++a) {}
-        for (b = 0; b < CHEM_MAX_TYPES && !((res_mask[a] >> b) & 1u); ++b) {}
-        throw ChemError(CHEM_ENOTIMPL, "resolution-scaled type pair (" + std::to_string(std::min(a, b)) + "," + std::to_string(std::max(a, b)) + ") next to a registered Coulomb pair: the two terms are not served in one context");
-      }
-      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a resolution pair marked only tpp = 1 (or 0, automatic) is built");
-      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a resolution pair marked only pair_block = 512 is built");
-    }
-    const bool capm = caps_on();
-    if (capm) {      // the kernels with the cap radii: the same build again, and not next to the Coulomb term
-      if (coul) {
-        int a = 0, b = 0;
-        for (int k = CHEM_MAX_TYPES * CHEM_MAX_TYPES; k-- > 0;) if (cap_rad[k / CHEM_MAX_TYPES][k % CHEM_MAX_TYPES] > 0 && k / CHEM_MAX_TYPES <= k % CHEM_MAX_TYPES) { a = k / CHEM_MAX_TYPES; b = k % CHEM_MAX_TYPES; }      // (the first capped pair)
-        throw ChemError(CHEM_ENOTIMPL, "capped type pair (" + std::to_string(a) + "," + std::to_string(b) + ") next to a registered Coulomb pair: the two terms are not served in one context");
-      }
-      if (opt_tpp > 1) throw ChemError(CHEM_EINVAL, "option tpp = " + std::to_string(opt_tpp) + ": with a capped pair registered only tpp = 1 (or 0, automatic) is built");
-      if (pair_bs != 512) throw ChemError(CHEM_EINVAL, "option pair_block = " + std::to_string(pair_bs) + ": with a capped pair registered only pair_block = 512 is built");
-    }
+    PairInput in{use_tiles, n, opt_tpp, pair_bs, ENERGY, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
+    if (in.coul && in.res) first_res_pair(res_mask, in.res_a, in.res_b);
+    if (in.coul && in.cap) first_cap_pair(cap_rad, in.cap_a, in.cap_b);
+    const PairPlan plan = pair_plan(in);
+    if (plan.code != CHEM_OK) throw ChemError(plan.code, pair_refusal_text(plan));
+    const PairVariant& v = plan.v;
     const bool inline_now = bonds_inline();
     int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;      // (what the LAST rebuild did: both only change where a rebuild is forced)
     if (bond_mode == 2 && dd_on) {      // slabs: the host knows which launch follows a rebuild (mode 3 = mode 2 + record the partner slots now)
@@ -1625,126 +1627,76 @@ template <typename R> struct CtxT : Ctx {
       const TileSub ts{tl.base1, tl.n1, tl.base2};
       const int nsub = tl.count;
       if (nsub <= 0) return 0;
-#define LTD(T, M, B, D) hipLaunchKernelGGL((k_pair_tiles<R, T, ENERGY, B, M, D>), dim3(nsub), dim3(B), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p, \
-                                 nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, uni, eout.p, hs, ctl.p, pair_guard, opt_ablate, dbg_on ? dbgbuf.p : (long long*)nullptr, ts, pair_da, \
-                                 (inline_now && (!ENERGY || bond_mode >= 2)) ? bslots.p : (uint4*)nullptr, inline_K, inline_r0, bond_mode, act, brec)
-#define LT(T, M, B) LTD(T, M, B, false)
-      // diagnostics (options debug_stamps / ablate): one instantiation, one lane per particle, 512 threads
-#define LTB(T, M) do { if ((dbg_on || opt_ablate) && !ENERGY) { if (T != 1 || pair_bs != 512) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate need tpp=1 and pair_block=512"); LTD(1, M, 512, true); } \
-                       else if (pair_bs == 256) LT(T, M, 256); else if (pair_bs == 512) LT(T, M, 512); else LT(T, M, 1024); } while (0)
-#define LTT(M) do { switch (tpp) { case 1: LTB(1, M); break; case 2: LTB(2, M); break; case 8: LTB(8, M); break; default: LTB(4, M); break; } } while (0)
-      if (coul) {      // MODE 4: general + Coulomb, one instantiation per precision and ENERGY
-        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with the Coulomb term");
-        const CoulArgs<R> ca = coul_args((size_t)nsub);
-        hipLaunchKernelGGL((k_pair_tiles_q<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
-                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, ca);
-        return ntiles;
-      }
-      if (resm) {      // MODE 5: general + resolution scaling, one instantiation per precision and ENERGY
-        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with the resolution scaling");
-        if (capm) {      // MODE 7: ... + capped type pairs
-          hipLaunchKernelGGL((k_pair_tiles_rescap<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
-                             nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, res_args(), cap_args());
-          return ntiles;
-        }
-        hipLaunchKernelGGL((k_pair_tiles_res<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
-                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, res_args());
-        return ntiles;
-      }
-      if (capm) {      // MODE 6: general + capped type pairs, one instantiation per precision and ENERGY
-        if (dbg_on || opt_ablate) throw ChemError(CHEM_EINVAL, "debug_stamps / ablate are not built for the force kernel with capped pairs");
-        hipLaunchKernelGGL((k_pair_tiles_cap<R, ENERGY>), dim3(nsub), dim3(512), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p,
-                           nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, pair_guard, ts, pair_da, cap_args());
-        return ntiles;
-      }
-      const int mode = ENERGY ? (cubic_tab ? 3 : 0) : (uniform_lj ? 2 : (lj_only ? 1 : (cubic_tab ? 3 : 0)));
-      if (mode == 2) LTT(2); else if (mode == 1) LTT(1); else if (mode == 3) LTT(3); else LTT(0);
-#undef LTT
-#undef LTB
-#undef LT
-#undef LTD
+      // what every tile kernel takes, then what MODE 0..3 and MODE 4..7 take behind it
+      auto launch = [&](auto kern, const auto&... tail) {
+        hipLaunchKernelGGL(kern, dim3(nsub), dim3(v.block), pair_lds_bytes(), stream, nsub, tile_cap, x4.p, fdst, tdesc.p, nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, tail...);
+      };
+      auto feature = [&](auto kern, const auto&... packs) { launch(kern, eout.p, hs, ctl.p, pair_guard, ts, pair_da, packs...); };
+      with_tile_kernel<R>(v, [&](auto kern, auto M_) {
+        constexpr int M = decltype(M_)::value;
+        if constexpr (M == 4) feature(kern, coul_args((size_t)nsub));
+        else if constexpr (M == 5) feature(kern, res_args());
+        else if constexpr (M == 6) feature(kern, cap_args());
+        else if constexpr (M == 7) feature(kern, res_args(), cap_args());
+        else launch(kern, uni, eout.p, hs, ctl.p, pair_guard, opt_ablate, dbg_on ? dbgbuf.p : (long long*)nullptr, ts, pair_da,
+                    (inline_now && (!ENERGY || bond_mode >= 2)) ? bslots.p : (uint4*)nullptr, inline_K, inline_r0, bond_mode, act, brec);
+      });
       return ntiles;
     }
-    if (coul) {
-      const int nbq = cdiv((long long)n * 4, 256);
-      hipLaunchKernelGGL((k_pair_force<R, 4, ENERGY, true, true>), dim3(nbq), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
-                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, coul_args((size_t)nbq));
-      return nbq;
-    }
-    if (resm && capm) {
-      const int nbr = cdiv((long long)n * 4, 256);
-      hipLaunchKernelGGL((k_pair_force_rescap<R, 4, ENERGY>), dim3(nbr), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
-                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, res_args(), cap_args());
-      return nbr;
-    }
-    if (capm) {
-      const int nbc = cdiv((long long)n * 4, 256);
-      hipLaunchKernelGGL((k_pair_force_cap<R, 4, ENERGY>), dim3(nbc), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
-                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, cap_args());
-      return nbc;
-    }
-    if (resm) {
-      const int nbr = cdiv((long long)n * 4, 256);
-      hipLaunchKernelGGL((k_pair_force_res<R, 4, ENERGY>), dim3(nbr), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box,
-                         pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, res_args());
-      return nbr;
-    }
-    const int nb = cdiv((long long)n * tpp, 256);
-#define LPC(T, CU) hipLaunchKernelGGL((k_pair_force<R, T, ENERGY, CU>), dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, \
-                                 pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p)
-#define LP(T) do { if (cubic_tab) LPC(T, true); else LPC(T, false); } while (0)
-    switch (tpp) {
-      case 1: LP(1); break; case 2: LP(2); break; case 4: LP(4); break; case 8: LP(8); break;
-      case 16: LP(16); break; case 32: LP(32); break; default: LP(64); break;
-    }
-#undef LP
-#undef LPC
+    const int nb = cdiv((long long)n * v.tpp, 256);
+    auto launch = [&](auto kern, const auto&... packs) {
+      hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, packs...);
+    };
+    with_row_kernel<R>(v, [&](auto kern, auto M_) {
+      constexpr int M = decltype(M_)::value;
+      if constexpr (M == 4) launch(kern, coul_args((size_t)nb));
+      else if constexpr (M == 5) launch(kern, res_args());
+      else if constexpr (M == 6) launch(kern, cap_args());
+      else if constexpr (M == 7) launch(kern, res_args(), cap_args());
+      else launch(kern, CoulArgs<R>{});
+    });
     return nb;
   }
 
   void compute_forces(bool speculative = false, int subset = 0, bool decide = false) {      // decide: single domain, no neighbour launch on this step (guard 3)
     pair_guard = decide ? 3 : (speculative ? (pair_da.gathered ? 2 : 1) : 0);
     pair_subset = subset;
-    const int tpp = pick_tpp();
     const bool timed = timed_step && subset == 0;
     if (timed) tbeg(0);
-    launch_pair<false>(f4.p, tpp);
+    launch_pair<false>(f4.p);
     if (timed) tend();
     pair_subset = 0;
     if (subset == 1) { pair_guard = 0; return; }   // interior tiles only: bonded terms follow with the boundary launch
-    const bool inl = nbent > 0 && bonds_inline();
-    if (inl && excl_over == 0) {
-      // harmonic bonds were evaluated by the force kernel (inline bonds): no bonded launch
-    } else if (nbent > 0 && (use_fused || dd_on)) {
+    // the bonded term (chem_launch_host.hpp): nothing where the force kernel has evaluated the harmonic bonds (inline bonds)
+    const BondedPlan bp = bonded_plan(BondedInput{nbent, nbent > 0 && bonds_inline(), excl_over, use_fused || dd_on, has_coul14, has_hybrid, bonds_only, nb_owner});
+    // the kernel of the plan's kind behind `launch`'s own arguments: hybrid lists add the lambda of every hybrid entry at the step
+    // these forces belong to, a 1-4 Coulomb list the charges by tag as well, read at every evaluation (and what `more` holds)
+    auto by_kind = [&](auto launch, auto plain, auto hyb, auto charged, const auto&... more) {
+      if (bp.kind == BondedKind::charged) launch(charged, hybrid_args(), (const R*)qtag.p, more...);
+      else if (bp.kind == BondedKind::hybrid) launch(hyb, hybrid_args());
+      else launch(plain);
+    };
+    if (bp.launch == BondedLaunch::work_list) {
       // work-list kernel: owners only, partner indices resolved at the last rebuild
       if (bwork_dirty) {   // bonded lists changed without a rebuild since
         HIPCHK(hipMemsetAsync(&ctl.p->bw64, 0, sizeof(unsigned long long), stream));
         hipLaunchKernelGGL(k_bonded_prep, dim3(std::max(1, std::min(cdiv(n, 256), 1024))), dim3(256), 0, stream, G, n, tag.p, rtag.p, bstart.p, bent.p, bwork.p, bj.p, ctl.p,
-                           inl ? (const int*)excl_start.p : (const int*)nullptr);
+                           bp.inline_bonds ? (const int*)excl_start.p : (const int*)nullptr);
         bwork_dirty = false;
       }
       if (timed) tbeg(3);
-      const int nown = inl ? (int)std::min<int64_t>(nb_owner, excl_over) : nb_owner;   // (inline bonds: the list holds the owners with > kBondSlots exclusions only)
-      if (has_coul14) {      // 1-4 Coulomb list: charges by tag, read at every evaluation
-        if (bonds_only) hipLaunchKernelGGL((k_bonded_work_q<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args(), (const R*)qtag.p, (const int*)tag.p);
-        else hipLaunchKernelGGL((k_bonded_work_q<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args(), (const R*)qtag.p, (const int*)tag.p);
-      }
-      else if (has_hybrid) {      // lambda of every hybrid entry at the step these forces belong to
-        if (bonds_only) hipLaunchKernelGGL((k_bonded_work_hyb<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
-        else hipLaunchKernelGGL((k_bonded_work_hyb<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), hybrid_args());
-      }
-      else if (bonds_only) hipLaunchKernelGGL((k_bonded_work<R, true>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
-      else hipLaunchKernelGGL((k_bonded_work<R, false>), dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view());
+      auto work = [&](auto kern, const auto&... packs) {
+        hipLaunchKernelGGL(kern, dim3(cdiv(bp.nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), packs...);
+      };
+      if (bp.bonds_only) by_kind(work, &k_bonded_work<R, true>, &k_bonded_work_hyb<R, true>, &k_bonded_work_q<R, true>, (const int*)tag.p);
+      else by_kind(work, &k_bonded_work<R, false>, &k_bonded_work_hyb<R, false>, &k_bonded_work_q<R, false>, (const int*)tag.p);
       if (timed) tend();
-    } else if (nbent > 0 && has_coul14)
-      hipLaunchKernelGGL((k_bonded_q<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
-    else if (nbent > 0 && has_hybrid)
-      hipLaunchKernelGGL((k_bonded_hyb<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
-    else if (nbent > 0)
-      hipLaunchKernelGGL((k_bonded<R, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view());
+    } else if (bp.launch == BondedLaunch::per_particle) {
+      auto each = [&](auto kern, const auto&... packs) {
+        hipLaunchKernelGGL(kern, dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, elist.p, ctl.p, btab_view(), packs...);
+      };
+      by_kind(each, &k_bonded<R, false>, &k_bonded_hyb<R, false>, &k_bonded_q<R, false>);
+    }
     pair_guard = 0;
   }
 
@@ -1760,12 +1712,8 @@ template <typename R> struct CtxT : Ctx {
     // CapForce acts on the freshly evaluated conservative force: every launch that applies the thermostat
     // consumes exactly that; without a thermostat f4 is never overwritten, so every launch does.
     const R cap = (cap_force > 0 && (with_lang || !lang)) ? (R)cap_force : (R)0;
-    if (with_lang && storef)
-      hipLaunchKernelGGL((k_integrate<R, MODE, true, true>), dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg());
-    else if (with_lang)
-      hipLaunchKernelGGL((k_integrate<R, MODE, true, false>), dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg());
-    else
-      hipLaunchKernelGGL((k_integrate<R, MODE, false, false>), dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg());
+    const auto kern = with_lang ? (storef ? &k_integrate<R, MODE, true, true> : &k_integrate<R, MODE, true, false>) : &k_integrate<R, MODE, false, false>;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg());
   }
 
   void check_flags() {
@@ -1920,7 +1868,7 @@ template <typename R> struct CtxT : Ctx {
   // asks for the rebuild behind the next drift.  One host synchronisation of its own (on the fused path the run loop's look at the
   // control block in front of it, for a stop by the device, is a second; the rebuild that follows has its own).
   void baro_step() {
-    const int nb = launch_pair<true>(x4o.p, pick_tpp());      // (scratch force buffer: f4 keeps the step's forces)
+    const int nb = launch_pair<true>(x4o.p);      // (scratch force buffer: f4 keeps the step's forces)
     const int nbv = nbent > 0 ? launch_bonded_virial(false) : 0;
     const int nkb = cdiv(n, 256);
     hipLaunchKernelGGL(k_kinetic<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, ekout.p);
@@ -2809,8 +2757,7 @@ template <typename R> struct CtxT : Ctx {
     flush_host_state();
     if (resort) { rebuild_now(); compute_forces(); }   // a rebuild re-sorts the particles but not f4: keep it aligned for get_state(FORCE)
     std::memset(out, 0, sizeof(*out));
-    const int tpp = pick_tpp();
-    const int nb = launch_pair<true>(x4o.p, tpp);  // scratch force buffer: leaves f4 untouched
+    const int nb = launch_pair<true>(x4o.p);  // scratch force buffer: leaves f4 untouched
     HIPCHK(hipMemsetAsync(elist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream));
     if (nbent > 0 && has_coul14)
       hipLaunchKernelGGL((k_bonded_q<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
