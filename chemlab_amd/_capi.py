@@ -110,6 +110,11 @@ class Pressure(C.Structure):
                 ("virial_list", C.c_double * CHEM_MAX_LISTS), ("virial", C.c_double)]
 
 
+class BarostatState(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pressure_last", C.c_double), ("momentum", C.c_double), ("eps_dot", C.c_double),
+                ("mu_next", C.c_double), ("sv_next", C.c_double)]
+
+
 class Timers(C.Structure):
     _fields_ = [("run_wall_s", C.c_double), ("steps", C.c_int64), ("rebuilds", C.c_int64),
                 ("reaction_steps", C.c_int64), ("nlist_entries", C.c_int64),
@@ -213,6 +218,9 @@ PRODUCT_ONLY = {
     "get_pressure": (_i, [_P, C.POINTER(Pressure)]),
     "barostat_berendsen": (_i, [_P, _d, _d]),
     "get_box": (_i, [_P, _pd]),
+    # Langevin piston barostat and the read-back of either barostat's state
+    "barostat_langevin": (_i, [_P, _d, _d, _d, _d, _u64]),
+    "barostat_state_get": (_i, [_P, C.POINTER(BarostatState)]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

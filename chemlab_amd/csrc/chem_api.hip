@@ -104,7 +104,18 @@ struct Ctx {
   double baro_charge = 0, baro_charge_ref = 0; int baro_seen_builds = -1, baro_seen_ref = -1;
   double half_skin_eff() const { return std::max(0.5 * skin_eff() - baro_charge, 0.0); }
   double half_skin_ref() const { return std::max(0.5 * skin - baro_charge_ref, 0.0); }
-  bool baro_on() const { return baro_tau > 0; }
+  // Langevin piston (chem_barostat_langevin): on while pist_w > 0; never together with the Berendsen barostat.  pist_pe is the
+  // host's copy of the piston momentum the device keeps (pist_pe_upload: the device's word has to be written first), pist_sv and
+  // pist_mu the factors of the next step as the device computed them at the last kick.
+  double pist_w = 0, pist_gamma = 0, pist_kT = 0; uint64_t pist_seed = 0;
+  double pist_pe = 0, pist_eps = 0, pist_sv = 1, pist_mu = 1, baro_p_last = 0; bool pist_pe_upload = false, pist_mu_upload = false;
+  bool piston_on() const { return pist_w > 0; }
+  bool baro_on() const { return baro_tau > 0 || pist_w > 0; }
+  const char* baro_name() const { return piston_on() ? "Langevin" : "Berendsen"; }
+  void baro_forget() {      // a barostat goes off: nothing of it stays (lists that scalings have aged are built again first)
+    if (baro_charge > 0 || baro_charge_ref > 0) resort = true;
+    baro_keep = false; baro_charge = baro_charge_ref = 0; baro_seen_builds = baro_seen_ref = -1; baro_p_last = 0;
+  }
   HostTopology top;
   std::vector<double> pos0, vel0;  // staged particle data (tag order) until first upload
   int ntypes = 1;
@@ -1712,8 +1723,16 @@ template <typename R> struct CtxT : Ctx {
     // CapForce acts on the freshly evaluated conservative force: every launch that applies the thermostat
     // consumes exactly that; without a thermostat f4 is never overwritten, so every launch does.
     const R cap = (cap_force > 0 && (with_lang || !lang)) ? (R)cap_force : (R)0;
+    if constexpr (MODE == 1 || MODE == 2) {
+      if (piston_on()) {      // Langevin piston: the two half steps carry the factors of the step (the fused integrate is off then)
+        const PistonP<R> pp{(R)pist_sv, (R)(1.0 / std::sqrt(pist_mu))};
+        const auto kern = with_lang ? (storef ? &k_integrate<R, MODE, true, true, true> : &k_integrate<R, MODE, true, false, true>) : &k_integrate<R, MODE, false, false, true>;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg(), pp);
+        return;
+      }
+    }
     const auto kern = with_lang ? (storef ? &k_integrate<R, MODE, true, true> : &k_integrate<R, MODE, true, false>) : &k_integrate<R, MODE, false, false>;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg());
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n, x4.p + G, v4.p + G, f4.p + G, tag.p + G, (R)dt, lp, blockmax.p, opt_criterion ? x0.p + G : (const V4*)nullptr, cap, pos_scale(), (const DevCtl*)ctl.p, fold_arg(), PistonP<R>{});
   }
 
   void check_flags() {
@@ -1862,44 +1881,74 @@ template <typename R> struct CtxT : Ctx {
     }
   }
   bool baro_replan_pending = false;      // geom_dirty was raised by a scaling, not by the caller: the forces in f4 stay valid
-  // One barostat action, behind the second half kick (and the velocity rescaling) of the step that has just been counted:
-  // P from the positions and velocities of this step and the virial of its force evaluation (the energy instantiation over the
-  // same lists: a second pair pass), mu on the device, the fp64 positions scaled there; the host reads mu, moves the box and
-  // asks for the rebuild behind the next drift.  One host synchronisation of its own (on the fused path the run loop's look at the
-  // control block in front of it, for a stop by the device, is a second; the rebuild that follows has its own).
-  void baro_step() {
+  // One barostat action has two halves.
+  // baro_measure(), behind the second half kick (and the velocity rescaling) of the step that has just been counted: P from the
+  // positions and velocities of this step and the virial of its force evaluation (the energy instantiation over the same lists: a
+  // second pair pass), the rule on the device (Berendsen: mu; Langevin piston: the kick of the momentum kept on the device and the
+  // factors of the next step), the results copied into pinned words.  One host synchronisation of its own (on the fused path the
+  // run loop's look at the control block in front of it, for a stop by the device, is a second).  Returns mu.
+  // baro_apply(mu, mu_dev): the box, the fp64 positions, what the device keeps in absolute length, the charge to the lists and the
+  // re-plan.  Berendsen calls it at once; the piston behind the next step's drift, in front of launch_fix and the rebuild decision.
+  static constexpr int kBaroWords = 16, kPistonPe = 8;      // words of baro_buf; the piston momentum's place in it
+  int launch_baro_partials(int& nbv, int& nkb) {
     const int nb = launch_pair<true>(x4o.p);      // (scratch force buffer: f4 keeps the step's forces)
-    const int nbv = nbent > 0 ? launch_bonded_virial(false) : 0;
-    const int nkb = cdiv(n, 256);
+    nbv = nbent > 0 ? launch_bonded_virial(false) : 0;
+    nkb = cdiv(n, 256);
     hipLaunchKernelGGL(k_kinetic<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, ekout.p);
-    baro_buf.alloc(8);
+    baro_buf.alloc(kBaroWords);
+    if (!baro_pin) HIPCHK(hipHostMalloc((void**)&baro_pin, 8 * sizeof(double), hipHostMallocDefault));
+    return nb;
+  }
+  double baro_measure() {
+    int nbv, nkb;
+    const int nb = launch_baro_partials(nbv, nkb);
     const bool cq = coul_on();
+    double* h = baro_pin;
+    if (piston_on()) {
+      if (pist_pe_upload) { HIPCHK(hipMemcpyAsync(baro_buf.p + kPistonPe, &pist_pe, sizeof(double), hipMemcpyHostToDevice, stream)); pist_pe_upload = false; }
+      hipLaunchKernelGGL(k_baro_piston, dim3(1), dim3(256), 0, stream, (const double*)ekout.p, nkb, (const double*)eout.p, nb, cq ? (const double*)eoutq.p : (const double*)nullptr, cq ? nb : 0,
+                         (const double*)vpart.p, nbv, L[0] * L[1] * L[2], dt, baro_p0, pist_w, pist_gamma, pist_kT, 3.0 * (double)n, pist_seed, (uint64_t)step, baro_buf.p + kPistonPe, baro_buf.p);
+      HIPCHK(hipMemcpyAsync(h, baro_buf.p, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      baro_p_last = h[0];
+      const double sv = piston_sv(h[1], pist_w, 3.0 * (double)n, dt), mu = piston_mu(h[1], pist_w, dt);
+      if (!piston_ok(h[1], mu, sv)) {
+        char msg[320];
+        snprintf(msg, sizeof(msg), "Langevin barostat: piston momentum pe = %.6g (mu = %.6g, sv = %.6g) at step %lld (P = %.6g, P0 = %.6g, mass = %.6g): the box cannot follow; use a larger mass",
+                 h[1], mu, sv, (long long)step, h[0], baro_p0, pist_w);
+        pist_pe = h[1];
+        throw ChemError(CHEM_ESTATE, msg);
+      }
+      pist_pe = h[1]; pist_eps = h[2]; pist_sv = h[3]; pist_mu = h[4];
+      return pist_mu;
+    }
     hipLaunchKernelGGL(k_baro_mu, dim3(1), dim3(256), 0, stream, (const double*)ekout.p, nkb, (const double*)eout.p, nb, cq ? (const double*)eoutq.p : (const double*)nullptr, cq ? nb : 0,
                        (const double*)vpart.p, nbv, L[0] * L[1] * L[2], dt, baro_tau, baro_p0, baro_buf.p);
-    if constexpr (!kFixed) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x4.p, (const double*)(baro_buf.p + 1), (const DevCtl*)ctl.p);
-    if (!baro_pin) HIPCHK(hipHostMalloc((void**)&baro_pin, 8 * sizeof(double), hipHostMallocDefault));
-    double* h = baro_pin;
     HIPCHK(hipMemcpyAsync(h, baro_buf.p, 6 * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
+    baro_p_last = h[0];
     if (!baro_mu3_ok(h[2])) {
       char msg[256];
       snprintf(msg, sizeof(msg), "Berendsen barostat: mu^3 = %.6g <= 0 at step %lld (P = %.6g, P0 = %.6g, dt/tau = %.6g): the box cannot be scaled; use a larger tau",
                h[2], (long long)step, h[0], baro_p0, dt / baro_tau);
       throw ChemError(CHEM_ESTATE, msg);
     }
-    const double mu = h[1];
+    return h[1];
+  }
+  void baro_apply(double mu, const double* mu_dev) {
+    if constexpr (!kFixed) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x4.p, mu_dev, (const DevCtl*)ctl.p);
     for (int d = 0; d < 3; ++d) L[d] *= mu;
     // The box lengths reach every kernel by value from here on; what the device keeps in absolute length follows mu: the
     // reference positions of the displacement criterion (fp64 build) and the length fields of the tile descriptors.
     refresh_box_lengths();
-    if constexpr (!kFixed) if (opt_criterion) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x0.p, (const double*)(baro_buf.p + 1), (const DevCtl*)ctl.p);
+    if constexpr (!kFixed) if (opt_criterion) hipLaunchKernelGGL(k_baro_scale_x, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, x0.p, mu_dev, (const DevCtl*)ctl.p);
     if (use_tiles) hipLaunchKernelGGL((k_baro_tile_desc<R>), dim3(std::min(ntiles, 2048)), dim3(128), 0, stream, ntiles, tile_cap, (const int*)cell_start.p, box, tdesc.p, ctl.p,
                                       (const int*)cell_sub.p, (use_fused && opt_lpt) ? (const int*)tile_pos.p : (const int*)nullptr);
     // The lists stay.  A scaling changes a listed separation by at most |mu - 1| (rc + skin_eff): half of that per particle
     // (baro_list_charge), plus |mu - 1| skin_eff / 2 for the displacement already accumulated, which scales too, is charged
     // as displacement -- taken off the half skin of every later decision, under both criteria, until the device has built lists
     // again (its counters say so).  Where the charge and the distance accumulated so far already exceed the half skin, the
-    // lists are built behind the next drift whatever the device decides.
+    // lists are built behind the next drift (the piston: behind the drift this scaling belongs to) whatever the device decides.
     const DevCtl hc = read_ctl();
     if (hc.rebuild_count != baro_seen_builds) { baro_charge = 0; baro_seen_builds = hc.rebuild_count; }
     if (hc.ref_rebuilds != baro_seen_ref) { baro_charge_ref = 0; baro_seen_ref = hc.ref_rebuilds; }
@@ -1914,6 +1963,7 @@ template <typename R> struct CtxT : Ctx {
       geom_dirty = true; baro_replan_pending = true; resort = true; hint_invalidate();
     }
   }
+  void baro_step() { const double mu = baro_measure(); baro_apply(mu, baro_buf.p + 1); }      // Berendsen: both halves back to back
 
   // Does step `step` get its neighbour launch?  (single domain, fused rebuild; the rule and its reasons: chem_idle_host.hpp)
   // The host enqueues far faster than the device runs, so it first lets the device come within idle_lag steps: it spins on the
@@ -1942,7 +1992,7 @@ template <typename R> struct CtxT : Ctx {
   // ---- the hot call -------------------------------------------------------------------
   void run(int64_t nsteps) override {
     if (!(dt > 0)) throw ChemError(CHEM_ESTATE, "dt not set");
-    if (baro_on() && dd_on) throw ChemError(CHEM_ENOTIMPL, "Berendsen barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
+    if (baro_on() && dd_on) throw ChemError(CHEM_ENOTIMPL, std::string(baro_name()) + " barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
     // barostat: the forces of the last run's final step (evaluated before its scaling) are the ones this run starts from,
     // provided nothing has touched the system or re-sorted the particles since
     const bool keep_forces = baro_on() && baro_keep && !(particles_dirty || (geom_dirty && !baro_replan_pending) || labels_dirty || pair_dirty || coul_dirty || res_dirty || cap_dirty || fix_dirty || bonded_dirty || excl_dirty);
@@ -2003,7 +2053,16 @@ template <typename R> struct CtxT : Ctx {
     for (int64_t s = 0; s < nsteps; ++s) {
       // (a stop the device has already told the pinned words about need not wait for the next synchronisation)
       if (!resume && hflag && skip_applies() && const_cast<const volatile IdleHint*>(hint_host())->halted == hint_gen && halted(s)) { --s; continue; }
-      if (need_int1) { launch_integrate<2>(false, false, step, 1); launch_fix(); need_int1 = false; }
+      if (need_int1) {
+        launch_integrate<2>(false, false, step, 1);
+        // Langevin piston: the box and the drifted positions take the step's mu (computed at the last kick) in front of the
+        // fixed distances, which are absolute lengths, and of the rebuild decision
+        if (piston_on() && pist_mu != 1.0) {
+          if (pist_mu_upload) { baro_buf.alloc(kBaroWords); HIPCHK(hipMemcpyAsync(baro_buf.p + 4, &pist_mu, sizeof(double), hipMemcpyHostToDevice, stream)); pist_mu_upload = false; }
+          baro_apply(pist_mu, baro_buf.p + 4);
+        }
+        launch_fix(); need_int1 = false;
+      }
       timed_step = opt_time_pair && (pair_launch_no++ % opt_time_pair) == 0;
       if (timed_step) timed_extra = 1 + (int)((pair_launch_no / opt_time_pair) % 3);
       const bool react_due = react_on && interval > 0 && ((step + 1) % interval == 0);
@@ -2031,7 +2090,8 @@ template <typename R> struct CtxT : Ctx {
         ++step;
         if (resc_kind == 1 || resc_kind == 3 || (resc_kind == 2 && step % (int64_t)resc_param == 0)) rescale_velocities();
         if ((react_due || atrp_due || last || baro_on()) && halted(s)) { --s; continue; }   // (the loop's ++s lands on the stopped step)
-        if (baro_on()) baro_step();      // aftIntV: behind the velocity rescaling, in front of the reaction work
+        // aftIntV: behind the velocity rescaling, in front of the reaction work
+        if (piston_on()) baro_measure(); else if (baro_on()) baro_step();
         if (react_due || atrp_due || last) skip_log_confirm();
         if (react_due && !dissociations.empty()) diss_step();   // bonds break before the association scan of the step
         if (react_due) react_step();      // (takes the type snapshot of the removal rules where it finds events)
@@ -3409,13 +3469,51 @@ int chem_barostat_berendsen(chem_ctx* ctx, double pressure, double tau) {
   API_BEGIN
   Ctx& c = CTX;
   if (!(tau > 0)) {      // off: nothing of it stays (lists that scalings have aged are built again first)
-    if (c.baro_charge > 0 || c.baro_charge_ref > 0) c.resort = true;
-    c.baro_tau = 0; c.baro_p0 = 0; c.baro_keep = false; c.baro_charge = c.baro_charge_ref = 0; c.baro_seen_builds = c.baro_seen_ref = -1;
+    if (c.piston_on()) return 0;      // (the other barostat is the one that is on: its state stays)
+    c.baro_forget();
+    c.baro_tau = 0; c.baro_p0 = 0;
     return 0;
   }
   REQUIRE(std::isfinite(pressure) && std::isfinite(tau), CHEM_EINVAL, "Berendsen barostat: pressure and tau must be finite");
+  REQUIRE(!c.piston_on(), CHEM_EINVAL, "Berendsen barostat: the Langevin barostat is on (one barostat at a time: switch it off first, chem_barostat_langevin with mass 0)");
   REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "Berendsen barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
   c.baro_p0 = pressure; c.baro_tau = tau;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_barostat_langevin(chem_ctx* ctx, double pressure, double mass, double gammaP, double kT, uint64_t seed) {
+  API_BEGIN
+  Ctx& c = CTX;
+  if (!(mass > 0)) {      // off: nothing of it stays, the piston momentum included
+    if (!c.piston_on()) return 0;      // (a Berendsen barostat that is on stays)
+    c.baro_forget();
+    c.pist_w = c.pist_gamma = c.pist_kT = 0; c.pist_seed = 0; c.baro_p0 = 0;
+    c.pist_pe = c.pist_eps = 0; c.pist_sv = c.pist_mu = 1; c.pist_pe_upload = c.pist_mu_upload = false;
+    return 0;
+  }
+  REQUIRE(std::isfinite(pressure) && std::isfinite(mass) && std::isfinite(gammaP) && std::isfinite(kT), CHEM_EINVAL, "Langevin barostat: pressure, mass, gammaP and kT must be finite");
+  REQUIRE(gammaP >= 0 && kT >= 0, CHEM_EINVAL, "Langevin barostat: gammaP and kT must not be negative");
+  REQUIRE(!(c.baro_tau > 0), CHEM_EINVAL, "Langevin barostat: the Berendsen barostat is on (one barostat at a time: switch it off first, chem_barostat_berendsen with tau 0)");
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "Langevin barostat on a decomposed context: a gap of the decomposed path (the box of a slab cannot change)");
+  if (!c.piston_on()) { c.pist_pe = c.pist_eps = 0; c.pist_sv = c.pist_mu = 1; c.pist_pe_upload = true; c.pist_mu_upload = false; }      // switched on: the piston starts at rest
+  else if (mass != c.pist_w && c.dt > 0) {      // the momentum survives; the factors of the next step follow the new mass
+    const double nf = 3.0 * (double)c.top.n, sv = chem::piston_sv(c.pist_pe, mass, nf, c.dt), mu = chem::piston_mu(c.pist_pe, mass, c.dt);
+    REQUIRE(chem::piston_ok(c.pist_pe, mu, sv), CHEM_EINVAL, "Langevin barostat: the piston momentum in force cannot be carried by this mass");
+    c.pist_eps = c.pist_pe / mass; c.pist_sv = sv; c.pist_mu = mu; c.pist_mu_upload = true;      // (the device's copy of mu is the old mass's)
+  }
+  c.baro_p0 = pressure; c.pist_w = mass; c.pist_gamma = gammaP; c.pist_kT = kT; c.pist_seed = seed;
+  return 0;
+  API_END(ctx)
+}
+
+int chem_barostat_state_get(chem_ctx* ctx, chem_barostat_state* out) {
+  API_BEGIN
+  REQUIRE(out, CHEM_EINVAL, "null output");
+  const Ctx& c = CTX;
+  std::memset(out, 0, sizeof(*out));
+  out->kind = c.piston_on() ? 2 : (c.baro_tau > 0 ? 1 : 0);
+  out->pressure_last = c.baro_p_last; out->momentum = c.pist_pe; out->eps_dot = c.pist_eps; out->mu_next = c.pist_mu; out->sv_next = c.pist_sv;
   return 0;
   API_END(ctx)
 }

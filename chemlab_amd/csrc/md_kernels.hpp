@@ -279,12 +279,16 @@ __device__ __forceinline__ void langevin_force(const LangevinP<R>& lp, int tag, 
 // x0 != nullptr: rebuild criterion "displacement" (max |x - x_at_last_build|^2); nullptr: the
 // reference's accumulated per-step maxima (max |dt v|^2 of this step)
 template <typename R> struct PosScale { R s[3], inv[3]; };   // fixed-point scale of the positions (fp32 build; unused in fp64)
-template <typename R, int MODE, bool LANG, bool STOREF>
+// Langevin piston (chem_barostat_langevin; PISTON instantiations only): sv multiplies the velocities in front of the first half
+// kick (mode 2) and behind the second (mode 1); the drift is dt v / sqrt(mu) in the box before its scaling (rsmu = 1 / sqrt(mu)),
+// which is also what the rebuild criterion sees.  The factors cost nothing next to the kernel's HBM traffic.
+template <typename R> struct PistonP { R sv, rsmu; };
+template <typename R, int MODE, bool LANG, bool STOREF, bool PISTON = false>
 __global__ __launch_bounds__(256) void k_integrate(int n, Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ v4,
                                                     Vec4<R>* __restrict__ f4, const int* __restrict__ tag,
                                                     R dt, LangevinP<R> lp, unsigned long long* __restrict__ blockmax,
                                                     const Vec4<R>* __restrict__ x0, R cap, PosScale<R> ps, const DevCtl* __restrict__ ctl,
-                                                    unsigned long long* __restrict__ foldmax = nullptr) {
+                                                    unsigned long long* __restrict__ foldmax = nullptr, PistonP<R> pp = PistonP<R>{}) {
   // foldmax (decomposed path): kFoldSlots words that collect the block maxima with one atomicMax per block (block b -> word
   // b % kFoldSlots: a few dozen atomics per address, spread over the launch) -- the one-block fold launch between this kernel
   // and the halo exchange is gone; the words travel with the halo, the force kernel's prologue takes the maximum and clears them
@@ -329,10 +333,13 @@ __global__ __launch_bounds__(256) void k_integrate(int n, Vec4<R>* __restrict__ 
     }
     R hm = (R)0.5 * dt / v.w;
     if (MODE & 1) { v.x += hm * f.x; v.y += hm * f.y; v.z += hm * f.z; }
+    if (PISTON && MODE == 1) { v.x *= pp.sv; v.y *= pp.sv; v.z *= pp.sv; }
+    if (PISTON && MODE == 2) { v.x *= pp.sv; v.y *= pp.sv; v.z *= pp.sv; }
     if (MODE & 2) {
       v.x += hm * f.x; v.y += hm * f.y; v.z += hm * f.z;
       Vec4<R> x = xx[u];
       R dx = dt * v.x, dy = dt * v.y, dz = dt * v.z;
+      if (PISTON && MODE == 2) { dx *= pp.rsmu; dy *= pp.rsmu; dz *= pp.rsmu; }
       x.x = pos_add(x.x, dx, ps.inv[0]); x.y = pos_add(x.y, dy, ps.inv[1]); x.z = pos_add(x.z, dz, ps.inv[2]);
       x4[i] = x;
       if (x0) { const Vec4<R> o = x0[i]; dx = pos_diff(x.x, o.x, ps.s[0]); dy = pos_diff(x.y, o.y, ps.s[1]); dz = pos_diff(x.z, o.z, ps.s[2]); }
@@ -3779,6 +3786,31 @@ __global__ __launch_bounds__(256) void k_baro_mu(const double* __restrict__ ekpa
     const double p = baro_pressure(mv2, wnb + wb, volume);
     const double mu3 = baro_mu3(dt, tau, p0, p);
     out[0] = p; out[1] = baro_mu3_ok(mu3) ? baro_mu(mu3) : 1.0; out[2] = mu3; out[3] = mv2; out[4] = wnb; out[5] = wb;
+  }
+}
+// The Langevin piston's kick (chem_barostat_langevin; the rules: chem_baro_host.hpp): one block folds the same partials as
+// k_baro_mu into P, draws the step's uniform, moves the piston momentum kept in device memory (*pe) and computes the factors of
+// the next step.  out: [0] P, [1] pe (new), [2] eps_dot, [3] sv, [4] mu, [5] sum m v^2, [6] non-bonded virial, [7] bonded virial.
+// Where the new state is not acceptable (piston_ok) sv = mu = 1 are written and *pe keeps the value that says why: the host
+// reads [1] and stops the run.
+__global__ __launch_bounds__(256) void k_baro_piston(const double* __restrict__ ekpart, int nk, const double* __restrict__ epart, int ne, const double* __restrict__ qpart, int nq,
+                                                     const double* __restrict__ bpart, int nbv, double volume, double dt, double p0, double w, double gamma_p, double kT,
+                                                     double nf, uint64_t seed, uint64_t step, double* __restrict__ pe, double* __restrict__ out) {
+  __shared__ double red[4];
+  const double ek = baro_block_sum(ekpart, nk, 4, 0, red);
+  const double wnb = baro_block_sum(epart, ne, 3, 2, red) + baro_block_sum(qpart, nq, 2, 1, red);
+  const double wb = baro_block_sum(bpart, nbv, 1, 0, red);
+  if (threadIdx.x == 0) {
+    const double mv2 = 2.0 * ek;
+    const double p = baro_pressure(mv2, wnb + wb, volume);
+    uint32_t r[4];
+    chem_philox::barostat_draw(seed, step, r);
+    const double pe0 = *pe;
+    const double pen = pe0 + dt * piston_force(volume, p, p0, nf, mv2, gamma_p, pe0, w, kT, dt, chem_philox::u01(r[0]));
+    const double sv = piston_sv(pen, w, nf, dt), mu = piston_mu(pen, w, dt);
+    const bool ok = piston_ok(pen, mu, sv);
+    *pe = pen;
+    out[0] = p; out[1] = pen; out[2] = pen / w; out[3] = ok ? sv : 1.0; out[4] = ok ? mu : 1.0; out[5] = mv2; out[6] = wnb; out[7] = wb;
   }
 }
 // After a scaling the tile descriptors of the last list build keep their lengths in the old unit: periodic shifts, the

@@ -527,6 +527,22 @@ class Engine:
             raise NotImplementedError("BerendsenBarostat: the CPU checker has no barostat (its box is fixed)")
         self._ck(fn(self.ctx, float(pressure), float(tau)))
 
+    def barostat_langevin(self, pressure, mass, gammaP, kT, seed=0):
+        """Langevin piston barostat (isotropic) on every step; mass <= 0 switches it off and resets the piston momentum."""
+        fn = getattr(self.api, "barostat_langevin", None)
+        if fn is None:
+            raise NotImplementedError("LangevinBarostat: the CPU checker has no barostat (its box is fixed)")
+        self._ck(fn(self.ctx, float(pressure), float(mass), float(gammaP), float(kT), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def barostat_state(self):
+        """dict(kind, pressure_last, momentum, eps_dot, mu_next, sv_next): kind 0 off, 1 Berendsen, 2 Langevin piston."""
+        fn = getattr(self.api, "barostat_state_get", None)
+        if fn is None:
+            raise NotImplementedError("LangevinBarostat: the CPU checker has no barostat (its box is fixed)")
+        s = _capi.BarostatState()
+        self._ck(fn(self.ctx, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in _capi.BarostatState._fields_}
+
     def box(self):
         """The current box edges (they move while a barostat is on)."""
         fn = getattr(self.api, "get_box", None)

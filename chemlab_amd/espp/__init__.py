@@ -928,6 +928,48 @@ class _BerendsenBarostat(object):
         self.system.engine.barostat_berendsen(0.0, 0.0)
 
 
+class _LangevinBarostat(object):
+    """integrator.LangevinBarostat(system, rng, temperature): .gammaP, .mass, .pressure (start_simulation.py:361-367): the
+    Langevin piston of include/chem_mi355.h chem_barostat_langevin.  `temperature` is kT (the driver passes T * kb); the seed of
+    the piston's noise is the rng's.  Attributes set after addExtension reach the engine at once."""
+
+    def __init__(self, system, rng, temperature):
+        if system is None or rng is None:
+            raise NotImplementedError("integrator.LangevinBarostat needs a system and its rng")
+        self.__dict__.update(system=system, rng=rng, temperature=float(temperature), _pressure=1.0, _mass=0.0, _gammaP=0.0, _connected=False)
+
+    def _push(self):
+        if self._connected:
+            self.system.engine.barostat_langevin(self._pressure, self._mass, self._gammaP, self.temperature, self.rng.get_seed())
+
+    pressure = property(lambda self: self._pressure)
+    mass = property(lambda self: self._mass)
+    gammaP = property(lambda self: self._gammaP)
+
+    @pressure.setter
+    def pressure(self, v):
+        self.__dict__["_pressure"] = float(v)
+        self._push()
+
+    @mass.setter
+    def mass(self, v):
+        self.__dict__["_mass"] = float(v)
+        self._push()
+
+    @gammaP.setter
+    def gammaP(self, v):
+        self.__dict__["_gammaP"] = float(v)
+        self._push()
+
+    def _connect(self, integrator):
+        self.__dict__["_connected"] = True
+        self._push()
+
+    def disconnect(self):
+        self.__dict__["_connected"] = False
+        self.system.engine.barostat_langevin(0.0, 0.0, 0.0, 0.0, 0)
+
+
 class _Isokinetic(object):
     """integrator.Isokinetic(system): .temperature, .coupling = rescale every `coupling` steps (start_simulation.py:345-348)."""
 
@@ -1536,7 +1578,7 @@ integrator = _ns(
     TopologyParticleProperties=_TopologyParticleProperties, TopologyManager=_TopologyManager, ExtAnalyze=_ExtAnalyze,
     StochasticVelocityRescaling=_StochasticVelocityRescaling,
     BerendsenThermostat=_BerendsenThermostat, BerendsenBarostat=_BerendsenBarostat,
-    Isokinetic=_Isokinetic, LangevinBarostat=_unsupported("integrator.LangevinBarostat"),
+    Isokinetic=_Isokinetic, LangevinBarostat=_LangevinBarostat,
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
     DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
     ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"),

@@ -605,6 +605,43 @@ int chem_get_pressure(chem_ctx* ctx, chem_pressure* out);
  * Not on the decomposed path, a gap of that path: the call is CHEM_ENOTIMPL after chem_comm_init*, and chem_run refuses a
  * context that was decomposed after the call. */
 int chem_barostat_berendsen(chem_ctx* ctx, double pressure, double tau);
+/* Langevin piston barostat, isotropic: integrator.LangevinBarostat(system, rng, kT) with .gammaP / .mass / .pressure --
+ * start_simulation.py:361-367.  The arithmetic is in the external fork, so this rule set is this build's own ([EXT-RECALL],
+ * parity unpinned): the Quigley-Probert / Hoover Langevin piston, discretised symmetrically so that it has a conserved quantity.
+ * State: the piston momentum pe, a half-step quantity, 0 when the barostat is switched on.  Parameters: target P0, piston mass
+ * W > 0, friction gammaP >= 0, kT >= 0, seed.  N_f = 3 n over all particles (dummies included, as in chem_get_pressure),
+ * c = 1 + 3 / N_f.  One step, with eps_dot = pe / W, sv = exp(-c eps_dot dt / 2) and mu = exp(eps_dot dt), all three computed in
+ * double at the end of the previous step:
+ *   1. v <- sv v, then v <- v + dt f / 2m  (f: what the step starts with, thermostat force included);
+ *   2. drift and box: x <- mu (x + dt v / sqrt(mu)), L <- mu L.  The displacement dt v / sqrt(mu) is what the rebuild criterion
+ *      sees; the scaling by mu is charged to the lists exactly as a Berendsen scaling is, and reference positions, tile
+ *      descriptors, the unfolded-image bookkeeping and the re-plan of the geometry follow as they do there.  In the fp32 build
+ *      the positions are box fractions: the drift is in the old box, the box then becomes mu L.  Fixed distances are absolute
+ *      lengths: they are restored behind the scaling;
+ *   3. rebuild decision / list build, forces at the new x, L; thermalize;
+ *   4. v <- v + dt f / 2m, then v <- sv v; then a velocity-rescale thermostat, if any;
+ *   5. the piston's kick, at the reference's aftIntV point, in front of the reaction / dissociation / ATRP work:
+ *        P = (sum m v^2 + W_vir) / 3V from the step's own x, v, L and virial,
+ *        G = 3V (P - P0) + (3 / N_f) sum m v^2 - gammaP pe + sqrt(24 gammaP W kT / dt) (u - 1/2),   pe <- pe + dt G,
+ *      u = u01(out[0]) of chem_philox::barostat_draw(seed, step), step = the number of the step just counted; then sv and mu of
+ *      the next step.
+ * With pe = 0, sv = mu = 1: the first step after switching on is the plain velocity-Verlet step.  The state between steps is
+ * consistent (the forces read back are those at the positions and the box read back), and run(a); run(b) is run(a + b) bit for
+ * bit when nothing touches the system in between.  With gammaP = 0 and no thermostat,
+ *   H = sum m v^2 / 2 + U + P0 V + (pe + dt G / 2)^2 / 2W,  evaluated behind 4. with that step's G, is conserved to O(dt^2).
+ * A pe, mu or sv that is not finite (or a mu of 0) stops chem_run with CHEM_ESTATE "Langevin barostat: ..." naming the step, P,
+ * P0 and pe; there is no clamp.  mass <= 0 switches it off and resets pe: the context then enqueues exactly the launches it
+ * enqueued before.  A call that only changes parameters while it is on keeps pe.  While it is on, what holds for the Berendsen
+ * barostat holds: a host wait on every step, no fused integrate, no skip_idle shortcut, the virial from a second pair pass.
+ * One barostat at a time: switching one on while the other is on is CHEM_EINVAL.  CHEM_ENOTIMPL on a decomposed context. */
+int chem_barostat_langevin(chem_ctx* ctx, double pressure, double mass, double gammaP, double kT, uint64_t seed);
+/* The barostat in force.  kind: 0 off, 1 Berendsen, 2 Langevin piston.  pressure_last: P of the last step's barostat action.
+ * Langevin piston: momentum = pe, eps_dot = pe / W, mu_next and sv_next the factors of the next step (Berendsen: 0, 0, 1, 1). */
+typedef struct chem_barostat_state {
+  int kind;
+  double pressure_last, momentum, eps_dot, mu_next, sv_next;
+} chem_barostat_state;
+int chem_barostat_state_get(chem_ctx* ctx, chem_barostat_state* out);
 /* system.bc.boxL: the current box edges */
 int chem_get_box(chem_ctx* ctx, double L[3]);
 

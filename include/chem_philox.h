@@ -79,6 +79,13 @@ CHEM_HD void atrp_draw(uint64_t seed, uint64_t step, uint32_t tag, uint32_t out[
   philox4x32_10(ctr, key, out);
 }
 
+/* Langevin piston (chem_barostat_langevin): out[0] is the uniform of the piston's noise at step `step`; one draw per step. */
+CHEM_HD void barostat_draw(uint64_t seed, uint64_t step, uint32_t out[4]) {
+  uint32_t ctr[4] = {0u, (uint32_t)step, (uint32_t)(step >> 32), 0x50495354u};
+  uint32_t key[2] = {(uint32_t)seed ^ 0x4241524Fu, (uint32_t)(seed >> 32)};
+  philox4x32_10(ctr, key, out);
+}
+
 /* ---- StochasticVelocityRescaling (Bussi, Donadio, Parrinello, J. Chem. Phys. 126, 014101 (2007)) ----
  * One scalar per step: the new kinetic energy drawn from the canonical distribution relaxing with time
  * constant taut (in steps).  The stream is keyed (seed, step); oracle and device run this same code on

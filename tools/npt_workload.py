@@ -2,13 +2,16 @@
 """The price of the barostat per step ("Pressure and barostat"; profiles/npt_kernels.txt): the C3 set-up
 of tools/bench_configs.py -- 128k beads of a tabulated polymer melt with harmonic bonds and angles -- with the barostat off
 (--tau 0: the launches every context enqueued before) or on (--tau T: a second pair pass for the virial, k_bonded_virial,
-k_baro_mu, the refresh of the tile descriptors and the host's waits per step; the lists live on across the scalings).
+k_baro_mu, the refresh of the tile descriptors and the host's waits per step; the lists live on across the scalings), or
+with the Langevin piston on (--piston W: k_baro_piston in the place of k_baro_mu, the scaling behind the next drift).
 
-    python3 tools/npt_workload.py [--tau T] [--dp D] [--steps K] [--warmup W] [--prec 32|64] [--chains N] [--time_pair N]
+    python3 tools/npt_workload.py [--tau T | --piston W [--gammaP G]] [--dp D] [--steps K] [--warmup W] [--prec 32|64] [--chains N] [--time_pair N]
 
 The target pressure is the melt's own pressure after the warm-up plus --dp, so that the box moves but slowly.  The rule has no
 compressibility factor, so tau carries it: this stiff melt needs --tau of 100 or more (profiles/npt_kernels.txt uses 500; with
 --tau 5 the box oscillates with growing amplitude and the run stops with the barostat's mu^3 <= 0 error after five steps).
+The piston's mass sets the period of the box: with 128k beads 3V dp is about 5e4 per unit of dp, so --piston 1e8 keeps the
+box within a percent over a few thousand steps.
 Prints one JSON line: particles, steps, steps per second, the box edge before and after, per-kernel times (time_pair_kernel)."""
 import argparse
 import json
@@ -24,6 +27,8 @@ from chemlab_amd.engine import Engine           # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tau", type=float, default=0.0)
+    ap.add_argument("--piston", type=float, default=0.0)
+    ap.add_argument("--gammaP", type=float, default=1.0)
     ap.add_argument("--dp", type=float, default=0.5)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
@@ -41,6 +46,10 @@ def main():
         p = g.pressure()
         out.update(pressure_start=p["pressure"], p0=p["pressure"] + a.dp)
         g.barostat_berendsen(p["pressure"] + a.dp, a.tau)
+    if a.piston > 0:
+        p = g.pressure()
+        out.update(pressure_start=p["pressure"], p0=p["pressure"] + a.dp, piston=a.piston, gammaP=a.gammaP)
+        g.barostat_langevin(p["pressure"] + a.dp, a.piston, a.gammaP, spec["kT"], 7)
     if has_box:
         out["box_start"] = float(g.box()[0])
     if a.time_pair:
