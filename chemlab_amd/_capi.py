@@ -110,6 +110,12 @@ class Pressure(C.Structure):
                 ("virial_list", C.c_double * CHEM_MAX_LISTS), ("virial", C.c_double)]
 
 
+class PressureTensor(C.Structure):
+    # six components each, in the order xx, yy, zz, xy, xz, yz
+    _fields_ = [("volume", C.c_double), ("kinetic", C.c_double * 6), ("virial_nb", C.c_double * 6),
+                ("virial_list", (C.c_double * 6) * CHEM_MAX_LISTS), ("virial", C.c_double * 6), ("tensor", C.c_double * 6)]
+
+
 class BarostatState(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pressure_last", C.c_double), ("momentum", C.c_double), ("eps_dot", C.c_double),
                 ("mu_next", C.c_double), ("sv_next", C.c_double)]
@@ -216,6 +222,7 @@ PRODUCT_ONLY = {
     "fix_joins": (_i64, [_P, C.POINTER(FixRecord), _i64]),
     # pressure observable, Berendsen barostat, current box (the CPU oracle has a fixed box and no virial of the lists)
     "get_pressure": (_i, [_P, C.POINTER(Pressure)]),
+    "get_pressure_tensor": (_i, [_P, C.POINTER(PressureTensor)]),
     "barostat_berendsen": (_i, [_P, _d, _d]),
     "get_box": (_i, [_P, _pd]),
     # Langevin piston barostat and the read-back of either barostat's state

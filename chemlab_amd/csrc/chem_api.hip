@@ -23,6 +23,7 @@
 #include "chem_geom_host.hpp"
 #include "chem_idle_host.hpp"
 #include "chem_launch_host.hpp"
+#include "chem_tensor_host.hpp"
 #include "chem_host.hpp"
 #include "chem_react_host.hpp"
 #include "chem_res_host.hpp"
@@ -278,6 +279,7 @@ struct Ctx {
   virtual int64_t get_state(int what, void* out, int64_t cap) = 0;
   virtual void observe(chem_obs* out) = 0;
   virtual void pressure(chem_pressure* out) = 0;
+  virtual void pressure_tensor(chem_pressure_tensor* out) = 0;
   virtual int64_t verlet_pairs(int64_t* out, int64_t cap) = 0;
   virtual void modify_particle(int tag, int what, double value) = 0;
   virtual int res_apply_completions() = 0;
@@ -1603,6 +1605,21 @@ template <typename R> struct CtxT : Ctx {
   // ---- forces -------------------------------------------------------------------------
   int pick_tpp() const { return chem::pick_tpp(use_tiles, n, opt_tpp); }
 
+  // device copy of what the force launch behind a rebuild needs to record the partner slots (refreshed when a pointer or the box changed)
+  const BondRec<R>* bond_rec_dev() {
+    BondRec<R> now;
+    std::memset(&now, 0, sizeof(now));      // (compared bytewise below: no indeterminate padding)
+    now.tag = tag.p; now.excl_start = excl_start.p; now.excl_list = excl_list.p; now.rtag = rtag.p;
+    now.gtag = dd_on ? gtag.p : nullptr; now.real0 = dd_on ? G : 0; now.real1 = dd_on ? G + n : 0x7fffffff;
+    std::memcpy(&now.box, &box, sizeof(box));
+    if (!brec_dev.p) brec_dev.alloc(1);
+    if (!brec_valid || std::memcmp(&now, &brec_host, sizeof(now)) != 0) {
+      brec_host = now; brec_valid = true;
+      HIPCHK(hipMemcpyAsync(brec_dev.p, &brec_host, sizeof(now), hipMemcpyHostToDevice, stream));
+    }
+    return brec_dev.p;
+  }
+
   // the pair forces into fdst (ENERGY: and the energy words into eout); the kernel is chem_launch_host.hpp's choice
   template <bool ENERGY> int launch_pair(V4* fdst) {
     const double hs = half_skin_eff();
@@ -1618,20 +1635,7 @@ template <typename R> struct CtxT : Ctx {
       if (dd_record_bonds) bond_mode = 3;
       if (pair_subset != 1) dd_record_bonds = false;      // (a launch of the interior tiles alone is followed by the boundary launch of the same step)
     }
-    const BondRec<R>* brec = nullptr;
-    if (bond_mode >= 2) {      // device copy of what the force launch behind a rebuild needs to record the partner slots (refreshed when a pointer or the box changed)
-      BondRec<R> now;
-      std::memset(&now, 0, sizeof(now));      // (compared bytewise below: no indeterminate padding)
-      now.tag = tag.p; now.excl_start = excl_start.p; now.excl_list = excl_list.p; now.rtag = rtag.p;
-      now.gtag = dd_on ? gtag.p : nullptr; now.real0 = dd_on ? G : 0; now.real1 = dd_on ? G + n : 0x7fffffff;
-      std::memcpy(&now.box, &box, sizeof(box));
-      if (!brec_dev.p) brec_dev.alloc(1);
-      if (!brec_valid || std::memcmp(&now, &brec_host, sizeof(now)) != 0) {
-        brec_host = now; brec_valid = true;
-        HIPCHK(hipMemcpyAsync(brec_dev.p, &brec_host, sizeof(now), hipMemcpyHostToDevice, stream));
-      }
-      brec = brec_dev.p;
-    }
+    const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
     if (use_tiles) {
       // which tiles: all (default), or the interior / boundary subset of a slab (see TileSub)
       const TileLayers tl = tile_subset(ntiles, ntxy(), pair_subset);
@@ -1869,6 +1873,92 @@ template <typename R> struct CtxT : Ctx {
     for (size_t l = 0; l < top.lists.size(); ++l) { out->virial_list[l] = hv[l]; w += hv[l]; }
     out->virial = w;
     out->pressure = baro_pressure(out->mv2, w, out->volume);
+  }
+
+  // ---- pressure tensor (chem_get_pressure_tensor; the rules: include/chem_mi355.h, the kernel: chem_tensor_host.hpp) ----
+  // Everything below is allocated and launched by the call alone.
+  DBuf<double> tpart, tredbuf;      // per-list sums, kinetic and pair block partials (one buffer, one download); the ranks' sums
+  // the tensor pass over the lists of the step's forces into tpart (six words per block); returns the number of blocks.  The
+  // arguments are those of launch_pair<true>: fdst is scratch, the excluded pairs of inline bonds are taken out again.
+  int launch_pair_tensor(V4* fdst, size_t off) {      // off: where the partials start in tpart
+    const double hs = half_skin_eff();
+    PairInput in{use_tiles, n, opt_tpp, pair_bs, true, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
+    if (in.coul && in.res) first_res_pair(res_mask, in.res_a, in.res_b);
+    if (in.coul && in.cap) first_cap_pair(cap_rad, in.cap_a, in.cap_b);
+    const TensorPlan plan = tensor_plan(in);
+    if (plan.code != CHEM_OK) throw ChemError(plan.code, pair_refusal_text(plan.refused));
+    const TensorVariant& v = plan.v;
+    const int nblk = use_tiles ? ntiles : cdiv((long long)n * v.tpp, v.block);
+    if (nblk <= 0) return 0;
+    tpart.alloc(off + 6 * (size_t)nblk + 8);
+    double* const tout = tpart.p + off;
+    HIPCHK(hipMemsetAsync(tout, 0, sizeof(double) * 6 * (size_t)nblk, stream));      // (a halted context's kernels leave at once)
+    const CoulArgs<R> ca = v.mode == 4 ? coul_args((size_t)nblk) : CoulArgs<R>{};
+    const ResArgs<R> ra = (v.mode == 5 || v.mode == 7) ? res_args() : ResArgs<R>{};
+    const CapArgs<R> cp = (v.mode == 6 || v.mode == 7) ? cap_args() : CapArgs<R>{};
+    bool found = false;
+    if (use_tiles) {
+      const bool inline_now = bonds_inline();
+      int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;
+      if (bond_mode == 2 && dd_on && dd_record_bonds) { bond_mode = 3; dd_record_bonds = false; }      // (as launch_pair: the launch behind a slab rebuild records the partner slots)
+      const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
+      const TileSub ts{0, ntiles, 0};
+      const size_t lds = pair_lds_bytes();
+      found = pick_among<3, 4, 5, 6, 7>(v.mode, [&](auto M_) {
+        auto kern = &k_pair_tiles_tensor<R, decltype(M_)::value>;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, stream, nblk, tile_cap, x4.p, fdst, tdesc.p, nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, ts,
+                           (v.mode == 3 && inline_now && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, brec, ca, ra, cp, tout);
+        return true;
+      });
+    } else {
+      found = pick_among<0, 4, 5, 6, 7>(v.mode, [&](auto M_) {
+        hipLaunchKernelGGL((k_pair_force_tensor<R, decltype(M_)::value>), dim3(nblk), dim3(256), 0, stream, n, x4.p, fdst, nlist.p, nn.p, S, box, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p,
+                           ca, ra, cp, tout);
+        return true;
+      });
+    }
+    if (!found || !tensor_variant_built(v.family, v.mode, v.tpp, v.block)) throw ChemError(CHEM_ESTATE, "internal: no pressure-tensor kernel is built for the planned variant");
+    HIPCHK(hipGetLastError());
+    return nblk;
+  }
+  void pressure_tensor(chem_pressure_tensor* out) override {
+    flush_host_state();
+    if (resort) { rebuild_now(); compute_forces(); }      // (the route of observe(): a rebuild re-sorts the particles but not f4)
+    std::memset(out, 0, sizeof(*out));
+    constexpr int kParts = 2 + CHEM_MAX_LISTS;              // kinetic, non-bonded, the lists
+    // one buffer, one download: [per-list sums | kinetic block partials | pair block partials]
+    const int nkb = cdiv(n, 256);
+    const size_t o_k = 6 * CHEM_MAX_LISTS, o_p = o_k + 6 * (size_t)nkb;
+    const int nb = launch_pair_tensor(x4o.p, o_p);          // scratch force buffer: leaves f4 untouched
+    const bool bonded = nbent > 0 && nkb > 0;
+    tpart.alloc(o_p + 8);                                   // (launch_pair_tensor has sized it where there are pairs)
+    HIPCHK(hipMemsetAsync(tpart.p, 0, sizeof(double) * 6 * CHEM_MAX_LISTS, stream));
+    if (nkb > 0) hipLaunchKernelGGL(k_kinetic_tensor<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, tpart.p + o_k);
+    if (bonded)
+      hipLaunchKernelGGL((k_bonded_virial_tensor<R>), dim3(nkb), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, tpart.p,
+                         ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+    std::vector<double> h;
+    tpart.download(h, o_p + 6 * (size_t)nb, stream);
+    double acc[6 * kParts] = {0};                           // block partials folded in block order
+    for (int b = 0; b < nkb; ++b) for (int c = 0; c < 6; ++c) acc[c] += h[o_k + 6 * (size_t)b + c];
+    for (int b = 0; b < nb; ++b) for (int c = 0; c < 6; ++c) acc[6 + c] += h[o_p + 6 * (size_t)b + c];
+    for (int k = 0; k < 6 * CHEM_MAX_LISTS; ++k) acc[12 + k] = h[k];
+    if (dd_on && P > 1) {      // one all-reduce of the 6 + 6 + 6 * CHEM_MAX_LISTS sums
+      tredbuf.alloc(6 * kParts);
+      HIPCHK(hipMemcpyAsync(tredbuf.p, acc, sizeof(acc), hipMemcpyHostToDevice, stream));
+      tr->allreduce_sum_f64(tredbuf.p, 6 * kParts, stream);
+      HIPCHK(hipMemcpyAsync(acc, tredbuf.p, sizeof(acc), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    out->volume = L[0] * L[1] * L[2];
+    for (int c = 0; c < 6; ++c) {
+      out->kinetic[c] = acc[c]; out->virial_nb[c] = acc[6 + c];
+      double w = acc[6 + c];
+      for (size_t l = 0; l < top.lists.size(); ++l) { out->virial_list[l][c] = acc[12 + 6 * l + c]; w += acc[12 + 6 * l + c]; }
+      out->virial[c] = w;
+      out->tensor[c] = (acc[c] + w) / out->volume;
+    }
   }
   // the box lengths alone changed (same cell grid, same plan): everything the kernels take by value
   void refresh_box_lengths() {
@@ -3464,6 +3554,7 @@ int chem_get_coulomb(chem_ctx* ctx, double* epot, double* virial) {
 }
 
 int chem_get_pressure(chem_ctx* ctx, chem_pressure* out) { API_BEGIN REQUIRE(out, CHEM_EINVAL, "null output"); CTX.pressure(out); return 0; API_END(ctx) }
+int chem_get_pressure_tensor(chem_ctx* ctx, chem_pressure_tensor* out) { API_BEGIN REQUIRE(out, CHEM_EINVAL, "null output"); CTX.pressure_tensor(out); return 0; API_END(ctx) }
 
 int chem_barostat_berendsen(chem_ctx* ctx, double pressure, double tau) {
   API_BEGIN

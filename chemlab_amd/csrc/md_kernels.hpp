@@ -1207,14 +1207,36 @@ __device__ __forceinline__ void pair_term(const PairCore<R> pc, const PairExt<R>
 // both table kinds); lambda through tag[j] -> stamp, evaluated per neighbour
 // (the body of k_pair_force and of k_pair_force_res, which alone takes the resolution arguments)
 // CAPPED: type pairs with a cap radius (k_pair_force_cap, k_pair_force_rescap, launched only while a type pair is capped)
-template <typename R, int TPP, bool ENERGY, bool CUBIC, bool COUL, bool RES, bool CAPPED = false>
+// TENSOR (k_pair_force_tensor, K13): the pair's whole term -- law, resolution weight and cap, Coulomb term -- goes into zeroed
+// temporaries first, as res_pair does, and d_a t_b is added to six fp64 sums; tout[6 * block + c] = the block's half sums
+// (xx, yy, zz, xy, xz, yz).  Not compiled into the instantiations of the step.
+__device__ __forceinline__ void tensor_add(double (&tw)[6], double dx, double dy, double dz, double tx, double ty, double tz) {
+  tw[0] += dx * tx; tw[1] += dy * ty; tw[2] += dz * tz; tw[3] += dx * ty; tw[4] += dx * tz; tw[5] += dy * tz;
+}
+// the six sums of a block of NW waves: wave reduction, then the waves' words in their order; `scale` times the sum to out[0..5]
+template <int NW>
+__device__ __forceinline__ void tensor_block_out(double (&tw)[6], double scale, double* __restrict__ out) {
+  __shared__ double tred[6][NW];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    for (int o = 32; o > 0; o >>= 1) tw[c] += __shfl_xor(tw[c], o);
+    if (lane_id() == 0) tred[c][threadIdx.x >> 6] = tw[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double s = 0;
+    for (int k = 0; k < NW; ++k) s += tred[threadIdx.x][k];
+    out[threadIdx.x] = scale * s;
+  }
+}
+template <typename R, int TPP, bool ENERGY, bool CUBIC, bool COUL, bool RES, bool CAPPED = false, bool TENSOR = false>
 __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ nlist, const int* __restrict__ nn, int S,
                                                     const Box<R>& box, const PairCore<R>* __restrict__ pcore,
                                                     const PairExt<R>* __restrict__ pext, int ntypes,
                                                     const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                     double half_skin, DevCtl* ctl, const CoulArgs<R>& ca, const ResArgs<R>& ra,
-                                                    const CapArgs<R>& cp = CapArgs<R>{}) {
+                                                    const CapArgs<R>& cp = CapArgs<R>{}, double* __restrict__ tout = nullptr) {
   __shared__ PairCore<R> spc[kMaxTypes * kMaxTypes];
   for (int k = threadIdx.x; k < ntypes * ntypes; k += blockDim.x) spc[k] = pcore[k];
   [[maybe_unused]] const R* sfm = nullptr;
@@ -1228,6 +1250,7 @@ __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict
   R fx = 0, fy = 0, fz = 0;
   double e_lj = 0, e_tab = 0, vir = 0;
   [[maybe_unused]] double e_q = 0, v_q = 0;
+  [[maybe_unused]] double tw[6] = {0, 0, 0, 0, 0, 0};
   if (i < n) {
     const Vec4<R> xi = x4[i];
     const int ti = (int)xi.w;
@@ -1264,6 +1287,18 @@ __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict
         const int pidx = pbase + (int)xj.w;
         [[maybe_unused]] R c2 = (R)0;
         if constexpr (CAPPED) c2 = sc2[ti * kMaxTypes + (int)xj.w];
+        if constexpr (TENSOR) {
+          R tx = 0, ty = 0, tz = 0;
+          if constexpr (RES) {
+            const int tj = (int)xj.w;
+            res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
+                                lami, ls[u], ((rrow >> tj) & 1u) != 0, sfm[ti * kMaxTypes + tj], dx, dy, dz, tx, ty, tz, e_lj, e_tab, vir);
+          } else
+          pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, tx, ty, tz, e_lj, e_tab, vir, c2);
+          if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, tx, ty, tz, e_q, v_q);
+          fx += tx; fy += ty; fz += tz;
+          tensor_add(tw, (double)dx, (double)dy, (double)dz, (double)tx, (double)ty, (double)tz);
+        } else {
         if constexpr (RES) {
           const int tj = (int)xj.w;
           res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
@@ -1271,6 +1306,7 @@ __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict
         } else
         pair_term<R, ENERGY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir, c2);
         if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
+        }
       }
     }
   }
@@ -1302,6 +1338,7 @@ __device__ __forceinline__ void pair_force_body(int n, const Vec4<R>* __restrict
       }
     }
   }
+  if constexpr (TENSOR) tensor_block_out<4>(tw, 0.5, tout + 6 * (size_t)blockIdx.x);      // (full list: half weights, as above)
 }
 template <typename R, int TPP, bool ENERGY, bool CUBIC = false, bool COUL = false>
 __global__ __launch_bounds__(256) void k_pair_force(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
@@ -2471,7 +2508,8 @@ struct DecideArgs { const double* gathered; int n; volatile int* host_flag; int 
 // guard != 0: speculative launch of the decomposed path -- leave at once while a rebuild is pending.
 // (the body of k_pair_tiles and of k_pair_tiles_q, which alone takes the Coulomb arguments: the kernels of every other mode keep
 //  their argument block)
-template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG>
+// TENSOR (k_pair_tiles_tensor, K13): as in pair_force_body; tout[6 * block + c]
+template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG, bool TENSOR = false>
 __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                    const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
                                                    const int* __restrict__ nnh, int S16,
@@ -2481,7 +2519,8 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                                                    DecideArgs da, uint4* __restrict__ bslots,
                                                    double bond_K, double bond_r0, int bond_mode, ActMask bact,
                                                    const BondRec<R>* __restrict__ brec,
-                                                   const CoulArgs<R> ca, const ResArgs<R> ra, const CapArgs<R> cp = CapArgs<R>{}) {
+                                                   const CoulArgs<R> ca, const ResArgs<R> ra, const CapArgs<R> cp = CapArgs<R>{},
+                                                   double* __restrict__ tout = nullptr) {
   constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE >= 3, COUL = MODE == 4, RES = MODE == 5 || MODE == 7, CAPPED = MODE == 6 || MODE == 7;
 #ifndef CHEM_NCH
 #define CHEM_NCH 3
@@ -2604,6 +2643,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   if (DIAG && dbg) st2 = wall_clock64();
   double e_lj = 0, e_tab = 0, vir = 0;
   [[maybe_unused]] double e_q = 0, v_q = 0;
+  [[maybe_unused]] double tw[6] = {0, 0, 0, 0, 0, 0};
   for (int q0 = 0; q0 < nhome; q0 += NSL) {
     const int q = q0 + slice;
     R fx = 0, fy = 0, fz = 0;
@@ -2683,6 +2723,18 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
               const int pidx = pbase + (int)xj.w;
               [[maybe_unused]] R c2 = (R)0;
               if constexpr (CAPPED) c2 = sc2[(int)xi.w * kMaxTypes + (int)xj.w];
+              if constexpr (TENSOR) {
+                R tx = 0, ty = 0, tz = 0;
+                if constexpr (RES) {
+                  const int tj = (int)xj.w;
+                  res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
+                                      lami, qs[u], ((rrow >> tj) & 1u) != 0, sfm[(int)xi.w * kMaxTypes + tj], dx, dy, dz, tx, ty, tz, e_lj, e_tab, vir);
+                } else
+                pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, tx, ty, tz, e_lj, e_tab, vir, c2);
+                if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, tx, ty, tz, e_q, v_q);
+                fx += tx; fy += ty; fz += tz;
+                tensor_add(tw, (double)dx, (double)dy, (double)dz, (double)tx, (double)ty, (double)tz);
+              } else {
               if constexpr (RES) {
                 const int tj = (int)xj.w;
                 res_pair<R, ENERGY>([&](R& ax, R& ay, R& az, double& a1, double& a2, double& av) { pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, ax, ay, az, a1, a2, av, c2); },
@@ -2690,6 +2742,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
               } else
               pair_accum<R, ENERGY, LJONLY, CUBIC, CAPPED>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, fx, fy, fz, e_lj, e_tab, vir, c2);
               if constexpr (COUL) coul_term<R, ENERGY>(kqi, qs[u], ((crow >> (int)xj.w) & 1u) != 0, ca.rc2, r2, dx, dy, dz, fx, fy, fz, e_q, v_q);
+              }
             }
           }
         }
@@ -2749,6 +2802,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                 const int pidx = pbase + (int)xj.w;
                 pair_accum<R, ENERGY, LJONLY, CUBIC>(spc[pidx], pext, pidx, tab, r2, dx, dy, dz, tx, ty, tz, te1, te2, tv);
                 fx -= tx; fy -= ty; fz -= tz; e_lj -= te1; e_tab -= te2; vir -= tv;
+                if constexpr (TENSOR) tensor_add(tw, (double)dx, (double)dy, (double)dz, -(double)tx, -(double)ty, -(double)tz);
               }
             }
             if (!ENERGY) {
@@ -2793,6 +2847,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
       }
     }
   }
+  if constexpr (TENSOR) tensor_block_out<BS / 64>(tw, 0.5, tout + 6 * (size_t)blockIdx.x);
 }
 
 template <typename R, int TPP, bool ENERGY, int BS, int MODE, bool DIAG = false>
@@ -2867,6 +2922,17 @@ __device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a
 __device__ __forceinline__ double dot3(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ D3 cross3(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
+// a b - c d with the rounding error of c d recovered by fused multiply-adds (Kahan): a cross product of nearly parallel vectors
+// keeps its relative accuracy (bonded_term EXACT)
+__device__ __forceinline__ double diff_of_products(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double w = c * d;
+  const double e = __builtin_fma(-c, d, w), f = __builtin_fma(a, b, -w);
+  return f + e;
+}
+__device__ __forceinline__ D3 cross3_exact(D3 a, D3 b) {
+  return {diff_of_products(a.y, b.z, a.z, b.y), diff_of_products(a.z, b.x, a.x, b.z), diff_of_products(a.x, b.y, a.y, b.x)};
+}
 struct BoxD { double L[3], invL[3]; double qs[3], qh[3]; };   // qs, qh: fixed-point decoding of the fp32 build's positions (Box<R>)
 __device__ __forceinline__ D3 minimgD(const BoxD& b, D3 d) {
   return {d.x - b.L[0] * rint(d.x * b.invL[0]), d.y - b.L[1] * rint(d.y * b.invL[1]), d.z - b.L[2] * rint(d.z * b.invL[2])};
@@ -2914,7 +2980,12 @@ __device__ __forceinline__ void btab_lookup(const BTab& bt, const int h, const d
 // and table code is not compiled in, which is what brings the per-step kernel from 209 to a few dozen registers
 // HYB: the pair term (force and energy) is scaled by `lam` (hybrid lists); not compiled into the other instantiations
 // COUL: the 1-4 Coulomb kind (CHEM_POT_COULOMB_BOND) with the two members' charges q0, q1; not compiled into the others either
-template <typename R, bool ENERGY, bool BONDS_ONLY = false, bool HYB = false, bool COUL = false>
+// EXACT (k_bonded_virial_tensor alone): the bending term in a form that keeps its digits next to a straight or folded angle
+// ("Conditioning of the bending term"): r1 x r2 by compensated products, theta and sin(theta) from atan2(|r1 x r2|,
+// r1 . r2), the two forces as (r1 x r2) x r1 and r2 x (r1 x r2) instead of differences of nearly equal vectors times dU / sin.
+// The same law; at 1e-5 off folded with theta0 = pi the plain form is off by 1e-10 of the list's d (x) F, which an observable
+// compared at that level cannot afford.  Not compiled into the other instantiations.
+template <typename R, bool ENERGY, bool BONDS_ONLY = false, bool HYB = false, bool COUL = false, bool EXACT = false>
 __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me, const int j0, const int j1, const int j2, const int j3,
                                             const Vec4<R>* __restrict__ x4, const BoxD& box, D3& f, double* __restrict__ elist, DevCtl* ctl, const BTab& bt,
                                             const double lam = 1.0, const double q0 = 0.0, const double q1 = 0.0) {
@@ -2963,8 +3034,11 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
       const double n1 = sqrt(dot3(r1, r1)), n2 = sqrt(dot3(r2, r2));
       double c = dot3(r1, r2) / (n1 * n2);
       c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-      const double th = acos(c);
+      double th = acos(c);
       double s = sqrt(1.0 - c * c);
+      [[maybe_unused]] D3 x12 = {0, 0, 0}; [[maybe_unused]] double sn = 0;
+      if constexpr (EXACT) { x12 = cross3_exact(r1, r2); sn = sqrt(dot3(x12, x12)); th = atan2(sn, dot3(r1, r2)); s = sn / (n1 * n2); }
+      [[maybe_unused]] const bool perp = EXACT && s >= 1e-9;
       if (s < 1e-9) s = 1e-9;
       double dU = 0;
       if (bp.kind == CHEM_POT_ANG_HARMONIC) { const double d = th - p[1]; u = p[0] * d * d; dU = 2.0 * p[0] * d; }
@@ -2975,8 +3049,10 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
         dU = -fv;
       }
       const double a = dU / s;
-      const D3 fi = a * ((1.0 / (n1 * n2)) * r2 - (c / (n1 * n1)) * r1);
-      const D3 fk = a * ((1.0 / (n1 * n2)) * r1 - (c / (n2 * n2)) * r2);
+      D3 fi = a * ((1.0 / (n1 * n2)) * r2 - (c / (n1 * n1)) * r1);
+      D3 fk = a * ((1.0 / (n1 * n2)) * r1 - (c / (n2 * n2)) * r2);
+      // EXACT: the same two vectors without the difference of nearly equal ones: n1^2 r2 - (r1 . r2) r1 = (r1 x r2) x r1
+      if constexpr (EXACT) if (perp) { fi = (dU / (sn * n1 * n1)) * cross3(x12, r1); fk = (dU / (sn * n2 * n2)) * cross3(r2, x12); }
       if (me == 0) f = f + fi; else if (me == 2) f = f + fk; else f = f - (fi + fk);
     } else {
       if ((j0 | j1 | j2 | j3) < 0) { ctl->bonded_missing = 1; return; }
@@ -3845,6 +3921,100 @@ __global__ __launch_bounds__(256) void k_baro_scale_x(int n, double4* __restrict
   double4 x = x4[i];
   x.x *= s; x.y *= s; x.z *= s;
   x4[i] = x;
+}
+
+// =======================================================================================
+// K13 pressure tensor (analysis.PressureTensor; rule set in include/chem_mi355.h "pressure tensor"; the kernel of a context:
+//     chem_tensor_host.hpp).  Six components in the order xx, yy, zz, xy, xz, yz.  Launched by chem_get_pressure_tensor alone.
+// =======================================================================================
+// K_ab = sum m v_a v_b: out[6 * block + c]
+template <typename R>
+__global__ __launch_bounds__(256) void k_kinetic_tensor(int i0, int n, const Vec4<R>* __restrict__ v4, double* __restrict__ out) {
+  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+  double tw[6] = {0, 0, 0, 0, 0, 0};
+  if (i < i0 + n) {
+    const Vec4<R> v = v4[i];
+    const double m = (double)v.w, vx = (double)v.x, vy = (double)v.y, vz = (double)v.z;
+    tensor_add(tw, vx, vy, vz, m * vx, m * vy, m * vz);
+  }
+  tensor_block_out<4>(tw, 1.0, out + 6 * (size_t)blockIdx.x);
+}
+// Bonded part: the walk of k_bonded_virial over every arity, the entry counted at member 0.  Pairs: d_ij (x) F_i.  Triples
+// (i, j, k), centre j: d_ij (x) F_i + d_kj (x) F_k.  Quadruples (i, j, k, l): d_ij (x) F_i + d_kj (x) F_k + (d_kj + d_lk) (x) F_l.
+// The forces are bonded_term's, one call per member, in its EXACT instantiation; the d are the minimum-image differences it forms.
+// vlist[6 * l + c] += the share of list l (atomics: an observable; nothing reads a sum over the lists, so no block partials).
+template <typename R>
+__global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                              const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                              const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ vlist,
+                                                              DevCtl* ctl, BTab bt, HybridArgs hy, const R* __restrict__ qtag) {
+  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < i0 + n) {
+    const int tg = tag[i];
+    const int e0 = bstart[tg], e1 = bstart[tg + 1];
+    for (int e = e0; e < e1; ++e) {
+      const BondedEntry be = bent[e];
+      const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+      const BondedParam& bp = bpar[slot];
+      const int ar = bp.arity;
+      int j3 = 0;
+      if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }      // (quadruples occupy two consecutive entries)
+      if (me != 0) continue;
+      const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
+      if ((j0 | j1 | j2 | j3) < 0) { ctl->bonded_missing = 1; continue; }
+      double q0 = 0, q1 = 0;
+      if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
+      const double lam = ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0;
+      const D3 x0 = posD<R>(x4[j0], box), x1 = posD<R>(x4[j1], box);
+      const D3 dij = minimgD(box, x0 - x1);
+      double t[6] = {0, 0, 0, 0, 0, 0};
+      D3 f = {0, 0, 0};
+      bonded_term<R, false, false, true, true, true>(bp, 0, j0, j1, j2, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
+      tensor_add(t, dij.x, dij.y, dij.z, f.x, f.y, f.z);
+      if (ar > 2) {
+        const D3 dkj = minimgD(box, posD<R>(x4[j2], box) - x1);
+        f = {0, 0, 0};
+        bonded_term<R, false, false, true, true, true>(bp, 2, j0, j1, j2, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
+        tensor_add(t, dkj.x, dkj.y, dkj.z, f.x, f.y, f.z);
+        if (ar == 4) {
+          const D3 dlj = dkj + minimgD(box, posD<R>(x4[j3], box) - posD<R>(x4[j2], box));
+          f = {0, 0, 0};
+          bonded_term<R, false, false, true, true, true>(bp, 3, j0, j1, j2, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
+          tensor_add(t, dlj.x, dlj.y, dlj.z, f.x, f.y, f.z);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 6; ++c) atomicAdd(&vlist[6 * bp.list + c], t[c]);
+    }
+  }
+}
+// Non-bonded part, per-particle rows: the TENSOR instantiation of pair_force_body, four lanes per particle, both table kinds.
+// MODE 0 the plain kernel, 4 Coulomb, 5 resolution, 6 caps, 7 resolution and caps (chem_tensor_host.hpp tensor_plan); f4 is scratch.
+template <typename R, int MODE>
+__global__ __launch_bounds__(256) void k_pair_force_tensor(int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                           const int* __restrict__ nlist, const int* __restrict__ nn, int S,
+                                                           Box<R> box, const PairCore<R>* __restrict__ pcore,
+                                                           const PairExt<R>* __restrict__ pext, int ntypes,
+                                                           const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                           double half_skin, DevCtl* ctl, CoulArgs<R> ca, ResArgs<R> ra, CapArgs<R> cp, double* __restrict__ tout) {
+  static_assert(MODE == 0 || (MODE >= 4 && MODE <= 7), "row tensor kernels: MODE 0, 4, 5, 6, 7");
+  pair_force_body<R, 4, true, true, MODE == 4, MODE == 5 || MODE == 7, MODE == 6 || MODE == 7, true>(n, x4, f4, nlist, nn, S, box, pcore, pext, ntypes, tab, eout, half_skin, ctl, ca, ra, cp, tout);
+}
+// ... tiles: the TENSOR instantiation of pair_tiles_body, one lane per particle, 512 threads.  MODE 3 (general, both table kinds:
+// what the energy pass of MODE 0..3 evaluates, the excluded pairs of inline bonds taken out again) and 4..7.
+// (The launch bounds are those of the 512-thread force kernels on purpose: bond_record is a real function, and the register
+//  budget of a function follows from the bounds of ALL kernels that call it -- a caller with looser bounds changes the others.)
+template <typename R, int MODE>
+__global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_tensor(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                           const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
+                                                           const int* __restrict__ nnh, int S16,
+                                                           const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
+                                                           int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
+                                                           double half_skin, DevCtl* ctl, TileSub sub_, uint4* __restrict__ bslots, int bond_mode, ActMask bact,
+                                                           const BondRec<R>* __restrict__ brec, CoulArgs<R> ca, ResArgs<R> ra, CapArgs<R> cp, double* __restrict__ tout) {
+  static_assert(MODE >= 3 && MODE <= 7, "tile tensor kernels: MODE 3..7");
+  pair_tiles_body<R, 1, true, 512, MODE, false, true>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, 0, 0, nullptr,
+                                                      sub_, DecideArgs{}, bslots, 0.0, 0.0, bond_mode, bact, brec, ca, ra, cp, tout);
 }
 
 // =======================================================================================

@@ -520,6 +520,19 @@ class Engine:
         return dict(pressure=p.pressure, volume=p.volume, mv2=p.mv2, virial_nb=p.virial_nb,
                     virial_list=list(p.virial_list)[:len(self._lists)], virial=p.virial)
 
+    def pressure_tensor(self):
+        """Pi_ab = (K_ab + W_ab) / V at the current state, components in the order xx, yy, zz, xy, xz, yz: dict(volume,
+        kinetic[6], virial_nb[6], virial_list[lists, 6], virial[6], tensor[6]) of numpy arrays."""
+        fn = getattr(self.api, "get_pressure_tensor", None)
+        if fn is None:
+            raise NotImplementedError("PressureTensor: the CPU checker has no virial tensor")
+        p = _capi.PressureTensor()
+        self._ck(fn(self.ctx, C.byref(p)))
+        nl = len(self._lists)
+        return dict(volume=p.volume, kinetic=np.array(p.kinetic, dtype=np.float64), virial_nb=np.array(p.virial_nb, dtype=np.float64),
+                    virial_list=np.array([list(p.virial_list[l]) for l in range(nl)], dtype=np.float64).reshape(nl, 6),
+                    virial=np.array(p.virial, dtype=np.float64), tensor=np.array(p.tensor, dtype=np.float64))
+
     def barostat_berendsen(self, pressure, tau):
         """Isotropic Berendsen barostat on every step; tau <= 0 switches it off."""
         fn = getattr(self.api, "barostat_berendsen", None)

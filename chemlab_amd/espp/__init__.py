@@ -1650,6 +1650,17 @@ class _Pressure(_Observable):
         return self.system.engine.pressure()["pressure"]
 
 
+class _PressureTensor(_Observable):
+    """analysis.PressureTensor(system).compute(): the six components (K_ab + W_ab) / V in the order xx, yy, zz, xy, xz, yz, in
+    the engine's units (include/chem_mi355.h chem_get_pressure_tensor)."""
+
+    def __init__(self, system):
+        _Observable.__init__(self, system)
+
+    def compute(self):
+        return [float(c) for c in self.system.engine.pressure_tensor()["tensor"]]
+
+
 class _BoxSize(_Observable):
     """The `L` column that goes with `P` (start_simulation.py:466-469): the x edge of the current box.  The reference's
     class is in the external fork; what it reports for a box that is not cubic is unpinned."""
@@ -1799,7 +1810,7 @@ analysis = _ns(
     NFixedPairListEntries=_NFixedPairListEntries, NumFixDistances=_NumFixDistances, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
-    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_unsupported("analysis.PressureTensor"),
+    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor,
 )
 
 esutil = _ns(RNG=_RNG)

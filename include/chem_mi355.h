@@ -582,6 +582,36 @@ typedef struct chem_pressure {
   double virial;                       /* W = virial_nb + sum of virial_list */
 } chem_pressure;
 int chem_get_pressure(chem_ctx* ctx, chem_pressure* out);
+/* Pressure tensor: analysis.PressureTensor(system).compute().  This build's own rule set, as the pressure above.
+ *     Pi_ab = (K_ab + W_ab) / V,   six components in the order xx, yy, zz, xy, xz, yz  (every array [6] below).
+ * K_ab = sum_i m_i v_i,a v_i,b over all particles, dummies included, with the mass the device integrates with.
+ * W_ab = sum d_a F_b (a <= b) over the interactions of the scalar W, with the same forces and the same weights: the Coulomb
+ * term, capped pairs with the force that was applied, lambda-weighted and force-capped resolution pairs, hybrid lists times
+ * lambda, 1-4 Coulomb lists; a pair between two slabs is counted once.
+ *   - a non-bonded pair or an entry of a pair list: d = the minimum-image vector the force law itself uses, F = the force on
+ *     the first member;
+ *   - triples and quadruples ARE evaluated (their trace vanishes, their components do not):
+ *       triple (i, j, k), centre j:   d_ij (x) F_i + d_kj (x) F_k;
+ *       quadruple (i, j, k, l):       d_ij (x) F_i + d_kj (x) F_k + (d_kj + d_lk) (x) F_l;
+ *     the d are the minimum-image differences the bonded term forms; the entry is counted once, at member 0, as its energy is.
+ *     The bending term of this pass is the force kernels' law in a form that keeps its digits next to a straight or folded
+ *     angle (r1 x r2 by compensated products, the angle from atan2, the forces as double cross products); the force kernels'
+ *     own form is off by about 1e-10 of a list's d (x) F at 1e-5 off folded, see DESIGN.md.
+ * Not in W, as in the scalar: thermostat friction and noise, the clipping of chem_cap_force, the chem_fix_* constraint.
+ * (K_xx + K_yy + K_zz = chem_pressure.mv2 and W_xx + W_yy + W_zz = chem_pressure.virial to rounding, part by part.)
+ * Preconditions and side effects are those of chem_get_pressure and no others (the chem_observe route; a list build where the
+ * skin is used up); works on slabs, every rank returns the global value.  The non-bonded part is a pass of its own over the
+ * lists the step's forces used; which kernel runs is chem_tensor_host.hpp's rule, which refuses what the force launch refuses.
+ * A context that never calls this allocates and launches nothing for it. */
+typedef struct chem_pressure_tensor {
+  double volume;
+  double kinetic[6];
+  double virial_nb[6];
+  double virial_list[CHEM_MAX_LISTS][6];
+  double virial[6];                    /* virial_nb + sum of virial_list */
+  double tensor[6];                    /* (kinetic + virial) / volume */
+} chem_pressure_tensor;
+int chem_get_pressure_tensor(chem_ctx* ctx, chem_pressure_tensor* out);
 /* Berendsen barostat, isotropic, on every step at the reference's aftIntV point: after the second half kick of step s and
  * after a velocity-rescale thermostat (if any), before the reaction, dissociation or ATRP work of that step.
  *     mu = [1 - (dt / tau) (P0 - P)]^(1/3),   P from x(t+dt), v(t+dt) and the virial of the step's own force evaluation;
