@@ -1601,6 +1601,15 @@ template <typename R> struct CtxT : Ctx {
     HIPCHK(hipStreamSynchronize(stream));
     h.nl_overflow = (int)v[0]; h.stage_overflow = (int)v[1]; h.mig_error = (int)v[2]; h.skin_violation = (int)v[3];
   }
+  // the host sums v[0..nv) of an observable, summed over the ranks of a decomposition in place (through buf; one rank: nothing)
+  void allreduce_host_sums(double* v, int nv, DBuf<double>& buf) {
+    if (!(dd_on && P > 1)) return;
+    buf.alloc((size_t)nv);
+    HIPCHK(hipMemcpyAsync(buf.p, v, sizeof(double) * nv, hipMemcpyHostToDevice, stream));
+    tr->allreduce_sum_f64(buf.p, nv, stream);
+    HIPCHK(hipMemcpyAsync(v, buf.p, sizeof(double) * nv, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
 
   // ---- forces -------------------------------------------------------------------------
   int pick_tpp() const { return chem::pick_tpp(use_tiles, n, opt_tpp); }
@@ -1620,21 +1629,32 @@ template <typename R> struct CtxT : Ctx {
     return brec_dev.p;
   }
 
-  // the pair forces into fdst (ENERGY: and the energy words into eout); the kernel is chem_launch_host.hpp's choice
-  template <bool ENERGY> int launch_pair(V4* fdst) {
-    const double hs = half_skin_eff();
-    PairInput in{use_tiles, n, opt_tpp, pair_bs, ENERGY, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
+  // what a pair launch asks its plan with (pair_plan, tensor_plan)
+  PairInput pair_input(bool energy) {
+    PairInput in{use_tiles, n, opt_tpp, pair_bs, energy, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
     if (in.coul && in.res) first_res_pair(res_mask, in.res_a, in.res_b);
     if (in.coul && in.cap) first_cap_pair(cap_rad, in.cap_a, in.cap_b);
-    const PairPlan plan = pair_plan(in);
-    if (plan.code != CHEM_OK) throw ChemError(plan.code, pair_refusal_text(plan));
-    const PairVariant& v = plan.v;
-    const bool inline_now = bonds_inline();
-    int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;      // (what the LAST rebuild did: both only change where a rebuild is forced)
-    if (bond_mode == 2 && dd_on) {      // slabs: the host knows which launch follows a rebuild (mode 3 = mode 2 + record the partner slots now)
+    return in;
+  }
+  // bond_mode of a pair launch over the tiles: 0 no inline bonds, 1 / 2 what the LAST rebuild did (both only change where a rebuild
+  // is forced), 3 = 2 + record the partner slots now -- on slabs the host knows which launch follows a rebuild, and takes the note back
+  int inline_bond_mode() {
+    int bond_mode = bonds_inline() ? (bond_by_pass() ? 2 : 1) : 0;
+    if (bond_mode == 2 && dd_on) {
       if (dd_record_bonds) bond_mode = 3;
       if (pair_subset != 1) dd_record_bonds = false;      // (a launch of the interior tiles alone is followed by the boundary launch of the same step)
     }
+    return bond_mode;
+  }
+
+  // the pair forces into fdst (ENERGY: and the energy words into eout); the kernel is chem_launch_host.hpp's choice
+  template <bool ENERGY> int launch_pair(V4* fdst) {
+    const double hs = half_skin_eff();
+    const PairPlan plan = pair_plan(pair_input(ENERGY));
+    if (plan.code != CHEM_OK) throw ChemError(plan.code, pair_refusal_text(plan));
+    const PairVariant& v = plan.v;
+    const int bond_mode = inline_bond_mode();
+    const bool inline_now = bond_mode != 0;
     const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
     if (use_tiles) {
       // which tiles: all (default), or the interior / boundary subset of a slab (see TileSub)
@@ -1684,13 +1704,6 @@ template <typename R> struct CtxT : Ctx {
     if (subset == 1) { pair_guard = 0; return; }   // interior tiles only: bonded terms follow with the boundary launch
     // the bonded term (chem_launch_host.hpp): nothing where the force kernel has evaluated the harmonic bonds (inline bonds)
     const BondedPlan bp = bonded_plan(BondedInput{nbent, nbent > 0 && bonds_inline(), excl_over, use_fused || dd_on, has_coul14, has_hybrid, bonds_only, nb_owner});
-    // the kernel of the plan's kind behind `launch`'s own arguments: hybrid lists add the lambda of every hybrid entry at the step
-    // these forces belong to, a 1-4 Coulomb list the charges by tag as well, read at every evaluation (and what `more` holds)
-    auto by_kind = [&](auto launch, auto plain, auto hyb, auto charged, const auto&... more) {
-      if (bp.kind == BondedKind::charged) launch(charged, hybrid_args(), (const R*)qtag.p, more...);
-      else if (bp.kind == BondedKind::hybrid) launch(hyb, hybrid_args());
-      else launch(plain);
-    };
     if (bp.launch == BondedLaunch::work_list) {
       // work-list kernel: owners only, partner indices resolved at the last rebuild
       if (bwork_dirty) {   // bonded lists changed without a rebuild since
@@ -1700,19 +1713,36 @@ template <typename R> struct CtxT : Ctx {
         bwork_dirty = false;
       }
       if (timed) tbeg(3);
-      auto work = [&](auto kern, const auto&... packs) {
-        hipLaunchKernelGGL(kern, dim3(cdiv(bp.nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, speculative ? 1 : 0, btab_view(), packs...);
-      };
-      if (bp.bonds_only) by_kind(work, &k_bonded_work<R, true>, &k_bonded_work_hyb<R, true>, &k_bonded_work_q<R, true>, (const int*)tag.p);
-      else by_kind(work, &k_bonded_work<R, false>, &k_bonded_work_hyb<R, false>, &k_bonded_work_q<R, false>, (const int*)tag.p);
+      if (bp.bonds_only) launch_bonded_work<true>(bp.kind, bp.nown, speculative ? 1 : 0);
+      else launch_bonded_work<false>(bp.kind, bp.nown, speculative ? 1 : 0);
       if (timed) tend();
     } else if (bp.launch == BondedLaunch::per_particle) {
-      auto each = [&](auto kern, const auto&... packs) {
-        hipLaunchKernelGGL(kern, dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, f4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, elist.p, ctl.p, btab_view(), packs...);
-      };
-      by_kind(each, &k_bonded<R, false>, &k_bonded_hyb<R, false>, &k_bonded_q<R, false>);
+      launch_bonded_each<false>(bp.kind, f4.p);
     }
     pair_guard = 0;
+  }
+  // The bonded kernel of a family (bonded_kind, chem_launch_host.hpp) behind `launch`'s own arguments: hybrid lists add the lambda
+  // of every hybrid entry at the step these forces belong to, a 1-4 Coulomb list the charges by tag as well, read at every
+  // evaluation (and what `more` holds).
+  template <class Launch, class K0, class K1, class K2, class... More>
+  void launch_bonded_kind(BondedKind kind, Launch launch, K0 plain, K1 hyb, K2 charged, const More&... more) {
+    if (kind == BondedKind::charged) launch(charged, hybrid_args(), (const R*)qtag.p, more...);
+    else if (kind == BondedKind::hybrid) launch(hyb, hybrid_args());
+    else launch(plain);
+  }
+  // every particle walks its own entries: forces added into fdst, ENERGY: and the lists' energies into elist (observe())
+  template <bool ENERGY> void launch_bonded_each(BondedKind kind, V4* fdst) {
+    auto each = [&](auto kern, const auto&... packs) {
+      hipLaunchKernelGGL(kern, dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, fdst, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, elist.p, ctl.p, btab_view(), packs...);
+    };
+    launch_bonded_kind(kind, each, &k_bonded<R, ENERGY>, &k_bonded_hyb<R, ENERGY>, &k_bonded_q<R, ENERGY>);
+  }
+  // the first `nown` owners of the work list, forces added into f4
+  template <bool BONDS_ONLY> void launch_bonded_work(BondedKind kind, int nown, int guard) {
+    auto work = [&](auto kern, const auto&... packs) {
+      hipLaunchKernelGGL(kern, dim3(cdiv(nown, 256)), dim3(256), 0, stream, x4.p, f4.p, bwork.p, bj.p, bent.p, bpar.p, boxd, ctl.p, guard, btab_view(), packs...);
+    };
+    launch_bonded_kind(kind, work, &k_bonded_work<R, BONDS_ONLY>, &k_bonded_work_hyb<R, BONDS_ONLY>, &k_bonded_work_q<R, BONDS_ONLY>, (const int*)tag.p);
   }
 
   LangevinP<R> lang_params(int64_t istep, int phase) const {
@@ -1862,12 +1892,7 @@ template <typename R> struct CtxT : Ctx {
     std::memset(out, 0, sizeof(*out));
     std::vector<double> hv(CHEM_MAX_LISTS, 0.0);
     if (nbent > 0 && n > 0) { launch_bonded_virial(); vlist.download(hv, CHEM_MAX_LISTS, stream); }
-    if (dd_on && P > 1) {
-      HIPCHK(hipMemcpyAsync(redbuf.p, hv.data(), sizeof(double) * CHEM_MAX_LISTS, hipMemcpyHostToDevice, stream));
-      tr->allreduce_sum_f64(redbuf.p, CHEM_MAX_LISTS, stream);
-      HIPCHK(hipMemcpyAsync(hv.data(), redbuf.p, sizeof(double) * CHEM_MAX_LISTS, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-    }
+    allreduce_host_sums(hv.data(), CHEM_MAX_LISTS, redbuf);
     out->volume = L[0] * L[1] * L[2]; out->mv2 = 2.0 * ob.ekin; out->virial_nb = ob.virial_nb;
     double w = ob.virial_nb;
     for (size_t l = 0; l < top.lists.size(); ++l) { out->virial_list[l] = hv[l]; w += hv[l]; }
@@ -1882,10 +1907,7 @@ template <typename R> struct CtxT : Ctx {
   // arguments are those of launch_pair<true>: fdst is scratch, the excluded pairs of inline bonds are taken out again.
   int launch_pair_tensor(V4* fdst, size_t off) {      // off: where the partials start in tpart
     const double hs = half_skin_eff();
-    PairInput in{use_tiles, n, opt_tpp, pair_bs, true, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
-    if (in.coul && in.res) first_res_pair(res_mask, in.res_a, in.res_b);
-    if (in.coul && in.cap) first_cap_pair(cap_rad, in.cap_a, in.cap_b);
-    const TensorPlan plan = tensor_plan(in);
+    const TensorPlan plan = tensor_plan(pair_input(true));
     if (plan.code != CHEM_OK) throw ChemError(plan.code, pair_refusal_text(plan.refused));
     const TensorVariant& v = plan.v;
     const int nblk = use_tiles ? ntiles : cdiv((long long)n * v.tpp, v.block);
@@ -1898,9 +1920,7 @@ template <typename R> struct CtxT : Ctx {
     const CapArgs<R> cp = (v.mode == 6 || v.mode == 7) ? cap_args() : CapArgs<R>{};
     bool found = false;
     if (use_tiles) {
-      const bool inline_now = bonds_inline();
-      int bond_mode = inline_now ? (bond_by_pass() ? 2 : 1) : 0;
-      if (bond_mode == 2 && dd_on && dd_record_bonds) { bond_mode = 3; dd_record_bonds = false; }      // (as launch_pair: the launch behind a slab rebuild records the partner slots)
+      const int bond_mode = inline_bond_mode();      // (pair_subset is 0 here: a launch behind a slab rebuild records the partner slots)
       const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
       const TileSub ts{0, ntiles, 0};
       const size_t lds = pair_lds_bytes();
@@ -1908,7 +1928,7 @@ template <typename R> struct CtxT : Ctx {
         auto kern = &k_pair_tiles_tensor<R, decltype(M_)::value>;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, stream, nblk, tile_cap, x4.p, fdst, tdesc.p, nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, ts,
-                           (v.mode == 3 && inline_now && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, brec, ca, ra, cp, tout);
+                           (v.mode == 3 && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, brec, ca, ra, cp, tout);
         return true;
       });
     } else {
@@ -1944,13 +1964,7 @@ template <typename R> struct CtxT : Ctx {
     for (int b = 0; b < nkb; ++b) for (int c = 0; c < 6; ++c) acc[c] += h[o_k + 6 * (size_t)b + c];
     for (int b = 0; b < nb; ++b) for (int c = 0; c < 6; ++c) acc[6 + c] += h[o_p + 6 * (size_t)b + c];
     for (int k = 0; k < 6 * CHEM_MAX_LISTS; ++k) acc[12 + k] = h[k];
-    if (dd_on && P > 1) {      // one all-reduce of the 6 + 6 + 6 * CHEM_MAX_LISTS sums
-      tredbuf.alloc(6 * kParts);
-      HIPCHK(hipMemcpyAsync(tredbuf.p, acc, sizeof(acc), hipMemcpyHostToDevice, stream));
-      tr->allreduce_sum_f64(tredbuf.p, 6 * kParts, stream);
-      HIPCHK(hipMemcpyAsync(acc, tredbuf.p, sizeof(acc), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-    }
+    allreduce_host_sums(acc, 6 * kParts, tredbuf);      // one all-reduce of the 6 + 6 + 6 * CHEM_MAX_LISTS sums
     out->volume = L[0] * L[1] * L[2];
     for (int c = 0; c < 6; ++c) {
       out->kinetic[c] = acc[c]; out->virial_nb[c] = acc[6 + c];
@@ -2909,15 +2923,7 @@ template <typename R> struct CtxT : Ctx {
     std::memset(out, 0, sizeof(*out));
     const int nb = launch_pair<true>(x4o.p);  // scratch force buffer: leaves f4 untouched
     HIPCHK(hipMemsetAsync(elist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream));
-    if (nbent > 0 && has_coul14)
-      hipLaunchKernelGGL((k_bonded_q<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
-    else if (nbent > 0 && has_hybrid)
-      hipLaunchKernelGGL((k_bonded_hyb<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view(), hybrid_args());
-    else if (nbent > 0)
-      hipLaunchKernelGGL((k_bonded<R, true>), dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, x4o.p, tag.p, rtag.p, bstart.p, bent.p,
-                         bpar.p, boxd, elist.p, ctl.p, btab_view());
+    if (nbent > 0) launch_bonded_each<true>(bonded_kind(has_coul14, has_hybrid), x4o.p);
     const int nkb = cdiv(n, 256);
     hipLaunchKernelGGL(k_kinetic<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, ekout.p);
     std::vector<double> he, hk, hl;
@@ -2930,12 +2936,7 @@ template <typename R> struct CtxT : Ctx {
     }
     for (int b = 0; b < nkb; ++b) { acc[3] += hk[4 * b]; acc[4] += hk[4 * b + 1]; acc[5] += hk[4 * b + 2]; acc[6] += hk[4 * b + 3]; }
     for (int l = 0; l < CHEM_MAX_LISTS; ++l) acc[8 + l] = hl[l];
-    if (dd_on && P > 1) {
-      HIPCHK(hipMemcpyAsync(redbuf.p, acc, sizeof(acc), hipMemcpyHostToDevice, stream));
-      tr->allreduce_sum_f64(redbuf.p, 9 + CHEM_MAX_LISTS, stream);
-      HIPCHK(hipMemcpyAsync(acc, redbuf.p, sizeof(acc), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-    }
+    allreduce_host_sums(acc, 9 + CHEM_MAX_LISTS, redbuf);
     out->step = step; out->npart = nglob; out->ekin = acc[3]; out->temperature = 2.0 * acc[3] / (3.0 * nglob);
     coul_epot = acc[7]; coul_virial = acc[8 + CHEM_MAX_LISTS];
     out->epot_lj = acc[0]; out->epot_tab = acc[1]; out->virial_nb = acc[2] + coul_virial;      // (sum over ALL non-bonded pairs)

@@ -166,6 +166,10 @@ struct HostPairPot {
 // Device-facing bonded parameter slot and CSR entry (mirrors md_kernels.hpp)
 struct HBondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };
 struct HBondedEntry { int t0, t1, t2, meta; };
+// the entry word: the parameter slot and which member of the tuple the entry's owner is (constexpr: host and device code alike)
+constexpr int bonded_meta(int slot, int member) { return slot | (member << 28); }
+constexpr int bonded_slot(int meta) { return meta & 0x0fffffff; }
+constexpr int bonded_member(int meta) { return (meta >> 28) & 3; }
 // birth step of a hybrid pair as it travels in the unused third tag: always negative, so that no reader takes it for a tag
 inline int32_t encode_birth(int64_t birth) { return ~(int32_t)birth; }
 
@@ -499,7 +503,7 @@ struct HostTopology {
         if (slot < 0) continue;
         for (int k = 0; k < l.arity; ++k) {
           int32_t& pos = fill[tt[k]];
-          bent[pos++] = HBondedEntry{tt[0], tt[1], l.arity > 2 ? tt[2] : (l.hybrid ? encode_birth(l.birth[e / 2]) : 0), slot | (k << 28)};
+          bent[pos++] = HBondedEntry{tt[0], tt[1], l.arity > 2 ? tt[2] : (l.hybrid ? encode_birth(l.birth[e / 2]) : 0), bonded_meta(slot, k)};
           if (l.arity == 4) bent[pos++] = HBondedEntry{tt[3], 0, 0, 0};
         }
       }

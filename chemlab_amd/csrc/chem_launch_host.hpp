@@ -155,6 +155,8 @@ inline void first_cap_pair(const double (*cap_rad)[CHEM_MAX_TYPES], int& a, int&
 // ---- bonded term behind the pair forces ----------------------------------------------------------------------------------------
 enum class BondedLaunch { none, work_list, per_particle };   // nothing / owners of the work list (k_bonded_work*) / every particle (k_bonded*)
 enum class BondedKind { plain, hybrid, charged };            // k_bonded(_work) / ..._hyb (lambda of hybrid entries) / ..._q (1-4 Coulomb list)
+// the family of a context: a 1-4 Coulomb list takes the charged kernels (which carry the lambda code along), else a hybrid list the hybrid ones
+constexpr BondedKind bonded_kind(bool has_coul14, bool has_hybrid) { return has_coul14 ? BondedKind::charged : has_hybrid ? BondedKind::hybrid : BondedKind::plain; }
 struct BondedInput {
   long long nbent;           // bonded entries
   bool inline_bonds;         // CtxT::bonds_inline(): the force kernel has evaluated the harmonic bonds
@@ -173,7 +175,7 @@ inline BondedPlan bonded_plan(const BondedInput& in) {
   BondedPlan p{BondedLaunch::none, BondedKind::plain, false, false, 0};
   if (in.nbent <= 0) return p;
   if (in.inline_bonds && in.excl_over == 0) return p;      // all of them were evaluated by the force kernel
-  p.kind = in.has_coul14 ? BondedKind::charged : in.has_hybrid ? BondedKind::hybrid : BondedKind::plain;
+  p.kind = bonded_kind(in.has_coul14, in.has_hybrid);
   if (!in.work_list) { p.launch = BondedLaunch::per_particle; return p; }
   p.launch = BondedLaunch::work_list;
   p.bonds_only = in.bonds_only;

@@ -124,7 +124,7 @@ __device__ __forceinline__ void publish_hint(IdleHint* hint, int gen, long long 
 
 // bonded tables (per-tag CSR, see K4-K6 below; declared here because the list build records the LDS slots of bonded partners)
 constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 16-byte quads)
-struct BondedEntry { int t0, t1, t2, meta; };   // tuple tags in order (self included); meta = slot | mypos<<28; quadruples use a 2nd entry for t3
+struct BondedEntry { int t0, t1, t2, meta; };   // tuple tags in order (self included); meta = bonded_meta(slot, mypos) (chem_host.hpp); quadruples use a 2nd entry for t3
                                                 // pairs: t2 = 0, or ~birth step (< 0) for an entry of a hybrid list (chem_list_set_hybrid)
 struct BondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };   // pad = 1: slot of a hybrid list, (lambda0, rate) in HybridArgs::par[slot]
 // Hybrid pair lists: what the HYB instantiations of the bonded kernels get beside the regular arguments.  lambda of an entry is a
@@ -3092,11 +3092,21 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
     if (ENERGY && me == 0) atomicAdd(&elist[bp.list], u);
 }
 
-template <typename R, bool ENERGY>
-__global__ __launch_bounds__(256) void k_bonded(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
-                                                const int* __restrict__ tag, const int* __restrict__ rtag,
-                                                const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
-                                                const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt) {
+// The entry points of the bonded forces.  Two launch shapes -- one thread per particle walking its rows of the per-tag CSR
+// (k_bonded*: the launch without a work list, and observe()), one thread per owner of the work list (k_bonded_work*: every
+// step) -- and one body each, bonded_particle_body and bonded_work_body, which hold the entry walk.  HYB compiles in the lambda
+// of a hybrid pair entry (hybrid_lambda: 1 for entries of lists that are not hybrid), COUL the two charges of a 1-4 Coulomb
+// entry (CHEM_POT_COULOMB_BOND; type R, the product is formed in fp64) and with them the matching code of bonded_term; `hy`,
+// `qtag` and the work list's `tag` are read under those flags only.  A context with both kinds of list runs the COUL family,
+// which carries the lambda code along, so there is no fourth.  The families stay separate kernels, chosen on the host
+// (bonded_kind, chem_launch_host.hpp), and not one kernel with flags: the plain kernels run every step of every workload
+// and keep the registers and the argument list they were measured with.
+template <typename R, bool ENERGY, bool HYB, bool COUL>
+__device__ __forceinline__ void bonded_particle_body(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                     const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                     const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                     const BondedParam* __restrict__ bpar, const BoxD& box, double* __restrict__ elist, DevCtl* ctl, const BTab& bt,
+                                                     [[maybe_unused]] const HybridArgs& hy, [[maybe_unused]] const R* __restrict__ qtag) {
   const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= i0 + n) return;
   const int tg = tag[i];
@@ -3105,77 +3115,50 @@ __global__ __launch_bounds__(256) void k_bonded(int i0, int n, const Vec4<R>* __
   D3 f = {0, 0, 0};
   for (int e = e0; e < e1; ++e) {
     const BondedEntry be = bent[e];
-    const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+    const int slot = bonded_slot(be.meta), me = bonded_member(be.meta);
     const BondedParam& bp = bpar[slot];
     const int ar = bp.arity;
     const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
     int j3 = 0;
     if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }   // quadruples occupy two consecutive entries: (t0,t1,t2,meta),(t3,-,-,-)
-    bonded_term<R, ENERGY>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt);
+    if constexpr (COUL) {
+      double q0 = 0, q1 = 0;
+      if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
+      bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
+    } else if constexpr (HYB) {
+      bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
+    } else {
+      bonded_term<R, ENERGY>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt);
+    }
   }
   Vec4<R> fo = f4[i];
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
   f4[i] = fo;
 }
-// The same with at least one hybrid list in the context (chosen on the host: CtxT::has_hybrid): a pair entry is scaled by its
-// lambda.  A kernel of its own, not a flag of k_bonded, so that k_bonded stays the code it was.
+template <typename R, bool ENERGY>
+__global__ __launch_bounds__(256) void k_bonded(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
+                                                const int* __restrict__ tag, const int* __restrict__ rtag,
+                                                const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
+                                                const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt) {
+  bonded_particle_body<R, ENERGY, false, false>(i0, n, x4, f4, tag, rtag, bstart, bent, bpar, box, elist, ctl, bt, HybridArgs{}, nullptr);
+}
+// at least one hybrid list in the context (CtxT::has_hybrid)
 template <typename R, bool ENERGY>
 __global__ __launch_bounds__(256) void k_bonded_hyb(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                     const int* __restrict__ tag, const int* __restrict__ rtag,
                                                     const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
                                                     const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt,
                                                     HybridArgs hy) {
-  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= i0 + n) return;
-  const int tg = tag[i];
-  const int e0 = bstart[tg], e1 = bstart[tg + 1];
-  if (e0 == e1) return;
-  D3 f = {0, 0, 0};
-  for (int e = e0; e < e1; ++e) {
-    const BondedEntry be = bent[e];
-    const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
-    const BondedParam& bp = bpar[slot];
-    const int ar = bp.arity;
-    const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
-    int j3 = 0;
-    if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }
-    bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
-  }
-  Vec4<R> fo = f4[i];
-  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
-  f4[i] = fo;
+  bonded_particle_body<R, ENERGY, true, false>(i0, n, x4, f4, tag, rtag, bstart, bent, bpar, box, elist, ctl, bt, hy, nullptr);
 }
-
-// The same with at least one 1-4 Coulomb list (CHEM_POT_COULOMB_BOND) in the context (chosen on the host: CtxT::has_coul14).  The
-// two members of a Coulomb entry read their charges by tag (qtag, type R; the product is formed in fp64); the lambda code is
-// carried along (1 for entries of lists that are not hybrid), so a context with both kinds of list needs no fourth family.
+// at least one 1-4 Coulomb list in the context (CtxT::has_coul14): the two members of a Coulomb entry read their charges by tag
 template <typename R, bool ENERGY>
 __global__ __launch_bounds__(256) void k_bonded_q(int i0, int n, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                   const int* __restrict__ tag, const int* __restrict__ rtag,
                                                   const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
                                                   const BondedParam* __restrict__ bpar, BoxD box, double* __restrict__ elist, DevCtl* ctl, BTab bt,
                                                   HybridArgs hy, const R* __restrict__ qtag) {
-  const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= i0 + n) return;
-  const int tg = tag[i];
-  const int e0 = bstart[tg], e1 = bstart[tg + 1];
-  if (e0 == e1) return;
-  D3 f = {0, 0, 0};
-  for (int e = e0; e < e1; ++e) {
-    const BondedEntry be = bent[e];
-    const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
-    const BondedParam& bp = bpar[slot];
-    const int ar = bp.arity;
-    const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
-    int j3 = 0;
-    if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }
-    double q0 = 0, q1 = 0;
-    if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
-    bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
-  }
-  Vec4<R> fo = f4[i];
-  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
-  f4[i] = fo;
+  bonded_particle_body<R, ENERGY, true, true>(i0, n, x4, f4, tag, rtag, bstart, bent, bpar, box, elist, ctl, bt, hy, qtag);
 }
 
 // exclusive scan over the block (BS threads, BS/64 <= 16 waves); returns the exclusive prefix of v,
@@ -3297,77 +3280,59 @@ __global__ __launch_bounds__(256) void k_bonded_prep(int i0, int n, const int* _
   dev_bonded_prep<256>(i0, n, tag, rtag, bstart, bent, bwork, bj, ctl, over_excl);
 }
 
-template <typename R, bool BONDS_ONLY = false>
-__global__ __launch_bounds__(256) void k_bonded_work(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
-                                                     const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt) {
+// one owner of the work list per thread (HYB, COUL: see bonded_particle_body).  jj.z of a hybrid pair is ~birth step, handed
+// on by the work-list build.  The records carry particle indices, so a charge is qtag[tag[j]] -- ghosts included, as in
+// CoulArgs -- and is read at every evaluation: nothing in a record can go stale when a charge changes between two list builds.
+template <typename R, bool BONDS_ONLY, bool HYB, bool COUL>
+__device__ __forceinline__ void bonded_work_body(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
+                                                 const BondedParam* __restrict__ bpar, const BoxD& box, DevCtl* ctl, int guard, const BTab& bt,
+                                                 [[maybe_unused]] const HybridArgs& hy, [[maybe_unused]] const R* __restrict__ qtag,
+                                                 [[maybe_unused]] const int* __restrict__ tag) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= (int)(ctl->bw64 & 0xffffffffull) || (guard && ctl->need_rebuild) || ctl->halt) return;
   const int4 wk = bwork[k];
   D3 f = {0, 0, 0};
   for (int e = wk.y; e < wk.y + wk.z; ++e) {
     const int4 jj = bj[e];
-    const int meta = jj.w;
-    const int slot = meta & 0x0fffffff, me = (meta >> 28) & 3;
+    const int slot = bonded_slot(jj.w), me = bonded_member(jj.w);
     const BondedParam& bp = bpar[slot];
     int j3 = 0;
     if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
-    bonded_term<R, false, BONDS_ONLY>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt);
+    const int j2 = (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0;
+    if constexpr (HYB || COUL) {
+      const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
+      if constexpr (COUL) {
+        double q0 = 0, q1 = 0;
+        if (bp.kind == CHEM_POT_COULOMB_BOND && (jj.x | jj.y) >= 0) { q0 = (double)qtag[tag[jj.x]]; q1 = (double)qtag[tag[jj.y]]; }   // (a missing partner: bonded_term reports it)
+        bonded_term<R, false, BONDS_ONLY, true, true>(bp, me, jj.x, jj.y, j2, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
+      } else {
+        bonded_term<R, false, BONDS_ONLY, true>(bp, me, jj.x, jj.y, j2, j3, x4, box, f, nullptr, ctl, bt, lam);
+      }
+    } else {
+      bonded_term<R, false, BONDS_ONLY>(bp, me, jj.x, jj.y, j2, j3, x4, box, f, nullptr, ctl, bt);
+    }
   }
   Vec4<R> fo = f4[wk.x];
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
   f4[wk.x] = fo;
 }
-// ... with at least one hybrid list in the context (see k_bonded_hyb): jj.z of a hybrid pair is ~birth step, handed on by the
-// work-list build
+// (`bent` is not read: the records of bj hold all of an entry.  It stays in the launch signature.)
+template <typename R, bool BONDS_ONLY = false>
+__global__ __launch_bounds__(256) void k_bonded_work(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
+                                                     const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt) {
+  bonded_work_body<R, BONDS_ONLY, false, false>(x4, f4, bwork, bj, bpar, box, ctl, guard, bt, HybridArgs{}, nullptr, nullptr);
+}
 template <typename R, bool BONDS_ONLY = false>
 __global__ __launch_bounds__(256) void k_bonded_work_hyb(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
                                                          const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt,
                                                          HybridArgs hy) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= (int)(ctl->bw64 & 0xffffffffull) || (guard && ctl->need_rebuild) || ctl->halt) return;
-  const int4 wk = bwork[k];
-  D3 f = {0, 0, 0};
-  for (int e = wk.y; e < wk.y + wk.z; ++e) {
-    const int4 jj = bj[e];
-    const int meta = jj.w;
-    const int slot = meta & 0x0fffffff, me = (meta >> 28) & 3;
-    const BondedParam& bp = bpar[slot];
-    int j3 = 0;
-    if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
-    const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
-    bonded_term<R, false, BONDS_ONLY, true>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt, lam);
-  }
-  Vec4<R> fo = f4[wk.x];
-  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
-  f4[wk.x] = fo;
+  bonded_work_body<R, BONDS_ONLY, true, false>(x4, f4, bwork, bj, bpar, box, ctl, guard, bt, hy, nullptr, nullptr);
 }
-
-// ... with at least one 1-4 Coulomb list in the context (see k_bonded_q).  The work-list records carry particle indices, so a
-// charge is qtag[tag[j]] -- ghosts included, as in CoulArgs -- and is read at every evaluation: nothing in a record can go stale
-// when a charge changes between two list builds.
 template <typename R, bool BONDS_ONLY = false>
 __global__ __launch_bounds__(256) void k_bonded_work_q(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
                                                        const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar, BoxD box, DevCtl* ctl, int guard, BTab bt,
                                                        HybridArgs hy, const R* __restrict__ qtag, const int* __restrict__ tag) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= (int)(ctl->bw64 & 0xffffffffull) || (guard && ctl->need_rebuild) || ctl->halt) return;
-  const int4 wk = bwork[k];
-  D3 f = {0, 0, 0};
-  for (int e = wk.y; e < wk.y + wk.z; ++e) {
-    const int4 jj = bj[e];
-    const int meta = jj.w;
-    const int slot = meta & 0x0fffffff, me = (meta >> 28) & 3;
-    const BondedParam& bp = bpar[slot];
-    int j3 = 0;
-    if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
-    const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
-    double q0 = 0, q1 = 0;
-    if (bp.kind == CHEM_POT_COULOMB_BOND && (jj.x | jj.y) >= 0) { q0 = (double)qtag[tag[jj.x]]; q1 = (double)qtag[tag[jj.y]]; }   // (a missing partner: bonded_term reports it)
-    bonded_term<R, false, BONDS_ONLY, true, true>(bp, me, jj.x, jj.y, (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0, j3, x4, box, f, nullptr, ctl, bt, lam, q0, q1);
-  }
-  Vec4<R> fo = f4[wk.x];
-  fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
-  f4[wk.x] = fo;
+  bonded_work_body<R, BONDS_ONLY, true, true>(x4, f4, bwork, bj, bpar, box, ctl, guard, bt, hy, qtag, tag);
 }
 
 // =======================================================================================
@@ -3826,7 +3791,7 @@ __global__ __launch_bounds__(256) void k_bonded_virial(int i0, int n, const Vec4
     const int e0 = bstart[tg], e1 = bstart[tg + 1];
     for (int e = e0; e < e1; ++e) {
       const BondedEntry be = bent[e];
-      const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+      const int slot = bonded_slot(be.meta), me = bonded_member(be.meta);
       const BondedParam& bp = bpar[slot];
       if (bp.arity == 4) ++e;      // (quadruples occupy two consecutive entries)
       if (bp.arity != 2 || me != 0) continue;
@@ -3954,7 +3919,7 @@ __global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, con
     const int e0 = bstart[tg], e1 = bstart[tg + 1];
     for (int e = e0; e < e1; ++e) {
       const BondedEntry be = bent[e];
-      const int slot = be.meta & 0x0fffffff, me = (be.meta >> 28) & 3;
+      const int slot = bonded_slot(be.meta), me = bonded_member(be.meta);
       const BondedParam& bp = bpar[slot];
       const int ar = bp.arity;
       int j3 = 0;
@@ -4707,7 +4672,7 @@ __global__ void k_bt_fill(int ne, const int4* __restrict__ fent, const int* __re
   const int tg[4] = {tt.x, tt.y, tt.z, tt.w};
   for (int q = 0; q < arity; ++q) {
     const int pos = start[tg[q]] + atomicAdd(&cursor[tg[q]], w);
-    bent[pos] = BondedEntry{tt.x, tt.y, (arity > 2 || keys[slot].pad) ? tt.z : 0, slot | (q << 28)};      // (pad: hybrid pair list, z = ~birth step)
+    bent[pos] = BondedEntry{tt.x, tt.y, (arity > 2 || keys[slot].pad) ? tt.z : 0, bonded_meta(slot, q)};      // (pad: hybrid pair list, z = ~birth step)
     bkey[pos] = 2 * e;
     if (arity == 4) { bent[pos + 1] = BondedEntry{tt.w, 0, 0, 0}; bkey[pos + 1] = 2 * e + 1; }
   }

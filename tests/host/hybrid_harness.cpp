@@ -59,7 +59,7 @@ int main() {
       std::vector<int32_t> bstart; std::vector<HBondedEntry> bent; std::vector<HBondedParam> bp;
       t.build_bonded(bstart, bent, bp);
       printf("entries %zu\n", bent.size());
-      for (auto& e : bent) printf("%d %d %d %d %d\n", e.t0, e.t1, e.t2, e.meta & 0x0fffffff, (e.meta >> 28) & 3);
+      for (auto& e : bent) printf("%d %d %d %d %d\n", e.t0, e.t1, e.t2, bonded_slot(e.meta), bonded_member(e.meta));
     }
   }
   return 0;

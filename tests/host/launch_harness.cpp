@@ -7,6 +7,7 @@
 //   respair m0 .. m15                                 "pair a b"   (first_res_pair of the 16 mask words)
 //   cappair k a1 b1 .. ak bk                          "pair a b"   (first_cap_pair with those entries capped, as given: not mirrored)
 //   bonded nbent inline excl_over work_list coul14 hybrid bonds_only nb_owner      "bonded <none|work|each> <plain|hybrid|charged> bonds_only inline nown"
+//   kind coul14 hybrid                                "kind <plain|hybrid|charged>"   (bonded_kind: the family rule on its own)
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -57,6 +58,10 @@ int main() {
       const BondedPlan p = bonded_plan(in);
       printf("bonded %s %s %d %d %d\n", p.launch == BondedLaunch::none ? "none" : p.launch == BondedLaunch::work_list ? "work" : "each",
              p.kind == BondedKind::plain ? "plain" : p.kind == BondedKind::hybrid ? "hybrid" : "charged", p.bonds_only ? 1 : 0, p.inline_bonds ? 1 : 0, p.nown);
+    } else if (cmd == "kind") {
+      const bool coul14 = rb(is), hybrid = rb(is);
+      const BondedKind k = bonded_kind(coul14, hybrid);
+      printf("kind %s\n", k == BondedKind::plain ? "plain" : k == BondedKind::hybrid ? "hybrid" : "charged");
     } else printf("error unknown command\n");
   }
   return 0;

@@ -40,7 +40,7 @@ int main() {
       for (int64_t i = 0; i < t.n; ++i) printf("%d %d\n", t.res_id[i], t.mol_id[i]);
       std::vector<int32_t> bs; std::vector<HBondedEntry> be; std::vector<HBondedParam> bp; t.build_bonded(bs, be, bp);
       printf("csr %zu %zu\n", be.size(), bp.size());
-      for (int64_t i = 0; i < t.n; ++i) { printf("%lld:", (long long)i); for (int e = bs[i]; e < bs[i + 1]; ++e) printf(" (%d %d %d s%d m%d)", be[e].t0, be[e].t1, be[e].t2, be[e].meta & 0x0fffffff, (be[e].meta >> 28) & 3); printf("\n"); }
+      for (int64_t i = 0; i < t.n; ++i) { printf("%lld:", (long long)i); for (int e = bs[i]; e < bs[i + 1]; ++e) printf(" (%d %d %d s%d m%d)", be[e].t0, be[e].t1, be[e].t2, bonded_slot(be[e].meta), bonded_member(be[e].meta)); printf("\n"); }
     }
   }
   return 0;

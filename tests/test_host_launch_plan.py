@@ -239,3 +239,10 @@ def test_bonded_plan_table(harness):
     out = H.run_harness(harness, ["bonded " + " ".join("%d" % v for v in inp) for inp, _ in BONDED])
     for (inp, want), w in zip(BONDED, out):
         assert (w[1], w[2], int(w[3]), int(w[4]), int(w[5])) == want, (inp, w)
+
+
+def test_bonded_family_rule(harness):
+    """bonded_kind on its own (CtxT::observe asks it without a plan): charged if a 1-4 Coulomb list exists, else hybrid."""
+    want = {(0, 0): "plain", (0, 1): "hybrid", (1, 0): "charged", (1, 1): "charged"}
+    out = H.run_harness(harness, ["kind %d %d" % k for k in want])
+    assert [(w[0], w[1]) for w in out] == [("kind", v) for v in want.values()]
