@@ -228,6 +228,9 @@ PRODUCT_ONLY = {
     # Langevin piston barostat and the read-back of either barostat's state
     "barostat_langevin": (_i, [_P, _d, _d, _d, _d, _u64]),
     "barostat_state_get": (_i, [_P, C.POINTER(BarostatState)]),
+    # checkpoint and exact restart (the CPU checker has none)
+    "checkpoint_save": (_i64, [_P, _P, _i64]),
+    "checkpoint_load": (_i, [_P, _P, _i64]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

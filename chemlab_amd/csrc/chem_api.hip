@@ -28,6 +28,7 @@
 #include "chem_react_host.hpp"
 #include "chem_res_host.hpp"
 #include "chem_fix_host.hpp"
+#include "chem_ckpt_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
 
@@ -119,6 +120,15 @@ struct Ctx {
   }
   HostTopology top;
   std::vector<double> pos0, vel0;  // staged particle data (tag order) until first upload
+  // Checkpoints (chem_checkpoint_save / chem_checkpoint_load; chem_ckpt_host.hpp).  img0: staged image counters of a restored
+  // state -- while it is not empty, pos0 holds the device's own coordinates, which the upload takes as they are (no fold, no
+  // count).  ckpt_pull: the device's particle data and chemical states into pos0 / vel0 / img0 and the mirrors; ckpt_reset: what
+  // the typed context derives from the host data is forgotten.  Between them save and load put the same host data in place and
+  // raise every dirty flag, so both contexts go on through one code path.
+  std::vector<int32_t> img0;
+  virtual void ckpt_pull() = 0;
+  virtual void ckpt_reset() = 0;
+  int64_t tm_base_rebuilds = 0, tm_base_list_rebuilds = 0;      // the device's counters start again with every upload of the particles
   int ntypes = 1;
   HostPairPot pp[CHEM_MAX_TYPES][CHEM_MAX_TYPES];
   // Truncated Coulomb term (chem_nb_coulomb): one (prefactor, rc) for every registered type pair, a symmetric type-pair bit mask
@@ -745,7 +755,9 @@ template <typename R> struct CtxT : Ctx {
     nglob = (int)top.n;
     n = nglob; G = 0; nglo = ngup = 0; cap = nglob;
     std::vector<V4> hx, hv; std::vector<int> ht; std::vector<int4> hi;
+    const bool raw = !img0.empty();      // a restored state: coordinates and image counters as the device held them
     if (dd_on) {
+      if (raw) throw ChemError(CHEM_ENOTIMPL, "a context that holds a restored checkpoint cannot be decomposed: a gap of the decomposed path");
       skin_list = pick_list_skin();   // (the slab bounds below must be those of the geometry set up afterwards)
       setup_box();   // slab bounds (z0, ncz, nzg)
       const SlabCaps sc = slab_capacities(nglob, nzg, ncz);
@@ -771,10 +783,13 @@ template <typename R> struct CtxT : Ctx {
       for (int t = 0; t < n; ++t) {
         if constexpr (kFixed) {   // folded on the host, images counted (the fp64 build leaves that to the first binning pass)
           for (int d = 0; d < 3; ++d) {
-            const double x = pos0[3 * t + d], xf = fold_coord(x, L[d]);
-            (&hx[t].x)[d] = enc_pos(xf, d); (&hi[t].x)[d] = (int)std::llrint((x - xf) / L[d]);
+            const double x = pos0[3 * t + d], xf = raw ? x : fold_coord(x, L[d]);
+            (&hx[t].x)[d] = enc_pos(xf, d); (&hi[t].x)[d] = raw ? img0[3 * t + d] : (int)std::llrint((x - xf) / L[d]);
           }
-        } else { hx[t].x = (R)pos0[3 * t]; hx[t].y = (R)pos0[3 * t + 1]; hx[t].z = (R)pos0[3 * t + 2]; }
+        } else {
+          hx[t].x = (R)pos0[3 * t]; hx[t].y = (R)pos0[3 * t + 1]; hx[t].z = (R)pos0[3 * t + 2];
+          if (raw) { hi[t].x = img0[3 * t]; hi[t].y = img0[3 * t + 1]; hi[t].z = img0[3 * t + 2]; }
+        }
         hx[t].w = (R)top.type[t];
         hv[t].x = (R)vel0[3 * t]; hv[t].y = (R)vel0[3 * t + 1]; hv[t].z = (R)vel0[3 * t + 2]; hv[t].w = (R)top.mass[t];
         ht[t] = t;
@@ -806,7 +821,7 @@ template <typename R> struct CtxT : Ctx {
       for (int k = 0; k < 4; ++k) { mig[k].alloc(mb); HIPCHK(hipMemsetAsync(mig[k].p, 0, mb, stream)); }
     }
     HIPCHK(hipStreamSynchronize(stream));
-    pos0.clear(); pos0.shrink_to_fit(); vel0.clear(); vel0.shrink_to_fit();
+    pos0.clear(); pos0.shrink_to_fit(); vel0.clear(); vel0.shrink_to_fit(); img0.clear(); img0.shrink_to_fit();
     particles_dirty = false; labels_dirty = true; geom_dirty = true; resort = true; device_ready = true;
   }
 
@@ -1089,6 +1104,35 @@ template <typename R> struct CtxT : Ctx {
     refresh_state_mirror();
     pos0 = std::move(p); vel0 = std::move(v);
     particles_dirty = true;
+  }
+  // Checkpoint: the particle data as the device holds it (coordinates not folded again, image counters beside them), so that
+  // the upload that follows puts back exactly these words; chemical states into the mirror (types, masses, charges and labels
+  // are current after join_async).  A context whose state is staged already (loaded or saved, not run since) has nothing to pull.
+  void ckpt_count_builds() { const DevCtl h = read_ctl(); tm_base_rebuilds += h.ref_rebuilds; tm_base_list_rebuilds += h.rebuild_count; }
+  void ckpt_pull() override {
+    if (particles_dirty && !img0.empty()) return;
+    flush_host_state();      // (a context that never ran: positions are folded and counted once, by the upload's own rule)
+    HIPCHK(hipStreamSynchronize(stream));
+    ckpt_count_builds();
+    std::vector<int> ht; std::vector<V4> hx, hv; std::vector<int4> hi;
+    tag.download(ht, (size_t)n, stream); x4.download(hx, (size_t)n, stream); v4.download(hv, (size_t)n, stream); img4.download(hi, (size_t)n, stream);
+    pos0.assign((size_t)3 * n, 0.0); vel0.assign((size_t)3 * n, 0.0); img0.assign((size_t)3 * n, 0);
+    for (int i = 0; i < n; ++i) {
+      const size_t t = (size_t)ht[i];
+      if (t >= (size_t)n) throw ChemError(CHEM_ESTATE, "internal: checkpoint found a tag outside the particle set");
+      pos0[3 * t] = dec_pos(hx[i].x, 0); pos0[3 * t + 1] = dec_pos(hx[i].y, 1); pos0[3 * t + 2] = dec_pos(hx[i].z, 2);
+      vel0[3 * t] = (double)hv[i].x; vel0[3 * t + 1] = (double)hv[i].y; vel0[3 * t + 2] = (double)hv[i].z;
+      img0[3 * t] = hi[i].x; img0[3 * t + 1] = hi[i].y; img0[3 * t + 2] = hi[i].z;
+    }
+    refresh_state_mirror(true);
+    particles_dirty = true;
+  }
+  void ckpt_reset() override {
+    if (stream) HIPCHK(hipStreamSynchronize(stream));
+    if (device_ready && !particles_dirty) ckpt_count_builds();      // (a load into a context that has run)
+    state_mirror_stale = false; baro_replan_pending = false; react_tables_reserved = false;
+    excl_deg.clear(); excl_deg_upto = 0; excl_over = 0;
+    brec_valid = false; box_dev_valid = false;
   }
 
   // ---- per-tag CSR tables built on the device from flat, append-only arrays (md_kernels.hpp "Per-tag CSR tables") ----
@@ -1730,12 +1774,27 @@ template <typename R> struct CtxT : Ctx {
     else if (kind == BondedKind::hybrid) launch(hyb, hybrid_args());
     else launch(plain);
   }
+  // Observables per list (energies, virials, virial tensors): the passes leave ncomp words per entry of bent in `lent`,
+  // k_list_sums adds them up per list in an order that depends on the entry table alone: the same bits for the same state.
+  DBuf<double> lent;
+  double* list_words(int ncomp) {
+    const size_t need = (size_t)ncomp * (size_t)std::max<int64_t>(nbent, 1);
+    if (lent.n < need) lent.alloc(need + need / 2);
+    HIPCHK(hipMemsetAsync(lent.p, 0, need * sizeof(double), stream));
+    return lent.p;
+  }
+  void launch_list_sums(int ncomp, const double* val, double* out) {
+    const int nl = (int)top.lists.size(), nt = nglob > 0 ? nglob : (int)top.n;
+    if (nl > 0) hipLaunchKernelGGL(k_list_sums, dim3(nl * ncomp), dim3(256), 0, stream, (const int*)(bstart.p + nt), ncomp, (const BondedEntry*)bent.p, (const BondedParam*)bpar.p, val, out);
+  }
   // every particle walks its own entries: forces added into fdst, ENERGY: and the lists' energies into elist (observe())
   template <bool ENERGY> void launch_bonded_each(BondedKind kind, V4* fdst) {
+    double* const words = ENERGY ? list_words(1) : elist.p;
     auto each = [&](auto kern, const auto&... packs) {
-      hipLaunchKernelGGL(kern, dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, fdst, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, elist.p, ctl.p, btab_view(), packs...);
+      hipLaunchKernelGGL(kern, dim3(cdiv(n, 256)), dim3(256), 0, stream, G, n, x4.p, fdst, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, words, ctl.p, btab_view(), packs...);
     };
     launch_bonded_kind(kind, each, &k_bonded<R, ENERGY>, &k_bonded_hyb<R, ENERGY>, &k_bonded_q<R, ENERGY>);
+    if (ENERGY) launch_list_sums(1, words, elist.p);
   }
   // the first `nown` owners of the work list, forces added into f4
   template <bool BONDS_ONLY> void launch_bonded_work(BondedKind kind, int nown, int guard) {
@@ -1777,8 +1836,8 @@ template <typename R> struct CtxT : Ctx {
               (g.stamp[3] - g.stamp[2]) * 0.01, (g.stamp[4] - g.stamp[3]) * 0.01, (g.stamp[5] - g.stamp[4]) * 0.01, (g.stamp[6] - g.stamp[5]) * 0.01);
     }
     if (dd_on) agree_flags(h);
-    tm.rebuilds = h.ref_rebuilds + (dd_on ? dd_direct_rebuilds : 0);   // the reference rule's count (== the list builds unless a wider list skin is in use)
-    tm.list_rebuilds = dd_on ? dd_rebuilds : h.rebuild_count;
+    tm.rebuilds = tm_base_rebuilds + h.ref_rebuilds + (dd_on ? dd_direct_rebuilds : 0);   // the reference rule's count (== the list builds unless a wider list skin is in use)
+    tm.list_rebuilds = dd_on ? dd_rebuilds : tm_base_list_rebuilds + h.rebuild_count;
     if (h.mig_error) throw ChemError(CHEM_ESTATE, "domain decomposition: particle migration error " + std::to_string(h.mig_error));
     if (h.bonded_missing) throw ChemError(CHEM_ESTATE, "domain decomposition: a bonded partner is farther than the ghost layer (rc+skin)");
     if (h.stage_overflow) throw ChemError(CHEM_ENOSPC, "cell stencil exceeded the LDS tile capacity (" + std::to_string(h.stage_overflow) + " particles)");
@@ -1882,8 +1941,10 @@ template <typename R> struct CtxT : Ctx {
     const int nbv = cdiv(n, 256);
     if (vpart.n < (size_t)nbv) vpart.alloc((size_t)nbv + 64);
     if (per_list) { vlist.alloc(CHEM_MAX_LISTS); HIPCHK(hipMemsetAsync(vlist.p, 0, sizeof(double) * CHEM_MAX_LISTS, stream)); }
-    hipLaunchKernelGGL((k_bonded_virial<R>), dim3(nbv), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, per_list ? vlist.p : (double*)nullptr, vpart.p,
+    double* const words = per_list ? list_words(1) : nullptr;
+    hipLaunchKernelGGL((k_bonded_virial<R>), dim3(nbv), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, words, vpart.p,
                        ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+    if (per_list) launch_list_sums(1, words, vlist.p);
     return nbv;
   }
   void pressure(chem_pressure* out) override {
@@ -1955,9 +2016,12 @@ template <typename R> struct CtxT : Ctx {
     tpart.alloc(o_p + 8);                                   // (launch_pair_tensor has sized it where there are pairs)
     HIPCHK(hipMemsetAsync(tpart.p, 0, sizeof(double) * 6 * CHEM_MAX_LISTS, stream));
     if (nkb > 0) hipLaunchKernelGGL(k_kinetic_tensor<R>, dim3(nkb), dim3(256), 0, stream, G, n, v4.p, tpart.p + o_k);
-    if (bonded)
-      hipLaunchKernelGGL((k_bonded_virial_tensor<R>), dim3(nkb), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, tpart.p,
+    if (bonded) {
+      double* const words = list_words(6);
+      hipLaunchKernelGGL((k_bonded_virial_tensor<R>), dim3(nkb), dim3(256), 0, stream, G, n, x4.p, tag.p, rtag.p, bstart.p, bent.p, bpar.p, boxd, words,
                          ctl.p, btab_view(), hybrid_args(), (const R*)qtag.p);
+      launch_list_sums(6, words, tpart.p);
+    }
     std::vector<double> h;
     tpart.download(h, o_p + 6 * (size_t)nb, stream);
     double acc[6 * kParts] = {0};                           // block partials folded in block order
@@ -3093,6 +3157,89 @@ struct chem_ctx { std::unique_ptr<Ctx> c; };
     catch (const std::exception& e) { (ctxp)->c->err = e.what(); return CHEM_EINVAL; }
 #define REQUIRE(cond, code, msg) do { if (!(cond)) throw ChemError((code), (msg)); } while (0)
 
+// ---- checkpoints: the host data of a context as a CkptState and back (format, reader and writer: chem_ckpt_host.hpp) ----
+static CkptFingerprint ckpt_fingerprint(const Ctx& c) {
+  CkptFingerprint fp;
+  for (const HostList& l : c.top.lists) fp.lists.push_back(CkptListKind{l.arity, l.kind, l.by_types, l.hybrid ? 1 : 0});
+  fp.n_reactions = (int32_t)c.reactions.size(); fp.n_dissociations = (int32_t)c.dissociations.size(); fp.n_fix_sets = (int32_t)c.fix.sets.size();
+  fp.atrp_on = c.atrp_on ? 1 : 0; fp.npart = c.top.n;
+  return fp;
+}
+static int ckpt_baro_kind(const Ctx& c) { return c.piston_on() ? 2 : (c.baro_tau > 0 ? 1 : 0); }
+// (the particle data is taken from the staging arrays: Ctx::ckpt_pull has filled them, or -- for the size alone -- zeros stand in)
+static CkptState ckpt_collect(const Ctx& c) {
+  const HostTopology& t = c.top;
+  const size_t n = (size_t)t.n;
+  CkptState s;
+  s.step = c.step; for (int d = 0; d < 3; ++d) s.L[d] = c.L[d];
+  s.react_on = c.react_on ? 1 : 0; s.ran = c.ran ? 1 : 0;
+  s.baro_kind = ckpt_baro_kind(c); s.baro_p_last = c.baro_p_last; s.pist_pe = c.pist_pe; s.pist_eps = c.pist_eps; s.pist_sv = c.pist_sv; s.pist_mu = c.pist_mu;
+  s.baro_charge = c.baro_charge; s.baro_charge_ref = c.baro_charge_ref;
+  s.id = t.id; s.type = t.type; s.state = t.state; s.res_id = t.res_id; s.mol_id = t.mol_id; s.mass = t.mass; s.q = t.q;
+  s.pos = c.pos0; s.vel = c.vel0; s.image = c.img0;
+  s.pos.resize(3 * n, 0.0); s.vel.resize(3 * n, 0.0); s.image.resize(3 * n, 0);
+  s.res_lambda0 = c.res.lambda0; s.res_s0 = c.res.s0; s.res_seen = c.res.seen;
+  s.lists.resize(t.lists.size());
+  for (size_t l = 0; l < t.lists.size(); ++l) { s.lists[l].ent = t.lists[l].ent; if (t.lists[l].hybrid) s.lists[l].birth = t.lists[l].birth; }
+  for (const auto& e : t.excl_log) { s.excl.push_back(e.first); s.excl.push_back(e.second); }
+  for (size_t a = 0; a < n; ++a) for (int32_t b : t.graph[a]) if ((size_t)b > a) { s.graph.push_back((int32_t)a); s.graph.push_back(b); }
+  s.fix_sets.resize(c.fix.sets.size());
+  for (size_t f = 0; f < c.fix.sets.size(); ++f) { s.fix_sets[f].next_seq = c.fix.sets[f].next_seq; s.fix_sets[f].ent = c.fix.sets[f].ent; }
+  s.fix_log = c.fix.log; s.fix_joins = c.fix.join_log;
+  for (const Ctx::RemovedRec& r : c.removed_log) s.removed.push_back(CkptRemoved{r.step, r.near, r.far, r.list, r.reaction});
+  s.ev_a = c.arena.a; s.ev_b = c.arena.b; s.ev_r = c.arena.r; s.ev_d2 = c.arena.d2; s.ev_intra = c.arena.intra;
+  for (const auto& b : c.arena.blocks) { s.ev_block_step.push_back(b.first); s.ev_block_first.push_back((uint64_t)b.second); }
+  if (c.atrp_on) { s.atrp_ratio_activator = c.atrp.ratio_activator; s.atrp_ratio_deactivator = c.atrp.ratio_deactivator; }
+  s.atrp_stats = c.atrp_stats;
+  return s;
+}
+// The state goes into the host data and every dirty flag is raised: particles, labels, tables, lists and forces are built again
+// from it at the next call that needs the device.  Both chem_checkpoint_load and chem_checkpoint_save end here.
+static void ckpt_apply(Ctx& c, CkptState&& s) {
+  HostTopology& t = c.top;
+  const size_t n = (size_t)t.n;
+  c.ckpt_reset();      // (first: it may still have to look at the device, and nothing has changed if it fails)
+  c.step = s.step; t.cur_step = s.step; for (int d = 0; d < 3; ++d) c.L[d] = s.L[d];
+  c.react_on = s.react_on != 0; c.ran = s.ran != 0;
+  c.baro_p_last = s.baro_p_last; c.pist_pe = s.pist_pe; c.pist_eps = s.pist_eps; c.pist_sv = s.pist_sv; c.pist_mu = s.pist_mu;
+  c.pist_pe_upload = c.pist_mu_upload = c.piston_on();      // (the device's words are written before they are read)
+  c.baro_keep = false; c.baro_charge = s.baro_charge; c.baro_charge_ref = s.baro_charge_ref; c.baro_seen_builds = c.baro_seen_ref = -1;
+  t.type = std::move(s.type); t.state = std::move(s.state); t.res_id = std::move(s.res_id); t.mol_id = std::move(s.mol_id); t.mass = std::move(s.mass); t.q = std::move(s.q);
+  c.pos0 = std::move(s.pos); c.vel0 = std::move(s.vel); c.img0 = std::move(s.image);
+  c.res.lambda0 = std::move(s.res_lambda0); c.res.s0 = std::move(s.res_s0); c.res.seen = std::move(s.res_seen);
+  for (size_t li = 0; li < t.lists.size(); ++li) {
+    HostList& l = t.lists[li];
+    l.ent = std::move(s.lists[li].ent); l.birth = std::move(s.lists[li].birth);
+    l.seen.clear();
+    for (size_t e = 0; e + l.arity <= l.ent.size(); e += l.arity) l.seen.insert(tuple_key(&l.ent[e], l.arity));
+  }
+  t.excl.assign(n, TagRow()); t.excl_log.clear(); t.n_excl_pairs = 0;
+  for (size_t e = 0; e + 1 < s.excl.size(); e += 2) {      // (the log as it was, a pair that entered it twice included; rows and count hold every pair once)
+    const int32_t a = s.excl[e], b = s.excl[e + 1];
+    t.excl_log.emplace_back(a, b);
+    if (HostTopology::sorted_insert(t.excl[a], b)) { HostTopology::sorted_insert(t.excl[b], a); ++t.n_excl_pairs; }
+  }
+  t.graph.assign(n, TagRow());
+  for (size_t e = 0; e + 1 < s.graph.size(); e += 2) t.graph_add(s.graph[e], s.graph[e + 1]);
+  c.fix.targets.clear(); c.fix.anchors.clear();
+  for (size_t f = 0; f < c.fix.sets.size(); ++f) {
+    FixSet& fs = c.fix.sets[f];
+    fs.next_seq = s.fix_sets[f].next_seq; fs.ent = std::move(s.fix_sets[f].ent);
+    for (const FixEntry& e : fs.ent) { c.fix.targets.insert(e.target); ++c.fix.anchors[e.anchor]; }
+  }
+  c.fix.log = std::move(s.fix_log); c.fix.join_log = std::move(s.fix_joins);
+  c.removed_log.clear();
+  for (const CkptRemoved& r : s.removed) c.removed_log.push_back(Ctx::RemovedRec{r.step, r.near, r.far, r.list, r.reaction});
+  c.arena.clear(); c.events.clear();
+  c.arena.a = std::move(s.ev_a); c.arena.b = std::move(s.ev_b); c.arena.r = std::move(s.ev_r); c.arena.d2 = std::move(s.ev_d2); c.arena.intra = std::move(s.ev_intra);
+  for (size_t b = 0; b < s.ev_block_step.size(); ++b) c.arena.blocks.emplace_back(s.ev_block_step[b], (size_t)s.ev_block_first[b]);
+  c.arena.mirror_pos = c.arena.size();      // (the mirrors above are those behind the last event)
+  if (c.atrp_on) { c.atrp.ratio_activator = s.atrp_ratio_activator; c.atrp.ratio_deactivator = s.atrp_ratio_deactivator; }
+  c.atrp_stats = std::move(s.atrp_stats);
+  c.particles_dirty = c.geom_dirty = c.pair_dirty = c.bonded_dirty = c.excl_dirty = c.labels_dirty = true; c.resort = true;
+  c.coul_dirty = c.res_dirty = c.fix_dirty = true;
+}
+
 extern "C" {
 
 int chem_abi_version(void) { return CHEM_ABI_VERSION; }
@@ -3176,7 +3323,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   c.particles_dirty = c.pair_dirty = c.bonded_dirty = c.excl_dirty = c.labels_dirty = true; c.resort = true;
   c.coul_dirty = true;
   c.res.clear(); c.res_dirty = true;      // (a new particle set: every lambda is 1 again; rates, marks and reaction rules stay)
-  c.step = 0; c.events.clear(); c.arena.clear();
+  c.step = 0; c.events.clear(); c.arena.clear(); c.img0.clear();
   // (fixed distances: entries and log go with the tags; sets, post-processes and release rules stay)
   for (FixSet& fs : c.fix.sets) { fs.ent.clear(); fs.next_seq = 0; }
   c.fix.targets.clear(); c.fix.anchors.clear(); c.fix.log.clear(); c.fix.join_log.clear(); c.removed_log.clear(); c.fix_dirty = true; c.ran = false;
@@ -3191,6 +3338,7 @@ int chem_add_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   REQUIRE(t.n > 0, CHEM_ESTATE, "add_particles: set particles first");
   REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "add_particles is not available on the decomposed path");
   REQUIRE(c.step == 0 && !c.ran, CHEM_ESTATE, "add_particles: only at step 0 and before the first chem_run");
+  REQUIRE(c.img0.empty(), CHEM_ESTATE, "add_particles: the context holds the staged state of a checkpoint (add the particles before chem_checkpoint_load)");
   REQUIRE(n > 0 && id && type && pos && mass, CHEM_EINVAL, "add_particles: null or empty input");
   REQUIRE(t.n + n < (1ll << 27), CHEM_EINVAL, "add_particles: too many particles for one context");
   std::vector<int64_t> order(n);
@@ -3923,6 +4071,45 @@ int chem_reaction_set_rate(chem_ctx* ctx, int r, double rate) {
   const int row = CTX.pub_map[r];
   if (row >= 0) CTX.reactions[row].rate = rate;
   else { REQUIRE(rate >= 0, CHEM_EINVAL, "diss_rate must not be negative"); CTX.dissociations[~row].diss_rate = rate; }
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_checkpoint_save(chem_ctx* ctx, void* buf, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "checkpoint_save on a decomposed context: a gap of the decomposed path (the state lives on several ranks)");
+  REQUIRE(c.top.n > 0, CHEM_ESTATE, "checkpoint_save: set particles first");
+  if (!buf) return (int64_t)ckpt_write(c.prec, ckpt_fingerprint(c), ckpt_collect(c)).size();      // (the size depends on counts alone: the device is not asked)
+  REQUIRE(cap >= 0, CHEM_EINVAL, "checkpoint_save: capacity");
+  {      // refused before anything is touched
+    const int64_t need = (int64_t)ckpt_write(c.prec, ckpt_fingerprint(c), ckpt_collect(c)).size();
+    REQUIRE(cap >= need, CHEM_ENOSPC, "checkpoint_save: capacity " + std::to_string(cap) + " is less than the " + std::to_string(need) + " bytes the blob needs");
+  }
+  c.ckpt_pull();
+  CkptState s = ckpt_collect(c);
+  const std::vector<uint8_t> blob = ckpt_write(c.prec, ckpt_fingerprint(c), s);
+  REQUIRE((int64_t)blob.size() <= cap, CHEM_ENOSPC, "checkpoint_save: capacity");
+  std::memcpy(buf, blob.data(), blob.size());
+  ckpt_apply(c, std::move(s));      // the context goes on from the blob's data, exactly as one that loads it
+  return (int64_t)blob.size();
+  API_END(ctx)
+}
+
+int chem_checkpoint_load(chem_ctx* ctx, const void* buf, int64_t nbytes) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "checkpoint_load on a decomposed context: a gap of the decomposed path (the state lives on several ranks)");
+  REQUIRE(c.top.n > 0, CHEM_ESTATE, "checkpoint_load: set the context up first, chem_set_particles with the ids of the saved one included");
+  REQUIRE(buf && nbytes >= 0, CHEM_EINVAL, "checkpoint_load: no blob");
+  CkptState s; std::string why;
+  const int rc = ckpt_read(buf, nbytes, c.prec, ckpt_fingerprint(c), s, why);
+  if (rc != 0) throw ChemError(rc, why);
+  for (size_t t = 0; t < s.id.size(); ++t)
+    REQUIRE(s.id[t] == c.top.id[t], CHEM_EINVAL, "checkpoint: the particle ids differ from the context's (tag " + std::to_string(t) + ": blob " + std::to_string(s.id[t]) + ", context " + std::to_string(c.top.id[t]) + ")");
+  REQUIRE(s.baro_kind == ckpt_baro_kind(c), CHEM_EINVAL, "checkpoint: the configuration differs from the one the blob was saved under: barostat kind (blob " + std::to_string(s.baro_kind) +
+                                                          ", context " + std::to_string(ckpt_baro_kind(c)) + ")");
+  ckpt_apply(c, std::move(s));
   return 0;
   API_END(ctx)
 }

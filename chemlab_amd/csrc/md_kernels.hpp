@@ -3089,7 +3089,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
       else g = (-1.0 - s32) * g4 + s12 * g1;
       f = f - dU * g;
     }
-    if (ENERGY && me == 0) atomicAdd(&elist[bp.list], u);
+    if (ENERGY && me == 0) *elist += u;      // (the caller's own word: the entry's energy, summed per list by k_list_sums)
 }
 
 // The entry points of the bonded forces.  Two launch shapes -- one thread per particle walking its rows of the per-tag CSR
@@ -3120,16 +3120,22 @@ __device__ __forceinline__ void bonded_particle_body(int i0, int n, const Vec4<R
     const int ar = bp.arity;
     const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
     int j3 = 0;
+    // ENERGY: elist holds one word per entry of bent; member 0 leaves the entry's energy there (no atomics: the sums per list
+    // are k_list_sums', in an order that depends on the entry table alone -- the same bits for the same state)
+    [[maybe_unused]] const int es = e;
+    [[maybe_unused]] double ue = 0.0;
+    double* const ep = ENERGY ? &ue : elist;
     if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }   // quadruples occupy two consecutive entries: (t0,t1,t2,meta),(t3,-,-,-)
     if constexpr (COUL) {
       double q0 = 0, q1 = 0;
       if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
-      bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
+      bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
     } else if constexpr (HYB) {
-      bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
+      bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
     } else {
-      bonded_term<R, ENERGY>(bp, me, j0, j1, j2, j3, x4, box, f, elist, ctl, bt);
+      bonded_term<R, ENERGY>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt);
     }
+    if constexpr (ENERGY) { if (me == 0) elist[es] = ue; }
   }
   Vec4<R> fo = f4[i];
   fo.x += (R)f.x; fo.y += (R)f.y; fo.z += (R)f.z;
@@ -3777,8 +3783,8 @@ __device__ __forceinline__ double baro_block_sum(const double* __restrict__ part
 // once (as the energy does), so the sum is right on slabs, where the partner may be a ghost.  The force law is bonded_term's
 // own (hybrid lambda and 1-4 Coulomb charges included: qtag is read for Coulomb entries only, hy.par for hybrid slots only).
 // Triples and quadruples depend on angles alone: their virial vanishes identically and is left at zero.
-// vlist[l] += the share of list l (atomics: an observable; nullptr: not wanted); part[block] = the block's sum over all lists, reduced in a fixed
-// order (what the barostat reads: the same bits for the same state).
+// vlist[e] = the share of entry e of bent (one word per entry, summed per list by k_list_sums; nullptr: not wanted); part[block] =
+// the block's sum over all lists, reduced in a fixed order (what the barostat reads).  Both: the same bits for the same state.
 template <typename R>
 __global__ __launch_bounds__(256) void k_bonded_virial(int i0, int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, const int* __restrict__ rtag,
                                                        const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
@@ -3803,7 +3809,7 @@ __global__ __launch_bounds__(256) void k_bonded_virial(int i0, int n, const Vec4
       bonded_term<R, false, false, true, true>(bp, 0, j0, j1, 0, 0, x4, box, f, nullptr, ctl, bt, hybrid_lambda(hy, bp, slot, be.t2), q0, q1);
       const D3 d = minimgD(box, posD<R>(x4[j0], box) - posD<R>(x4[j1], box));
       const double t = dot3(d, f);
-      if (vlist) atomicAdd(&vlist[bp.list], t);      // (the per-step launch of the barostat reads part[] alone)
+      if (vlist) vlist[e] = t;      // (the per-step launch of the barostat reads part[] alone)
       w += t;
     }
   }
@@ -3907,7 +3913,8 @@ __global__ __launch_bounds__(256) void k_kinetic_tensor(int i0, int n, const Vec
 // Bonded part: the walk of k_bonded_virial over every arity, the entry counted at member 0.  Pairs: d_ij (x) F_i.  Triples
 // (i, j, k), centre j: d_ij (x) F_i + d_kj (x) F_k.  Quadruples (i, j, k, l): d_ij (x) F_i + d_kj (x) F_k + (d_kj + d_lk) (x) F_l.
 // The forces are bonded_term's, one call per member, in its EXACT instantiation; the d are the minimum-image differences it forms.
-// vlist[6 * l + c] += the share of list l (atomics: an observable; nothing reads a sum over the lists, so no block partials).
+// vlist[6 * e + c] = the share of entry e of bent (six words per entry, summed per list by k_list_sums; nothing reads a sum over
+// the lists, so no block partials).
 template <typename R>
 __global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, const int* __restrict__ rtag,
                                                               const int* __restrict__ bstart, const BondedEntry* __restrict__ bent,
@@ -3923,6 +3930,7 @@ __global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, con
       const BondedParam& bp = bpar[slot];
       const int ar = bp.arity;
       int j3 = 0;
+      const int es = e;
       if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }      // (quadruples occupy two consecutive entries)
       if (me != 0) continue;
       const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
@@ -3949,9 +3957,25 @@ __global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, con
         }
       }
 #pragma unroll
-      for (int c = 0; c < 6; ++c) atomicAdd(&vlist[6 * bp.list + c], t[c]);
+      for (int c = 0; c < 6; ++c) vlist[6 * (size_t)es + c] = t[c];
     }
   }
+}
+// Sums per list of what the observable passes above left per entry: block (l, c) of nlists * ncomp adds val[ncomp * e + c] over
+// the entries e < *nent of list l -- strided over the block's threads, then folded in a fixed tree -- into out[ncomp * l + c].
+// The order depends on the entry table alone (not on atomics, not on where the particles sit), so a state gives the same bits
+// every time it is observed, in every context that holds it.  (The second entry of a quadruple carries no slot: it reads as
+// slot 0 and holds zero.)
+__global__ __launch_bounds__(256) void k_list_sums(const int* __restrict__ nent, int ncomp, const BondedEntry* __restrict__ bent, const BondedParam* __restrict__ bpar,
+                                                   const double* __restrict__ val, double* __restrict__ out) {
+  const int l = (int)blockIdx.x / ncomp, c = (int)blockIdx.x % ncomp, ne = *nent;
+  double s = 0;
+  for (int e = threadIdx.x; e < ne; e += 256) if (bpar[bonded_slot(bent[e].meta)].list == l) s += val[(size_t)ncomp * e + c];
+  __shared__ double red[4];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane_id() == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 // Non-bonded part, per-particle rows: the TENSOR instantiation of pair_force_body, four lanes per particle, both table kinds.
 // MODE 0 the plain kernel, 4 Coulomb, 5 resolution, 6 caps, 7 resolution and caps (chem_tensor_host.hpp tensor_plan); f4 is scratch.

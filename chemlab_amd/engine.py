@@ -4,6 +4,7 @@ One Engine == one `chem_ctx` == one GPU.  All arrays cross the boundary as plain
 pointers + sizes (numpy buffers); nothing here computes physics.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -233,7 +234,48 @@ class Engine:
     def supports(self, name):
         """Whether this engine's library exports the entry point `name` (without the prefix), e.g. 'reaction_join': the CPU
         checker lacks what only the product has."""
+        if name == "checkpoint":
+            name = "checkpoint_save"
         return getattr(self.api, name, None) is not None
+
+    # ---- checkpoint and exact restart (include/chem_mi355.h, chem_checkpoint_save / chem_checkpoint_load) ----
+    def _ckpt_entry(self, name):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("checkpoint: the CPU checker has no checkpoint")
+        return fn
+
+    def checkpoint_save(self, path=None):
+        """The state of the context as bytes; with `path` it is written there instead (to a temporary name beside it, then
+        renamed: a job that is killed while it writes leaves the last complete file) and the byte count is returned.  A set-up
+        repeated on a fresh engine followed by checkpoint_load goes on bit for bit; the call is a list-build point."""
+        fn = self._ckpt_entry("checkpoint_save")
+        need = self._ck(fn(self.ctx, None, 0))
+        buf = C.create_string_buffer(need)
+        got = self._ck(fn(self.ctx, C.cast(buf, C.c_void_p), need))
+        blob = buf.raw[:got]
+        if path is None:
+            return blob
+        path = os.fspath(path)
+        tmp = "%s.tmp.%d" % (path, os.getpid())
+        with open(tmp, "wb") as f:
+            f.write(blob)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+        return got
+
+    def checkpoint_load(self, path_or_bytes):
+        """Put back what checkpoint_save wrote (bytes, or the path of a file), after the set-up calls of the saved engine."""
+        fn = self._ckpt_entry("checkpoint_load")
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            blob = bytes(path_or_bytes)
+        else:
+            with open(os.fspath(path_or_bytes), "rb") as f:
+                blob = f.read()
+        buf = C.create_string_buffer(max(len(blob), 1))
+        C.memmove(buf, blob, len(blob))
+        self._ck(fn(self.ctx, C.cast(buf, C.c_void_p), len(blob)))
 
     # ---- reverse reactions (include/chem_mi355.h, chem_reaction_remove_bond / chem_reaction_join) ----
     def _reverse_entry(self, name, what):

@@ -827,6 +827,54 @@ int chem_reactions_enable(chem_ctx* ctx, int on);
 /* per-reaction rate update (Arrhenius hook, start_simulation.py:785-796); on an index of chem_dissociation_add: diss_rate */
 int chem_reaction_set_rate(chem_ctx* ctx, int reaction, double rate);
 
+/* ---- checkpoint and exact restart ------------------------------------------------------ */
+/* Stop a run and go on with it in another process (the reference's jobs are 5 M-step runs under wall limits of 24 to 72 h,
+ * examples/mf/espp_cg_1/params and the *.pbs files).  The reference has no such call: this rule set is
+ * this build's own (DESIGN.md "Checkpoint").
+ *
+ * A blob holds the STATE of a context, not its CONFIGURATION.
+ *   configuration  what the set-up calls define and no chem_run changes: box-independent lengths (cutoffs, skin), dt, pair
+ *                  potentials and tables, the list table (arity, kind, by types, hybrid) and every list's parameters and
+ *                  registered type tuples, thermostat and barostat parameters, reaction, dissociation, neighbour, removal, join,
+ *                  release and ATRP descriptors, restrictions and constraints, fix sets with their post-processes, resolution
+ *                  marks, caps and rates, options.  The caller repeats those calls on a fresh context -- chem_set_particles (and
+ *                  chem_add_particles) with the ids of the saved context included, whatever else it passes there -- and then loads.
+ *   state          everything chem_run changes: the step; the box; the barostat's state (what chem_barostat_state_get shows, and
+ *                  what the scalings since the last list build were charged to the lists); the particle table in id order (id,
+ *                  type, chemical state, res_id, mol_id, mass, charge, position, image counters, velocity), particles of
+ *                  chem_add_particles included; the resolution stamps; every list's entries in order, with the birth steps of a
+ *                  hybrid list; the exclusions; the bond graph of the topology manager; the entries of every fix set with
+ *                  chem_fix_log and chem_fix_joins; chem_reaction_removed; the event log (chem_get_events on the restored context
+ *                  returns the whole log); the ATRP statistics and catalyst ratios; chem_reactions_enable.
+ *   not state      rebuild and idle-launch diagnostics (the counters of chem_get_timers, chem_debug_*): they go on counting in the
+ *                  saving context and start at zero in the loading one.
+ * The contract.  Context A has run; blob = chem_checkpoint_save(A).  Context B is set up like A and calls chem_checkpoint_load(B,
+ * blob).  From then on A and B are indistinguishable: every chem_get_* / chem_*_get / chem_observe value is equal, floating-point
+ * values bit for bit, at once and after any further chem_run(b), in both precisions and on every list path (tiles, per-cell
+ * lists, brute force).  This is how it is kept: save pulls the device's particle data into the host's staging arrays (coordinates
+ * as the device holds them, image counters beside them), writes the blob from the host data, and then leaves A exactly as load
+ * leaves B -- the same routine puts the blob's data in place and raises every dirty flag, so that particles, tables and lists are
+ * uploaded and built again and the forces are evaluated anew at the next call that needs them.  So
+ *   - chem_checkpoint_save is a list-build point: a run that saved differs in the last bits (the summation order of the forces
+ *     follows the particle order of the list build) from one that never did; the time of a step is not touched;
+ *   - chem_get_state(CHEM_STATE_FORCE) between a save (or load) and the next chem_run shows zeros, as after chem_set_particles;
+ *   - two saves with nothing run between them, and a save right after a load, give the loaded bytes again.
+ * chem_checkpoint_save(ctx, NULL, 0) returns the bytes needed and touches nothing; with a buffer it returns the bytes written,
+ * CHEM_ENOSPC (nothing touched) if cap is smaller.  The blob: magic, format version, precision, then sections that each carry
+ * their length -- the first is a fingerprint of the configuration: the CHEM_MAX_* values, the list table (arity, kind, by_types,
+ * hybrid per handle), the lengths of the reaction and dissociation tables, the fix-set count, whether ATRP is on, the particle
+ * count -- and a checksum at the end (chem_ckpt_host.hpp).  chem_checkpoint_load validates the whole blob before it changes
+ * anything; a refused load leaves the context as it was.
+ *   CHEM_ENOTIMPL  save or load on a decomposed context (after chem_comm_init*): a gap of the decomposed path, like the barostats;
+ *                  decomposing a context that holds a loaded state is refused at its next upload likewise.
+ *   CHEM_EINVAL    precision or fingerprint mismatch, naming the first field that differs; other particle ids; another barostat
+ *                  kind; a short, truncated or corrupt blob or an unknown format version (never a read past nbytes).
+ *   CHEM_ESTATE    chem_checkpoint_save or _load before chem_set_particles; chem_add_particles on a context that holds a staged
+ *                  state (add before loading).
+ * Out of scope: blobs across precisions or format versions, saving the configuration, the driver's loop counter. */
+int64_t chem_checkpoint_save(chem_ctx* ctx, void* buf, int64_t cap);
+int     chem_checkpoint_load(chem_ctx* ctx, const void* buf, int64_t nbytes);
+
 /* ---- the hot call -------------------------------------------------------------------- */
 /* integrator.run(n)  start_simulation.py:780.  No host round trip per step. */
 int chem_run(chem_ctx* ctx, int64_t nsteps);
