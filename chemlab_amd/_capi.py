@@ -19,6 +19,7 @@ CHEM_MAX_LISTS = 32
 CHEM_MAX_TYPES = 16
 CHEM_MAX_POT_PARAMS = 6
 CHEM_MAX_FIX_SETS = 8
+CHEM_MAX_REGIONS = 16
 
 # error codes
 OK, EINVAL, ENOSPC, EDEVICE, ESTATE, ENOTIMPL, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -96,6 +97,21 @@ class NbRemove(C.Structure):
 
 class BondRecord(C.Structure):
     _fields_ = [("step", C.c_int64), ("id_near", C.c_int64), ("id_far", C.c_int64), ("list", C.c_int32), ("reaction", C.c_int32)]
+
+
+class RegionDesc(C.Structure):
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("target_type", C.c_int32), ("new_type", C.c_int32),
+                ("new_mass", C.c_double), ("new_q", C.c_double), ("interval", C.c_int32), ("mode", C.c_int32),
+                ("value", C.c_double), ("num", C.c_int32), ("reset_velocity", C.c_int32), ("reset_force", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class RegionChange(C.Structure):
+    _fields_ = [("step", C.c_int64), ("id", C.c_int64), ("rule", C.c_int32), ("pad", C.c_int32)]
+
+
+class RegionStats(C.Structure):
+    _fields_ = [("step", C.c_int64), ("rule", C.c_int64), ("candidates", C.c_int64), ("changed", C.c_int64)]
 
 
 class Obs(C.Structure):
@@ -228,6 +244,12 @@ PRODUCT_ONLY = {
     # Langevin piston barostat and the read-back of either barostat's state
     "barostat_langevin": (_i, [_P, _d, _d, _d, _d, _u64]),
     "barostat_state_get": (_i, [_P, C.POINTER(BarostatState)]),
+    # region rules: FreezeRegion, ChangeParticleType (the CPU checker has none)
+    "region_add": (_i, [_P, C.POINTER(RegionDesc)]),
+    "region_enable": (_i, [_P, _i, _i]),
+    "region_get_changes": (_i64, [_P, C.POINTER(RegionChange), _i64]),
+    "region_get_stats": (_i64, [_P, C.POINTER(RegionStats), _i64]),
+    "region_counters": (_i, [_P, _pi64, _pi64]),
     # checkpoint and exact restart (the CPU checker has none)
     "checkpoint_save": (_i64, [_P, _P, _i64]),
     "checkpoint_load": (_i, [_P, _P, _i64]),

@@ -135,6 +135,11 @@ class SetupReactions(object):
             if not self.system.engine.supports("reaction_join" if cfg["ext_type"] == "JoinMolecule" else "reaction_remove_bond"):
                 raise NotImplementedError("reaction extension %s (%s): the CPU checker has no reverse reactions" % (name, cfg["ext_type"]))
             return self._setup_join_molecule(cfg) if cfg["ext_type"] == "JoinMolecule" else self._setup_remove_neighbour_bonds(cfg)
+        if cfg.get("ext_type") in ("FreezeRegion", "ChangeParticleType"):
+            # asked first, as for JoinMolecule: the CPU checker has no region rules, whatever keys the section holds
+            if not self.system.engine.supports("region"):
+                raise NotImplementedError("reaction extension %s (%s): the CPU checker has no region rules" % (name, cfg["ext_type"]))
+            return self._setup_freeze_region(cfg) if cfg["ext_type"] == "FreezeRegion" else (self._setup_change_particle_type(cfg), None)
         if cfg.get("ext_type") != "ChangeNeighboursProperty":
             raise NotImplementedError("reaction extension %s (%s) is outside the hot-path scope (SURVEY f-4)" % (name, cfg.get("ext_type")))
         e, n2t = self.espp, self.name2type
@@ -258,6 +263,63 @@ class SetupReactions(object):
         self.dynamic_types.update((host_type_id, target_type_id, final_type_id, dummy_type_id))
         self.use_thermal_group = True        # the dummies must not be thermalised
         return [(join_pp, "type_1"), (dummy_pp, "type_2")]
+
+    def _setup_freeze_region(self, cfg):
+        """[ext_*] ext_type=FreezeRegion (reaction_post_process.py:139-201): slabs of `width` at the box faces named in
+        `directions` (default all six; `width_type=ratio`: width times the box edge) act as sinks -- a particle of `target_type`
+        inside one becomes the new type FREEZE_<id> (the next free type id: no potential, no thermal group), with velocity and
+        stored force set to zero.  `prob` / `p_num` / `p_percentage` select among the candidates of a step.  One ChangeInRegion
+        per direction, ALL of them returned as integrator extensions (the reference builds them all and returns the last)."""
+        from .. import _capi
+        e, topol = self.espp, self.topol
+        faces = ("-x", "x", "-y", "y", "-z", "z")
+        directions = [d.strip() for d in cfg.get("directions", ",".join(faces)).split(",")]
+        for d in directions:
+            if d not in faces:
+                raise RuntimeError("FreezeRegion: unknown direction %s, only %s" % (d, ",".join(faces)))
+        target_type_id = topol.atomsym_atomtype[cfg["target_type"]]
+        out_prefix = getattr(self.args, "output_prefix", "sim") if self.args is not None else "sim"
+        seed = getattr(self.args, "rng_seed", 0) if self.args is not None else 0
+        stats_file = cfg.get("stats_file") or "%s_%s_freeze_stats.dat" % (out_prefix, seed)
+        if str(cfg.get("remove_particles", "False")).strip() not in ("False", "false", "0", ""):
+            raise NotImplementedError("FreezeRegion remove_particles: the engine cannot remove particles")
+        prob = float(cfg["prob"]) if cfg.get("prob") else None
+        p_num = int(cfg["p_num"]) if cfg.get("p_num") else None
+        p_percentage = float(cfg["p_percentage"]) if cfg.get("p_percentage") else None
+        if p_percentage is not None and not (0.0 <= p_percentage <= 1.0):
+            raise RuntimeError("p_percentage not in the range (0.0, 1.0)")
+        final_type_id = max(topol.atomsym_atomtype.values()) + 1
+        if final_type_id >= _capi.CHEM_MAX_TYPES:
+            raise RuntimeError("FreezeRegion: the frozen type would get id %d, the engine holds %d types (CHEM_MAX_TYPES)" % (final_type_id, _capi.CHEM_MAX_TYPES))
+        topol.add_new_atomtype(final_type_id, "FREEZE_%d" % final_type_id, False)
+        box = [float(b) for b in self.system.bc.boxL]
+        w = float(cfg["width"])
+        width = [w * b for b in box] if cfg.get("width_type", "static") == "ratio" else [w] * 3
+        made = []
+        for d in directions:
+            axis, upper = "xyz".index(d[-1]), not d.startswith("-")
+            lo, hi = [0.0, 0.0, 0.0], list(box)
+            if upper:
+                lo[axis] = box[axis] - width[axis]
+            else:
+                hi[axis] = width[axis]
+            region = e.ParticleRegion(self.system.storage, self.system.integrator, e.Real3D(*lo), e.Real3D(*hi))
+            region.add_type_id(target_type_id)
+            cir = e.integrator.ChangeInRegion(self.system, region, prob=prob, p_num=p_num, p_num_percentage=p_percentage)
+            cir.set_particle_properties(target_type_id, e.integrator.TopologyParticleProperties(type=final_type_id))
+            cir.set_flags(target_type_id, reset_velocity=True, reset_force=True, remove_particle=False)
+            cir.stats_filename = stats_file
+            made.append((cir, None))
+        self.dynamic_types.update((target_type_id, final_type_id))
+        # (thermal groups are not switched on here, as in the reference: whether the thermostat moves the frozen type is the
+        #  run's own choice -- a ReleaseMolecule extension next to this one switches them on, and FREEZE_<id> is in no group)
+        return made
+
+    def _setup_change_particle_type(self, cfg):
+        """[ext_*] ext_type=ChangeParticleType (reaction_post_process.py:364-378): every `interval` steps `num_particles` random
+        particles of type id `type_id` become `new_type_id`."""
+        self.dynamic_types.update((int(cfg["type_id"]), int(cfg["new_type_id"])))
+        return self.espp.integrator.ChangeParticleType(self.system, int(cfg["interval"]), int(cfg["num_particles"]), int(cfg["type_id"]), int(cfg["new_type_id"]))
 
     def _setup_atrp_activator(self, cfg):
         """[ext_*] ext_type=ATRPActivator -> integrator extension (reaction_post_process.py:380-426):

@@ -28,6 +28,7 @@
 #include "chem_react_host.hpp"
 #include "chem_res_host.hpp"
 #include "chem_fix_host.hpp"
+#include "chem_region_host.hpp"
 #include "chem_ckpt_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
@@ -189,6 +190,15 @@ struct Ctx {
   std::vector<NbCons> constraints;   // ReactionConstraintNeighbourState (chem_reaction_constraint)
   // integrator.ATRPActivator (chem_atrp_init; reaction_post_process.py:380-426)
   bool atrp_on = false; chem_atrp_desc atrp{}; std::vector<AtrpCenter> atrp_centers; std::vector<chem_atrp_stats> atrp_stats;
+  // Region rules (chem_region_add; chem_region_host.hpp): descriptors and switches live on the host and travel to the scan
+  // kernel by value; the logs hold tags.  region_keep: a rule changed something at the step the last run ended on -- the stored
+  // forces (resets included) are the ones the next run starts from, and the list build it asked for comes behind the next drift,
+  // as in an uninterrupted run -- unless something has touched the system or re-sorted the particles since.
+  std::vector<chem_region_desc> regions; std::vector<uint8_t> region_enabled;
+  std::vector<RegionChange> region_log; std::vector<RegionStat> region_stats;
+  int64_t region_firings = 0, region_syncs = 0, region_counted = 0; bool region_keep = false;
+  bool region_any() const { for (uint8_t e : region_enabled) if (e) return true; return false; }
+  bool region_due_at(int64_t s) const { for (size_t k = 0; k < regions.size(); ++k) if (region_due(regions[k], region_enabled[k] != 0, s)) return true; return false; }
   std::vector<chem_event> events;   // expanded, canonical order (filled lazily from the arena by chem_get_events)
   // event arena: SoA copy of the device records of every reaction step, appended in device order (amortised growth:
   // fresh vectors per step cost their page faults every time -- 4 ms for 2.8e5 events); blocks = (step, first index).
@@ -860,6 +870,7 @@ template <typename R> struct CtxT : Ctx {
     for (auto& r : dissociations) { nt = std::max(nt, std::max(r.new_type_1, r.new_type_2) + 1); }
     for (auto& r : nb_rules) nt = std::max(nt, r.new_type + 1);
     for (auto& c : atrp_centers) nt = std::max(nt, std::max(c.type, c.new_type) + 1);
+    for (auto& r : regions) nt = std::max(nt, std::max(r.target_type, r.new_type) + 1);
     for (int a = 0; a < CHEM_MAX_TYPES; ++a) if (coul_mask[a]) nt = std::max(nt, a + 1);
     for (const ResRate& r : res.rate) if (r.alpha > 0.0) nt = std::max(nt, r.new_type + 1);
     for (const FixSet& fs : fix.sets) for (const FixPost& fp : fs.post) nt = std::max(nt, fp.new_type + 1);
@@ -1567,6 +1578,7 @@ template <typename R> struct CtxT : Ctx {
     const double t0 = now_s();
     hint_invalidate();
     baro_keep = false;      // (a list build re-sorts the particles, not f4)
+    region_keep = false;
     bool counted = resumed && halt_kind == 3;
     for (int attempt = 0; attempt < 6; ++attempt) {
       if (dd_on) {      // (a slab rebuild the host calls for, not one of the device's decisions: counted on the host)
@@ -2165,6 +2177,10 @@ template <typename R> struct CtxT : Ctx {
     // provided nothing has touched the system or re-sorted the particles since
     const bool keep_forces = baro_on() && baro_keep && !(particles_dirty || (geom_dirty && !baro_replan_pending) || labels_dirty || pair_dirty || coul_dirty || res_dirty || cap_dirty || fix_dirty || bonded_dirty || excl_dirty);
     baro_keep = false;
+    // region rules: likewise behind a change at the last run's final step (the force list is then built behind the first drift)
+    const bool dirty_any = particles_dirty || geom_dirty || labels_dirty || pair_dirty || coul_dirty || res_dirty || cap_dirty || fix_dirty || bonded_dirty || excl_dirty;
+    const bool keep_region = region_keep && !baro_on() && !dd_on && !dirty_any && device_ready;
+    region_keep = false;
     flush_host_state();
     hint_invalidate();      // (whatever the last call's launches published: the first step of a call gets its neighbour launch)
     const double t0 = now_s();
@@ -2190,13 +2206,15 @@ template <typename R> struct CtxT : Ctx {
     }
     if (react_on && !reactions.empty()) reserve_reaction_tables();
     force_step_off = 0;
-    if (!keep_forces) {
+    if (!keep_forces && !keep_region) {
       if (resort) rebuild_now();
       compute_forces();
       if (lang) launch_integrate<0>(true, true, step, 0);  // thermalize: f += friction + noise, stored
     }
     bool need_int1 = true;
     const int64_t step0 = step;
+    bool run_cut = false;      // region rules next to tracked stamps: the call ends behind a firing that changed something
+    const bool regions_on = region_any() && !dd_on;
     bool resume = false;       // re-entering the step at which the device stopped the run (DevCtl::halt)
     // The device may stop an asynchronous run (fused rebuild: a cell outgrew its bucket row).  Every launch behind that
     // point has left at once; the host learns of it at its next synchronisation -- a reaction / ATRP step or the end of
@@ -2210,6 +2228,16 @@ template <typename R> struct CtxT : Ctx {
       if (!h.halt) return false;
       s = h.halt_step - step0; step = h.halt_step;
       set_ctl_field(&DevCtl::halt, 0);
+      if (h.halt == 4) {
+        // a region rule stopped the run behind step halt_step: that step is complete, its forces are stored, nothing of the
+        // next one has happened (the launches enqueued behind the stop left at once).  Apply the change and go on from there.
+        need_int1 = true; fused_par = h.halt_par & 1;
+        skip_log_stop(h.halt_step);
+        ++region_syncs;
+        region_apply();
+        if (res_tracking()) run_cut = true;      // (a stamp set here may create a completion step: the piece ends, chem_run asks afresh)
+        return true;
+      }
       resort = true; resume = true; need_int1 = false;
       resume_kind = h.halt; resume_par = fused_par = h.halt_par & 1;      // (the launches enqueued behind the stop flipped the host's parity and left at once)
       skip_log_stop(h.halt_step);
@@ -2218,9 +2246,9 @@ template <typename R> struct CtxT : Ctx {
       if (g_trace) fprintf(stderr, "[chem trace] run stopped by the device at step %lld (bucket rows of %d, tile capacity %d, list rows of %d): recovering\n", (long long)h.halt_step, bcap, tile_cap, S);
       return true;
     };
-    for (int64_t s = 0; s < nsteps; ++s) {
+    for (int64_t s = 0; s < nsteps && !run_cut; ++s) {
       // (a stop the device has already told the pinned words about need not wait for the next synchronisation)
-      if (!resume && hflag && skip_applies() && const_cast<const volatile IdleHint*>(hint_host())->halted == hint_gen && halted(s)) { --s; continue; }
+      if (!resume && hflag && (skip_applies() || regions_on) && const_cast<const volatile IdleHint*>(hint_host())->halted == hint_gen && halted(s)) { --s; continue; }
       if (need_int1) {
         launch_integrate<2>(false, false, step, 1);
         // Langevin piston: the box and the drifted positions take the step's mu (computed at the last kick) in front of the
@@ -2235,6 +2263,7 @@ template <typename R> struct CtxT : Ctx {
       if (timed_step) timed_extra = 1 + (int)((pair_launch_no / opt_time_pair) % 3);
       const bool react_due = react_on && interval > 0 && ((step + 1) % interval == 0);
       const bool atrp_due = atrp_on && ((step + 1) % atrp.interval == 0);
+      const bool reg_due = regions_on && region_due_at(step + 1);      // (the two half kicks apart: the rule sees x(s), v(s) complete)
       const bool last = (s == nsteps - 1);
       force_step_off = 1;      // (hybrid lists: these are the forces of step + 1, whose counter moves behind the integration)
       if (resume) { resume = false; skip_log_add(false); rebuild_now(true, resume_kind, resume_par); compute_forces(); }   // (positions are drifted, forces of this step were never evaluated)
@@ -2253,7 +2282,7 @@ template <typename R> struct CtxT : Ctx {
       force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
 
-      if (last || react_due || atrp_due || !opt_fuse || resc_kind || baro_on()) {
+      if (last || react_due || atrp_due || reg_due || !opt_fuse || resc_kind || baro_on()) {
         launch_integrate<1>(lang, lang, step, 1);
         ++step;
         if (resc_kind == 1 || resc_kind == 3 || (resc_kind == 2 && step % (int64_t)resc_param == 0)) rescale_velocities();
@@ -2267,6 +2296,7 @@ template <typename R> struct CtxT : Ctx {
         if (atrp_due) atrp_step();      // behind the reaction step: the driver adds the extension after `ar` (start_simulation.py:737-740)
         if ((react_due || atrp_due) && res_tracking()) res_after_reactions();
         if ((react_due || atrp_due) && fix_tracking()) fix_after_reactions(react_due);
+        if (reg_due && region_step(last) && res_tracking()) run_cut = true;      // behind everything else of the step
         need_int1 = true;
       } else {
         tbeg(2);
@@ -2280,7 +2310,8 @@ template <typename R> struct CtxT : Ctx {
     check_flags();
     baro_keep = baro_on();
     tm.run_wall_s += now_s() - t0;
-    tm.steps += nsteps;
+    tm.steps += step - step0;
+    if (nsteps == 0 && keep_region) region_keep = true;      // (nothing ran: the stored forces are still the ones to go on with)
     if (opt_time_pair && !ev_used && timed_idle_skips) { tm.decide_kernel_ms = 0; tm.decide_kernel_launches = timed_idle_skips; }
     if (opt_time_pair && ev_used) {
       // Decomposed path: speculative pair launches that met a pending rebuild leave at once; they are not
@@ -2900,6 +2931,96 @@ template <typename R> struct CtxT : Ctx {
     }
   }
 
+  // ---- region rules (rule set: include/chem_mi355.h; selection: chem_region_host.hpp; scan: md_kernels.hpp) ----------------
+  // region_step: the scan of a firing step, one launch on the run's stream.  On the fused tile path the host does not wait: a
+  // firing that changes something stops the run on the device and comes back through run()'s halted().  Elsewhere (the
+  // unfused rebuild chain does not know a stopped run; a barostat waits on every step anyway) and at the end of a call the
+  // host looks at once.  Returns whether a change was applied here.
+  DBuf<RegionCand> region_rec; DBuf<RegionOut> region_out; DBuf<RegionReset> region_reset_dev;
+  bool region_step(bool last) {
+    RegionSet rs{};
+    rs.par = fused_par; rs.gen = hint_gen; rs.step = (unsigned long long)step;
+    for (size_t k = 0; k < regions.size(); ++k) {
+      const chem_region_desc& d = regions[k];
+      if (!region_due(d, region_enabled[k] != 0, step)) continue;
+      RegionDev& r = rs.r[rs.n++];
+      for (int a = 0; a < 3; ++a) { r.lo[a] = d.lo[a]; r.hi[a] = d.hi[a]; }
+      r.value = d.value; r.seed = d.seed; r.target_type = d.target_type; r.mode = d.mode; r.num = d.num; r.rule = (int)k;
+      rs.type_mask |= 1u << d.target_type;
+    }
+    if (rs.n == 0) return false;
+    if (step > region_counted) { ++region_firings; region_counted = step; }      // (a step redone behind a stopped run counts once)
+    if (region_rec.n < (size_t)n) {
+      region_rec.alloc((size_t)n); region_out.alloc(1);
+      HIPCHK(hipMemsetAsync(region_out.p, 0, sizeof(RegionOut), stream));
+    }
+    const bool wait = last || !use_fused || baro_on();
+    IdleHint* hint = nullptr;
+    if (!wait) { ensure_hflag(); hint = hint_dev(); }
+    hipLaunchKernelGGL((k_region_scan<R>), dim3(cdiv(n, 256)), dim3(256), 0, stream, n, (const V4*)(x4.p + G), (const int*)(tag.p + G), boxd, rs,
+                       region_rec.p, (int)region_rec.n, region_out.p, ctl.p, hint);
+    HIPCHK(hipGetLastError());
+    if (!wait) return false;
+    if (!last) ++region_syncs;
+    HIPCHK(hipStreamSynchronize(stream));
+    const DevCtl h = read_ctl();
+    if (h.halt != 4) return false;
+    set_ctl_field(&DevCtl::halt, 0);
+    if (last) ++region_syncs;
+    region_apply();
+    return true;
+  }
+  // The change of a firing step, on the host: records down, the selection over them, properties through the route of every
+  // host-decided change (mirrors, k_apply_props, charges), the resets, then what follows a type change by any route.  Forces
+  // are not evaluated here: the list build is requested for the next evaluation.
+  void region_apply() {
+    HIPCHK(hipStreamSynchronize(stream));
+    join_async();      // the mirrors are written below
+    RegionOut ro{};
+    HIPCHK(hipMemcpyAsync(&ro, region_out.p, sizeof(RegionOut), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const size_t nrec = (size_t)std::min<int64_t>(std::max(ro.nrec, 0), (int64_t)region_rec.n);
+    std::vector<RegionCand> recs;
+    if (nrec) region_rec.download(recs, nrec, stream);
+    HIPCHK(hipMemsetAsync(region_out.p, 0, sizeof(RegionOut), stream));
+    std::vector<RegionChange> chgs;
+    region_fire(regions, region_enabled, step, recs, chgs, region_stats);
+    if (chgs.empty()) return;
+    // a particle hit by several rules of the step: properties of the last, resets of all
+    std::vector<int32_t> tags; std::map<int32_t, int> flags;
+    for (const RegionChange& c : chgs) {
+      const chem_region_desc& d = regions[c.rule];
+      const int32_t t = c.tag;
+      top.type[t] = d.new_type;
+      if (!(d.new_mass < 0)) { top.mass[t] = d.new_mass; top.q[t] = d.new_q; }
+      flags[t] |= (d.reset_velocity ? 1 : 0) | (d.reset_force ? 2 : 0);
+      region_log.push_back(c);
+    }
+    std::vector<HostTopology::PropChange> props; std::vector<RegionReset> resets;
+    for (const auto& f : flags) {
+      const int32_t t = f.first;
+      props.push_back(HostTopology::PropChange{t, top.type[t], 0, 0, top.mass[t], top.q[t]});
+      if (f.second) resets.push_back(RegionReset{t, f.second});
+    }
+    apply_prop_changes(props, false);
+    if (!resets.empty()) {
+      region_reset_dev.upload(resets, stream);
+      hipLaunchKernelGGL((k_region_reset<R>), dim3(cdiv((long long)resets.size(), 256)), dim3(256), 0, stream, (int)resets.size(), region_reset_dev.p, rtag.p, v4.p, f4.p);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    if (res.on()) {      // re-stamped under the old type's rate, at this step
+      res.ensure(top.type);
+      std::vector<int32_t> changed;
+      res.restamp_type_changes(top.type, step, changed);
+      res_push(changed);
+    }
+    if (any_typed_list()) upload_bonded(false);
+    request_rebuild();
+    if (fix_tracking()) fix_after_reactions(false);      // a typed set judges its entries with the new type
+    region_keep = true;
+  }
+
   // ---- read-back ------------------------------------------------------------------------
   // ---- cross-rank gather of fixed-size host records (read-back paths only) ---------------
   DBuf<unsigned char> gbuf;
@@ -3203,6 +3324,7 @@ static void ckpt_apply(Ctx& c, CkptState&& s) {
   c.react_on = s.react_on != 0; c.ran = s.ran != 0;
   c.baro_p_last = s.baro_p_last; c.pist_pe = s.pist_pe; c.pist_eps = s.pist_eps; c.pist_sv = s.pist_sv; c.pist_mu = s.pist_mu;
   c.pist_pe_upload = c.pist_mu_upload = c.piston_on();      // (the device's words are written before they are read)
+  c.region_keep = false; c.region_counted = s.step;
   c.baro_keep = false; c.baro_charge = s.baro_charge; c.baro_charge_ref = s.baro_charge_ref; c.baro_seen_builds = c.baro_seen_ref = -1;
   t.type = std::move(s.type); t.state = std::move(s.state); t.res_id = std::move(s.res_id); t.mol_id = std::move(s.mol_id); t.mass = std::move(s.mass); t.q = std::move(s.q);
   c.pos0 = std::move(s.pos); c.vel0 = std::move(s.vel); c.img0 = std::move(s.image);
@@ -3327,6 +3449,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   // (fixed distances: entries and log go with the tags; sets, post-processes and release rules stay)
   for (FixSet& fs : c.fix.sets) { fs.ent.clear(); fs.next_seq = 0; }
   c.fix.targets.clear(); c.fix.anchors.clear(); c.fix.log.clear(); c.fix.join_log.clear(); c.removed_log.clear(); c.fix_dirty = true; c.ran = false;
+  c.region_log.clear(); c.region_stats.clear(); c.region_counted = 0; c.region_keep = false;      // (region rules and their switches stay)
   return 0;
   API_END(ctx)
 }
@@ -4052,6 +4175,60 @@ int64_t chem_atrp_get_stats(chem_ctx* ctx, chem_atrp_stats* out, int64_t cap) {
   API_END(ctx)
 }
 
+// ---- region rules (rule set in the header; chem_region_host.hpp) ----
+int chem_region_add(chem_ctx* ctx, const chem_region_desc* d) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(!c.dd_on, CHEM_ENOTIMPL, "region rules are not available on the decomposed path (a selection by count would need a gather across ranks)");
+  REQUIRE(d, CHEM_EINVAL, "region_add: null descriptor");
+  std::string why;
+  if (region_validate(*d, why) != 0) throw ChemError(CHEM_EINVAL, "region_add: " + why);
+  REQUIRE((int)c.regions.size() < CHEM_MAX_REGIONS, CHEM_ENOSPC, "region_add: more than CHEM_MAX_REGIONS rules");
+  c.regions.push_back(*d); c.region_enabled.push_back(0);
+  c.pair_dirty = true;    // (the type-pair tables must cover the new type)
+  return (int)c.regions.size() - 1;
+  API_END(ctx)
+}
+
+int chem_region_enable(chem_ctx* ctx, int rule, int on) {
+  API_BEGIN
+  Ctx& c = CTX;
+  REQUIRE(rule >= 0 && rule < (int)c.regions.size(), CHEM_EINVAL, "region_enable: unknown rule");
+  c.region_enabled[rule] = on ? 1 : 0;
+  return 0;
+  API_END(ctx)
+}
+
+int64_t chem_region_get_changes(chem_ctx* ctx, chem_region_change* out, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  const int64_t m = (int64_t)c.region_log.size();
+  if (!out) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "region_get_changes: capacity");
+  for (int64_t k = 0; k < m; ++k) { const RegionChange& r = c.region_log[k]; out[k] = chem_region_change{r.step, c.top.id[r.tag], r.rule, 0}; }
+  return m;
+  API_END(ctx)
+}
+
+int64_t chem_region_get_stats(chem_ctx* ctx, chem_region_stats* out, int64_t cap) {
+  API_BEGIN
+  Ctx& c = CTX;
+  const int64_t m = (int64_t)c.region_stats.size();
+  if (!out) return m;
+  REQUIRE(cap >= m, CHEM_ENOSPC, "region_get_stats: capacity");
+  for (int64_t k = 0; k < m; ++k) { const RegionStat& r = c.region_stats[k]; out[k] = chem_region_stats{r.step, (int64_t)r.rule, r.candidates, r.changed}; }
+  return m;
+  API_END(ctx)
+}
+
+int chem_region_counters(chem_ctx* ctx, int64_t* firings, int64_t* syncs) {
+  API_BEGIN
+  if (firings) *firings = CTX.region_firings;
+  if (syncs) *syncs = CTX.region_syncs;
+  return 0;
+  API_END(ctx)
+}
+
 int chem_topology_register(chem_ctx* ctx, int arity, int list, const int32_t* types) {
   API_BEGIN
   HostTopology& t = CTX.top;
@@ -4110,6 +4287,7 @@ int chem_checkpoint_load(chem_ctx* ctx, const void* buf, int64_t nbytes) {
   REQUIRE(s.baro_kind == ckpt_baro_kind(c), CHEM_EINVAL, "checkpoint: the configuration differs from the one the blob was saved under: barostat kind (blob " + std::to_string(s.baro_kind) +
                                                           ", context " + std::to_string(ckpt_baro_kind(c)) + ")");
   ckpt_apply(c, std::move(s));
+  c.region_log.clear(); c.region_stats.clear();      // (not part of a blob: from here on they hold what happens since the load)
   return 0;
   API_END(ctx)
 }
@@ -4154,7 +4332,8 @@ int chem_run(chem_ctx* ctx, int64_t nsteps) {
     if (c.react_on && c.interval > 0) sooner(c.interval);
     if (c.atrp_on && c.atrp.interval > 0) sooner(c.atrp.interval);
     const int64_t len = res_next_piece(c.step, left, stop);
-    c.run(len); left -= len;
+    const int64_t from = c.step;
+    c.run(len); left -= c.step - from;      // (a region rule that changed something ends the piece there: its stamps may complete early)
     if (completions() && left == 0) c.run(0);
   }
   return 0;
@@ -4307,6 +4486,7 @@ int chem_comm_init(chem_ctx* ctx, int nranks, int rank, const int node_grid[3], 
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
+  REQUIRE(c.regions.empty(), CHEM_ENOTIMPL, "region rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on, CHEM_ESTATE, "comm_init: already initialised");
   if (nranks == 1 && !uid) return 0;   // single domain, nothing to do
   REQUIRE(node_grid && node_grid[0] == 1 && node_grid[1] == 1 && node_grid[2] == nranks, CHEM_ENOTIMPL,
@@ -4376,6 +4556,7 @@ int chem_comm_init_ipc(chem_ctx* ctx, int nranks, int rank, const char* shm_name
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
+  REQUIRE(c.regions.empty(), CHEM_ENOTIMPL, "region rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_ipc must precede the first run");
   HIPCHK(hipSetDevice(c.device));
   c.tr.reset(new IpcTransport(nranks, rank, shm_name));
@@ -4392,6 +4573,7 @@ int chem_comm_init_local(chem_ctx* ctx, int nranks, int rank, int hub_id) {
   REQUIRE(c.res_rules.empty(), CHEM_ENOTIMPL, "reaction_set_resolution rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.fix.any() && c.fix.rules.empty(), CHEM_ENOTIMPL, "fixed-distance entries or release rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.reverse_on(), CHEM_ENOTIMPL, "bond-removal or join rules are registered: they are not available on the decomposed path");
+  REQUIRE(c.regions.empty(), CHEM_ENOTIMPL, "region rules are registered: they are not available on the decomposed path");
   REQUIRE(!c.dd_on && c.particles_dirty, CHEM_ESTATE, "comm_init_local must precede the first run");
   c.tr.reset(new LocalTransport(nranks, rank, hub_id));
   c.dd_on = true; c.P = nranks; c.rk = rank; c.geom_dirty = true;

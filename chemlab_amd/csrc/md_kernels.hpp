@@ -17,6 +17,7 @@
 #include "chem_idle_host.hpp"
 #include "chem_roworder_host.hpp"
 #include "chem_baro_host.hpp"
+#include "chem_region_host.hpp"
 
 namespace chem {
 
@@ -4719,6 +4720,96 @@ __global__ void k_bt_sort(int n, const int* __restrict__ start, int* __restrict_
 template <typename T> __global__ void k_fill(T* p, T v, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+
+// ---- region rules (chem_region_add; rule set in include/chem_mi355.h, selection in chem_region_host.hpp) -------------------
+// k_region_scan: a launch of its own behind the second half kick of a step on which an enabled rule is due.  One thread per
+// particle: one 16/32-byte load of (x, y, z, type), an exit on the type mask of the due rules, then the fp64 box test of every
+// due rule on the decoded, folded position -- the expressions of chem_get_state(CHEM_STATE_POS), without FMA contraction.
+// A particle that is a candidate of at least one due rule is compacted (wave ballot, one atomic per wave) as (tag, type, bits
+// of the boxes it is in); candidates and mode-1 acceptances are counted per rule.  The last workgroup to finish knows the
+// counts: if no rule changes anything it clears them and the run goes on, no host involved; otherwise it stops the
+// asynchronous run (DevCtl::halt = 4: "step halt_step is complete, nothing of the next one has happened"), every later launch
+// leaves at once, and the host applies the selection over the records and resumes.
+struct RegionDev { double lo[3], hi[3], value; unsigned long long seed; int target_type, mode, num, rule; };
+struct RegionSet { int n, par, gen; unsigned int type_mask; unsigned long long step; RegionDev r[kRegionMaxRules]; };
+struct RegionOut { int nrec, done, ncand[kRegionMaxRules], nacc[kRegionMaxRules]; };
+__device__ __forceinline__ double region_coord(float c, double qs, double qh) {
+#pragma clang fp contract(off)
+  const double p = (double)qbits(c) * qs;
+  return p + qh;
+}
+__device__ __forceinline__ double region_coord(double c, double, double) { return c; }
+template <typename R>
+__global__ __launch_bounds__(256) void k_region_scan(int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, BoxD box, RegionSet rs,
+                                                     RegionCand* __restrict__ rec, int rec_cap, RegionOut* __restrict__ out, DevCtl* ctl, IdleHint* hint) {
+  if (ctl->halt) return;   // (a stopped run: the step this launch belongs to is redone)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned int candm = 0, accm = 0;
+  RegionCand c{0, 0, 0u, 0u};
+  if (i < n) {
+    const Vec4<R> p = x4[i];
+    const int ty = (int)p.w;
+    if ((rs.type_mask >> (ty & 31)) & 1u) {
+      const double x = region_fold(region_coord(p.x, box.qs[0], box.qh[0]), box.L[0]), y = region_fold(region_coord(p.y, box.qs[1], box.qh[1]), box.L[1]),
+                   z = region_fold(region_coord(p.z, box.qs[2], box.qh[2]), box.L[2]);
+      const int tg = tag[i];
+      for (int k = 0; k < rs.n; ++k) {
+        const RegionDev& D = rs.r[k];
+        if (!region_inside(D.lo, D.hi, x, y, z)) continue;
+        c.inbox |= 1u << D.rule;
+        if (D.target_type != ty) continue;
+        candm |= 1u << k;
+        if (D.mode == kRegionProb) {
+          uint32_t rr[4];
+          chem_philox::region_draw(D.seed, rs.step, (uint32_t)tg, (uint32_t)D.rule, rr);
+          if (chem_philox::u01(rr[1]) < D.value) accm |= 1u << k;
+        }
+      }
+      c.tag = tg; c.type = ty;
+    }
+  }
+  const unsigned long long m = __ballot(candm != 0);
+  if (m) {
+    const int leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane_id() == leader) base = atomicAdd(&out->nrec, __popcll(m));
+    base = __shfl(base, leader);
+    if (candm) { const int pos = base + __popcll(m & lanemask_lt()); if (pos < rec_cap) rec[pos] = c; }
+    for (int k = 0; k < rs.n; ++k) {
+      const int nc = __popcll(__ballot((candm >> k) & 1u)), na = __popcll(__ballot((accm >> k) & 1u));
+      if (lane_id() == leader) { if (nc) atomicAdd(&out->ncand[k], nc); if (na) atomicAdd(&out->nacc[k], na); }
+    }
+  }
+  __shared__ int last;
+  __syncthreads();
+  if (threadIdx.x == 0) { __threadfence(); last = atomicAdd(&out->done, 1) == (int)gridDim.x - 1; }
+  __syncthreads();
+  if (!last || threadIdx.x != 0) return;
+  __threadfence();
+  bool change = false;
+  for (int k = 0; k < rs.n; ++k)
+    change |= region_quota(rs.r[k].mode, rs.r[k].value, rs.r[k].num, atomicAdd(&out->ncand[k], 0), atomicAdd(&out->nacc[k], 0)) > 0;
+  if (change) {
+    ctl->halt_step = (long long)rs.step; ctl->halt_par = rs.par; ctl->halt = 4;
+    if (hint) { volatile IdleHint* h = hint; h->halted = rs.gen; }
+  } else {
+    out->nrec = 0;
+    for (int k = 0; k < rs.n; ++k) { out->ncand[k] = 0; out->nacc[k] = 0; }
+  }
+  out->done = 0;
+}
+
+// the resets of a region rule, behind k_apply_props: v := 0 (flag 1), stored force := 0 (flag 2), exactly
+struct RegionReset { int tag, flags; };
+template <typename R>
+__global__ void k_region_reset(int nchg, const RegionReset* __restrict__ chg, const int* __restrict__ rtag, Vec4<R>* __restrict__ v4, Vec4<R>* __restrict__ f4) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nchg) return;
+  const int i = rtag[chg[k].tag];
+  if (i < 0) return;
+  if (chg[k].flags & 1) { Vec4<R> v = v4[i]; v.x = v.y = v.z = (R)0; v4[i] = v; }
+  if (chg[k].flags & 2) { Vec4<R> f = f4[i]; f.x = f.y = f.z = (R)0; f4[i] = f; }
 }
 
 }  // namespace chem

@@ -236,7 +236,61 @@ class Engine:
         checker lacks what only the product has."""
         if name == "checkpoint":
             name = "checkpoint_save"
+        if name == "region":
+            name = "region_add"
         return getattr(self.api, name, None) is not None
+
+    # ---- region rules: FreezeRegion, ChangeParticleType (include/chem_mi355.h, chem_region_add ff.) ----
+    REGION_MODES = dict(all=0, prob=1, num=2, fraction=3)
+
+    def _region_entry(self, name, what="region rules"):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("%s: the CPU checker has no region rules" % what)
+        return fn
+
+    def region_add(self, lo, hi, target_type, new_type, interval=1, mode="all", value=0.0, num=0, new_mass=-1.0, new_q=0.0,
+                   reset_velocity=False, reset_force=False, seed=0, what="region rules"):
+        """A region rule over the box [lo, hi) (folded coordinates): every `interval` steps the selected particles of
+        target_type inside become new_type.  mode 'all' | 'prob' (value) | 'num' (num) | 'fraction' (value); new_mass < 0 keeps
+        mass and charge.  Returns the rule index; the rule is off until region_enable."""
+        fn = self._region_entry("region_add", what)
+        d = _capi.RegionDesc()
+        for k in range(3):
+            d.lo[k], d.hi[k] = float(lo[k]), float(hi[k])
+        d.target_type, d.new_type, d.new_mass, d.new_q = int(target_type), int(new_type), float(new_mass), float(new_q)
+        d.interval, d.mode, d.value, d.num = int(interval), int(self.REGION_MODES.get(mode, mode)), float(value), int(num)
+        d.reset_velocity, d.reset_force, d.seed = int(bool(reset_velocity)), int(bool(reset_force)), int(seed) & (2 ** 64 - 1)
+        return self._ck(fn(self.ctx, C.byref(d)))
+
+    def region_enable(self, rule, on=True):
+        self._ck(self._region_entry("region_enable")(self.ctx, int(rule), 1 if on else 0))
+
+    def region_changes(self):
+        """Every change (step, id, rule), ordered by step, then rule, then id."""
+        fn = self._region_entry("region_get_changes")
+        n = self._ck(fn(self.ctx, None, 0))
+        buf = (_capi.RegionChange * max(n, 1))()
+        if n:
+            self._ck(fn(self.ctx, buf, n))
+        dt = np.dtype([("step", "i8"), ("id", "i8"), ("rule", "i4"), ("pad", "i4")])
+        return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+    def region_stats(self):
+        """One row (step, rule, candidates, changed) per firing of a rule that changed something."""
+        fn = self._region_entry("region_get_stats")
+        n = self._ck(fn(self.ctx, None, 0))
+        buf = (_capi.RegionStats * max(n, 1))()
+        if n:
+            self._ck(fn(self.ctx, buf, n))
+        dt = np.dtype([("step", "i8"), ("rule", "i8"), ("candidates", "i8"), ("changed", "i8")])
+        return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+    def region_counters(self):
+        """(firing steps, host synchronisations the rules caused) since the context was created."""
+        f, s = C.c_int64(0), C.c_int64(0)
+        self._ck(self._region_entry("region_counters")(self.ctx, C.byref(f), C.byref(s)))
+        return int(f.value), int(s.value)
 
     # ---- checkpoint and exact restart (include/chem_mi355.h, chem_checkpoint_save / chem_checkpoint_load) ----
     def _ckpt_entry(self, name):

@@ -1570,7 +1570,127 @@ class _PostProcessJoinParticles(object):
         self.fd, self.eq_length = fd, float(eq_length)
 
 
+class ParticleRegion(object):
+    """espressopp.ParticleRegion(storage, integrator, lo, hi) + add_type_id (reaction_post_process.py:186-191): the particles of
+    the listed types inside the box [lo, hi) of folded coordinates.  Nothing is tracked here: the engine tests the box on the
+    device at every firing of the rule that uses the region (chem_region_add)."""
+
+    def __init__(self, storage, integrator, lo, hi):
+        self.storage, self.integrator = storage, integrator
+        self.lo, self.hi = [float(v) for v in lo], [float(v) for v in hi]
+        self.type_ids = []
+
+    def add_type_id(self, type_id):
+        if int(type_id) not in self.type_ids:
+            self.type_ids.append(int(type_id))
+
+
+class _RegionExtension(object):
+    """what ChangeInRegion and ChangeParticleType share: rules sent once, enabled by _connect, disabled by disconnect"""
+
+    def _rules(self):
+        raise NotImplementedError
+
+    def _connect(self, integrator):
+        e = self.system.engine
+        if self._handles is None:
+            if self.system.storage is not None:
+                self.system.storage.decompose()
+            seed = self.system.rng.get_seed() if self.system.rng is not None else 0
+            self._handles = [e.region_add(seed=seed, what=type(self).__name__.lstrip("_"), **kw) for kw in self._rules()]
+        for h in self._handles:
+            e.region_enable(h, True)
+
+    def disconnect(self):
+        for h in self._handles or []:
+            self.system.engine.region_enable(h, False)
+
+
+class _ChangeInRegion(_RegionExtension):
+    """integrator.ChangeInRegion(system, region, prob=, p_num=, p_num_percentage=) + set_particle_properties(type,
+    TopologyParticleProperties), set_flags(type, reset_velocity, reset_force, remove_particle), stats_filename
+    (reaction_post_process.py:193-199): on every step the selected particles of the region's types that lie inside it get the
+    new properties.  Selection: prob, else p_num, else p_num_percentage (the order the reference names them); with none of them
+    every candidate.  One region rule per type that has properties (chem_region_add), on when the extension is added to the
+    integrator.  Removing particles is not served."""
+
+    def __init__(self, system, region, prob=None, p_num=None, p_num_percentage=None):
+        if not isinstance(region, ParticleRegion):
+            raise TypeError("ChangeInRegion(system, ParticleRegion, ...)")
+        self.system, self.region = system, region
+        self.prob, self.p_num, self.p_num_percentage = prob, p_num, p_num_percentage
+        self.stats_filename = None
+        self._props, self._flags, self._handles = {}, {}, None
+        regs = getattr(system, "_region_extensions", None)
+        if regs is None:
+            regs = system._region_extensions = []
+        regs.append(self)
+
+    def set_particle_properties(self, type_id, props):
+        if props.type is None:
+            raise ValueError("ChangeInRegion.set_particle_properties: the properties name no type")
+        self._props[int(type_id)] = props
+
+    def set_flags(self, type_id, reset_velocity=False, reset_force=False, remove_particle=False):
+        if remove_particle:
+            raise NotImplementedError("ChangeInRegion.set_flags(remove_particle=True): the engine cannot remove particles")
+        self._flags[int(type_id)] = (bool(reset_velocity), bool(reset_force))
+
+    def _selection(self):
+        if self.prob is not None:
+            return dict(mode="prob", value=float(self.prob))
+        if self.p_num is not None:
+            return dict(mode="num", num=int(self.p_num))
+        if self.p_num_percentage is not None:
+            return dict(mode="fraction", value=float(self.p_num_percentage))
+        return dict(mode="all")
+
+    def _rules(self):
+        out = []
+        for t in self.region.type_ids:
+            p = self._props.get(t)
+            if p is None:
+                continue
+            rv, rf = self._flags.get(t, (False, False))
+            kw = dict(lo=self.region.lo, hi=self.region.hi, target_type=t, new_type=int(p.type), interval=1, reset_velocity=rv, reset_force=rf)
+            if p.mass is not None:
+                kw.update(new_mass=float(p.mass), new_q=float(p.q or 0.0))
+            kw.update(self._selection())
+            out.append(kw)
+        return out
+
+    def save_stats(self, filename=None):
+        """`step rule candidates changed`, one row per firing of a rule that changed something: the rows of every ChangeInRegion
+        of the system that names the same file (the six regions of a FreezeRegion share one)."""
+        filename = filename or self.stats_filename
+        mine = set(h for x in self.system._region_extensions if (filename is None and x is self) or (filename and x.stats_filename == filename)
+                   for h in (x._handles or []))
+        rows = [r for r in self.system.engine.region_stats() if int(r["rule"]) in mine] if mine else []
+        if filename:
+            with _rank.wopen(filename, "w") as f:
+                f.write("# step rule candidates changed\n")
+                for r in rows:
+                    f.write("%d %d %d %d\n" % (r["step"], r["rule"], r["candidates"], r["changed"]))
+        return rows
+
+
+class _ChangeParticleType(_RegionExtension):
+    """integrator.ChangeParticleType(system, interval, num_particles, old_type, new_type) (reaction_post_process.py:364-378):
+    every `interval` steps `num_particles` random particles of old_type become new_type; mass, charge, velocity and force are
+    kept.  A region rule over the whole box, selection by count."""
+
+    def __init__(self, system, interval, num_particles, old_type, new_type):
+        self.system = system
+        self.interval, self.num_particles, self.old_type, self.new_type = int(interval), int(num_particles), int(old_type), int(new_type)
+        self._handles = None
+
+    def _rules(self):
+        return [dict(lo=[0.0, 0.0, 0.0], hi=[float(b) for b in self.system.bc.boxL], target_type=self.old_type, new_type=self.new_type,
+                     interval=self.interval, mode="num", num=self.num_particles)]
+
+
 integrator = _ns(
+    ChangeInRegion=_ChangeInRegion, ChangeParticleType=_ChangeParticleType,
     FixDistances=_FixDistances, PostProcessReleaseParticles=_PostProcessReleaseParticles,
     VelocityVerlet=_VelocityVerlet, FixedListDynamicResolution=_FixedListDynamicResolution, LangevinThermostat=_LangevinThermostat, ChemicalReaction=_ChemicalReaction,
     Reaction=_Reaction, PostProcessChangeProperty=_PostProcessChangeProperty,
@@ -1582,7 +1702,7 @@ integrator = _ns(
     CapForce=_CapForce, RestrictReaction=_RestrictReaction,
     DissociationReaction=_DissociationReaction, ATRPActivator=_ATRPActivator,
     ReactionCutoffRandom=_unsupported("integrator.ReactionCutoffRandom"),
-    ChangeInRegion=_unsupported("integrator.ChangeInRegion"), BasicDynamicResolution=_BasicDynamicResolution,
+    BasicDynamicResolution=_BasicDynamicResolution,
     PostProcessChangeNeighboursProperty=_PostProcessChangeNeighboursProperty,
     PostProcessRemoveNeighbourBond=_PostProcessRemoveNeighbourBond, PostProcessJoinParticles=_PostProcessJoinParticles,
 )

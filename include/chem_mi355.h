@@ -827,6 +827,77 @@ int chem_reactions_enable(chem_ctx* ctx, int on);
 /* per-reaction rate update (Arrhenius hook, start_simulation.py:785-796); on an index of chem_dissociation_add: diss_rate */
 int chem_reaction_set_rate(chem_ctx* ctx, int reaction, double rate);
 
+/* ---- region rules: FreezeRegion, ChangeParticleType ------------------------------------- */
+/* integrator.ChangeInRegion(system, ParticleRegion, prob | p_num | p_num_percentage) with set_particle_properties / set_flags
+ * (ext_type=FreezeRegion: box edges act as sinks, a particle of the target type that reaches one becomes an inert type), and
+ * integrator.ChangeParticleType(system, interval, num_particles, old_type, new_type) -- reaction_post_process.py:139-201,
+ * 364-378.  The arithmetic is in the external fork, so this rule set is this build's own ([EXT-RECALL], parity unpinned;
+ * DESIGN.md "Region rules").
+ *
+ * A rule holds a box [lo, hi) in folded coordinates, a target type and what becomes of a selected particle.
+ *   firing      an enabled rule fires at every step counter value s > 0 with s % interval == 0, behind the second half kick
+ *               that completes step s and behind the reaction, dissociation and ATRP work of the same s.  It works on the
+ *               positions x(s) exactly as chem_get_state(CHEM_STATE_POS) returns them at that step (decoded, folded), compared
+ *               in fp64 with lo / hi.  run(a); run(b) gives the same bits as run(a + b).
+ *   candidates  of rule k at step s: the particles of target_type with lo[d] <= x[d] < hi[d] on every axis.  Rules act in
+ *               insertion order; a particle changed by an earlier rule of the step is seen by later rules with its new type.
+ *   selection   out = chem_philox::region_draw(seed, s, tag, k): out[0] is the selection key (ties broken by tag), out[1]
+ *               gives the acceptance uniform u01(out[1]).
+ *                 mode 0  every candidate
+ *                 mode 1  the candidates with u01(out[1]) < value
+ *                 mode 2  the min(num, |C|) candidates with the smallest key
+ *                 mode 3  the floor(value |C|) candidates with the smallest key (fp64 product)
+ *               A pure function of (seed, step, tag, rule): never of thread or particle order.
+ *   the change  type := new_type; mass and charge := new_mass, new_q unless new_mass < 0 (then both are kept); v := 0 exactly
+ *               when reset_velocity; the stored force := 0 exactly when reset_force, so the next half kick adds nothing to the
+ *               particle.  Everything else is treated as after a type change by any route: the particle is re-stamped
+ *               (chem_set_resolution section), by-types list slots are resolved against the new type before the next force
+ *               evaluation, a typed fixed-distance set (chem_fix_create) judges its entries with the new type at once, the
+ *               chemical state is kept.  Forces are NOT evaluated again at s: every other particle keeps the stored force of
+ *               step s for one more half kick, as under the reference's integrator; the force list is rebuilt in front of the
+ *               next evaluation, which uses the new type -- also where a chem_run call ends at s and the next begins there.
+ *               Afterwards the particle is an ordinary particle of new_type (chem_thermostat_langevin_types decides whether the
+ *               thermostat moves it).
+ *   lifetime    regions are absolute lengths fixed at chem_region_add: a barostat does not move or scale them.  Rules survive
+ *               chem_set_particles, like reactions; the change log and the stats are cleared there.  A rule is off until
+ *               chem_region_enable(rule, 1).
+ *   cost        while an enabled rule is due, one scan launch on the run's stream per firing step, and that step's two
+ *               half kicks are launched apart (as on a reaction step).  A firing that changes nothing never synchronises the
+ *               host on the fused tile path; one that does stops the asynchronous run at that step (the DevCtl halt / resume
+ *               route), the host applies the change and resumes: one synchronisation per firing that changes something.  On
+ *               the per-cell and brute-force list paths (boxes of few cells) and under a barostat every firing synchronises.
+ *               A context without a rule launches and allocates nothing for this.
+ *   logs        chem_region_get_changes: every change as (step, id, rule), ordered by step, then rule, then id.
+ *               chem_region_get_stats: one row per firing of a rule that changed something, same order.  chem_region_counters:
+ *               firings = firing steps (steps on which at least one enabled rule was due) and syncs = host synchronisations
+ *               the rules caused, since the context was created.  out == NULL: the count alone.
+ *   checkpoint  the blob format and its fingerprint do not know the rules: the change log, the stats and the counters are not
+ *               part of a blob -- after a load they hold what happened since.  The draws are counter based, so a context set up
+ *               alike, with the same rules enabled, that loads a blob goes on bit for bit.
+ * CHEM_EINVAL: a type outside [0, CHEM_MAX_TYPES), lo > hi, a non-finite bound, interval < 1, value outside [0, 1] (modes 1
+ * and 3), num < 0 (mode 2), an unknown mode, new_mass == 0 or non-finite, an unknown rule index.  CHEM_ENOSPC: more than
+ * CHEM_MAX_REGIONS rules.  Not on the decomposed path (a selection by count would need a gather across ranks):
+ * chem_region_add after chem_comm_init*, and chem_comm_init* after a rule, are CHEM_ENOTIMPL. */
+#define CHEM_MAX_REGIONS 16
+typedef struct chem_region_desc {
+  double   lo[3], hi[3];        /* folded coordinates; a particle is inside when lo[d] <= x[d] < hi[d] on every axis */
+  int32_t  target_type, new_type;
+  double   new_mass, new_q;     /* new_mass < 0: mass and charge are kept (what both call sites do) */
+  int32_t  interval;            /* >= 1 */
+  int32_t  mode;                /* 0 all candidates, 1 prob, 2 num, 3 fraction */
+  double   value;               /* mode 1: probability in [0,1]; mode 3: fraction in [0,1] */
+  int32_t  num;                 /* mode 2 */
+  int32_t  reset_velocity, reset_force;
+  uint64_t seed;
+} chem_region_desc;
+typedef struct chem_region_change { int64_t step; int64_t id; int32_t rule, pad; } chem_region_change;
+typedef struct chem_region_stats { int64_t step; int64_t rule; int64_t candidates, changed; } chem_region_stats;
+int     chem_region_add(chem_ctx* ctx, const chem_region_desc* desc);      /* -> rule index >= 0 */
+int     chem_region_enable(chem_ctx* ctx, int rule, int on);
+int64_t chem_region_get_changes(chem_ctx* ctx, chem_region_change* out, int64_t cap);
+int64_t chem_region_get_stats(chem_ctx* ctx, chem_region_stats* out, int64_t cap);
+int     chem_region_counters(chem_ctx* ctx, int64_t* firings, int64_t* syncs);   /* either pointer may be NULL */
+
 /* ---- checkpoint and exact restart ------------------------------------------------------ */
 /* Stop a run and go on with it in another process (the reference's jobs are 5 M-step runs under wall limits of 24 to 72 h,
  * examples/mf/espp_cg_1/params and the *.pbs files).  The reference has no such call: this rule set is

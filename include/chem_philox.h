@@ -86,6 +86,14 @@ CHEM_HD void barostat_draw(uint64_t seed, uint64_t step, uint32_t out[4]) {
   philox4x32_10(ctr, key, out);
 }
 
+/* Region rules (chem_region_add): selection key out[0] (ties by tag) and acceptance uniform out[1] of particle `tag` for rule
+ * `rule` at step `step`. */
+CHEM_HD void region_draw(uint64_t seed, uint64_t step, uint32_t tag, uint32_t rule, uint32_t out[4]) {
+  uint32_t ctr[4] = {tag, (uint32_t)step, (uint32_t)(step >> 32), 0x5245474Eu ^ (rule << 8)};
+  uint32_t key[2] = {(uint32_t)seed ^ 0x52474E53u, (uint32_t)(seed >> 32)};
+  philox4x32_10(ctr, key, out);
+}
+
 /* ---- StochasticVelocityRescaling (Bussi, Donadio, Parrinello, J. Chem. Phys. 126, 014101 (2007)) ----
  * One scalar per step: the new kinetic energy drawn from the canonical distribution relaxing with time
  * constant taut (in steps).  The stream is keyed (seed, step); oracle and device run this same code on
