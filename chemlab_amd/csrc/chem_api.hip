@@ -3057,7 +3057,9 @@ template <typename R> struct CtxT : Ctx {
     switch (what) {   // replicated by-tag data: no gather
       case CHEM_STATE_STATE: { std::vector<int> h; state.download(h, nglob, stream); std::copy(h.begin(), h.end(), i32); return nglob; }
       case CHEM_STATE_RESID: { std::vector<int> h; res_id.download(h, nglob, stream); std::copy(h.begin(), h.end(), i32); return nglob; }
-      case CHEM_STATE_MOLID: { std::vector<int> h; mol_id.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) i32[t] = (int32_t)top.id[h[t]]; return nglob; }
+      case CHEM_STATE_MOLID: {      // an id in an int32 array: refused where an id does not fit (ids are ascending by tag: the ends decide)
+        if (nglob > 0 && (!fits_int32(top.id.front()) || !fits_int32(top.id.back()))) throw ChemError(CHEM_EINVAL, "get_state: CHEM_STATE_MOLID is an int32 read-back of particle ids and this context holds ids beyond 32 bits");
+        std::vector<int> h; mol_id.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) i32[t] = (int32_t)top.id[h[t]]; return nglob; }
       case CHEM_STATE_ID: for (int t = 0; t < nglob; ++t) i64[t] = top.id[t]; return nglob;
       case CHEM_STATE_CHARGE: {      // the device's by-tag array while it is alive (charges_on), the host mirror otherwise
         if (charges_on() && qtag.p) { std::vector<R> h; qtag.download(h, nglob, stream); for (int t = 0; t < nglob; ++t) d[t] = (double)h[t]; }
@@ -3420,6 +3422,7 @@ int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
   API_BEGIN
   REQUIRE(n > 0 && id && type && pos && mass, CHEM_EINVAL, "set_particles: null or empty input");
   REQUIRE(n < (1ll << 27), CHEM_EINVAL, "set_particles: too many particles for one context");
+  if (!res_id) for (int64_t i = 0; i < n; ++i) REQUIRE(fits_int32(id[i]), CHEM_EINVAL, "set_particles: the default res_id is the particle id, and id " + std::to_string(id[i]) + " does not fit its 32 bits: pass res_id");
   Ctx& c = CTX; HostTopology& t = c.top;
   std::vector<int64_t> order(n);
   for (int64_t i = 0; i < n; ++i) order[i] = i;
@@ -3474,6 +3477,7 @@ int chem_add_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_
     REQUIRE(k == 0 || id[s] != id[order[k - 1]], CHEM_EINVAL, "add_particles: duplicate particle id");
     REQUIRE(type[s] >= 0 && type[s] < CHEM_MAX_TYPES, CHEM_EINVAL, "add_particles: particle type out of range [0," + std::to_string(CHEM_MAX_TYPES) + "): CHEM_MAX_TYPES is the limit");
     REQUIRE(mass[s] > 0, CHEM_EINVAL, "add_particles: particle mass must be positive");
+    REQUIRE(res_id || fits_int32(id[s]), CHEM_EINVAL, "add_particles: the default res_id is the particle id, and id " + std::to_string(id[s]) + " does not fit its 32 bits: pass res_id");
     for (int d = 0; d < 3; ++d) REQUIRE(std::isfinite(pos[3 * s + d]), CHEM_EINVAL, "add_particles: position");
   }
   c.add_particles_prepare();      // (nothing has failed so far; particle data back in pos0 / vel0 if it was on the device)
@@ -3662,13 +3666,11 @@ int chem_set_exclusions(chem_ctx* ctx, int64_t n, const int64_t* p) {
   API_BEGIN
   HostTopology& t = CTX.top;
   REQUIRE(t.n > 0, CHEM_ESTATE, "set particles before exclusions");
+  std::vector<int32_t> tags((size_t)(n > 0 ? 2 * n : 0));      // (every id is resolved before the old exclusions go: a refused call leaves them as they were)
+  for (size_t k = 0; k < tags.size(); ++k) { tags[k] = t.tag_of(p[k]); REQUIRE(tags[k] >= 0, CHEM_EINVAL, "exclusion: unknown particle id " + std::to_string(p[k])); }
   for (auto& r : t.excl) r.clear();
   t.n_excl_pairs = 0; t.excl_log.clear();
-  for (int64_t k = 0; k < n; ++k) {
-    const int a = t.tag_of(p[2 * k]), b = t.tag_of(p[2 * k + 1]);
-    REQUIRE(a >= 0 && b >= 0, CHEM_EINVAL, "exclusion: unknown particle id");
-    t.exclude(a, b);
-  }
+  for (int64_t k = 0; k < n; ++k) t.exclude(tags[2 * k], tags[2 * k + 1]);
   CTX.excl_dirty = true; CTX.resort = true;
   return 0;
   API_END(ctx)
@@ -3945,9 +3947,10 @@ int chem_list_add(chem_ctx* ctx, int list, int64_t n, const int64_t* ids) {
   HostList& l = t.lists[list];
   t.cur_step = CTX.step;
   std::vector<std::pair<int32_t, int32_t>> nb;
+  std::vector<int32_t> tags((size_t)(n > 0 ? n : 0) * l.arity);      // (every id is resolved before the first entry goes in: a refused call leaves the list as it was)
+  for (size_t k = 0; k < tags.size(); ++k) { tags[k] = t.tag_of(ids[k]); REQUIRE(tags[k] >= 0, CHEM_EINVAL, "list_add: unknown particle id " + std::to_string(ids[k])); }
   for (int64_t e = 0; e < n; ++e) {
-    int32_t tg[4];
-    for (int k = 0; k < l.arity; ++k) { tg[k] = t.tag_of(ids[e * l.arity + k]); REQUIRE(tg[k] >= 0, CHEM_EINVAL, "list_add: unknown particle id"); }
+    const int32_t* tg = &tags[(size_t)e * l.arity];
     if (t.list_insert(l, tg) && l.arity == 2) nb.emplace_back(tg[0], tg[1]);
   }
   for (auto& e : nb) t.graph_add(e.first, e.second);
@@ -4132,9 +4135,12 @@ int chem_reaction_restrict(chem_ctx* ctx, int reaction, int64_t n, const int64_t
   reaction = c.assoc_row(reaction);
   REQUIRE(reaction >= 0 && reaction < (int)c.reactions.size() && reaction < 32, CHEM_EINVAL, "reaction_restrict: reaction index");
   REQUIRE(n >= 0 && (n == 0 || p), CHEM_EINVAL, "reaction_restrict: pairs");
-  for (int64_t k = 0; k < n; ++k) {
+  for (int64_t k = 0; k < n; ++k) {      // (every pair is checked before the first one counts: a refused call leaves the reaction as it was)
     const int a = c.top.tag_of(p[2 * k]), b = c.top.tag_of(p[2 * k + 1]);
     REQUIRE(a >= 0 && b >= 0 && a != b, CHEM_EINVAL, "reaction_restrict: unknown id or self pair");
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    const int a = c.top.tag_of(p[2 * k]), b = c.top.tag_of(p[2 * k + 1]);
     c.restrict_map[{std::min(a, b), std::max(a, b)}] |= 1u << reaction;
   }
   c.restricted_mask |= 1u << reaction; c.restrict_dirty = true;

@@ -29,6 +29,10 @@ struct ChemError : std::runtime_error {
   ChemError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 
+// particle ids are int64 at the C boundary; the two int32 labels that are made of ids (the default res_id, CHEM_STATE_MOLID) exist
+// only for ids that fit
+inline bool fits_int32(int64_t id) { return id >= INT32_MIN && id <= INT32_MAX; }
+
 struct TupleKey {
   uint64_t a, b;
   bool operator==(const TupleKey& o) const { return a == o.a && b == o.b; }

@@ -99,7 +99,7 @@ extern "C" {
 #define CHEM_STATE_MASS    7   /* double[n]  the mass the device integrates with: (float)m in the CHEM_PREC_F32 build */
 #define CHEM_STATE_ID      8   /* int64[n]                                         */
 #define CHEM_STATE_IMAGE   9   /* int32[n*3] periodic image counters               */
-#define CHEM_STATE_MOLID  10   /* int32[n]  lowest particle id of the bonded cluster */
+#define CHEM_STATE_MOLID  10   /* int32[n]  lowest particle id of the bonded cluster (CHEM_EINVAL with ids beyond 32 bits: chem_set_particles) */
 #define CHEM_STATE_POS_UNFOLDED 11 /* double[n*3] = pos + image*L                  */
 #define CHEM_STATE_CHARGE  12  /* double[n]; also a `what` of chem_modify_particle  */
 #define CHEM_STATE_LAMBDA  13  /* double[n]  resolution lambda at the current step (chem_set_resolution); also a `what` of chem_modify_particle */
@@ -199,7 +199,16 @@ int chem_set_cutoff(chem_ctx* ctx, double max_cutoff, double skin);
 int chem_set_dt(chem_ctx* ctx, double dt);
 /* storage.addParticles(particle_list,'id','type','pos','mass','q','res_id','state',..)
  * + decompose()  start_simulation.py:169-171, gromacs_topology.py:1418-1441.
- * vel may be NULL (zeros); q, state, res_id may be NULL (0 / 0 / id). */
+ * vel may be NULL (zeros); q, state, res_id may be NULL (0 / 0 / id).
+ *
+ * Particle ids: any distinct int64 values, in any row order.  Inside, a particle is its TAG, the rank of its id among all ids
+ * (chem_add_particles appends: its ids lie above the present ones); ids exist at this boundary only, and every call that takes
+ * an id refuses one that no particle carries with CHEM_EINVAL and leaves the context as it was (a list of ids is resolved
+ * completely before anything is changed).  Random streams are keyed by tag (chem_philox.h), so two contexts whose ids differ
+ * but stand in the same order compute the same bits, whatever the row order.  Read-backs carry ids as int64.  Two int32 labels
+ * are MADE of ids and exist only for ids that fit 32 bits: the default res_id (res_id == NULL with such an id is CHEM_EINVAL
+ * here and in chem_add_particles: pass res_id) and CHEM_STATE_MOLID (chem_get_state answers CHEM_EINVAL for a context that
+ * holds such an id; the mol_id the reaction rules read is a tag and is not affected). */
 int chem_set_particles(chem_ctx* ctx, int64_t n, const int64_t* id, const int32_t* type,
                        const double* pos, const double* vel, const double* mass,
                        const double* q, const int32_t* state, const int32_t* res_id);

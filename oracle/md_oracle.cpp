@@ -816,6 +816,7 @@ int orc_set_particles(void* c, int64_t n, const int64_t* id, const int32_t* type
                       const int32_t* res_id) {
   Orc& o = O(c);
   if (n <= 0 || !id || !type || !pos || !mass) FAIL(CHEM_EINVAL, "set_particles: null/empty");
+  if (!res_id) for (int64_t i = 0; i < n; ++i) if (id[i] < INT32_MIN || id[i] > INT32_MAX) FAIL(CHEM_EINVAL, "set_particles: the default res_id is the particle id, which does not fit its 32 bits: pass res_id");
   std::vector<int64_t> order(n);
   for (int64_t i = 0; i < n; ++i) order[i] = i;
   std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return id[a] < id[b]; });
@@ -1040,6 +1041,8 @@ int64_t orc_get_state(void* c, int what, void* out, int64_t cap) {
   int per = (what == CHEM_STATE_POS || what == CHEM_STATE_VEL || what == CHEM_STATE_FORCE || what == CHEM_STATE_IMAGE || what == CHEM_STATE_POS_UNFOLDED) ? 3 : 1;
   if (cap < n * per) FAIL(CHEM_ENOSPC, "get_state cap");
   double* d = (double*)out; int32_t* i32 = (int32_t*)out; int64_t* i64 = (int64_t*)out;
+  if (what == CHEM_STATE_MOLID && n > 0 && (o.id.front() < INT32_MIN || o.id.back() > INT32_MAX))      // (ids ascend by tag)
+    FAIL(CHEM_EINVAL, "get_state: CHEM_STATE_MOLID is an int32 read-back of particle ids and this context holds ids beyond 32 bits");
   for (int64_t i = 0; i < n; ++i) {
     switch (what) {
       case CHEM_STATE_POS: { Vec3 p = o.x[i]; double* q = &p.x; for (int k = 0; k < 3; ++k) { double s = std::floor(q[k] / o.L[k]); q[k] -= s * o.L[k]; if (q[k] >= o.L[k]) q[k] -= o.L[k]; d[3 * i + k] = q[k]; } break; }
