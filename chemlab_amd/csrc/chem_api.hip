@@ -246,6 +246,7 @@ struct Ctx {
   bool opt_dd_fastx = true;  // decomposed path: excluded partners located as slots by the standalone list kernel (ghost copies through gtag)
   int opt_ablate_list = 0;  // diagnostics (with debug_stamps): parts of the list build left out, see tools/rebuild_stamps.py
                             // (1 tables + staging only, 3 no peel, 5 exclusions ignored, 4 home particles behind the first pass of 512 skipped: the lists are incomplete)
+  int opt_bond_slots_kernel = 0; // bond pass, single domain: 0 the fused rebuild's idle tail records the bonded partners' slots, 1 k_bond_slots behind every neighbour launch
   int opt_coop_overflow = 1; // list build: the home particles behind a tile's last full pass of 512 are swept by nine lanes each (dev_nlist_tile_f32)
   int opt_row_order = 1;    // fused rebuild: a tile's force-list rows stored by length, the shortest in the last pass (chem_roworder_host.hpp); 0 = natural order
   int opt_tiles = 1;        // LDS-tiled list/force kernels when the cell grid allows
@@ -441,13 +442,11 @@ template <typename R> struct CtxT : Ctx {
   }
   double inline_K = 0, inline_r0 = 0;
   // ... and where no particle has more than kBondSlots of them (single domain, fused rebuild), the list build does not look at
-  // the exclusions at all: a streaming pass behind the tiles records the partner slots, the force kernel takes the partners'
+  // the exclusions at all: the rebuild's idle tail (slabs: k_bond_slots behind the list launch) records the partner slots, the force kernel takes the partners'
   // pair term out of its sums again (k_pair_tiles bond_mode 2).  Option bond_pass = 0: the list build removes the pairs itself.
   bool opt_bond_pass = true;
   void set_bond_pass(bool v) override { opt_bond_pass = v; }
-  DBuf<BondRec<R>> brec_dev; BondRec<R> brec_host{}; bool brec_valid = false;
   bool bond_by_pass() { return opt_bond_pass && ((use_fused && !dd_on) || (dd_on && use_tiles && opt_dd_fastx)) && bonds_inline() && excl_over == 0; }
-  bool dd_record_bonds = false;      // slabs, bond pass: the next force launch records the partner slots (set by the slab rebuild)
   bool bonds_inline() {
     if (!opt_bonds_inline || !(use_fused || (dd_on && use_tiles)) || nbent <= 0 || !harmonic_only || !bonds_excluded) return false;
     if (coul_on()) return false;      // (the epilogue takes the partner's pair term out through pair_accum, which knows no charges)
@@ -727,11 +726,14 @@ template <typename R> struct CtxT : Ctx {
     if (bonds_inline() && !(sizeof(R) == 8 && want32)) {   // (the exact fp64 builder of the int32 rows locates no slots: ensure_list32 rebuilds again)
       if (bslots.n < 2 * (size_t)n) bslots.alloc(2 * (size_t)n + 1024);      // two quads (kBondSlots = 8 words) per particle
       a.bslots = bslots.p;
-      a.bond_pass = (bond_by_pass() && !want32) ? 1 : 0;    // (the int32 rows must leave the excluded pairs out: ensure_list32 rebuilds again behind them)
+      a.bond_pass = (bond_by_pass() && !want32) ? (opt_bond_slots_kernel ? 2 : 1) : 0;    // (the int32 rows must leave the excluded pairs out: ensure_list32 rebuilds again behind them)
       if (excl_over == 0) a.nbent = 0;                      // no work list needed; otherwise it holds the owners with > kBondSlots exclusions only
     }
     if (dbg_on || want32) hipLaunchKernelGGL((k_rebuild_fused<R, 512, true>), dim3(fused_grid_diag), dim3(512), list_lds_need(true), stream, a);
     else hipLaunchKernelGGL((k_rebuild_fused<R, 512>), dim3(fused_grid), dim3(512), list_lds_need(false), stream, a);
+    if (a.bond_pass == 2)      // (leaves at once unless the launch in front of it has rebuilt: DevCtl::need_rebuild)
+      hipLaunchKernelGGL((k_bond_slots<R>), dim3(ntiles), dim3(256), 0, stream, ntiles, (const TileLDS<R>*)tdesc.p, (const int*)tag.p, (const int*)excl_start.p,
+                         (const int*)excl_list.p, (const int*)rtag.p, (const int*)nullptr, 0, 0x7fffffff, (const V4*)x4.p, box, bslots.p, ctl.p);
     fused_par ^= 1;
   }
 
@@ -1143,7 +1145,7 @@ template <typename R> struct CtxT : Ctx {
     if (device_ready && !particles_dirty) ckpt_count_builds();      // (a load into a context that has run)
     state_mirror_stale = false; baro_replan_pending = false; react_tables_reserved = false;
     excl_deg.clear(); excl_deg_upto = 0; excl_over = 0;
-    brec_valid = false; box_dev_valid = false;
+    box_dev_valid = false;
   }
 
   // ---- per-tag CSR tables built on the device from flat, append-only arrays (md_kernels.hpp "Per-tag CSR tables") ----
@@ -1365,14 +1367,14 @@ template <typename R> struct CtxT : Ctx {
     DevCtl* c = ctl.p;
     const R rl2 = (R)((rc + skin_eff()) * (rc + skin_eff())), rl2_rows = (R)((rc + skin) * (rc + skin));   // (they differ on the tile path only)
     if (use_tiles) {
-      uint4* bs = nullptr;      // inline bonds (decomposed path: the standalone list kernel records the partner slots ...)
+      uint4* bs = nullptr, *record = nullptr;      // inline bonds (decomposed path: the standalone list kernel records the partner slots ...)
       int list_excl = has_excl;
       if (dd_on && bonds_inline()) {
         if (bslots.n < 2 * (size_t)acap()) bslots.alloc(2 * (size_t)acap() + 1024);
         bs = bslots.p;
-        // (... unless the bond pass is on: the list build ignores the exclusions = bonds, the force launch behind this rebuild
-        //  records the partner slots and every force launch takes the partners' pair term out again, as on the fused path)
-        if (bond_by_pass() && !want32) { bs = nullptr; list_excl = 0; dd_record_bonds = true; }
+        // (... unless the bond pass is on: the list build ignores the exclusions = bonds, k_bond_slots behind it records the
+        //  partner slots and every force launch takes the partners' pair term out again, as on the fused path)
+        if (bond_by_pass() && !want32) { bs = nullptr; list_excl = 0; record = bslots.p; }
       }
       hipLaunchKernelGGL((k_tile_desc<R>), dim3(std::min(ntiles, 2048)), dim3(128), 0, stream, ntiles, tile_cap, cell_start.p, box, tdesc.p, c, (const int*)cell_sub.p);
       hipLaunchKernelGGL((k_tile_scan<R>), dim3(1), dim3(1024), 0, stream, ntiles, tdesc.p, c);
@@ -1390,6 +1392,9 @@ template <typename R> struct CtxT : Ctx {
       hipLaunchKernelGGL((k_nlist_tiles<R, 512>), dim3(ntiles), dim3(512), list_lds_need(want32), stream, ntiles, tile_cap, x4.p, tag.p, tdesc.p, rl2,
                          excl_start.p, excl_list.p, list_excl, act, ntypes, nl16.p, S, nnh.p, want32 ? nlist.p : (int*)nullptr, S, nn.p, c, rl2_rows, bs,
                          bxp, (const int*)rtag.p, (const int*)gtag.p, G, G + n, opt_coop_overflow);
+      if (record)
+        hipLaunchKernelGGL((k_bond_slots<R>), dim3(ntiles), dim3(256), 0, stream, ntiles, (const TileLDS<R>*)tdesc.p, (const int*)tag.p, (const int*)excl_start.p,
+                           (const int*)excl_list.p, (const int*)rtag.p, (const int*)gtag.p, G, G + n, (const V4*)x4.p, box, record, c);
     } else if (box.nc[0] > 0)
       hipLaunchKernelGGL((k_nlist_cells<R, 1536>), dim3(std::min(box.ncell, 2560)), dim3(256), 0, stream, n, x4.p, tag.p, cell_start.p, box, rl2,
                          excl_start.p, excl_list.p, has_excl, nlist.p, nn.p, S, c);
@@ -1670,21 +1675,6 @@ template <typename R> struct CtxT : Ctx {
   // ---- forces -------------------------------------------------------------------------
   int pick_tpp() const { return chem::pick_tpp(use_tiles, n, opt_tpp); }
 
-  // device copy of what the force launch behind a rebuild needs to record the partner slots (refreshed when a pointer or the box changed)
-  const BondRec<R>* bond_rec_dev() {
-    BondRec<R> now;
-    std::memset(&now, 0, sizeof(now));      // (compared bytewise below: no indeterminate padding)
-    now.tag = tag.p; now.excl_start = excl_start.p; now.excl_list = excl_list.p; now.rtag = rtag.p;
-    now.gtag = dd_on ? gtag.p : nullptr; now.real0 = dd_on ? G : 0; now.real1 = dd_on ? G + n : 0x7fffffff;
-    std::memcpy(&now.box, &box, sizeof(box));
-    if (!brec_dev.p) brec_dev.alloc(1);
-    if (!brec_valid || std::memcmp(&now, &brec_host, sizeof(now)) != 0) {
-      brec_host = now; brec_valid = true;
-      HIPCHK(hipMemcpyAsync(brec_dev.p, &brec_host, sizeof(now), hipMemcpyHostToDevice, stream));
-    }
-    return brec_dev.p;
-  }
-
   // what a pair launch asks its plan with (pair_plan, tensor_plan)
   PairInput pair_input(bool energy) {
     PairInput in{use_tiles, n, opt_tpp, pair_bs, energy, coul_on(), res_pairs_on(), caps_on(), lj_only, uniform_lj, cubic_tab, dbg_on || opt_ablate != 0, 0, 0, 0, 0};
@@ -1693,15 +1683,8 @@ template <typename R> struct CtxT : Ctx {
     return in;
   }
   // bond_mode of a pair launch over the tiles: 0 no inline bonds, 1 / 2 what the LAST rebuild did (both only change where a rebuild
-  // is forced), 3 = 2 + record the partner slots now -- on slabs the host knows which launch follows a rebuild, and takes the note back
-  int inline_bond_mode() {
-    int bond_mode = bonds_inline() ? (bond_by_pass() ? 2 : 1) : 0;
-    if (bond_mode == 2 && dd_on) {
-      if (dd_record_bonds) bond_mode = 3;
-      if (pair_subset != 1) dd_record_bonds = false;      // (a launch of the interior tiles alone is followed by the boundary launch of the same step)
-    }
-    return bond_mode;
-  }
+  // is forced); the partner slots are recorded by the rebuild itself either way
+  int inline_bond_mode() { return bonds_inline() ? (bond_by_pass() ? 2 : 1) : 0; }
 
   // the pair forces into fdst (ENERGY: and the energy words into eout); the kernel is chem_launch_host.hpp's choice
   template <bool ENERGY> int launch_pair(V4* fdst) {
@@ -1711,7 +1694,6 @@ template <typename R> struct CtxT : Ctx {
     const PairVariant& v = plan.v;
     const int bond_mode = inline_bond_mode();
     const bool inline_now = bond_mode != 0;
-    const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
     if (use_tiles) {
       // which tiles: all (default), or the interior / boundary subset of a slab (see TileSub)
       const TileLayers tl = tile_subset(ntiles, ntxy(), pair_subset);
@@ -1730,7 +1712,7 @@ template <typename R> struct CtxT : Ctx {
         else if constexpr (M == 6) feature(kern, cap_args());
         else if constexpr (M == 7) feature(kern, res_args(), cap_args());
         else launch(kern, uni, eout.p, hs, ctl.p, pair_guard, opt_ablate, dbg_on ? dbgbuf.p : (long long*)nullptr, ts, pair_da,
-                    (inline_now && (!ENERGY || bond_mode >= 2)) ? bslots.p : (uint4*)nullptr, inline_K, inline_r0, bond_mode, act, brec);
+                    (inline_now && (!ENERGY || bond_mode >= 2)) ? bslots.p : (uint4*)nullptr, inline_K, inline_r0, bond_mode, act);
       });
       return ntiles;
     }
@@ -1993,15 +1975,14 @@ template <typename R> struct CtxT : Ctx {
     const CapArgs<R> cp = (v.mode == 6 || v.mode == 7) ? cap_args() : CapArgs<R>{};
     bool found = false;
     if (use_tiles) {
-      const int bond_mode = inline_bond_mode();      // (pair_subset is 0 here: a launch behind a slab rebuild records the partner slots)
-      const BondRec<R>* brec = bond_mode >= 2 ? bond_rec_dev() : nullptr;
+      const int bond_mode = inline_bond_mode();
       const TileSub ts{0, ntiles, 0};
       const size_t lds = pair_lds_bytes();
       found = pick_among<3, 4, 5, 6, 7>(v.mode, [&](auto M_) {
         auto kern = &k_pair_tiles_tensor<R, decltype(M_)::value>;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, stream, nblk, tile_cap, x4.p, fdst, tdesc.p, nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, ts,
-                           (v.mode == 3 && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, brec, ca, ra, cp, tout);
+                           (v.mode == 3 && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, ca, ra, cp, tout);
         return true;
       });
     } else {
@@ -4433,6 +4414,7 @@ int chem_set_option(chem_ctx* ctx, const char* name, double value) {
   else if (k == "rebuild_criterion") { CTX.opt_criterion = value != 0 ? 1 : 0; CTX.resort = true; CTX.geom_dirty = true; }
   else if (k == "bonds_inline") { CTX.opt_bonds_inline = value != 0; CTX.resort = true; }
   else if (k == "bond_pass") { CTX.set_bond_pass(value != 0); CTX.resort = true; }
+  else if (k == "bond_slots_kernel") { CTX.opt_bond_slots_kernel = value != 0 ? 1 : 0; CTX.resort = true; }
   else if (k == "bucket_cap") { CTX.opt_bucket_cap = (int)value; CTX.geom_dirty = true; }
   else if (k == "tile_split") { CTX.opt_tile_split = (int)value; CTX.geom_dirty = true; CTX.resort = true; }
   else if (k == "list_skin") { CTX.opt_list_skin = value; CTX.geom_dirty = true; CTX.resort = true; }

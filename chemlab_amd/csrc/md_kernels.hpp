@@ -2452,48 +2452,74 @@ __device__ __forceinline__ int tile_partner_slot(const TileLDS<R>& T, int g, con
   }
   return -1;
 }
-// what the force kernel needs to record the bonded partners' slots itself (bond_mode 2, launch of a rebuild step)
-template <typename R> struct BondRec { const int *tag, *excl_start, *excl_list, *rtag, *gtag; int real0, real1; Box<R> box; };   // (gtag, real0, real1: slabs)
-// The force launch behind a rebuild records, for home particle p of the tile described by *T, the LDS slots of its bonded
-// (= excluded) partners: tag -> exclusion row -> partner index -> partner position -> cell -> slot through the tile tables;
-// written out for the launches up to the next rebuild, first quad returned.  A real function call on purpose: inlined, its
-// registers cost the hot loop of k_pair_tiles 84-116 bytes of spills per lane; it runs once per list lifetime.  The partners are
-// walked one after the other (the launch behind a rebuild takes 128 us instead of 79): issuing each level of the chain for
-// four partners at once needs more registers in the callee, and THAT slowed every launch (same box, melt / late stage:
-// 62.7 / 85.8 us -> 66.7 / 93.8 us per force launch; tools/ab_late_lib.sh).
+// The list build of the bond pass (bond_mode 2) ignores the exclusions; the partner slots of every home particle are recorded
+// behind it, once per list lifetime, for the force launches up to the next rebuild (eight words per particle: two quads, ~0u
+// = no partner).  tag -> exclusion row -> partner index -> partner position -> cell -> slot through the tile tables in LDS.
+// One lane per home particle of the tile described by T; the loads of each level of the chain are issued for up to four
+// partners before the first is consumed, the second quad (five to eight partners, rare) takes the same path once more.
+// gtag, real0, real1: slabs (the tag's ghost copy, the index range of the real particles), as in tile_partner_slot.
+// Runs in the idle tail of k_rebuild_fused (single domain) and as k_bond_slots behind every other list build.  Inlined into the
+// rebuild it costs 28 bytes of scratch per lane and no register (128, occupancy 4); as a real call it cost 112.
 template <typename R>
-__device__ __noinline__ uint4 bond_record(const TileLDS<R>* T, int p, const BondRec<R>* __restrict__ brec_p, const Vec4<R>* __restrict__ x4,
-                                          uint4* __restrict__ bslots, DevCtl* ctl) {
-  const BondRec<R>& brec = *brec_p;
-  unsigned int w[kBondSlots];
+__device__ __forceinline__ void bond_slots_quad(const TileLDS<R>& T, const int e0, const int ne, const int* __restrict__ excl_list,
+                                                const int* __restrict__ rtag, const int* __restrict__ gtag, const int real0, const int real1,
+                                                const Vec4<R>* __restrict__ x4, const Box<R>& bx, const int hz, DevCtl* ctl, unsigned int* w) {
+  int tj[4], g[4];
+  Vec4<R> xg[4];
 #pragma unroll
-  for (int k = 0; k < kBondSlots; ++k) w[k] = ~0u;
-  const int tg = brec.tag[p];
-  const int e0 = brec.excl_start[tg], e1 = brec.excl_start[tg + 1];
-  int hz = 0;      // stencil row (z) of the home particle: from the home run that holds p
-  if (brec.box.zghost) {
-#pragma unroll 1
-    for (int k = 0; k < NHSEG; ++k) if (p >= T->hstart[k] && p < T->hstart[k] + (T->hoff[k + 1] - T->hoff[k])) hz = k / HY + 1;
-  }
-  if (e1 > e0 && e1 - e0 <= kBondSlots) {
+  for (int k = 0; k < 4; ++k) tj[k] = k < ne ? excl_list[e0 + k] : -1;
 #pragma unroll
-    for (int k = 0; k < kBondSlots; ++k) {
-      if (e0 + k >= e1) break;
-      const int tj = brec.excl_list[e0 + k];
-      const int g = brec.rtag[tj];
-      int sl = g >= 0 ? tile_partner_slot<R>(*T, g, x4[g], brec.box, ctl, brec.real0, brec.real1, hz) : -1;
-      if (sl < 0 && brec.gtag) {      // slabs: the tag's ghost copy
-        const int g2 = brec.gtag[tj];
-        if (g2 >= 0 && g2 != g) sl = tile_partner_slot<R>(*T, g2, x4[g2], brec.box, ctl, brec.real0, brec.real1, hz);
-      }
-      if (sl < 0) ctl->bond_slot_miss = 1;      // every bonded partner sits inside the stencil (bond length << cell edge)
-      else w[k] = (unsigned int)sl;
+  for (int k = 0; k < 4; ++k) g[k] = k < ne ? rtag[tj[k]] : -1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) xg[k] = g[k] >= 0 ? x4[g[k]] : Vec4<R>{};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k >= ne) break;
+    int sl = g[k] >= 0 ? tile_partner_slot<R>(T, g[k], xg[k], bx, ctl, real0, real1, hz) : -1;
+    if (sl < 0 && gtag) {      // slabs: the tag's ghost copy
+      const int g2 = gtag[tj[k]];
+      if (g2 >= 0 && g2 != g[k]) sl = tile_partner_slot<R>(T, g2, x4[g2], bx, ctl, real0, real1, hz);
     }
+    if (sl < 0) ctl->bond_slot_miss = 1;      // every bonded partner sits inside the stencil (bond length << cell edge)
+    else w[k] = (unsigned int)sl;
   }
-  const uint4 q0 = make_uint4(w[0], w[1], w[2], w[3]);
-  bslots[2 * (size_t)p] = q0;
-  if (w[3] != ~0u) bslots[2 * (size_t)p + 1] = make_uint4(w[4], w[5], w[6], w[7]);      // (only read behind a full first quad)
-  return q0;
+}
+template <typename R>
+__device__ __forceinline__ void dev_bond_slots_tile(const TileLDS<R>& T, const int* __restrict__ tag, const int* __restrict__ excl_start,
+                                                    const int* __restrict__ excl_list, const int* __restrict__ rtag, const int* __restrict__ gtag,
+                                                    const int real0, const int real1, const Vec4<R>* __restrict__ x4, const Box<R>& bx,
+                                                    uint4* __restrict__ bslots, DevCtl* ctl) {
+  const int nhome = T.geom[4];
+  for (int q = threadIdx.x; q < nhome; q += (int)blockDim.x) {
+    int sgi = 0;
+#pragma unroll
+    for (int k = 1; k < NHSEG; ++k) sgi += (q >= T.hoff[k]) ? 1 : 0;
+    const int p = T.hstart[sgi] + (q - T.hoff[sgi]);
+    const int hz = bx.zghost ? sgi / HY + 1 : 0;      // stencil row (z) of the home particle
+    const int tg = tag[p];
+    const int e0 = excl_start[tg], ne = excl_start[tg + 1] - e0;
+    unsigned int w[kBondSlots];
+#pragma unroll
+    for (int k = 0; k < kBondSlots; ++k) w[k] = ~0u;
+    if (ne > 0 && ne <= kBondSlots) {      // (more than kBondSlots: the particle's bonds stay with the work list)
+      bond_slots_quad<R>(T, e0, ne < 4 ? ne : 4, excl_list, rtag, gtag, real0, real1, x4, bx, hz, ctl, w);
+      if (ne > 4) bond_slots_quad<R>(T, e0 + 4, ne - 4, excl_list, rtag, gtag, real0, real1, x4, bx, hz, ctl, w + 4);
+    }
+    bslots[2 * (size_t)p] = make_uint4(w[0], w[1], w[2], w[3]);
+    if (w[3] != ~0u) bslots[2 * (size_t)p + 1] = make_uint4(w[4], w[5], w[6], w[7]);      // (only read behind a full first quad)
+  }
+}
+// ... behind the list launch of the unfused chain and of a slab rebuild: one workgroup per tile, the tables from desc[]
+template <typename R>
+__global__ __launch_bounds__(256) void k_bond_slots(int ntiles, const TileLDS<R>* __restrict__ desc, const int* __restrict__ tag,
+                                                    const int* __restrict__ excl_start, const int* __restrict__ excl_list,
+                                                    const int* __restrict__ rtag, const int* __restrict__ gtag, int real0, int real1,
+                                                    const Vec4<R>* __restrict__ x4, const Box<R> box, uint4* __restrict__ bslots, DevCtl* ctl) {
+  if (!ctl->need_rebuild || ctl->halt) return;      // (halt: the rebuild in front of this launch could not finish its lists)
+  __shared__ TileLDS<R> T;
+  tile_load_desc<R>(T, desc, blockIdx.x);
+  __syncthreads();
+  dev_bond_slots_tile<R>(T, tag, excl_start, excl_list, rtag, gtag, real0, real1, x4, box, bslots, ctl);
 }
 
 // (fold != nullptr: `gathered` holds n * kFoldSlots bit patterns of squared displacements -- every rank's fold words, see
@@ -2519,7 +2545,6 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                                                    double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
                                                    DecideArgs da, uint4* __restrict__ bslots,
                                                    double bond_K, double bond_r0, int bond_mode, ActMask bact,
-                                                   const BondRec<R>* __restrict__ brec,
                                                    const CoulArgs<R> ca, const ResArgs<R> ra, const CapArgs<R> cp = CapArgs<R>{},
                                                    double* __restrict__ tout = nullptr) {
   constexpr bool LJONLY = MODE == 1 || MODE == 2, CUBIC = MODE >= 3, COUL = MODE == 4, RES = MODE == 5 || MODE == 7, CAPPED = MODE == 6 || MODE == 7;
@@ -2608,10 +2633,6 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   int p = -1, cnt = 0, hslot = 0, qq = 0;
   uint4 pkv[NCH];
   uint4 bwv = make_uint4(~0u, ~0u, ~0u, ~0u);
-  // (uniform.  Single domain: set by the rebuild of THIS step, cleared by the next idle decision; slabs: the host rebuilds, it
-  //  asks for the record with bond_mode 3 = mode 2 + record now)
-  //  (guard 3: a step without a rebuild, and workgroup 0 is writing the word)
-  const bool bond_rec = bslots && brec && ((bond_mode == 2 && guard != 3 && ctl->need_rebuild != 0) || bond_mode == 3);
 #ifndef CHEM_NT_PRE
 #define CHEM_NT_PRE 1
 #endif
@@ -2628,7 +2649,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
     const int hr = (sgi / HY + 1) * SY + (sgi % HY + 1);
     hslot = T.rowoff[hr] + T.celloff[hr][1] + inrun;      // the home particle's own slot in the staged tile
     cnt = row_word_count(cw);
-    if (bslots && !bond_rec) bwv = bslots[2 * (size_t)p];   // (inline bonds: first quad, issued with the list chunks, consumed after the pair loop)
+    if (bslots) bwv = bslots[2 * (size_t)p];   // (inline bonds: first quad, issued with the list chunks, consumed after the pair loop)
 #pragma unroll
     for (int c = 0; c < NCH; ++c)                           // the tile's region is always allocated: safe before cnt is known
       pkv[c] = (sub + c * TPP) * 8 < S16 ? (CHEM_NT_PRE ? nt_load_u4(&reg[(size_t)(sub + c * TPP) * nhome + q]) : reg[(size_t)(sub + c * TPP) * nhome + q]) : make_uint4(0, 0, 0, 0);
@@ -2776,10 +2797,9 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
         // image (tile-local coordinates: 2.4e-7 in the fp32 build, exact in fp64) -- no bonded launch, no second pass over f4.
         // bond_mode 1: the list build removed the excluded pairs from the force list (decomposed path) -- add the bonds.
         // bond_mode 2: the list build IGNORED the exclusions (single domain: locating the partners inside the list phase cost
-        //   196 us of a 709-us late-stage rebuild, profiles/round3_rebuild_ablation.txt; a streaming pass behind it records the
-        //   slots instead) -- the partners' pair term is in the sums above: take it out again, then add the bonds.  An excluded
+        //   196 us of a 709-us late-stage rebuild, profiles/round3_rebuild_ablation.txt; the rebuild's idle tail records the
+        //   slots instead, dev_bond_slots_tile) -- the partners' pair term is in the sums above: take it out again, then add the bonds.  An excluded
         //   pair within the cutoff now was within the list radius at the build, i.e. it IS in the list if its type pair is active.
-        if (bond_rec) bwv = bond_record<R>(&T, p, brec, x4, bslots, ctl);      // (the launch behind a rebuild, bond_mode 2)
         const R m2K = (R)(-2.0 * bond_K), r0b = (R)bond_r0;              // (one parameter set: kernel arguments, no table)
         auto bond_quad = [&](const uint4 bq) {
           const unsigned int bws[4] = {bq.x, bq.y, bq.z, bq.w};
@@ -2859,11 +2879,10 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
                                                    int ntypes, const Vec4<R>* __restrict__ tab, UniLJ uni, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
                                                    DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
-                                                   double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{},
-                                                   const BondRec<R>* __restrict__ brec = nullptr) {      // (device copy: by value it was spilled to every lane's stack at kernel start)
+                                                   double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{}) {
   static_assert(MODE < 4, "MODE 4 is k_pair_tiles_q, MODE 5 k_pair_tiles_res, MODE 6 k_pair_tiles_cap, MODE 7 k_pair_tiles_rescap");
   pair_tiles_body<R, TPP, ENERGY, BS, MODE, DIAG>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, uni, eout, half_skin, ctl, guard, ablate, dbg,
-                                                  sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, brec, CoulArgs<R>{}, ResArgs<R>{});
+                                                  sub_, da, bslots, bond_K, bond_r0, bond_mode, bact, CoulArgs<R>{}, ResArgs<R>{});
 }
 // MODE 4: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2874,7 +2893,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CoulArgs<R> ca) {
   pair_tiles_body<R, 1, ENERGY, 512, 4, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, ca, ResArgs<R>{});
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, ca, ResArgs<R>{});
 }
 // MODE 5: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2885,7 +2904,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra) {
   pair_tiles_body<R, 1, ENERGY, 512, 5, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ra);
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra);
 }
 // MODE 6: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2896,7 +2915,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CapArgs<R> cp) {
   pair_tiles_body<R, 1, ENERGY, 512, 6, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ResArgs<R>{}, cp);
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ResArgs<R>{}, cp);
 }
 // MODE 7: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2907,7 +2926,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra, CapArgs<R> cp) {
   pair_tiles_body<R, 1, ENERGY, 512, 7, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, nullptr, CoulArgs<R>{}, ra, cp);
+                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra, cp);
 }
 
 // =======================================================================================
@@ -3360,6 +3379,7 @@ struct GridBar {
   unsigned int gen[32];        // generation (release flag)
   unsigned int tq[8][32];      // tile queue heads, one per XCD
   unsigned int prepq[32];      // head of the bonded-work-list chunk queue
+  unsigned int bondq[32];      // head of the queue of tiles whose bonded partners' slots are to be recorded (bond pass)
   long long stamp[16];         // wall_clock64 of workgroup 0 at the phase boundaries of the last rebuild (diagnostics)
 };
 
@@ -3418,8 +3438,9 @@ template <typename R> struct FusedArgs {
   unsigned long long* blockmax; DevCtl* ctl; GridBar* gb;
   const int* bstart; const BondedEntry* bent; int4 *bwork, *bj; int nbent;
   uint4* bslots;         // inline bonds (non-null: the bonded partners' LDS slots are recorded, eight words per particle)
-  int bond_pass;         // 1: the list build ignores the exclusions (= bonds); the force launch of the rebuild step records the partner
-                         //    slots itself and every force launch takes the partners' pair term out again (k_pair_tiles bond_mode 2);
+  int bond_pass;         // 1: the list build ignores the exclusions (= bonds); workgroups that have run out of tiles record the partner
+                         //    slots (dev_bond_slots_tile) and every force launch takes the partners' pair term out again (k_pair_tiles bond_mode 2);
+                         //    2: as 1, but k_bond_slots behind this launch records the slots (option bond_slots_kernel);
                          //    0: the list build removes the excluded pairs and records their slots
   Box<R> box; ActMask act;
   long long* wgst;   // diagnostics (option debug_stamps=2): 8 wall-clock stamps per workgroup of the last rebuilding launch
@@ -3514,7 +3535,7 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
 #define WGST(K) do { if (wst && t == 0) wst[K] = wall_clock64(); } while (0)
   WGST(0);
   if (b == 0 && t < 8) a.gb->tq[t][0] = 0u;
-  if (b == 0 && t == 8) { ctl->bw64 = 0ull; a.gb->prepq[0] = 0u; }
+  if (b == 0 && t == 8) { ctl->bw64 = 0ull; a.gb->prepq[0] = 0u; a.gb->bondq[0] = 0u; }
   { MigBuf<R> none{}; dev_bin<R>(0, a.n, a.x4, a.v4, a.tag, a.img4, a.box, a.cell_cnt, a.cell_of, a.slot_of, none, none, ctl, a.bucket, a.bcap, a.btot, a.seg_shift); }
   WGST(1);
   if (!grid_barrier(a.gb, ctl)) return; WGST(2); if (b == 0 && t == 0) { const long long st = wall_clock64(); a.gb->stamp[1] = st; a.gb->stamp[2] = st; a.gb->stamp[3] = st; }
@@ -3676,6 +3697,21 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
           if (c == cc) { const int p_ = off + base[cc] + __popcll(m & lanemask_lt()); ord_w[p_] = off + k; pos_w[off + k] = p_; }
           base[cc] += __popcll(m);
         }
+      }
+    }
+    // bond pass: the list build ignored the exclusions, the bonded partners' slots of every home particle are recorded here for
+    // the force launches up to the next rebuild (nothing in this launch reads them).  One tile per item, claimed like the chunks
+    // of the work list below by workgroups that have run out of tiles; everything an item reads -- rtag, the sorted copies,
+    // cell_start / cell_sub, the exclusion rows -- is complete since the last barrier, so nobody waits for anybody.
+    if (a.bond_pass == 1 && a.bslots) {
+      for (;;) {
+        __syncthreads();
+        if (t == 0) s_tile = (int)atomicAdd(&a.gb->bondq[0], 1u);
+        __syncthreads();
+        const int tile = s_tile;
+        if (tile >= a.ntiles) break;
+        tile_tables<R>(T, a.CAP, tile, a.cell_start, a.box, ctl, a.cell_sub);      // ends with a workgroup barrier
+        dev_bond_slots_tile<R>(T, a.tago, a.excl_start, a.excl_list, a.rtag, nullptr, 0, 0x7fffffff, a.x4o, a.box, a.bslots, ctl);
       }
     }
     // bonded work list (nothing in this launch reads it): chunks of BS particles from a queue, taken by workgroups that
@@ -3992,8 +4028,6 @@ __global__ __launch_bounds__(256) void k_pair_force_tensor(int n, const Vec4<R>*
 }
 // ... tiles: the TENSOR instantiation of pair_tiles_body, one lane per particle, 512 threads.  MODE 3 (general, both table kinds:
 // what the energy pass of MODE 0..3 evaluates, the excluded pairs of inline bonds taken out again) and 4..7.
-// (The launch bounds are those of the 512-thread force kernels on purpose: bond_record is a real function, and the register
-//  budget of a function follows from the bounds of ALL kernels that call it -- a caller with looser bounds changes the others.)
 template <typename R, int MODE>
 __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_tiles_tensor(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4,
                                                            const TileLDS<R>* __restrict__ desc, const unsigned short* __restrict__ nl16,
@@ -4001,10 +4035,10 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                            const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
                                                            int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                            double half_skin, DevCtl* ctl, TileSub sub_, uint4* __restrict__ bslots, int bond_mode, ActMask bact,
-                                                           const BondRec<R>* __restrict__ brec, CoulArgs<R> ca, ResArgs<R> ra, CapArgs<R> cp, double* __restrict__ tout) {
+                                                           CoulArgs<R> ca, ResArgs<R> ra, CapArgs<R> cp, double* __restrict__ tout) {
   static_assert(MODE >= 3 && MODE <= 7, "tile tensor kernels: MODE 3..7");
   pair_tiles_body<R, 1, true, 512, MODE, false, true>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, 0, 0, nullptr,
-                                                      sub_, DecideArgs{}, bslots, 0.0, 0.0, bond_mode, bact, brec, ca, ra, cp, tout);
+                                                      sub_, DecideArgs{}, bslots, 0.0, 0.0, bond_mode, bact, ca, ra, cp, tout);
 }
 
 // =======================================================================================
