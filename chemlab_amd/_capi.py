@@ -215,6 +215,7 @@ PRODUCT_ONLY = {
     "nb_coulomb": (_i, [_P, _i, _i, _d, _d]),   # (the CPU oracle has no Coulomb term)
     "get_coulomb": (_i, [_P, _pd, _pd]),
     "list_set_hybrid": (_i, [_P, _i, _d, _d]),   # (the CPU oracle has no hybrid lists)
+    "list_set_hybrid_tuples": (_i, [_P, _i, _d, _d]),   # (nor hybrid angles and dihedrals)
     "list_get_lambda": (_i64, [_P, _i, _pd, _i64]),
     # per-particle resolution lambda (the CPU oracle has none)
     "nb_resolution": (_i, [_P, _i, _i, _i, _d]),

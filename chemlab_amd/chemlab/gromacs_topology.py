@@ -392,6 +392,7 @@ def set_angle_interactions(espressopp, system, gt, dynamic_type_ids=(), table_di
             p = [float(x) for x in spec["params"]]
             ids = [gt.used_atomsym_atomtype[n] for n in (n1, n2, n3)]
             inter.setPotential(ids[0], ids[1], ids[2], pot_of(1, p))
+        ftl.typed_class = "FixedTripleListTypesAngularHarmonic"
         system.addInteraction(inter, "angle_dynamic")
         out["angle_dynamic"] = (ftl, inter)
     return out
@@ -455,11 +456,30 @@ def set_dihedral_interactions(espressopp, system, gt, dynamic_type_ids=(), table
                 continue
             ids = [gt.used_atomsym_atomtype[n] for n in (n1, n2, n3, n4)]
             inter.setPotential(ids[0], ids[1], ids[2], ids[3], pot_of(func, [float(x) if func != 8 else x for x in spec["params"]]))
+        fql.typed_class = typed_cls[func]
         system.addInteraction(inter, "dihedral_dynamic")
         out["dihedral_dynamic"] = (fql, inter)
     if len(funcs) > 1:
         raise NotImplementedError("dynamic dihedrals of more than one functional form in one topology")
     return out
+
+
+def add_hybrid_tuple_list(espressopp, system, lists, kind):
+    """--t_hybrid_angle / --t_hybrid_dihedral (app_args.py:206-209): beside `<kind>_dynamic` (kind "angle" or "dihedral") a
+    second, empty Types list of the Lambda kind with the same registered potentials, `<kind>_hybrid`.  The driver points the
+    topology manager at it, so what a reaction spawns ramps up from lambda = 0, while the topology's own tuples stay in the
+    plain dynamic list at full strength.  Returns (list, interaction), or None where the topology has no dynamic list."""
+    if kind + "_dynamic" not in lists:
+        return None
+    dyn_list, dyn_inter = lists[kind + "_dynamic"]
+    list_cls = espressopp.FixedTripleListLambda if kind == "angle" else espressopp.FixedQuadrupleListLambda
+    hyb = list_cls(system.storage, 0.0)
+    inter = getattr(espressopp.interaction, dyn_list.typed_class.replace("ListTypes", "ListTypesLambda"))(system, hyb)
+    for types_, pot in dyn_inter._typed.items():
+        inter.setPotential(*(tuple(types_) + (pot,)))
+    system.addInteraction(inter, kind + "_hybrid")
+    lists[kind + "_hybrid"] = (hyb, inter)
+    return hyb, inter
 
 
 def set_pair_interactions(espressopp, system, gt, lj_cutoff, dynamic_type_ids=(), qq_cutoff=0.0, pairs_coulomb=False):

@@ -1189,7 +1189,7 @@ template <typename R> struct CtxT : Ctx {
   // wait = false: everything is only enqueued (reaction step: the host goes on with its own bookkeeping meanwhile);
   // the table sizes the host needs (entry and owner counts) are upper bounds from the flat arrays, the kernels
   // themselves read the exact figures from device memory
-  size_t fent_members = 0;     // sum of arity * (2 for quadruples) over the flat tuples
+  size_t fent_members = 0;     // sum of arity * HostList::entry_width over the flat tuples
   std::vector<HBondedParam> stage_hp; std::vector<HostTopology::HSlotKey> stage_hk;
   PinnedVec<int4> stage_ne; PinnedVec<int> stage_nl; PinnedVec<int2> stage_ep;   // pinned: a pageable async copy blocks for ~0.1 ms
   void upload_bonded(bool full = true, bool wait = true) {
@@ -1240,13 +1240,15 @@ template <typename R> struct CtxT : Ctx {
       for (size_t e = list_uploaded[li]; e < have; ++e) {
         const int32_t* t = &l.ent[e * l.arity];
         int z = l.arity > 2 ? t[2] : -1;
-        if (l.hybrid) {      // the birth step travels in the unused third tag (BondedEntry::t2)
+        if (l.hybrid) {      // the birth step travels in the unused third tag (BondedEntry::t2) of a pair,
           if (l.birth[e] < 0 || l.birth[e] > 0x7fffffff) throw ChemError(CHEM_ESTATE, "hybrid list: birth step beyond 2^31 - 1");
-          z = encode_birth(l.birth[e]);
+          if (l.arity == 2) z = encode_birth(l.birth[e]);
         }
         ne.push_back(make_int4(t[0], t[1], z, l.arity > 3 ? t[3] : -1)); nl.push_back((int)li);
+        // of a triple or quadruple in a second flat record that belongs to no list (k_bt_count passes it by, k_bt_fill reads it)
+        if (l.hybrid && l.arity > 2) { ne.push_back(make_int4(encode_birth(l.birth[e]), -1, -1, -1)); nl.push_back(-1); }
       }
-      fent_members += (have - list_uploaded[li]) * (size_t)(l.arity == 4 ? 8 : l.arity);
+      fent_members += (have - list_uploaded[li]) * (size_t)(l.arity * l.entry_width());
       list_uploaded[li] = have;
     }
     grow(fent, fent_n, fent_n + ne.size(), stream); grow(flist, fent_n, fent_n + ne.size(), stream);
@@ -1289,7 +1291,7 @@ template <typename R> struct CtxT : Ctx {
     if (react_tables_reserved) return;
     react_tables_reserved = true;
     const size_t nt = (size_t)(nglob > 0 ? nglob : (int)top.n);
-    const size_t per = top.spawns_tuples() ? 4 : 1;      // tuples a new bond may add (itself + spawned angles / dihedrals)
+    const size_t per = top.spawns_tuples() ? (top.any_hybrid() ? 8 : 4) : 1;      // flat records a new bond may add (itself + spawned angles / dihedrals, two each in a hybrid list)
     for (auto& d : reactions) if (!d.is_virtual && d.bond_list >= 0 && d.bond_list < (int)top.lists.size()) {
       HostList& l = top.lists[d.bond_list];
       l.seen.reserve(l.seen.used + nt); l.ent.reserve(l.ent.size() + 2 * nt);
@@ -3985,6 +3987,19 @@ int chem_list_set_hybrid(chem_ctx* ctx, int list, double lambda0, double rate) {
   REQUIRE(rc != CHEM_EINVAL, CHEM_EINVAL, "list_set_hybrid: needs a pair list, lambda0 in [0, 1] and a finite rate >= 0");
   REQUIRE(rc != CHEM_ESTATE, CHEM_ESTATE, "list_set_hybrid: the list already has entries (their birth steps are unknown)");
   CTX.bonded_dirty = true; CTX.resort = true;      // (a context with a hybrid list leaves the inline-bond mode: rebuild)
+  return 0;
+  API_END(ctx)
+}
+
+int chem_list_set_hybrid_tuples(chem_ctx* ctx, int list, double lambda0, double rate) {
+  API_BEGIN
+  HostTopology& t = CTX.top;
+  REQUIRE(list >= 0 && list < (int)t.lists.size(), CHEM_EINVAL, "list handle");
+  REQUIRE(t.lists[list].arity != 2, CHEM_EINVAL, "list_set_hybrid_tuples: needs a triple or quadruple list (pair lists: chem_list_set_hybrid)");
+  const int rc = t.lists[list].set_hybrid_tuples(lambda0, rate);
+  REQUIRE(rc != CHEM_EINVAL, CHEM_EINVAL, "list_set_hybrid_tuples: needs lambda0 in [0, 1] and a finite rate >= 0");
+  REQUIRE(rc != CHEM_ESTATE, CHEM_ESTATE, "list_set_hybrid_tuples: the list already has entries (their birth steps are unknown)");
+  CTX.bonded_dirty = true; CTX.resort = true;      // (as chem_list_set_hybrid: the bonded kernels of the hybrid family from the next launch on)
   return 0;
   API_END(ctx)
 }

@@ -316,7 +316,7 @@ inline int ckpt_read(const void* buf, int64_t nbytes, int precision, const CkptF
       if (!r.ok()) break;
       const CkptListKind& kd = fp.lists[li];
       r.expect(kd.arity >= 2 && kd.arity <= 4 && l.ent.size() % (size_t)kd.arity == 0, "entries are no multiple of the arity");
-      r.expect(l.birth.size() == (kd.hybrid && kd.arity == 2 ? l.ent.size() / 2 : 0), "birth steps do not match the entries");
+      r.expect(l.birth.size() == (kd.hybrid ? l.ent.size() / (size_t)kd.arity : 0), "birth steps do not match the entries");
       for (int32_t t : l.ent) if (!tag_ok(t)) { r.bad("entry names no particle"); break; }
       for (int64_t b : l.birth) if (b < 0 || b > s.step) { r.bad("birth step outside [0, step]"); break; }
     }

@@ -139,7 +139,8 @@ struct HostList {
   std::array<double, CHEM_MAX_POT_PARAMS> plain{};
   std::map<std::array<int, 4>, std::array<double, CHEM_MAX_POT_PARAMS>> typed;
   std::vector<std::array<int, 4>> registered;
-  // hybrid pair list (chem_list_set_hybrid): entry e acts with lambda(step) = min(1, lambda0 + rate (step - birth[e])).
+  // hybrid list (pairs: chem_list_set_hybrid, triples and quadruples: chem_list_set_hybrid_tuples): entry e acts with
+  // lambda(step) = min(1, lambda0 + rate (step - birth[e])).
   // birth is aligned with the entries and kept by every path that adds, removes or compacts them; a list that is not
   // hybrid keeps none (set_hybrid is refused once a list has entries, so their birth steps could never be read).
   bool hybrid = false;
@@ -158,6 +159,16 @@ struct HostList {
     hybrid = true; lambda0 = l0; rate = r; birth.clear();
     return 0;
   }
+  // chem_list_set_hybrid_tuples' rules (the same, for the other arities); 0 = accepted
+  int set_hybrid_tuples(double l0, double r) {
+    if (arity < 3 || !std::isfinite(l0) || !std::isfinite(r) || l0 < 0.0 || l0 > 1.0 || r < 0.0) return CHEM_EINVAL;
+    if (!ent.empty()) return CHEM_ESTATE;
+    hybrid = true; lambda0 = l0; rate = r; birth.clear();
+    return 0;
+  }
+  // entries a tuple of this list takes in a member's row of the bonded table (md_kernels.hpp BondedEntry): quadruples keep
+  // their fourth tag in a second entry, and that second entry is also where a hybrid triple or quadruple keeps ~birth (t2)
+  int entry_width() const { return (arity == 4 || (hybrid && arity == 3)) ? 2 : 1; }
 };
 
 struct HostPairPot {
@@ -174,7 +185,8 @@ struct HBondedEntry { int t0, t1, t2, meta; };
 constexpr int bonded_meta(int slot, int member) { return slot | (member << 28); }
 constexpr int bonded_slot(int meta) { return meta & 0x0fffffff; }
 constexpr int bonded_member(int meta) { return (meta >> 28) & 3; }
-// birth step of a hybrid pair as it travels in the unused third tag: always negative, so that no reader takes it for a tag
+// birth step of a hybrid entry as it travels in a third tag that is not one (pairs: their own t2, triples and quadruples: t2
+// of their second entry): always negative, so that no reader takes it for a tag
 inline int32_t encode_birth(int64_t birth) { return ~(int32_t)birth; }
 
 struct HostBondTable { double r0 = 0, dr = 1; int itype = 1; std::vector<double> e, f; };   // itype as HostPairPot
@@ -370,10 +382,12 @@ struct HostTopology {
         bool hit = false;
         for (int k = 0; k + 1 < l.arity; ++k) hit |= cut.contains(pair_key(l.ent[e + k], l.ent[e + k + 1]));
         if (hit) { l.seen.erase(tuple_key(&l.ent[e], l.arity)); continue; }
+        if (l.hybrid) l.birth[w / l.arity] = l.birth[e / l.arity];
         for (int k = 0; k < l.arity; ++k) l.ent[w + k] = l.ent[e + k];
         w += l.arity;
       }
       l.ent.resize(w);
+      if (l.hybrid) l.birth.resize(w / l.arity);
     }
     // fragment labels: every component that lost an edge is flooded once (one epoch for the whole batch)
     if (visit_stamp.size() != (size_t)n) { visit_stamp.assign((size_t)n, 0); visit_epoch = 0; }
@@ -485,10 +499,10 @@ struct HostTopology {
       return it == typed_slot[li].end() ? -1 : it->second;
     };
     bstart.assign((size_t)n + 1, 0);
-    // count: pairs/triples one entry per member, quadruples two
+    // count: pairs/triples one entry per member, quadruples and hybrid triples two (HostList::entry_width)
     for (size_t li = 0; li < lists.size(); ++li) {
       const HostList& l = lists[li];
-      const int w = l.arity == 4 ? 2 : 1;
+      const int w = l.entry_width();
       for (size_t e = 0; e + l.arity <= l.ent.size(); e += l.arity) {
         if (slot_of(li, &l.ent[e]) < 0) continue;
         for (int k = 0; k < l.arity; ++k) bstart[(size_t)l.ent[e + k] + 1] += w;
@@ -508,7 +522,8 @@ struct HostTopology {
         for (int k = 0; k < l.arity; ++k) {
           int32_t& pos = fill[tt[k]];
           bent[pos++] = HBondedEntry{tt[0], tt[1], l.arity > 2 ? tt[2] : (l.hybrid ? encode_birth(l.birth[e / 2]) : 0), bonded_meta(slot, k)};
-          if (l.arity == 4) bent[pos++] = HBondedEntry{tt[3], 0, 0, 0};
+          if (l.arity > 2 && l.hybrid) bent[pos++] = HBondedEntry{l.arity == 4 ? tt[3] : 0, 0, encode_birth(l.birth[e / l.arity]), 0};
+          else if (l.arity == 4) bent[pos++] = HBondedEntry{tt[3], 0, 0, 0};
         }
       }
     }

@@ -127,8 +127,10 @@ __device__ __forceinline__ void publish_hint(IdleHint* hint, int gen, long long 
 constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 16-byte quads)
 struct BondedEntry { int t0, t1, t2, meta; };   // tuple tags in order (self included); meta = bonded_meta(slot, mypos) (chem_host.hpp); quadruples use a 2nd entry for t3
                                                 // pairs: t2 = 0, or ~birth step (< 0) for an entry of a hybrid list (chem_list_set_hybrid)
+                                                // triples and quadruples of a hybrid list (chem_list_set_hybrid_tuples; pad of their slot): a 2nd entry
+                                                // (t3 or 0, 0, ~birth step, 0) -- the birth where the pairs keep it, so the work-list build hands it on
 struct BondedParam { int kind, list, arity, pad; double p[CHEM_MAX_POT_PARAMS]; };   // pad = 1: slot of a hybrid list, (lambda0, rate) in HybridArgs::par[slot]
-// Hybrid pair lists: what the HYB instantiations of the bonded kernels get beside the regular arguments.  lambda of an entry is a
+// Hybrid lists: what the HYB instantiations of the bonded kernels get beside the regular arguments.  lambda of an entry is a
 // pure function of (step, birth step); chem_host.hpp HostList::hybrid_lambda is the same expression on the host.
 struct HybridArgs { const double2* par; long long step; };
 __device__ __forceinline__ double hybrid_lambda(const HybridArgs& hy, const BondedParam& bp, const int slot, const int t2) {
@@ -137,6 +139,8 @@ __device__ __forceinline__ double hybrid_lambda(const HybridArgs& hy, const Bond
   const double l = h.x + h.y * (double)(hy.step - (long long)(~t2));
   return l < 1.0 ? l : 1.0;
 }
+// a triple of a hybrid list is two entries wide, as every quadruple is (HostList::entry_width is the same rule on the host)
+__device__ __forceinline__ bool hybrid_wide_triple(const BondedParam& bp) { return bp.pad && bp.arity == 3; }
 
 template <typename R> struct Box {
   R L[3], invL[3];
@@ -2998,7 +3002,8 @@ __device__ __forceinline__ void btab_lookup(const BTab& bt, const int h, const d
 // one bonded term seen from member `me` of the tuple (j0..j3 = particle indices of the tuple in order)
 // BONDS_ONLY: the caller guarantees arity 2 and an analytic kind (harmonic, FENE, FENE+LJ, LJ pair) -- the angle, dihedral
 // and table code is not compiled in, which is what brings the per-step kernel from 209 to a few dozen registers
-// HYB: the pair term (force and energy) is scaled by `lam` (hybrid lists); not compiled into the other instantiations
+// HYB: the term (force and energy) is scaled by `lam` (hybrid lists); a triple or quadruple whose lam is exactly 0 is left out
+// (its full term need not be finite); not compiled into the other instantiations
 // COUL: the 1-4 Coulomb kind (CHEM_POT_COULOMB_BOND) with the two members' charges q0, q1; not compiled into the others either
 // EXACT (k_bonded_virial_tensor alone): the bending term in a form that keeps its digits next to a straight or folded angle
 // ("Conditioning of the bending term"): r1 x r2 by compensated products, theta and sin(theta) from atan2(|r1 x r2|,
@@ -3049,6 +3054,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
     } else if (BONDS_ONLY) {
     } else if (bp.arity == 3) {
       if ((j0 | j1 | j2) < 0) { ctl->bonded_missing = 1; return; }
+      if (HYB && lam == 0.0) return;
       const D3 x0 = posD<R>(x4[j0], box), x1 = posD<R>(x4[j1], box), x2 = posD<R>(x4[j2], box);
       const D3 r1 = minimgD(box, x0 - x1), r2 = minimgD(box, x2 - x1);
       const double n1 = sqrt(dot3(r1, r1)), n2 = sqrt(dot3(r2, r2));
@@ -3068,6 +3074,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
         btab_lookup(bt, (int)p[0], th, u, fv);
         dU = -fv;
       }
+      if (HYB) { dU *= lam; u *= lam; }
       const double a = dU / s;
       D3 fi = a * ((1.0 / (n1 * n2)) * r2 - (c / (n1 * n1)) * r1);
       D3 fk = a * ((1.0 / (n1 * n2)) * r1 - (c / (n2 * n2)) * r2);
@@ -3076,6 +3083,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
       if (me == 0) f = f + fi; else if (me == 2) f = f + fk; else f = f - (fi + fk);
     } else {
       if ((j0 | j1 | j2 | j3) < 0) { ctl->bonded_missing = 1; return; }
+      if (HYB && lam == 0.0) return;
       const D3 x0 = posD<R>(x4[j0], box), x1 = posD<R>(x4[j1], box), x2 = posD<R>(x4[j2], box), x3 = posD<R>(x4[j3], box);
       const D3 b1 = minimgD(box, x1 - x0), b2 = minimgD(box, x2 - x1), b3 = minimgD(box, x3 - x2);
       const D3 m = cross3(b1, b2), nn = cross3(b2, b3);
@@ -3100,6 +3108,7 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
         btab_lookup(bt, (int)p[0], phi, u, fv);
         dU = -fv;
       }
+      if (HYB) { dU *= lam; u *= lam; }
       const D3 g1 = (-lb / m2) * m, g4 = (lb / n2) * nn;
       const double s12 = dot3(b1, b2) / lb2, s32 = dot3(b3, b2) / lb2;
       D3 g;
@@ -3115,7 +3124,8 @@ __device__ __forceinline__ void bonded_term(const BondedParam& bp, const int me,
 // The entry points of the bonded forces.  Two launch shapes -- one thread per particle walking its rows of the per-tag CSR
 // (k_bonded*: the launch without a work list, and observe()), one thread per owner of the work list (k_bonded_work*: every
 // step) -- and one body each, bonded_particle_body and bonded_work_body, which hold the entry walk.  HYB compiles in the lambda
-// of a hybrid pair entry (hybrid_lambda: 1 for entries of lists that are not hybrid), COUL the two charges of a 1-4 Coulomb
+// of a hybrid entry (hybrid_lambda: 1 for entries of lists that are not hybrid; a pair keeps ~birth in its own t2, a triple
+// or quadruple in t2 of its second entry), COUL the two charges of a 1-4 Coulomb
 // entry (CHEM_POT_COULOMB_BOND; type R, the product is formed in fp64) and with them the matching code of bonded_term; `hy`,
 // `qtag` and the work list's `tag` are read under those flags only.  A context with both kinds of list runs the COUL family,
 // which carries the lambda code along, so there is no fourth.  The families stay separate kernels, chosen on the host
@@ -3145,13 +3155,19 @@ __device__ __forceinline__ void bonded_particle_body(int i0, int n, const Vec4<R
     [[maybe_unused]] const int es = e;
     [[maybe_unused]] double ue = 0.0;
     double* const ep = ENERGY ? &ue : elist;
-    if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }   // quadruples occupy two consecutive entries: (t0,t1,t2,meta),(t3,-,-,-)
+    [[maybe_unused]] int tb = be.t2;      // HYB: the word that holds ~birth
+    if constexpr (HYB) {
+      if (ar == 4) { const BondedEntry b2 = bent[e + 1]; j3 = rtag[b2.t0]; tb = b2.t2; ++e; }
+      else if (hybrid_wide_triple(bp)) { tb = bent[e + 1].t2; ++e; }
+    } else {
+      if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }   // quadruples occupy two consecutive entries: (t0,t1,t2,meta),(t3,-,-,-)
+    }
     if constexpr (COUL) {
       double q0 = 0, q1 = 0;
       if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
-      bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0, q0, q1);
+      bonded_term<R, ENERGY, false, true, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, hybrid_lambda(hy, bp, slot, tb), q0, q1);
     } else if constexpr (HYB) {
-      bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0);
+      bonded_term<R, ENERGY, false, true>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt, hybrid_lambda(hy, bp, slot, tb));
     } else {
       bonded_term<R, ENERGY>(bp, me, j0, j1, j2, j3, x4, box, f, ep, ctl, bt);
     }
@@ -3306,8 +3322,8 @@ __global__ __launch_bounds__(256) void k_bonded_prep(int i0, int n, const int* _
   dev_bonded_prep<256>(i0, n, tag, rtag, bstart, bent, bwork, bj, ctl, over_excl);
 }
 
-// one owner of the work list per thread (HYB, COUL: see bonded_particle_body).  jj.z of a hybrid pair is ~birth step, handed
-// on by the work-list build.  The records carry particle indices, so a charge is qtag[tag[j]] -- ghosts included, as in
+// one owner of the work list per thread (HYB, COUL: see bonded_particle_body).  jj.z of a hybrid pair, and of the second
+// record of a hybrid triple or quadruple, is ~birth step, handed on by the work-list build.  The records carry particle indices, so a charge is qtag[tag[j]] -- ghosts included, as in
 // CoulArgs -- and is read at every evaluation: nothing in a record can go stale when a charge changes between two list builds.
 template <typename R, bool BONDS_ONLY, bool HYB, bool COUL>
 __device__ __forceinline__ void bonded_work_body(const Vec4<R>* __restrict__ x4, Vec4<R>* __restrict__ f4, const int4* __restrict__ bwork, const int4* __restrict__ bj,
@@ -3323,10 +3339,16 @@ __device__ __forceinline__ void bonded_work_body(const Vec4<R>* __restrict__ x4,
     const int slot = bonded_slot(jj.w), me = bonded_member(jj.w);
     const BondedParam& bp = bpar[slot];
     int j3 = 0;
-    if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
+    [[maybe_unused]] int tb = jj.z;      // HYB: the word that holds ~birth
+    if constexpr (HYB && !BONDS_ONLY) {
+      if (bp.arity == 4) { const int4 j2nd = bj[e + 1]; j3 = j2nd.x; tb = j2nd.z; ++e; }
+      else if (hybrid_wide_triple(bp)) { tb = bj[e + 1].z; ++e; }
+    } else {
+      if (!BONDS_ONLY && bp.arity == 4) { j3 = bj[e + 1].x; ++e; }
+    }
     const int j2 = (!BONDS_ONLY && bp.arity > 2) ? jj.z : 0;
     if constexpr (HYB || COUL) {
-      const double lam = (BONDS_ONLY || bp.arity == 2) ? hybrid_lambda(hy, bp, slot, jj.z) : 1.0;
+      const double lam = hybrid_lambda(hy, bp, slot, tb);
       if constexpr (COUL) {
         double q0 = 0, q1 = 0;
         if (bp.kind == CHEM_POT_COULOMB_BOND && (jj.x | jj.y) >= 0) { q0 = (double)qtag[tag[jj.x]]; q1 = (double)qtag[tag[jj.y]]; }   // (a missing partner: bonded_term reports it)
@@ -3819,7 +3841,7 @@ __device__ __forceinline__ double baro_block_sum(const double* __restrict__ part
 // Bonded virial: walks the bstart / bent / bpar entries of k_bonded<R, true>.  Member 0 of a pair entry contributes r_ij . F_ij
 // once (as the energy does), so the sum is right on slabs, where the partner may be a ghost.  The force law is bonded_term's
 // own (hybrid lambda and 1-4 Coulomb charges included: qtag is read for Coulomb entries only, hy.par for hybrid slots only).
-// Triples and quadruples depend on angles alone: their virial vanishes identically and is left at zero.
+// Triples and quadruples depend on angles alone: their virial vanishes identically, whatever their lambda, and is left at zero.
 // vlist[e] = the share of entry e of bent (one word per entry, summed per list by k_list_sums; nullptr: not wanted); part[block] =
 // the block's sum over all lists, reduced in a fixed order (what the barostat reads).  Both: the same bits for the same state.
 template <typename R>
@@ -3836,7 +3858,7 @@ __global__ __launch_bounds__(256) void k_bonded_virial(int i0, int n, const Vec4
       const BondedEntry be = bent[e];
       const int slot = bonded_slot(be.meta), me = bonded_member(be.meta);
       const BondedParam& bp = bpar[slot];
-      if (bp.arity == 4) ++e;      // (quadruples occupy two consecutive entries)
+      if (bp.arity == 4 || hybrid_wide_triple(bp)) ++e;      // (quadruples and hybrid triples occupy two consecutive entries)
       if (bp.arity != 2 || me != 0) continue;
       const int j0 = rtag[be.t0], j1 = rtag[be.t1];
       if ((j0 | j1) < 0) { ctl->bonded_missing = 1; continue; }
@@ -3968,13 +3990,15 @@ __global__ __launch_bounds__(256) void k_bonded_virial_tensor(int i0, int n, con
       const int ar = bp.arity;
       int j3 = 0;
       const int es = e;
-      if (ar == 4) { j3 = rtag[bent[e + 1].t0]; ++e; }      // (quadruples occupy two consecutive entries)
+      int tb = be.t2;      // the word that holds ~birth of a hybrid entry
+      if (ar == 4) { const BondedEntry b2 = bent[e + 1]; j3 = rtag[b2.t0]; tb = b2.t2; ++e; }      // (quadruples occupy two consecutive entries,
+      else if (hybrid_wide_triple(bp)) { tb = bent[e + 1].t2; ++e; }                             //  hybrid triples too)
       if (me != 0) continue;
       const int j0 = rtag[be.t0], j1 = rtag[be.t1], j2 = ar > 2 ? rtag[be.t2] : 0;
       if ((j0 | j1 | j2 | j3) < 0) { ctl->bonded_missing = 1; continue; }
       double q0 = 0, q1 = 0;
       if (bp.kind == CHEM_POT_COULOMB_BOND) { q0 = (double)qtag[be.t0]; q1 = (double)qtag[be.t1]; }
-      const double lam = ar == 2 ? hybrid_lambda(hy, bp, slot, be.t2) : 1.0;
+      const double lam = hybrid_lambda(hy, bp, slot, tb);
       const D3 x0 = posD<R>(x4[j0], box), x1 = posD<R>(x4[j1], box);
       const D3 dij = minimgD(box, x0 - x1);
       double t[6] = {0, 0, 0, 0, 0, 0};
@@ -4699,11 +4723,11 @@ __global__ void k_bt_count(int ne, const int4* __restrict__ fent, const int* __r
   const int4 tt = fent[e];
   const int li = flist[e];
   const int tg[4] = {tt.x, tt.y, tt.z, tt.w};
-  int slot = -1, arity = 2;
+  int slot = -1, arity = 2, pad = 0;
   for (int s = 0; s < nslot && slot < 0; ++s) {
     const SlotKey k = keys[s];
-    if (k.list != li) continue;
-    arity = k.arity;
+    if (k.list != li) continue;      // (li = -1: the second flat record of a hybrid triple or quadruple, read by k_bt_fill)
+    arity = k.arity; pad = k.pad;
     if (!k.by_types) { slot = s; break; }
     int ty[4] = {-1, -1, -1, -1};
     for (int q = 0; q < k.arity; ++q) {
@@ -4715,9 +4739,12 @@ __global__ void k_bt_count(int ne, const int4* __restrict__ fent, const int* __r
     for (int q = 0; q < k.arity; ++q) { fwd &= ty[q] == kt[q]; rev &= ty[k.arity - 1 - q] == kt[q]; }
     if (fwd || rev) slot = s;
   }
+  // a hybrid triple or quadruple without its second flat record has no birth step: it is dropped like a tuple without
+  // parameters (the host always writes both records), so k_bt_fill reads fent[e + 1] of what is left without a fallback value
+  if (slot >= 0 && pad && arity > 2 && !(e + 1 < ne && flist[e + 1] == -1)) slot = -1;
   eslot[e] = slot;
   if (slot < 0) return;
-  const int w = arity == 4 ? 2 : 1;
+  const int w = (arity == 4 || (pad && arity == 3)) ? 2 : 1;
   for (int q = 0; q < arity; ++q) atomicAdd(&cnt[tg[q]], w);
 }
 __global__ void k_bt_fill(int ne, const int4* __restrict__ fent, const int* __restrict__ eslot, const SlotKey* __restrict__ keys,
@@ -4727,13 +4754,16 @@ __global__ void k_bt_fill(int ne, const int4* __restrict__ fent, const int* __re
   const int slot = eslot[e];
   if (slot < 0) return;
   const int4 tt = fent[e];
-  const int arity = keys[slot].arity, w = arity == 4 ? 2 : 1;
+  const int arity = keys[slot].arity;
+  const bool hyt = keys[slot].pad && arity > 2;      // hybrid triple / quadruple: ~birth step in the next flat record (x), two entries
+  const int w = (arity == 4 || hyt) ? 2 : 1;
+  const int zb = hyt ? fent[e + 1].x : 0;      // (k_bt_count has seen that record)
   const int tg[4] = {tt.x, tt.y, tt.z, tt.w};
   for (int q = 0; q < arity; ++q) {
     const int pos = start[tg[q]] + atomicAdd(&cursor[tg[q]], w);
     bent[pos] = BondedEntry{tt.x, tt.y, (arity > 2 || keys[slot].pad) ? tt.z : 0, bonded_meta(slot, q)};      // (pad: hybrid pair list, z = ~birth step)
     bkey[pos] = 2 * e;
-    if (arity == 4) { bent[pos + 1] = BondedEntry{tt.w, 0, 0, 0}; bkey[pos + 1] = 2 * e + 1; }
+    if (w == 2) { bent[pos + 1] = BondedEntry{arity == 4 ? tt.w : 0, 0, zb, 0}; bkey[pos + 1] = 2 * e + 1; }
   }
 }
 // rows in flat-array order (key = 2 e + half); counts[0] = tags that own entries

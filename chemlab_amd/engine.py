@@ -405,6 +405,14 @@ class Engine:
             raise NotImplementedError("hybrid bonds: the CPU checker has no FixedPairListLambda")
         self._ck(fn(self.ctx, int(h), float(lambda0), float(rate)))
 
+    def list_set_hybrid_tuples(self, h, lambda0, rate):
+        """Make the (still empty) triple or quadruple list `h` hybrid: the same ramp as list_set_hybrid, on the angles and
+        dihedrals that are added from now on (include/chem_mi355.h, chem_list_set_hybrid_tuples)."""
+        fn = getattr(self.api, "list_set_hybrid_tuples", None)
+        if fn is None:
+            raise NotImplementedError("hybrid angles and dihedrals: the CPU checker has no FixedTripleListLambda / FixedQuadrupleListLambda")
+        self._ck(fn(self.ctx, int(h), float(lambda0), float(rate)))
+
     def list_get_lambda(self, h):
         """lambda of every entry of list `h` at the current step, in the order of get_list."""
         fn = getattr(self.api, "list_get_lambda", None)

@@ -383,6 +383,45 @@ class FixedQuadrupleList(_FixedList):
         return self._all()
 
 
+class _LambdaTuples(object):
+    """What FixedTripleListLambda and FixedQuadrupleListLambda add to their plain lists: entries act with lambda = min(1,
+    init_lambda + rate * (step - birth step)); the rate comes from integrator.FixedListDynamicResolution.register_triple_list /
+    register_quadruple_list (include/chem_mi355.h, chem_list_set_hybrid_tuples)."""
+
+    def _create(self, kind, by_types):      # (hybrid before the first entry: the engine refuses it on a list that has entries)
+        e = self.system.engine
+        h = e.list_create(self.arity, kind, by_types)
+        e.list_set_hybrid_tuples(h, self.init_lambda, self.rate)
+        return h
+
+    def _set_rate(self, rate):
+        self.rate = float(rate)
+        for h in self._handles.values():
+            self.system.engine.list_set_hybrid_tuples(h, self.init_lambda, self.rate)
+
+    def getAllLambda(self):
+        """lambda of every entry at the current step, in the order of getAllTriples / getAllQuadruples."""
+        if self.handle is None:
+            return [self.init_lambda] * len(self._pending)
+        return self.system.engine.list_get_lambda(self.handle).tolist()
+
+
+class FixedTripleListLambda(_LambdaTuples, FixedTripleList):
+    """espressopp.FixedTripleListLambda(storage, init_lambda): the angles of a hybrid triple list."""
+
+    def __init__(self, storage, init_lambda=0.0):
+        FixedTripleList.__init__(self, storage)
+        self.init_lambda, self.rate = float(init_lambda), 0.0
+
+
+class FixedQuadrupleListLambda(_LambdaTuples, FixedQuadrupleList):
+    """espressopp.FixedQuadrupleListLambda(storage, init_lambda): the dihedrals of a hybrid quadruple list."""
+
+    def __init__(self, storage, init_lambda=0.0):
+        FixedQuadrupleList.__init__(self, storage)
+        self.init_lambda, self.rate = float(init_lambda), 0.0
+
+
 # ---- potentials (parameter holders) -----------------------------------------------------------
 class _Pot(object):
     kind = None
@@ -761,6 +800,24 @@ class _FixedListLambdaInteraction(_FixedListInteraction):
         _FixedListInteraction.__init__(self, system, flist, potential)
 
 
+def _lambda_tuple_interaction(base, list_cls, name):
+    """interaction.Fixed{Triple,Quadruple}List[Types]Lambda<Potential>: the plain interaction of that shape, on a list of the
+    Lambda kind only (as _FixedListLambdaInteraction)."""
+    class _Inter(base):
+        def __init__(self, system, flist, *potential):
+            if not isinstance(flist, list_cls):
+                raise TypeError("interaction.%s*: the list must be an espressopp.%s" % (name, list_cls.__name__))
+            base.__init__(self, system, flist, *potential)
+    _Inter.__name__ = "_" + name + "Interaction"
+    return _Inter
+
+
+_FixedTripleListLambdaInteraction = _lambda_tuple_interaction(_FixedListInteraction, FixedTripleListLambda, "FixedTripleListLambda")
+_FixedTripleListTypesLambdaInteraction = _lambda_tuple_interaction(_FixedListTypesInteraction, FixedTripleListLambda, "FixedTripleListTypesLambda")
+_FixedQuadrupleListLambdaInteraction = _lambda_tuple_interaction(_FixedListInteraction, FixedQuadrupleListLambda, "FixedQuadrupleListLambda")
+_FixedQuadrupleListTypesLambdaInteraction = _lambda_tuple_interaction(_FixedListTypesInteraction, FixedQuadrupleListLambda, "FixedQuadrupleListTypesLambda")
+
+
 def _ns(**kw):
     return types.SimpleNamespace(**kw)
 
@@ -787,6 +844,11 @@ interaction = _ns(
     FixedTripleListTabulatedAngular=_FixedListInteraction, FixedTripleListTypesTabulatedAngular=_FixedListTypesInteraction,
     FixedPairListLambdaHarmonic=_FixedListLambdaInteraction, FixedPairListLambdaFENE=_FixedListLambdaInteraction,
     FixedPairListLambdaFENELennardJones=_FixedListLambdaInteraction, FixedPairListLambdaTabulated=_FixedListLambdaInteraction,
+    # hybrid angles and dihedrals: one class per angle / dihedral potential, plain and by types
+    **{"FixedTripleList%sLambda%s" % (ty, pot): (_FixedTripleListTypesLambdaInteraction if ty else _FixedTripleListLambdaInteraction)
+       for ty in ("", "Types") for pot in ("AngularHarmonic", "Cosine", "TabulatedAngular")},
+    **{"FixedQuadrupleList%sLambda%s" % (ty, pot): (_FixedQuadrupleListTypesLambdaInteraction if ty else _FixedQuadrupleListLambdaInteraction)
+       for ty in ("", "Types") for pot in ("DihedralHarmonicNCos", "DihedralRB", "DihedralHarmonic", "TabulatedDihedral")},
     VerletListDynamicResolutionLennardJones=_VerletListDynamicResolutionLennardJones,
     VerletListDynamicResolutionTabulated=_VerletListDynamicResolutionTabulated,
     MixedTabulated=_MixedTabulated, VerletListMixedTabulated=_VerletListMixedTabulated, MultiTabulated=_unsupported("interaction.MultiTabulated"),
@@ -1414,19 +1476,31 @@ class _ExtAnalyze(object):
 
 
 class _FixedListDynamicResolution(object):
-    """integrator.FixedListDynamicResolution(system) + register_pair_list(fpl, rate) (start_simulation.py:289-293): every
-    bond of the list gains `rate` of lambda per MD step up to 1.  Nothing runs per step here: the engine evaluates lambda
-    from the step counter and the bond's birth step."""
+    """integrator.FixedListDynamicResolution(system) + register_pair_list(fpl, rate) (start_simulation.py:289-293), and
+    register_triple_list(ftl, rate) / register_quadruple_list(fql, rate): every entry of the list gains `rate` of lambda per
+    MD step up to 1.  Nothing runs per step here: the engine evaluates lambda from the step counter and the entry's birth step."""
 
     def __init__(self, system):
         self.system = system
-        self.pair_lists = []
+        self.pair_lists, self.triple_lists, self.quadruple_lists = [], [], []
 
     def register_pair_list(self, fpl, rate):
         if not isinstance(fpl, FixedPairListLambda):
             raise TypeError("FixedListDynamicResolution.register_pair_list: needs an espressopp.FixedPairListLambda")
         fpl._set_rate(rate)
         self.pair_lists.append((fpl, float(rate)))
+
+    def register_triple_list(self, ftl, rate):
+        if not isinstance(ftl, FixedTripleListLambda):
+            raise TypeError("FixedListDynamicResolution.register_triple_list: needs an espressopp.FixedTripleListLambda")
+        ftl._set_rate(rate)
+        self.triple_lists.append((ftl, float(rate)))
+
+    def register_quadruple_list(self, fql, rate):
+        if not isinstance(fql, FixedQuadrupleListLambda):
+            raise TypeError("FixedListDynamicResolution.register_quadruple_list: needs an espressopp.FixedQuadrupleListLambda")
+        fql._set_rate(rate)
+        self.quadruple_lists.append((fql, float(rate)))
 
     def _connect(self, integrator):
         pass
@@ -1844,6 +1918,14 @@ class _ResolutionFixedPairList(_Observable):
         return float(sum(lam)) / len(lam) if len(lam) else 0.0
 
 
+class _ResolutionFixedTripleList(_ResolutionFixedPairList):
+    """analysis.ResolutionFixedTripleList(system, ftl): mean lambda of the list's angles, 0.0 for an empty list."""
+
+
+class _ResolutionFixedQuadrupleList(_ResolutionFixedPairList):
+    """analysis.ResolutionFixedQuadrupleList(system, fql): mean lambda of the list's dihedrals, 0.0 for an empty list."""
+
+
 class _CMVelocity(_Observable):
     def reset(self):
         pass   # the synthetic/initial velocities are generated with zero COM momentum
@@ -1930,6 +2012,7 @@ analysis = _ns(
     NFixedPairListEntries=_NFixedPairListEntries, NumFixDistances=_NumFixDistances, CMVelocity=_CMVelocity, ChemicalConversion=_ChemicalConversion,
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
+    ResolutionFixedTripleList=_ResolutionFixedTripleList, ResolutionFixedQuadrupleList=_ResolutionFixedQuadrupleList,
     Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor,
 )
 

@@ -114,7 +114,7 @@ def write_final_outputs(args, system, gt, conf, bonded, angles, dihedrals, chem_
     def split(groups):
         static, dynamic = [], []
         for name, (fl, inter) in groups.items():
-            if name.endswith("_dynamic"):
+            if name.endswith(("_dynamic", "_hybrid")):      # (the spawned tuples of a hybrid list are written out like the dynamic list's)
                 dynamic.append(fl)
             else:
                 static.append((fl, inter.params))
@@ -293,20 +293,37 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     for _, fpl, _ in chem_fpls:
         dynamic_exclusion_list.observe_tuple(fpl)
         topology_manager.observe_tuple(fpl)
+    # --t_hybrid_angle / --t_hybrid_dihedral N: what a reaction spawns goes to a second, hybrid Types list (angle_hybrid /
+    # dihedral_hybrid) and ramps up over N steps; the topology's own tuples stay in the plain dynamic list
+    hybrid_ftl = gromacs_topology.add_hybrid_tuple_list(espressopp, system, angles, "angle") if args.t_hybrid_angle > 0 else None
+    hybrid_fql = gromacs_topology.add_hybrid_tuple_list(espressopp, system, dihedrals, "dihedral") if args.t_hybrid_dihedral > 0 else None
+    for switch, value, made, kind in (("--t_hybrid_angle", args.t_hybrid_angle, hybrid_ftl, "angle"), ("--t_hybrid_dihedral", args.t_hybrid_dihedral, hybrid_fql, "dihedral")):
+        if value > 0 and made is None:      # (a switch is never dropped silently)
+            raise RuntimeError("%s %d: the topology has no %s_dynamic list (no %stypes among the reactive bead types), so no reaction can spawn a %s that would ramp"
+                               % (switch, value, kind, kind, kind))
     if "angle_dynamic" in angles:
         ftl, inter = angles["angle_dynamic"]
         dynamic_exclusion_list.observe_triple(ftl)
+        if hybrid_ftl is not None:
+            dynamic_exclusion_list.observe_triple(hybrid_ftl[0])
         for types_ in inter._typed:
-            topology_manager.register_triplet(ftl, *types_)
+            topology_manager.register_triplet(hybrid_ftl[0] if hybrid_ftl is not None else ftl, *types_)
     if "dihedral_dynamic" in dihedrals:                   # start_simulation.py:428-441
         fql, inter = dihedrals["dihedral_dynamic"]
         dynamic_exclusion_list.observe_quadruple(fql)
+        if hybrid_fql is not None:
+            dynamic_exclusion_list.observe_quadruple(hybrid_fql[0])
         for types_ in inter._typed:
-            topology_manager.register_quadruplet(fql, *types_)
-    if args.t_hybrid_bond > 0:                            # start_simulation.py:289-293
+            topology_manager.register_quadruplet(hybrid_fql[0] if hybrid_fql is not None else fql, *types_)
+    if args.t_hybrid_bond > 0 or hybrid_ftl is not None or hybrid_fql is not None:      # start_simulation.py:289-293
         list_dynamic_resolution = espressopp.integrator.FixedListDynamicResolution(system)
-        for _, fpl, _ in chem_fpls:
-            list_dynamic_resolution.register_pair_list(fpl, 1.0 / args.t_hybrid_bond)
+        if args.t_hybrid_bond > 0:
+            for _, fpl, _ in chem_fpls:
+                list_dynamic_resolution.register_pair_list(fpl, 1.0 / args.t_hybrid_bond)
+        if hybrid_ftl is not None:
+            list_dynamic_resolution.register_triple_list(hybrid_ftl[0], 1.0 / args.t_hybrid_angle)
+        if hybrid_fql is not None:
+            list_dynamic_resolution.register_quadruple_list(hybrid_fql[0], 1.0 / args.t_hybrid_dihedral)
         integrator.addExtension(list_dynamic_resolution)
     topology_manager.initialize_topology()
     integrator.addExtension(topology_manager)
@@ -329,6 +346,10 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
     if args.t_hybrid_bond > 0:                            # start_simulation.py:495-498
         for i, (gname, fpl, _) in enumerate(chem_fpls):
             mon.add_observable("res_fpl_%d" % i, espressopp.analysis.ResolutionFixedPairList(system, fpl))
+    if hybrid_ftl is not None:
+        mon.add_observable("res_ftl_0", espressopp.analysis.ResolutionFixedTripleList(system, hybrid_ftl[0]))
+    if hybrid_fql is not None:
+        mon.add_observable("res_fql_0", espressopp.analysis.ResolutionFixedQuadrupleList(system, hybrid_fql[0]))
     if args.count_fix_distances and sc is not None:       # start_simulation.py:561-563
         for fd_idx, fd in enumerate(sc.fix_distances):
             mon.add_observable("fd_%d" % fd_idx, espressopp.analysis.NumFixDistances(system, fd))
@@ -350,7 +371,7 @@ def main(argv=None, hooks=None, quiet=False, ranks=None):
                                                     ("angle", angles, dump_topol.add_static_triple, dump_topol.observe_triple, "angles"),
                                                     ("dihedral", dihedrals, dump_topol.add_static_quadruple, dump_topol.observe_quadruple, "dihedrals")):
         for cnt, (name, (fl, _inter)) in enumerate(sorted(lists.items())):     # :595-642
-            if name.endswith("_dynamic") and args.store_angdih:
+            if name.endswith(("_dynamic", "_hybrid")) and args.store_angdih:
                 observe(fl, "dynamic_%s_%d" % (label, cnt))
             else:
                 add_static(fl, "%s_%d" % (label, cnt))

@@ -530,13 +530,38 @@ int64_t chem_get_list(chem_ctx* ctx, int list, int64_t* out, int64_t cap_entries
  * the entry's force is lambda F, its share of chem_obs.epot_list is lambda U.  lambda is a pure function of the two step
  * numbers (no array that is updated per step), so it is the same on every rank and for run(a); run(b) as for run(a+b).
  * The pair is excluded from the non-bonded terms as soon as the bond exists, whatever its lambda; angles and dihedrals
- * spawned around it act at full strength; a dissociation reaction removes the birth step with the entry, a pair that
+ * spawned around it act at full strength unless their list is hybrid too (chem_list_set_hybrid_tuples); a dissociation reaction removes the birth step with the entry, a pair that
  * bonds again starts at lambda0.  Any pair kind, plain or by types.  Harmonic bonds of a context that has a hybrid list
  * are not evaluated inline (option bonds_inline has no effect).  (Parity unpinned: DESIGN.md "Hybrid bonds".)
  * CHEM_EINVAL: list of arity != 2, lambda0 outside [0, 1], rate < 0, a non-finite value; CHEM_ESTATE: the list already
  * has entries (calling it again on an empty list, e.g. to set the rate later, is allowed). */
 int chem_list_set_hybrid(chem_ctx* ctx, int list, double lambda0, double rate);
-/* analysis.ResolutionFixedPairList (start_simulation.py:495-498): lambda of every entry at the current step, in the order
+/* FixedTripleListLambda / FixedQuadrupleListLambda(storage, init_lambda) + FixedListDynamicResolution.register_triple_list /
+ * register_quadruple_list(list, rate), app_args.py:206-209 (--t_hybrid_angle, --t_hybrid_dihedral): a HYBRID triple or
+ * quadruple list, for the angles and dihedrals the topology manager spawns around a new bond (chem_topology_register).
+ * (Parity unpinned, as for hybrid bonds: the rule set below is this build's own; DESIGN.md "Hybrid bonds".)
+ *   - Arity 3 or 4 only; a pair list is CHEM_EINVAL (it is chem_list_set_hybrid's, which in turn refuses these lists).
+ *   - lambda0 outside [0, 1], rate < 0, a non-finite value, an unknown handle: CHEM_EINVAL.  A list that already has entries:
+ *     CHEM_ESTATE (their birth steps are unknown); calling it again on an empty list is allowed.
+ *   - Any angle or dihedral kind, plain or by types.
+ *   - Every entry remembers its birth step, the value of chem_get_step() when it was added: spawned in a reaction step, by
+ *     chem_list_add or by any other path that appends.
+ *   - The forces that are current at step s use, per entry, lambda = min(1, lambda0 + rate * (s - birth)), the expression of
+ *     chem_list_set_hybrid: the entry's force on every member is lambda F, its share of chem_obs.epot_list lambda U, its
+ *     contribution to the list virial of chem_get_pressure and to the list part of chem_get_pressure_tensor lambda times the
+ *     plain one.
+ *   - lambda is a pure function of the two step numbers: no kernel updates it and no array holds it, run(a); run(b) equals
+ *     run(a+b) bit for bit, every rank of a slab run computes the same value (the host topology is replicated, births are
+ *     global step numbers).
+ *   - An entry whose lambda is exactly 0 is skipped, not multiplied: a tuple spawned in a geometry where the full term is not
+ *     finite contributes exactly nothing.
+ *   - The 1-3 / 1-4 exclusion of a spawned tuple acts from the moment it is inserted, whatever lambda.
+ *   - Whatever removes a bond (a dissociation, chem_reaction_remove_bond) takes the birth step away with every tuple it
+ *     removes; the survivors keep theirs; a tuple spawned again after the pair bonds again starts at lambda0.
+ *   - chem_list_get_lambda serves these lists; a checkpoint carries their birth steps (same format version). */
+int chem_list_set_hybrid_tuples(chem_ctx* ctx, int list, double lambda0, double rate);
+/* analysis.ResolutionFixedPairList / ResolutionFixedTripleList / ResolutionFixedQuadrupleList (start_simulation.py:495-498):
+ * lambda of every entry at the current step, in the order
  * of chem_get_list (same count convention); 1.0 for every entry of a list that is not hybrid. */
 int64_t chem_list_get_lambda(chem_ctx* ctx, int list, double* out, int64_t cap_entries);
 
