@@ -20,6 +20,8 @@ CHEM_MAX_TYPES = 16
 CHEM_MAX_POT_PARAMS = 6
 CHEM_MAX_FIX_SETS = 8
 CHEM_MAX_REGIONS = 16
+CHEM_RDF_MAX_PAIRS = 8
+CHEM_RDF_MAX_BINS = 1024
 
 # error codes
 OK, EINVAL, ENOSPC, EDEVICE, ESTATE, ENOTIMPL, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -135,6 +137,11 @@ class PressureTensor(C.Structure):
 class BarostatState(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pressure_last", C.c_double), ("momentum", C.c_double), ("eps_dot", C.c_double),
                 ("mu_next", C.c_double), ("sv_next", C.c_double)]
+
+
+class RdfResult(C.Structure):
+    _fields_ = [("r_max", C.c_double), ("nbins", C.c_int32), ("npairs", C.c_int32), ("split", C.c_int32),
+                ("frames", C.c_int64), ("pairs", C.c_uint64 * CHEM_RDF_MAX_PAIRS), ("density", C.c_double * CHEM_RDF_MAX_PAIRS)]
 
 
 class Timers(C.Structure):
@@ -254,6 +261,12 @@ PRODUCT_ONLY = {
     # checkpoint and exact restart (the CPU checker has none)
     "checkpoint_save": (_i64, [_P, _P, _i64]),
     "checkpoint_load": (_i, [_P, _P, _i64]),
+    # radial distribution functions accumulated on the device (the CPU checker has no pair histogram)
+    "rdf_init": (_i, [_P, _d, _i, _i, _pi32, _i]),
+    "rdf_sample": (_i, [_P]),
+    "rdf_sample_every": (_i, [_P, _i]),
+    "rdf_get": (_i, [_P, C.POINTER(RdfResult), C.POINTER(C.c_uint64), _i64]),
+    "rdf_reset": (_i, [_P]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

@@ -187,3 +187,16 @@ def write_topology_dumps(prefix, system, fixed_pair_lists):
     with wopen(_prepare_path(prefix + "_residue_list.dat"), "w") as f:        # residue: its particles
         for r in sorted(members):
             f.write("%d: %s\n" % (r, " ".join(str(x) for x in sorted(members[r]))))
+
+
+def write_rdf(file_name, rdf, labels=None):
+    """The result of Engine.rdf() as text: a header line, then one row per bin, `r` (the bin centre) followed by one g column
+    per selector and part (with the molecule split: intra, then inter).  labels: one name per selector (default sel0, sel1, ..)."""
+    nsel, parts, nbins = rdf["g"].shape
+    labels = ["sel%d" % s for s in range(nsel)] if labels is None else list(labels)
+    cols = ["%s%s" % (labels[s], ("_intra", "_inter")[p] if parts == 2 else "") for s in range(nsel) for p in range(parts)]
+    out = ["# r " + " ".join("g_" + c for c in cols) + "   (frames %d, r_max %g)" % (rdf["frames"], rdf["r_max"])]
+    for k in range(nbins):
+        out.append("%.6f " % rdf["r"][k] + " ".join("%.8e" % rdf["g"][s, p, k] for s in range(nsel) for p in range(parts)))
+    with wopen(_prepare_path(file_name), "w") as f:
+        f.write("\n".join(out) + "\n")

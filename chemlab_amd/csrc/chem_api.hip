@@ -29,6 +29,7 @@
 #include "chem_res_host.hpp"
 #include "chem_fix_host.hpp"
 #include "chem_region_host.hpp"
+#include "chem_rdf_host.hpp"
 #include "chem_ckpt_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
@@ -301,6 +302,14 @@ struct Ctx {
   virtual void observe(chem_obs* out) = 0;
   virtual void pressure(chem_pressure* out) = 0;
   virtual void pressure_tensor(chem_pressure_tensor* out) = 0;
+  // Radial distribution functions (chem_rdf_*; rule set: include/chem_mi355.h, host rules: chem_rdf_host.hpp).  The configuration
+  // lives here, the accumulators on the device (allocated by rdf_configure only); neither is part of a checkpoint.  every > 0:
+  // chem_run takes a frame behind the force launch of every step s with s % every == 0.
+  struct RdfConf { bool on = false; double r_max = 0; int nbins = 0, npairs = 0, split = 0, every = 0; int32_t tp[2 * CHEM_RDF_MAX_PAIRS] = {}; } rdf;
+  virtual void rdf_configure() = 0;      // accumulators for rdf (zeroed), or freed where it is off
+  virtual void rdf_sample() = 0;
+  virtual void rdf_get(chem_rdf_result* out, uint64_t* counts, int64_t cap) = 0;
+  virtual void rdf_reset() = 0;
   virtual int64_t verlet_pairs(int64_t* out, int64_t cap) = 0;
   virtual void modify_particle(int tag, int what, double value) = 0;
   virtual int res_apply_completions() = 0;
@@ -1957,6 +1966,110 @@ template <typename R> struct CtxT : Ctx {
     out->pressure = baro_pressure(out->mv2, w, out->volume);
   }
 
+  // ---- radial distribution functions (chem_rdf_*; the rules and the launch plan: chem_rdf_host.hpp, the kernels: md_kernels.hpp) ----
+  DBuf<unsigned long long> rdf_acc;      // frames, pairs[8], density[8] (bits of doubles), type counts of the frame in flight, then the histograms from word kRdfHead on
+  int rdf_ncu = 0; size_t rdf_lds_set[2] = {0, 0};
+  // Slabs: every rank accumulates the pairs its home particles own (k_rdf_tiles takes a pair from its lower tag among the home
+  // particles, so a pair with a ghost member is counted by one owner) and a frame adds no communication.  The type counts of M
+  // have to be global, and the device holds types by slot of the owned particles only: the books (frames, pairs, density) are
+  // kept here on the host from top.type, which is replicated by tag -- the same on every rank.  chem_rdf_get sums the histograms.
+  uint64_t rdf_h_frames = 0, rdf_h_pairs[CHEM_RDF_MAX_PAIRS] = {}; double rdf_h_density[CHEM_RDF_MAX_PAIRS] = {};
+  DBuf<double> rdf_red;
+  size_t rdf_words() const { return rdf_hist_words(rdf.nbins, rdf.npairs, rdf.split ? 2 : 1); }
+  void rdf_configure() override {
+    if (!rdf.on) { if (rdf_acc.p) { HIPCHK(hipStreamSynchronize(stream)); rdf_acc.free(); rdf_red.free(); } return; }
+    rdf_acc.alloc((size_t)kRdfHead + rdf_words());
+    rdf_reset();
+  }
+  void rdf_reset() override {
+    HIPCHK(hipMemsetAsync(rdf_acc.p, 0, sizeof(unsigned long long) * ((size_t)kRdfHead + rdf_words()), stream));
+    rdf_h_frames = 0;
+    for (int s = 0; s < CHEM_RDF_MAX_PAIRS; ++s) { rdf_h_pairs[s] = 0; rdf_h_density[s] = 0.0; }
+  }
+  RdfArgs rdf_args() const {
+    RdfArgs a{};
+    a.dr = rdf.r_max / (double)rdf.nbins; a.inv_dr = 1.0 / a.dr;
+    a.nbins = rdf.nbins; a.nsel = rdf.npairs; a.parts = rdf.split ? 2 : 1;
+    rdf_fill_masks(rdf.npairs, rdf.tp, a.mask);
+    return a;
+  }
+  // what a frame needs of the set-up (asked where chem_run starts and at every frame: the cutoff can be set after chem_rdf_init,
+  // and the tile capacity can grow); the kernel is told its LDS here, so that a frame inside a run is launches and nothing else
+  // while the tile capacity stays what it was when the run started (a larger one sets the attribute once more)
+  RdfPlan rdf_plan_now() {
+    // (a decomposed context is always on the tile path: plan_tiles refuses a slab without it)
+    if (rdf.r_max > rc) throw ChemError(CHEM_EINVAL, "rdf: r_max = " + std::to_string(rdf.r_max) + " exceeds the list cutoff max_cutoff = " + std::to_string(rc) +
+                                                     " (the lists of the last build hold nothing beyond it)");
+    if (!rdf_ncu) { hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, device)); rdf_ncu = prop.multiProcessorCount; }
+    RdfPlan pl{}; std::string why;
+    const int path = use_tiles ? 0 : 1;
+    if (!rdf_plan(path, rdf.nbins, rdf.npairs, rdf.split ? 2 : 1, use_tiles ? tile_lds_bytes() : 0, kTileLdsBudget, rdf_ncu, use_tiles ? ntiles : n, pl, why))
+      throw ChemError(CHEM_EINVAL, why);
+    if (rdf_lds_set[path] < pl.lds_bytes) {
+      const void* fn = use_tiles ? reinterpret_cast<const void*>(&k_rdf_tiles<R, 512>) : reinterpret_cast<const void*>(&k_rdf_all<R>);
+      HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+      rdf_lds_set[path] = pl.lds_bytes;
+    }
+    return pl;
+  }
+  // one frame of the positions as they are, behind whatever the stream holds (the forces of the step): pair pass, then the books.
+  // (Slabs: dd_step_sync has returned, so the host knows the step's decision, a rebuild it asked for has happened, the ghost
+  //  positions are those the forces were evaluated at and nothing of the step is speculative any more.)
+  void rdf_launch() {
+    const RdfPlan pl = rdf_plan_now();
+    if ((rdf.split || dd_on) && (labels_pending || label_thr.joinable())) join_thread();      // the labels the reaction scan of this step would read
+    const RdfArgs a = rdf_args();
+    if (n > 0) {
+      if (use_tiles)
+        hipLaunchKernelGGL((k_rdf_tiles<R, 512>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, stream, ntiles, tile_cap, x4.p, tag.p, tdesc.p, mol_id.p, boxd, a,
+                           (int)pl.hist_off, rdf_acc.p, (const DevCtl*)ctl.p, (R)(0.5 * skin_eff()));
+      else
+        hipLaunchKernelGGL(k_rdf_all<R>, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, stream, n, x4.p + G, tag.p + G, mol_id.p, boxd, a, (int)pl.hist_off, rdf_acc.p,
+                           (const DevCtl*)ctl.p);
+    }
+    const double V = L[0] * L[1] * L[2];
+    if (dd_on) {
+      sync_type_mirrors();
+      long long c[CHEM_MAX_TYPES] = {};
+      for (int64_t t = 0; t < top.n; ++t) ++c[top.type[(size_t)t] & (CHEM_MAX_TYPES - 1)];
+      ++rdf_h_frames;
+      for (int s = 0; s < rdf.npairs; ++s) { const unsigned long long M = rdf_norm_pairs(a.mask, s, c); rdf_h_pairs[s] += M; rdf_h_density[s] += (double)M / V; }
+    } else {
+      if (n > 0) hipLaunchKernelGGL(k_rdf_count<R>, dim3(std::min(cdiv(n, 256), 4 * rdf_ncu)), dim3(256), 0, stream, G, n, x4.p, rdf_acc.p, (const DevCtl*)ctl.p);
+      hipLaunchKernelGGL(k_rdf_frame, dim3(1), dim3(64), 0, stream, a, V, rdf_acc.p, (const DevCtl*)ctl.p);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  void rdf_sample() override {      // chem_observe's preconditions
+    flush_host_state();
+    if (resort) { rebuild_now(); compute_forces(); }
+    rdf_launch();
+  }
+  void rdf_get(chem_rdf_result* out, uint64_t* counts, int64_t cap) override {      // collective on a decomposed context, like chem_get_pressure
+    const size_t nw = rdf_words();
+    if (counts && cap < (int64_t)nw) throw ChemError(CHEM_ENOSPC, "rdf_get: capacity " + std::to_string(cap) + " below npairs * (1 + split) * nbins = " + std::to_string(nw));
+    std::vector<unsigned long long> h;
+    const bool hist = counts || (dd_on && P > 1);      // (every rank takes part in the sum, whatever it asked for)
+    rdf_acc.download(h, hist ? (size_t)kRdfHead + nw : (size_t)kRdfHead, stream);
+    if (dd_on && P > 1) {
+      // the counts are integers far below 2^53: their sum as doubles is exact
+      std::vector<double> d(nw);
+      for (size_t k = 0; k < nw; ++k) d[k] = (double)h[kRdfHead + k];
+      allreduce_host_sums(d.data(), (int)nw, rdf_red);
+      for (size_t k = 0; k < nw; ++k) h[kRdfHead + k] = (unsigned long long)d[k];
+    }
+    std::memset(out, 0, sizeof(*out));
+    out->r_max = rdf.r_max; out->nbins = rdf.nbins; out->npairs = rdf.npairs; out->split = rdf.split ? 1 : 0;
+    if (dd_on) {
+      out->frames = (int64_t)rdf_h_frames;
+      for (int s = 0; s < rdf.npairs; ++s) { out->pairs[s] = rdf_h_pairs[s]; out->density[s] = rdf_h_density[s]; }
+    } else {
+      out->frames = (int64_t)h[kRdfFrames];
+      for (int s = 0; s < rdf.npairs; ++s) { out->pairs[s] = h[kRdfPairs + s]; std::memcpy(&out->density[s], &h[kRdfDensity + s], sizeof(double)); }
+    }
+    if (counts) for (size_t k = 0; k < nw; ++k) counts[k] = h[kRdfHead + k];
+  }
+
   // ---- pressure tensor (chem_get_pressure_tensor; the rules: include/chem_mi355.h, the kernel: chem_tensor_host.hpp) ----
   // Everything below is allocated and launched by the call alone.
   DBuf<double> tpart, tredbuf;      // per-list sums, kinetic and pair block partials (one buffer, one download); the ranks' sums
@@ -2165,6 +2278,8 @@ template <typename R> struct CtxT : Ctx {
     const bool keep_region = region_keep && !baro_on() && !dd_on && !dirty_any && device_ready;
     region_keep = false;
     flush_host_state();
+    const bool rdf_due = rdf.on && rdf.every > 0;
+    if (rdf_due) (void)rdf_plan_now();      // (refusals before the first step, not in the middle of the run)
     hint_invalidate();      // (whatever the last call's launches published: the first step of a call gets its neighbour launch)
     const double t0 = now_s();
     if (opt_time_pair) {
@@ -2264,6 +2379,7 @@ template <typename R> struct CtxT : Ctx {
       else { if (skip_applies()) skip_log_add(false); decide_and_rebuild(true); compute_forces(); }
       force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
+      if (rdf_due && (step + 1) % rdf.every == 0) rdf_launch();      // a frame of x(step + 1): behind its forces, in front of the kick (reads only)
 
       if (last || react_due || atrp_due || reg_due || !opt_fuse || resc_kind || baro_on()) {
         launch_integrate<1>(lang, lang, step, 1);
@@ -4293,6 +4409,39 @@ int chem_checkpoint_load(chem_ctx* ctx, const void* buf, int64_t nbytes) {
   return 0;
   API_END(ctx)
 }
+
+int chem_rdf_init(chem_ctx* ctx, double r_max, int nbins, int npairs, const int32_t* type_pairs, int split_molecules) {
+  API_BEGIN
+  Ctx& c = CTX;
+  std::string why;
+  if (rdf_validate(r_max, nbins, npairs, type_pairs, why) != 0) throw ChemError(CHEM_EINVAL, why);
+  Ctx::RdfConf r;
+  if (npairs > 0) {
+    r.on = true; r.r_max = r_max; r.nbins = nbins; r.npairs = npairs; r.split = split_molecules ? 1 : 0;
+    for (int k = 0; k < 2 * npairs; ++k) r.tp[k] = type_pairs[k];
+  }
+  c.rdf = r;      // (in-run sampling is off again: the accumulators start from nothing)
+  c.rdf_configure();
+  return 0;
+  API_END(ctx)
+}
+int chem_rdf_sample(chem_ctx* ctx) { API_BEGIN REQUIRE(CTX.rdf.on, CHEM_ESTATE, "rdf_sample before chem_rdf_init"); CTX.rdf_sample(); return 0; API_END(ctx) }
+int chem_rdf_sample_every(chem_ctx* ctx, int every) {
+  API_BEGIN
+  REQUIRE(CTX.rdf.on, CHEM_ESTATE, "rdf_sample_every before chem_rdf_init");
+  CTX.rdf.every = every > 0 ? every : 0;
+  return 0;
+  API_END(ctx)
+}
+int chem_rdf_get(chem_ctx* ctx, chem_rdf_result* out, uint64_t* counts, int64_t cap) {
+  API_BEGIN
+  REQUIRE(CTX.rdf.on, CHEM_ESTATE, "rdf_get before chem_rdf_init");
+  REQUIRE(out, CHEM_EINVAL, "null output");
+  CTX.rdf_get(out, counts, cap);
+  return 0;
+  API_END(ctx)
+}
+int chem_rdf_reset(chem_ctx* ctx) { API_BEGIN REQUIRE(CTX.rdf.on, CHEM_ESTATE, "rdf_reset before chem_rdf_init"); CTX.rdf_reset(); return 0; API_END(ctx) }
 
 int chem_run(chem_ctx* ctx, int64_t nsteps) {
   API_BEGIN_NOJOIN   // a pending label merge keeps running beside the MD steps; react_step joins it

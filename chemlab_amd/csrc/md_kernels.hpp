@@ -18,6 +18,7 @@
 #include "chem_roworder_host.hpp"
 #include "chem_baro_host.hpp"
 #include "chem_region_host.hpp"
+#include "chem_rdf_host.hpp"
 
 namespace chem {
 
@@ -4265,6 +4266,8 @@ __host__ __device__ constexpr size_t scan_roles_offset(int CAP, size_t slot_byte
 // the global arrays exactly as k_react_scan computes it, the reaction filters and the Philox draw.
 // Round 3: tag and role bits are staged beside the positions (k_react_roles), so a home particle without a role costs
 // nothing and a candidate reaches the global loads only if tag order and roles allow a reaction.
+// (k_rdf_tiles further down walks the stencil the same way -- home decode, x-window with slack, four-wide LDS gather, lower-tag
+//  rule -- as a copy: a change to the traversal here has to be made there too.)
 // Output: every tile appends to its own fixed region of `region` through an LDS counter (no
 // contended global atomic); k_cand_offsets / k_cand_gather compact the regions afterwards.
 template <typename R, int BS>
@@ -4874,6 +4877,223 @@ __global__ void k_region_reset(int nchg, const RegionReset* __restrict__ chg, co
   if (i < 0) return;
   if (chg[k].flags & 1) { Vec4<R> v = v4[i]; v.x = v.y = v.z = (R)0; v4[i] = v; }
   if (chg[k].flags & 2) { Vec4<R> f = f4[i]; f.x = f.y = f.z = (R)0; f4[i] = f; }
+}
+
+// =======================================================================================
+// Radial distribution functions (chem_rdf_*; rule set: include/chem_mi355.h, host rules and launch plan: chem_rdf_host.hpp).
+// Every unordered pair of distinct particles inside r_max is counted once, from its lower tag, excluded pairs included; the
+// distance is the reaction scan's (posD, minimgD, dist2_unfused), the bin is rdf_bin's.  The histogram of a workgroup is u32
+// words in LDS (behind whatever the kernel stages), bumped with LDS atomics; at the end the workgroup adds its non-zero words to
+// the u64 accumulators with global atomics whose result nobody reads.  The kernels only read the particle data, and a launch of
+// a stopped run (DevCtl::halt) leaves at once like every other launch of the step: that step is redone and sampled then.
+// =======================================================================================
+__device__ __forceinline__ void rdf_bump(unsigned int* const hist, const RdfArgs& a, unsigned int m, const int part, const int k) {
+  while (m) {
+    const int s = __ffs((int)m) - 1;
+    m &= m - 1;
+    atomicAdd(&hist[(s * a.parts + part) * a.nbins + k], 1u);
+  }
+}
+__device__ __forceinline__ void rdf_flush(const unsigned int* const hist, const int nh, unsigned long long* __restrict__ acc) {
+  for (int k = threadIdx.x; k < nh; k += blockDim.x) {
+    const unsigned int v = hist[k];
+    if (v) atomicAdd(&acc[kRdfHead + k], (unsigned long long)v);
+  }
+}
+
+// Tiles (fused and unfused rebuild): k_react_scan_tiles's traversal -- the stencil of a tile staged in LDS with the current
+// positions, the x-window of every stencil row widened by `slack` for the tables of the last rebuild, the fp32 pre-test against
+// the largest radius with its 1e-3 margin -- without the role, exclusion, state and label filters.  Persistent: the grid is a
+// small multiple of the compute units (rdf_plan), a workgroup loops over tiles and keeps its histogram until the end.
+// The traversal is a COPY of k_react_scan_tiles's, not shared code: keep the two in step by hand.
+template <typename R, int BS>
+__global__ __launch_bounds__(BS) void k_rdf_tiles(int ntiles, int CAP, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag,
+                                                  const TileLDS<R>* __restrict__ desc, const int* __restrict__ mol_id, BoxD box, RdfArgs a,
+                                                  int hist_off, unsigned long long* __restrict__ acc, const DevCtl* __restrict__ ctl, R slack) {
+  if (ctl->halt) return;
+  __shared__ TileLDS<R> T;
+  __shared__ unsigned char smask[kMaxTypes * kMaxTypes];
+  CHEM_DYN_LDS(R);
+  unsigned int* const hist = reinterpret_cast<unsigned int*>(chem_dyn_lds + hist_off);
+  const int nh = a.nbins * a.nsel * a.parts;
+  for (int k = threadIdx.x; k < nh; k += BS) hist[k] = 0u;
+  for (int k = threadIdx.x; k < kMaxTypes * kMaxTypes; k += BS) smask[k] = a.mask[k / kMaxTypes][k % kMaxTypes];
+  __syncthreads();
+  R maxcut2 = (R)rdf_edge2(a.nbins, a.dr);
+  maxcut2 *= (R)1.001;   // the staged positions carry the periodic shift: one more rounding than the global ones
+  for (int vb = blockIdx.x; vb < ntiles; vb += gridDim.x) {
+    const int tile = xcd_remap(vb, ntiles);
+    __syncthreads();
+    tile_load_desc<R>(T, desc, tile);
+    __syncthreads();
+    tile_fill<R, BS, true>(T, sx, CAP, x4, 1);
+    __syncthreads();
+    const int hx = T.geom[0], total = T.geom[3], nhome = T.geom[4];
+    for (int q = threadIdx.x; q < nhome; q += BS) {
+      int sgi = 0;
+#pragma unroll
+      for (int k = 1; k < NHSEG; ++k) sgi += (q >= T.hoff[k]) ? 1 : 0;
+      const int inrun = q - T.hoff[sgi];
+      const int p = T.hstart[sgi] + inrun;
+      const int ly = sgi % HY, lz = sgi / HY;
+      const int hr = (lz + 1) * SY + (ly + 1);
+      const int eh = inrun + T.celloff[hr][1];
+      int lx = 0;
+      for (int k = 2; k <= hx; ++k) lx += (eh >= T.celloff[hr][k]) ? 1 : 0;
+      const int sself = T.rowoff[hr] + eh;
+      if (sself >= CAP) continue;                             // (a tile beyond its capacity: stage_overflow is raised where the tables are built)
+      const Vec4<R> xi = sx[sself];
+      const int tgi = tag[p];
+      const Vec4<R> xgi = x4[p];
+      const int ti = (int)xgi.w & (kMaxTypes - 1);
+      const int mi = a.parts == 2 ? mol_id[tgi] : 0;
+      const R rmax = sqrt_r(maxcut2), weps = T.clen[0] * (R)2e-4;
+      auto suboff = [&](int r, int f, bool lower) {
+        const int k = f >> 2, j = f & 3;
+        const int base = T.celloff[r][k];
+        if (j == 0) return base;
+        const int pk = T.cellsub[r][k];
+        if (pk < 0) return lower ? base : T.celloff[r][k + 1];
+        return base + ((pk >> (8 * (j - 1))) & 0xff);
+      };
+#pragma unroll 1
+      for (int dzy = 0; dzy < 9; ++dzy) {
+        const int dz = dzy / 3, dy = dzy - 3 * dz;
+        const int r = (lz + dz) * SY + (ly + dy);
+        const R ylo = ((R)(ly + 1) - (R)kRefCells) * T.clen[1], zlo = ((R)(lz + 1) - (R)kRefCells) * T.clen[2];   // (staged coordinates are relative to T.org)
+        R ddy = dy == 0 ? xi.y - ylo : (dy == 2 ? ylo + T.clen[1] - xi.y : (R)0);
+        R ddz = dz == 0 ? xi.z - zlo : (dz == 2 ? zlo + T.clen[2] - xi.z : (R)0);
+        ddy -= slack + weps; ddz -= slack + weps;
+        ddy = ddy > 0 ? ddy : (R)0; ddz = ddz > 0 ? ddz : (R)0;
+        const R w2 = rmax * rmax - ddy * ddy - ddz * ddz;
+        if (w2 < (R)0) continue;
+        const R ws = (sqrt_r(w2) + slack + weps) * T.subinv, sxi = (xi.x + (R)kRefCells * T.clen[0]) * T.subinv;
+        int f_lo = (int)(sxi - ws), f_hi = (int)(sxi + ws);
+        f_lo = f_lo > lx * NSUB ? f_lo : lx * NSUB;
+        f_hi = f_hi < (lx + 3) * NSUB - 1 ? f_hi : (lx + 3) * NSUB - 1;
+        const int s0 = T.rowoff[r] + suboff(r, f_lo, true);
+        int b = T.rowoff[r] + suboff(r, f_hi + 1, false);
+        b = b < total ? b : total;
+        for (int sl0 = s0; sl0 < b; sl0 += 4) {
+          Vec4<R> xq[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) xq[u] = lds_gather4<R>(sx, sl0 + u < b ? sl0 + u : total);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int sl = sl0 + u;
+            const Vec4<R> xj = xq[u];
+            const R dx = xi.x - xj.x, dy_ = xi.y - xj.y, dz_ = xi.z - xj.z;
+            if (dx * dx + dy_ * dy_ + dz_ * dz_ > maxcut2 || sl == sself || sl >= b) continue;
+            const int wj = real_as_idx(xj.w);
+            const unsigned int m = smask[ti * kMaxTypes + (wj & (kMaxTypes - 1))];
+            if (!m) continue;
+            const int j = wj >> 5;
+            const int tgj = tag[j];
+            if (!(tgi < tgj)) continue;          // every pair once, from its lower tag
+            const D3 d = minimgD(box, posD<R>(xgi, box) - posD<R>(x4[j], box));
+            const int k = rdf_bin(dist2_unfused(d), a.dr, a.inv_dr, a.nbins);
+            if (k < 0) continue;
+            rdf_bump(hist, a, m, a.parts == 2 && mol_id[tgj] != mi ? 1 : 0, k);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  rdf_flush(hist, nh, acc);
+}
+
+// Per-cell and brute-force lists (single domain): all pairs.  These paths exist where the cell grid is too small for tiles, so a
+// particle's partners inside r_max are a large part of the system anyway; a workgroup stages kRdfChunk particles at a time
+// (decoded position, tag, type, molecule) and every thread tests its own particle against them.
+template <typename R>
+__global__ __launch_bounds__(kRdfChunk) void k_rdf_all(int n, const Vec4<R>* __restrict__ x4, const int* __restrict__ tag, const int* __restrict__ mol_id,
+                                                       BoxD box, RdfArgs a, int hist_off, unsigned long long* __restrict__ acc, const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  __shared__ unsigned char smask[kMaxTypes * kMaxTypes];
+  extern __shared__ __attribute__((aligned(16))) unsigned char chem_dyn_lds[];
+  double* const cx = reinterpret_cast<double*>(chem_dyn_lds);
+  int* const ci = reinterpret_cast<int*>(chem_dyn_lds + (size_t)kRdfChunk * 3 * sizeof(double));   // tag, type, molecule
+  unsigned int* const hist = reinterpret_cast<unsigned int*>(chem_dyn_lds + hist_off);
+  const int nh = a.nbins * a.nsel * a.parts, t = threadIdx.x;
+  for (int k = t; k < nh; k += kRdfChunk) hist[k] = 0u;
+  for (int k = t; k < kMaxTypes * kMaxTypes; k += kRdfChunk) smask[k] = a.mask[k / kMaxTypes][k % kMaxTypes];
+  for (int i0 = blockIdx.x * kRdfChunk; i0 < n; i0 += gridDim.x * kRdfChunk) {
+    const int i = i0 + t;
+    const bool live = i < n;
+    D3 pi = {0, 0, 0}; int tgi = 0, ti = 0, mi = 0;
+    if (live) { const Vec4<R> xi = x4[i]; pi = posD<R>(xi, box); ti = (int)xi.w & (kMaxTypes - 1); tgi = tag[i]; mi = a.parts == 2 ? mol_id[tgi] : 0; }
+    for (int j0 = 0; j0 < n; j0 += kRdfChunk) {
+      __syncthreads();
+      if (j0 + t < n) {
+        const Vec4<R> xj = x4[j0 + t];
+        const D3 pj = posD<R>(xj, box);
+        const int tgj = tag[j0 + t];
+        cx[3 * t] = pj.x; cx[3 * t + 1] = pj.y; cx[3 * t + 2] = pj.z;
+        ci[3 * t] = tgj; ci[3 * t + 1] = (int)xj.w & (kMaxTypes - 1); ci[3 * t + 2] = a.parts == 2 ? mol_id[tgj] : 0;
+      }
+      __syncthreads();
+      if (!live) continue;
+      const int nj = n - j0 < kRdfChunk ? n - j0 : kRdfChunk;
+      for (int jj = 0; jj < nj; ++jj) {
+        if (!(tgi < ci[3 * jj])) continue;
+        const unsigned int m = smask[ti * kMaxTypes + ci[3 * jj + 1]];
+        if (!m) continue;
+        const D3 pj = {cx[3 * jj], cx[3 * jj + 1], cx[3 * jj + 2]};
+        const int k = rdf_bin(dist2_unfused(minimgD(box, pi - pj)), a.dr, a.inv_dr, a.nbins);
+        if (k < 0) continue;
+        rdf_bump(hist, a, m, a.parts == 2 && ci[3 * jj + 2] != mi ? 1 : 0, k);
+      }
+    }
+  }
+  __syncthreads();
+  rdf_flush(hist, nh, acc);
+}
+
+// Frame bookkeeping behind the pair pass (single domain; on slabs the host keeps the books, see CtxT::rdf_launch).
+// k_rdf_count: the type counts of the owned particles, many workgroups, one global atomic per type and workgroup into the words
+// at kRdfTypes.  k_rdf_frame: one wave reads and clears them, computes M per selector (rdf_norm_pairs) and bumps frames,
+// pairs[s] += M, density[s] += M / V in frame order.  V comes in by value.
+template <typename R>
+__global__ __launch_bounds__(256) void k_rdf_count(int i0, int n, const Vec4<R>* __restrict__ x4, unsigned long long* __restrict__ acc, const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  __shared__ int cnt[kMaxTypes];
+  const int t = threadIdx.x;
+  if (t < kMaxTypes) cnt[t] = 0;
+  __syncthreads();
+  int mine[kMaxTypes];
+#pragma unroll
+  for (int u = 0; u < kMaxTypes; ++u) mine[u] = 0;
+  for (int i = blockIdx.x * 256 + t; i < n; i += gridDim.x * 256) {
+    const int ty = (int)x4[i0 + i].w & (kMaxTypes - 1);
+#pragma unroll
+    for (int u = 0; u < kMaxTypes; ++u) mine[u] += ty == u ? 1 : 0;
+  }
+#pragma unroll
+  for (int u = 0; u < kMaxTypes; ++u) {
+    int v = mine[u];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane_id() == 0 && v) atomicAdd(&cnt[u], v);
+  }
+  __syncthreads();
+  if (t < kMaxTypes && cnt[t]) atomicAdd(&acc[kRdfTypes + t], (unsigned long long)cnt[t]);
+}
+__global__ __launch_bounds__(64) void k_rdf_frame(RdfArgs a, double V, unsigned long long* __restrict__ acc, const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  __shared__ unsigned char smask[kMaxTypes][kMaxTypes];
+  __shared__ long long c[kMaxTypes];
+  const int t = threadIdx.x;
+  for (int k = t; k < kMaxTypes * kMaxTypes; k += 64) smask[k / kMaxTypes][k % kMaxTypes] = a.mask[k / kMaxTypes][k % kMaxTypes];
+  if (t < kMaxTypes) { c[t] = (long long)acc[kRdfTypes + t]; acc[kRdfTypes + t] = 0ull; }
+  __syncthreads();
+  if (t == 0) {
+    acc[kRdfFrames] += 1ull;
+    for (int s = 0; s < a.nsel; ++s) {
+      const unsigned long long M = rdf_norm_pairs(smask, s, c);
+      acc[kRdfPairs + s] += M;
+      acc[kRdfDensity + s] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)acc[kRdfDensity + s]) + (double)M / V);
+    }
+  }
 }
 
 }  // namespace chem

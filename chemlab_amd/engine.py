@@ -31,6 +31,25 @@ def comm_unique_id():
     return buf.raw
 
 
+def rdf_edges(r_max, nbins):
+    """The bin edges of the rule set: e[k] = k * (r_max / nbins) in fp64."""
+    return np.arange(nbins + 1, dtype=np.float64) * (np.float64(r_max) / np.float64(nbins))
+
+
+def rdf_result(r_max, counts, frames, pairs, density):
+    """The dict Engine.rdf() returns, from the raw integers and normalisers of chem_rdf_get (the division is done here)."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    nsel, parts, nbins = counts.shape
+    edges = rdf_edges(r_max, nbins)
+    shell = (4.0 * np.pi / 3.0) * (edges[1:] ** 3 - edges[:-1] ** 3)
+    g = np.zeros(counts.shape, dtype=np.float64)
+    for s in range(nsel):
+        if density[s] > 0:
+            g[s] = counts[s].astype(np.float64) / (density[s] * shell)
+    return dict(r=0.5 * (edges[1:] + edges[:-1]), edges=edges, counts=counts, g=g, frames=int(frames), pairs=np.asarray(pairs),
+                density=np.asarray(density), r_max=float(r_max), nbins=nbins, split=parts == 2)
+
+
 class Engine:
     def __init__(self, device=0, precision=32, api=None, ctx=None):
         """precision: 32 (fp32 arrays, fp64 bonded/reaction distance) or 64 (all fp64)."""
@@ -238,6 +257,8 @@ class Engine:
             name = "checkpoint_save"
         if name == "region":
             name = "region_add"
+        if name == "rdf":
+            name = "rdf_init"
         return getattr(self.api, name, None) is not None
 
     # ---- region rules: FreezeRegion, ChangeParticleType (include/chem_mi355.h, chem_region_add ff.) ----
@@ -291,6 +312,46 @@ class Engine:
         f, s = C.c_int64(0), C.c_int64(0)
         self._ck(self._region_entry("region_counters")(self.ctx, C.byref(f), C.byref(s)))
         return int(f.value), int(s.value)
+
+    # ---- radial distribution functions accumulated on the device (include/chem_mi355.h, chem_rdf_init ff.) ----
+    def _rdf_entry(self, name):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("rdf: the CPU checker has no pair histogram")
+        return fn
+
+    def rdf_init(self, r_max, nbins, type_pairs=((-1, -1),), split_molecules=False):
+        """Configure (and reset) the pair histograms: `nbins` bins up to r_max <= max_cutoff, one per unordered type pair of
+        `type_pairs` (-1 = any type; at most 8), two (intra, inter molecule) with split_molecules.  No pairs switches it off."""
+        fn = self._rdf_entry("rdf_init")
+        tp = np.ascontiguousarray(type_pairs, dtype=np.int32).reshape(-1, 2)
+        self._ck(fn(self.ctx, float(r_max), int(nbins), tp.shape[0], _ptr(tp, C.c_int32) if tp.shape[0] else None,
+                    1 if split_molecules else 0))
+
+    def rdf_sample(self):
+        """One frame of the current positions (the preconditions of observe())."""
+        self._ck(self._rdf_entry("rdf_sample")(self.ctx))
+
+    def rdf_sample_every(self, every):
+        """A frame inside run() at every step s with s % every == 0, without a host round trip; every <= 0: off."""
+        self._ck(self._rdf_entry("rdf_sample_every")(self.ctx, int(every)))
+
+    def rdf_reset(self):
+        """Zero the accumulators, keep the configuration."""
+        self._ck(self._rdf_entry("rdf_reset")(self.ctx))
+
+    def rdf(self):
+        """The accumulated histograms: dict of r (bin centres), edges, counts [npairs][parts][nbins] (exact integers), g (the
+        same shape: counts / (density * shell volume), zeros before the first frame), frames, pairs and density per selector,
+        r_max, nbins, split.  parts = 2 (intra, inter) with the molecule split, else 1."""
+        fn = self._rdf_entry("rdf_get")
+        res = _capi.RdfResult()
+        self._ck(fn(self.ctx, C.byref(res), None, 0))
+        nsel, parts, nbins = int(res.npairs), 1 + int(res.split), int(res.nbins)
+        counts = np.zeros((nsel, parts, nbins), dtype=np.uint64)
+        self._ck(fn(self.ctx, C.byref(res), _ptr(counts, C.c_uint64), counts.size))
+        return rdf_result(float(res.r_max), counts, int(res.frames), np.array(res.pairs[:nsel], dtype=np.uint64),
+                          np.array(res.density[:nsel], dtype=np.float64))
 
     # ---- checkpoint and exact restart (include/chem_mi355.h, chem_checkpoint_save / chem_checkpoint_load) ----
     def _ckpt_entry(self, name):

@@ -1855,6 +1855,41 @@ class _PressureTensor(_Observable):
         return [float(c) for c in self.system.engine.pressure_tensor()["tensor"]]
 
 
+class _RadialDistrF(_Observable):
+    """analysis.RadialDistrF(system): g(r) accumulated on the device (include/chem_mi355.h chem_rdf_*).
+
+    compute(nbins, r_max=None, types=None) takes one frame of the current configuration and returns g of the first selector as
+    a list of nbins values; `types` is a list of (t1, t2) pairs, -1 = any type (default: all pairs).  Upstream's class bins one
+    configuration on the host out to half the box; this one stops at the list cutoff max_cutoff (r_max=None means max_cutoff),
+    because the device's tile tables hold nothing beyond it.  For a time average inside integrator.run use
+    start(nbins, r_max, types, every, split_molecules) once and result() (the dict of Engine.rdf()) when the run is over."""
+
+    def __init__(self, system):
+        _Observable.__init__(self, system)
+
+    def _init(self, nbins, r_max, types, split_molecules=False):
+        e = self.system.engine
+        if not e.supports("rdf"):
+            raise NotImplementedError("rdf: the CPU checker has no pair histogram")
+        if r_max is None:
+            r_max = self.system.max_cutoff
+        if r_max is None:
+            raise ValueError("RadialDistrF: no r_max and no list cutoff yet (VerletList sets it)")
+        e.rdf_init(float(r_max), int(nbins), [(-1, -1)] if types is None else [tuple(t) for t in types], bool(split_molecules))
+        return e
+
+    def compute(self, nbins, r_max=None, types=None):
+        e = self._init(nbins, r_max, types)
+        e.rdf_sample()
+        return [float(v) for v in e.rdf()["g"][0, 0]]
+
+    def start(self, nbins, r_max=None, types=None, every=1, split_molecules=False):
+        self._init(nbins, r_max, types, split_molecules).rdf_sample_every(int(every))
+
+    def result(self):
+        return self.system.engine.rdf()
+
+
 class _BoxSize(_Observable):
     """The `L` column that goes with `P` (start_simulation.py:466-469): the x edge of the current box.  The reference's
     class is in the external fork; what it reports for a box that is not cubic is unpinned."""
@@ -2013,7 +2048,7 @@ analysis = _ns(
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
     ResolutionFixedTripleList=_ResolutionFixedTripleList, ResolutionFixedQuadrupleList=_ResolutionFixedQuadrupleList,
-    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor,
+    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor, RadialDistrF=_RadialDistrF,
 )
 
 esutil = _ns(RNG=_RNG)

@@ -980,6 +980,60 @@ int     chem_region_counters(chem_ctx* ctx, int64_t* firings, int64_t* syncs);  
 int64_t chem_checkpoint_save(chem_ctx* ctx, void* buf, int64_t cap);
 int     chem_checkpoint_load(chem_ctx* ctx, const void* buf, int64_t nbytes);
 
+/* ---- radial distribution functions ------------------------------------------------------ */
+/* Time-averaged g(r) per type pair, accumulated on the device as exact integer counts; a frame can be taken inside chem_run
+ * without a host round trip.  (Upstream's analysis.RadialDistrF bins one configuration on the host, out to half the box; this
+ * rule set is this build's own.)
+ *   Pairs.     Every unordered pair of distinct particles {i, j} of the whole system, dummies of fixed-distance sets and excluded
+ *              (bonded, 1-3, 1-4) pairs included, once per frame.
+ *   Distance.  d2 = the fp64 minimum-image r^2 of the decoded positions, without FMA contraction: the expression of the
+ *              reaction scan (the fp32 build decodes its fixed-point positions to double first).
+ *   Bins.      dr = r_max / nbins in fp64, e[k] = (double)k * dr, e2[k] = e[k] * e[k], k = 0..nbins.  A pair is in the bin k with
+ *              e2[k] <= d2 < e2[k+1] and is not counted when d2 >= e2[nbins].  The edges decide, never the rounding of a sqrt.
+ *              r_max <= max_cutoff (chem_set_cutoff): the tile tables of the last build hold every pair inside max_cutoff while
+ *              the skin lasts, and nothing beyond.  A wider range is out of scope.
+ *   Selectors. Up to CHEM_RDF_MAX_PAIRS unordered type pairs (t1, t2), -1 = any type.  A pair is counted in EVERY selector it
+ *              matches, so (-1, -1) is the total.  Types are those at the sampled step.
+ *   Split.     split_molecules != 0: two histograms per selector, intra (mol_id[i] == mol_id[j], the labels the reaction scan of
+ *              that step would read) and inter, in that order; otherwise one.
+ *   Normalisers, per selector and frame: M = the number of unordered pairs of distinct particles whose types match, from the
+ *              type counts c[]: the sum over matching type pairs u <= v of c_u (c_u - 1) / 2 (u == v) or c_u c_v.  Accumulated:
+ *              frames; pairs[sel] = sum of M_f; density[sel] = sum of M_f / V_f in frame order, V_f = Lx Ly Lz of that frame.
+ *   Result.    g_sel(k) = counts[sel][k] / (density[sel] (4 pi / 3) (e[k+1]^3 - e[k]^3)); the division is the caller's.
+ *   Frames.    chem_rdf_sample takes one now, with chem_observe's preconditions and side effects and no others.
+ *              chem_rdf_sample_every(every) takes one inside chem_run at every step s with s % every == 0: of the positions the
+ *              forces of step s were evaluated at (what CHEM_STATE_POS shows if the run ends at s), enqueued behind that step's
+ *              force launch and in front of the next integrate launch, without a host wait (with the split, a label merge of the
+ *              last reaction step that is still running on the host is joined first, as the reaction scan does); every <= 0
+ *              switches it off.  A run is not sampled at its starting step, so run(a); run(b) accumulates bit for bit what
+ *              run(a + b) does.
+ *   Read-only. With sampling on, positions, velocities, forces, events and rebuild counters are bit for bit those of the same
+ *              run without it.  A context that never calls chem_rdf_* allocates nothing and launches what it launched before.
+ *   Not state. Accumulators and configuration are no part of a checkpoint; save and load leave them alone.
+ * chem_rdf_init: npairs = 0 switches everything off and frees the buffers; a second call reconfigures and resets.
+ * chem_rdf_get returns the configuration and normalisers in *out and the counts as [npairs][1 + split][nbins] (counts may be
+ * NULL with cap 0 to read the normalisers alone).
+ *   CHEM_EINVAL    r_max not finite or not positive, nbins outside 1..CHEM_RDF_MAX_BINS, npairs outside 0..CHEM_RDF_MAX_PAIRS, a
+ *                  type outside -1..CHEM_MAX_TYPES-1; at the next sample or run: r_max > max_cutoff (both values named, since the
+ *                  cutoff can be set later), a histogram that does not fit the LDS beside the staged particles, or more than
+ *                  65536 particles on a path without tiles.
+ *   CHEM_ENOSPC    chem_rdf_get with a cap below npairs * (1 + split) * nbins.
+ *   CHEM_ESTATE    chem_rdf_sample, chem_rdf_sample_every, chem_rdf_get or chem_rdf_reset before chem_rdf_init (or after
+ *                  npairs = 0).
+ * Slabs.  Every rank accumulates the pairs of its own home particles; a pair with a ghost member is counted by the rank that owns
+ * its lower tag, and a frame adds no communication.  frames, pairs and density are kept on the host from the type table, which is
+ * replicated by tag.  chem_rdf_get is collective, like chem_get_pressure, and returns the global integers on every rank.
+ * The per-cell and brute-force paths of a single domain run an all-pairs pass, O(N^2): refused (CHEM_EINVAL, at the next sample or
+ * run) above 65536 particles.  Under a barostat V_f is the box the forces of the sampled step were evaluated in. */
+#define CHEM_RDF_MAX_PAIRS 8
+#define CHEM_RDF_MAX_BINS  1024
+int chem_rdf_init(chem_ctx* ctx, double r_max, int nbins, int npairs, const int32_t* type_pairs /* 2*npairs, -1 = any */, int split_molecules);
+int chem_rdf_sample(chem_ctx* ctx);
+int chem_rdf_sample_every(chem_ctx* ctx, int every);
+typedef struct chem_rdf_result { double r_max; int32_t nbins, npairs, split; int64_t frames; uint64_t pairs[CHEM_RDF_MAX_PAIRS]; double density[CHEM_RDF_MAX_PAIRS]; } chem_rdf_result;
+int chem_rdf_get(chem_ctx* ctx, chem_rdf_result* out, uint64_t* counts /* [npairs][1+split][nbins] */, int64_t cap);
+int chem_rdf_reset(chem_ctx* ctx);   /* zero the accumulators, keep the configuration */
+
 /* ---- the hot call -------------------------------------------------------------------- */
 /* integrator.run(n)  start_simulation.py:780.  No host round trip per step. */
 int chem_run(chem_ctx* ctx, int64_t nsteps);
