@@ -436,10 +436,14 @@ template <typename R> struct CtxT : Ctx {
   DBuf<int4> bwork, bj; int nb_owner = 0; bool bwork_dirty = true;   // bonded work list (see dev_bonded_prep)
   // Inline bonds: all bonded terms are 2-body bonds of ONE harmonic parameter set and the exclusion set is exactly the bond
   // set (chain-growth systems) -> the LDS slots of the excluded partners, which the list build locates anyway, ARE the bonded
-  // partners: it writes them out (bslots), the force kernel evaluates the bonds from its staged image, the per-step bonded
+  // partners: it writes them out (BondRecs, md_kernels.hpp), the force kernel evaluates the bonds from its staged image, the per-step bonded
   // launch disappears.  Particles with more than kBondSlots (8) exclusions stay with the work list (then launched for them alone).
   // Decided on the host from what it knows exactly (bonds_inline()).
-  DBuf<uint4> bslots; bool harmonic_only = false, bonds_excluded = false;
+  DBuf<BondRec> brec0, brec1; bool harmonic_only = false, bonds_excluded = false;      // (one 8-byte word per particle each: partners 1-4, partners 5-8)
+  BondRecs bond_recs(size_t np) {      // the two arrays, grown to np particles (every list build rewrites them)
+    if (brec0.n < np) { brec0.alloc(np + 1024); brec1.alloc(np + 1024); }
+    return BondRecs{brec0.p, brec1.p};
+  }
   std::vector<uint8_t> excl_deg; size_t excl_deg_upto = 0; int64_t excl_over = 0;   // particles with more than kBondSlots (8) exclusions: their bonds stay with the work-list kernel
   void update_excl_deg() {
     if (excl_deg.size() != (size_t)top.n) { excl_deg.assign((size_t)top.n, 0); excl_deg_upto = 0; excl_over = 0; }
@@ -465,6 +469,7 @@ template <typename R> struct CtxT : Ctx {
     // (a 1-4 Coulomb list with parameters is a second slot, so harmonic_only already rules it out; one without parameters does
     //  nothing but would pass that proof -- inline bonds stay off next to any Coulomb term, so ask directly)
     if (top.any_coulomb_bond()) return false;
+    if (!bond_records_fit(tile_cap)) return false;      // (a slot of the staged tile must fit the record's 16 bits)
     // the exclusion set must BE the bond set (bonds are a subset: bonds_excluded; both are duplicate-free): equal counts
     size_t nb2 = 0;
     for (const auto& l : top.lists) if (l.arity == 2) nb2 += (size_t)l.size();
@@ -731,10 +736,9 @@ template <typename R> struct CtxT : Ctx {
     a.bstart = bstart.p; a.bent = bent.p; a.bwork = bwork.p; a.bj = bj.p; a.nbent = (int)std::min<int64_t>(nbent, 1 << 30);
     a.fold = fold_sd() ? (ensure_hflag(), foldmax.p) : nullptr;
     a.hint = publish && fold_sd() ? hint_dev() : nullptr; a.gen = hint_gen;
-    a.bslots = nullptr; a.bond_pass = 0;
+    a.bslots = BondRecs{}; a.bond_pass = 0;
     if (bonds_inline() && !(sizeof(R) == 8 && want32)) {   // (the exact fp64 builder of the int32 rows locates no slots: ensure_list32 rebuilds again)
-      if (bslots.n < 2 * (size_t)n) bslots.alloc(2 * (size_t)n + 1024);      // two quads (kBondSlots = 8 words) per particle
-      a.bslots = bslots.p;
+      a.bslots = bond_recs((size_t)n);
       a.bond_pass = (bond_by_pass() && !want32) ? (opt_bond_slots_kernel ? 2 : 1) : 0;    // (the int32 rows must leave the excluded pairs out: ensure_list32 rebuilds again behind them)
       if (excl_over == 0) a.nbent = 0;                      // no work list needed; otherwise it holds the owners with > kBondSlots exclusions only
     }
@@ -742,7 +746,7 @@ template <typename R> struct CtxT : Ctx {
     else hipLaunchKernelGGL((k_rebuild_fused<R, 512>), dim3(fused_grid), dim3(512), list_lds_need(false), stream, a);
     if (a.bond_pass == 2)      // (leaves at once unless the launch in front of it has rebuilt: DevCtl::need_rebuild)
       hipLaunchKernelGGL((k_bond_slots<R>), dim3(ntiles), dim3(256), 0, stream, ntiles, (const TileLDS<R>*)tdesc.p, (const int*)tag.p, (const int*)excl_start.p,
-                         (const int*)excl_list.p, (const int*)rtag.p, (const int*)nullptr, 0, 0x7fffffff, (const V4*)x4.p, box, bslots.p, ctl.p);
+                         (const int*)excl_list.p, (const int*)rtag.p, (const int*)nullptr, 0, 0x7fffffff, (const V4*)x4.p, box, a.bslots, ctl.p);
     fused_par ^= 1;
   }
 
@@ -1378,14 +1382,13 @@ template <typename R> struct CtxT : Ctx {
     DevCtl* c = ctl.p;
     const R rl2 = (R)((rc + skin_eff()) * (rc + skin_eff())), rl2_rows = (R)((rc + skin) * (rc + skin));   // (they differ on the tile path only)
     if (use_tiles) {
-      uint4* bs = nullptr, *record = nullptr;      // inline bonds (decomposed path: the standalone list kernel records the partner slots ...)
+      BondRecs bs{}, record{};      // inline bonds (decomposed path: the standalone list kernel records the partner slots ...)
       int list_excl = has_excl;
       if (dd_on && bonds_inline()) {
-        if (bslots.n < 2 * (size_t)acap()) bslots.alloc(2 * (size_t)acap() + 1024);
-        bs = bslots.p;
+        bs = bond_recs((size_t)acap());
         // (... unless the bond pass is on: the list build ignores the exclusions = bonds, k_bond_slots behind it records the
         //  partner slots and every force launch takes the partners' pair term out again, as on the fused path)
-        if (bond_by_pass() && !want32) { bs = nullptr; list_excl = 0; record = bslots.p; }
+        if (bond_by_pass() && !want32) { record = bs; bs = BondRecs{}; list_excl = 0; }
       }
       hipLaunchKernelGGL((k_tile_desc<R>), dim3(std::min(ntiles, 2048)), dim3(128), 0, stream, ntiles, tile_cap, cell_start.p, box, tdesc.p, c, (const int*)cell_sub.p);
       hipLaunchKernelGGL((k_tile_scan<R>), dim3(1), dim3(1024), 0, stream, ntiles, tdesc.p, c);
@@ -1723,7 +1726,7 @@ template <typename R> struct CtxT : Ctx {
         else if constexpr (M == 6) feature(kern, cap_args());
         else if constexpr (M == 7) feature(kern, res_args(), cap_args());
         else launch(kern, uni, eout.p, hs, ctl.p, pair_guard, opt_ablate, dbg_on ? dbgbuf.p : (long long*)nullptr, ts, pair_da,
-                    (inline_now && (!ENERGY || bond_mode >= 2)) ? bslots.p : (uint4*)nullptr, inline_K, inline_r0, bond_mode, act);
+                    (inline_now && (!ENERGY || bond_mode >= 2)) ? BondRecs{brec0.p, brec1.p} : BondRecs{}, inline_K, inline_r0, bond_mode, act);
       });
       return ntiles;
     }
@@ -2097,7 +2100,7 @@ template <typename R> struct CtxT : Ctx {
         auto kern = &k_pair_tiles_tensor<R, decltype(M_)::value>;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, stream, nblk, tile_cap, x4.p, fdst, tdesc.p, nl16.p, nnh.p, S, pcore.p, pext.p, ntypes, tab.p, eout.p, hs, ctl.p, ts,
-                           (v.mode == 3 && bond_mode >= 2) ? bslots.p : (uint4*)nullptr, bond_mode, act, ca, ra, cp, tout);
+                           (v.mode == 3 && bond_mode >= 2) ? BondRecs{brec0.p, brec1.p} : BondRecs{}, bond_mode, act, ca, ra, cp, tout);
         return true;
       });
     } else {

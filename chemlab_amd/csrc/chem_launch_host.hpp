@@ -183,5 +183,11 @@ inline BondedPlan bonded_plan(const BondedInput& in) {
   p.nown = in.inline_bonds ? (int)std::min<long long>(in.nb_owner, in.excl_over) : in.nb_owner;
   return p;
 }
+// Inline bonds keep a bonded partner's LDS slot in 16 bits (BondRec, md_kernels.hpp), kBondRecNone = no partner.  A staged tile of
+// tile_cap slots numbers them 0 .. tile_cap - 1, so every slot a record can hold stays below the mark while tile_cap does not
+// exceed it.  Beyond that CtxT::bonds_inline() answers no and the bonds go to the work list (BondedInput::inline_bonds = false),
+// the route of every context the force kernel does not serve.
+constexpr unsigned int kBondRecNone = 0xffffu;
+constexpr bool bond_records_fit(long long tile_cap) { return tile_cap >= 0 && tile_cap <= (long long)kBondRecNone; }
 
 }  // namespace chem

@@ -15,6 +15,7 @@
 #include "../../include/chem_philox.h"
 #include "chem_geom_host.hpp"
 #include "chem_idle_host.hpp"
+#include "chem_launch_host.hpp"
 #include "chem_roworder_host.hpp"
 #include "chem_baro_host.hpp"
 #include "chem_region_host.hpp"
@@ -125,7 +126,29 @@ __device__ __forceinline__ void publish_hint(IdleHint* hint, int gen, long long 
 }
 
 // bonded tables (per-tag CSR, see K4-K6 below; declared here because the list build records the LDS slots of bonded partners)
-constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 16-byte quads)
+constexpr int kBondSlots = 8;   // inline bonds: recorded partner slots per home particle (two 8-byte words)
+// The record of a home particle: the LDS slots of its bonded partners, four 16-bit slots per 8-byte word (slot k of a word in bits
+// 16 k .. 16 k + 15, kBondRecNone = no partner; bond_records_fit, chem_launch_host.hpp, keeps every slot below it).  Two arrays,
+// one word per particle each, indexed by the particle's place in the sorted arrays: rec0 holds partners 1-4 and is read by every
+// lane of the force kernel as one dense stream, rec1 holds partners 5-8 and is written and read only behind a FULL rec0 (fourth
+// slot set) -- a stale rec1 behind a rec0 that is no longer full is never looked at.
+typedef uint2 BondRec;
+struct BondRecs {
+  BondRec* __restrict__ rec0; BondRec* __restrict__ rec1;
+  CHEM_HD explicit operator bool() const { return rec0 != nullptr; }
+};
+// ... from four slots (any value with the low 16 bits set, ~0u included: no partner) and back (kBondRecNone: no partner)
+CHEM_HD BondRec bond_rec_pack(unsigned int s0, unsigned int s1, unsigned int s2, unsigned int s3) {
+  BondRec r; r.x = (s0 & 0xffffu) | (s1 << 16); r.y = (s2 & 0xffffu) | (s3 << 16); return r;
+}
+CHEM_HD void bond_rec_unpack(const BondRec r, unsigned int (&s)[4]) { s[0] = r.x & 0xffffu; s[1] = r.x >> 16; s[2] = r.y & 0xffffu; s[3] = r.y >> 16; }
+CHEM_HD BondRec bond_rec_none() { return bond_rec_pack(kBondRecNone, kBondRecNone, kBondRecNone, kBondRecNone); }
+CHEM_HD bool bond_rec_full(const BondRec r) { return (r.y >> 16) != kBondRecNone; }
+// ... and slot k (0 .. kBondSlots - 1) of particle p's record in memory, for the one writer that records hit by hit (the generic
+// path of the list sweep): the same layout as bond_rec_pack's, written 16 bits at a time
+__device__ __forceinline__ unsigned short* bond_rec_slot(const BondRecs& b, size_t p, int k) {
+  return reinterpret_cast<unsigned short*>(k < 4 ? b.rec0 + p : b.rec1 + p) + (k & 3);
+}
 struct BondedEntry { int t0, t1, t2, meta; };   // tuple tags in order (self included); meta = bonded_meta(slot, mypos) (chem_host.hpp); quadruples use a 2nd entry for t3
                                                 // pairs: t2 = 0, or ~birth step (< 0) for an entry of a hybrid list (chem_list_set_hybrid)
                                                 // triples and quadruples of a hybrid list (chem_list_set_hybrid_tuples; pad of their slot): a 2nd entry
@@ -1950,7 +1973,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
                                                    const int* excl_start, const int* excl_list, const int has_excl,
                                                    unsigned short* nl16, const int S16, int* nnh, int* nlist, const int S, int* nn, DevCtl* ctl,
                                                    const Box<RS>* bx, const int* rtag, const Vec4<RS>* x4, const int ablate = 0, const float rl2_rows_ = -1.f,
-                                                   uint4* bslots = nullptr, const int* gtag = nullptr, const int real0 = 0, const int real1 = 0x7fffffff,
+                                                   const BondRecs bslots = BondRecs{}, const int* gtag = nullptr, const int real0 = 0, const int real1 = 0x7fffffff,
                                                    const int coop_on = 0, const int hbase_out = -1) {
   // (gtag, real0, real1: slab decomposition -- index of a tag's GHOST copy on this rank, range of the real particles;
   //  hbase_out >= 0: row base of the rows and counts in nl16 / nnh instead of the tile's own, see dev_row_order)
@@ -2054,20 +2077,20 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
   };
   // Inline bonds (force kernel epilogue).  The host enables this only where the exclusion set IS the bond set and all bonds
   // share one harmonic parameter set (chain-growth systems: every reaction bond is excluded, nothing else is): the LDS slots
-  // of the excluded partners are the bonded partners -- recorded as they are (eight 32-bit words per home particle, ~0 = none),
+  // of the excluded partners are the bonded partners -- recorded as they are (a BondRec of four 16-bit slots per home particle, a second one behind a full first),
   // no bonded table is consulted.  Located partners (<= 4 exclusions) are written here; on the generic path (5..8 exclusions,
   // or int32 rows wanted) every excluded hit is recorded as it is met in the sweep below.  More than kBondSlots exclusions:
   // the particle's bonds stay with the work list.
-  auto bonds_located = [&](const Home& h, unsigned int* const bsw) __attribute__((always_inline)) {
-    uint4 bw = make_uint4(~0u, ~0u, ~0u, ~0u);
+  auto bonds_located = [&](const Home& h) __attribute__((always_inline)) {
+    unsigned int w0 = ~0u, w1 = ~0u, w2 = ~0u, w3 = ~0u;
     if (h.fastx) {
-      if (h.xs0 >= 0) bw.x = (unsigned int)h.xs0; else if (h.e0 + 0 < h.e1) ctl->bond_slot_miss = 1;
-      if (h.xs1 >= 0) bw.y = (unsigned int)h.xs1; else if (h.e0 + 1 < h.e1) ctl->bond_slot_miss = 1;
-      if (h.xs2 >= 0) bw.z = (unsigned int)h.xs2; else if (h.e0 + 2 < h.e1) ctl->bond_slot_miss = 1;
-      if (h.xs3 >= 0) bw.w = (unsigned int)h.xs3; else if (h.e0 + 3 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs0 >= 0) w0 = (unsigned int)h.xs0; else if (h.e0 + 0 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs1 >= 0) w1 = (unsigned int)h.xs1; else if (h.e0 + 1 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs2 >= 0) w2 = (unsigned int)h.xs2; else if (h.e0 + 2 < h.e1) ctl->bond_slot_miss = 1;
+      if (h.xs3 >= 0) w3 = (unsigned int)h.xs3; else if (h.e0 + 3 < h.e1) ctl->bond_slot_miss = 1;
     }
-    *reinterpret_cast<uint4*>(bsw) = bw;
-    if (bw.w != ~0u) *reinterpret_cast<uint4*>(bsw + 4) = make_uint4(~0u, ~0u, ~0u, ~0u);   // (the second quad is only read behind a full first one)
+    bslots.rec0[h.p] = bond_rec_pack(w0, w1, w2, w3);
+    if (w3 != ~0u) bslots.rec1[h.p] = bond_rec_none();   // (the second word is only read behind a full first one)
   };
   auto window = [&](const Home& h, const int dzy, int& a, int& b) __attribute__((always_inline)) {
     const int dz = dzy / 3, dy = dzy - 3 * dz;
@@ -2142,10 +2165,10 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     const bool fastx = h.fastx;
     int cnt = 0, cnt16 = 0;
     int* row32 = nlist ? nlist + (size_t)p * S : nullptr;
-    unsigned int* const bsw = bslots ? reinterpret_cast<unsigned int*>(bslots) + (size_t)p * kBondSlots : nullptr;      // (indexed by the particle's place in the sorted arrays)
+    const bool bsw = (bool)bslots;      // (the record is indexed by the particle's place in the sorted arrays)
     int nbw = 0;
     const bool bond_rec = bsw && !fastx && e1 > e0 && e1 - e0 <= kBondSlots;      // generic path records while sweeping
-    if (bsw && (fastx || e1 == e0)) bonds_located(h, bsw);
+    if (bsw && (fastx || e1 == e0)) bonds_located(h);
     const bool plain = (e1 == e0 || fastx) && !row32;
     uint4* regq = reinterpret_cast<uint4*>(reg16) + q;   // chunk c of this particle: regq[c * nhome]
     // accepted slots are shifted into a 128-bit register; every 8th append stores one whole 16-byte chunk (one
@@ -2198,7 +2221,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
             if (e1 > e0) {
               const int tgj = tag[j];
               for (int ee = e0; ee < e1; ++ee) if (excl_list[ee] == tgj) { ok = false; break; }
-              if (!ok && bond_rec && nbw < kBondSlots) bsw[nbw++] = (unsigned int)sl;      // inline bonds: an excluded hit is a bonded partner
+              if (!ok && bond_rec && nbw < kBondSlots) *bond_rec_slot(bslots, (size_t)p, nbw++) = (unsigned short)sl;      // inline bonds: an excluded hit is a bonded partner
             }
             if (ok) {
               if (tm & bit) push((unsigned int)sl);      // (shell pairs included, as on the plain path: the force list does not depend on the path)
@@ -2210,7 +2233,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
     }
     if (bsw && !fastx && e1 > e0) {       // generic path: close the record (or leave it empty for a particle the work list keeps)
       if (bond_rec && nbw != e1 - e0) ctl->bond_slot_miss = 1;      // every excluded (= bonded) partner sits within the list radius
-      for (int k = bond_rec ? nbw : 0; k < kBondSlots; ++k) bsw[k] = ~0u;
+      for (int k = bond_rec ? nbw : 0; k < kBondSlots; ++k) *bond_rec_slot(bslots, (size_t)p, k) = (unsigned short)kBondRecNone;      // (both words, whatever the first holds: this path is rare)
     }
     // pad the last chunk with the far-away dummy slot (chunks are read whole)
     const int real16 = cnt16;
@@ -2266,7 +2289,7 @@ __device__ __forceinline__ void dev_nlist_tile_f32(const TileLDS<RS>& T, unsigne
           s00 = a & ~3;
           if (b - s00 > 128) fb = true;
           else {
-            if (row == 0 && bslots) bonds_located(h, reinterpret_cast<unsigned int*>(bslots) + (size_t)h.p * kBondSlots);
+            if (row == 0 && bslots) bonds_located(h);
             int k = 0;
             for (int s0 = s00; s0 < b; s0 += 32, ++k) {
               unsigned int tm;
@@ -2319,7 +2342,7 @@ __global__ __launch_bounds__(BS, 4) void k_nlist_tiles(int ntiles, int CAP, cons
                                                     const TileLDS<R>* __restrict__ desc, R rl2,
                                                     const int* __restrict__ excl_start, const int* __restrict__ excl_list, int has_excl,
                                                     ActMask act, int ntypes, unsigned short* __restrict__ nl16, int S16, int* __restrict__ nnh,
-                                                    int* __restrict__ nlist, int S, int* __restrict__ nn, DevCtl* ctl, R rl2_rows, uint4* __restrict__ bslots,
+                                                    int* __restrict__ nlist, int S, int* __restrict__ nn, DevCtl* ctl, R rl2_rows, BondRecs bslots,
                                                     const Box<R>* __restrict__ boxp, const int* __restrict__ rtag, const int* __restrict__ gtag, int real0, int real1, int coop) {
   // (rl2: the radius the 16-bit force list is built for, rc + list skin; rl2_rows: the int32 Verlet rows', rc + skin;
   //  boxp/rtag/gtag/real0/real1: located-partner path of the exclusions on a slab, boxp == nullptr: generic path)
@@ -2458,10 +2481,10 @@ __device__ __forceinline__ int tile_partner_slot(const TileLDS<R>& T, int g, con
   return -1;
 }
 // The list build of the bond pass (bond_mode 2) ignores the exclusions; the partner slots of every home particle are recorded
-// behind it, once per list lifetime, for the force launches up to the next rebuild (eight words per particle: two quads, ~0u
-// = no partner).  tag -> exclusion row -> partner index -> partner position -> cell -> slot through the tile tables in LDS.
+// behind it, once per list lifetime, for the force launches up to the next rebuild (a BondRec per particle, a second one behind
+// a full first).  tag -> exclusion row -> partner index -> partner position -> cell -> slot through the tile tables in LDS.
 // One lane per home particle of the tile described by T; the loads of each level of the chain are issued for up to four
-// partners before the first is consumed, the second quad (five to eight partners, rare) takes the same path once more.
+// partners before the first is consumed, the second word (five to eight partners, rare) takes the same path once more.
 // gtag, real0, real1: slabs (the tag's ghost copy, the index range of the real particles), as in tile_partner_slot.
 // Runs in the idle tail of k_rebuild_fused (single domain) and as k_bond_slots behind every other list build.  Inlined into the
 // rebuild it costs 28 bytes of scratch per lane and no register (128, occupancy 4); as a real call it cost 112.
@@ -2493,7 +2516,7 @@ template <typename R>
 __device__ __forceinline__ void dev_bond_slots_tile(const TileLDS<R>& T, const int* __restrict__ tag, const int* __restrict__ excl_start,
                                                     const int* __restrict__ excl_list, const int* __restrict__ rtag, const int* __restrict__ gtag,
                                                     const int real0, const int real1, const Vec4<R>* __restrict__ x4, const Box<R>& bx,
-                                                    uint4* __restrict__ bslots, DevCtl* ctl) {
+                                                    const BondRecs bslots, DevCtl* ctl) {
   const int nhome = T.geom[4];
   for (int q = threadIdx.x; q < nhome; q += (int)blockDim.x) {
     int sgi = 0;
@@ -2510,8 +2533,8 @@ __device__ __forceinline__ void dev_bond_slots_tile(const TileLDS<R>& T, const i
       bond_slots_quad<R>(T, e0, ne < 4 ? ne : 4, excl_list, rtag, gtag, real0, real1, x4, bx, hz, ctl, w);
       if (ne > 4) bond_slots_quad<R>(T, e0 + 4, ne - 4, excl_list, rtag, gtag, real0, real1, x4, bx, hz, ctl, w + 4);
     }
-    bslots[2 * (size_t)p] = make_uint4(w[0], w[1], w[2], w[3]);
-    if (w[3] != ~0u) bslots[2 * (size_t)p + 1] = make_uint4(w[4], w[5], w[6], w[7]);      // (only read behind a full first quad)
+    bslots.rec0[p] = bond_rec_pack(w[0], w[1], w[2], w[3]);
+    if (w[3] != ~0u) bslots.rec1[p] = bond_rec_pack(w[4], w[5], w[6], w[7]);      // (only read behind a full first word)
   }
 }
 // ... behind the list launch of the unfused chain and of a slab rebuild: one workgroup per tile, the tables from desc[]
@@ -2519,7 +2542,7 @@ template <typename R>
 __global__ __launch_bounds__(256) void k_bond_slots(int ntiles, const TileLDS<R>* __restrict__ desc, const int* __restrict__ tag,
                                                     const int* __restrict__ excl_start, const int* __restrict__ excl_list,
                                                     const int* __restrict__ rtag, const int* __restrict__ gtag, int real0, int real1,
-                                                    const Vec4<R>* __restrict__ x4, const Box<R> box, uint4* __restrict__ bslots, DevCtl* ctl) {
+                                                    const Vec4<R>* __restrict__ x4, const Box<R> box, BondRecs bslots, DevCtl* ctl) {
   if (!ctl->need_rebuild || ctl->halt) return;      // (halt: the rebuild in front of this launch could not finish its lists)
   __shared__ TileLDS<R> T;
   tile_load_desc<R>(T, desc, blockIdx.x);
@@ -2548,7 +2571,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
                                                    const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
                                                    int ntypes, const Vec4<R>* __restrict__ tab, UniLJ uni, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
-                                                   DecideArgs da, uint4* __restrict__ bslots,
+                                                   DecideArgs da, const BondRecs bslots,
                                                    double bond_K, double bond_r0, int bond_mode, ActMask bact,
                                                    const CoulArgs<R> ca, const ResArgs<R> ra, const CapArgs<R> cp = CapArgs<R>{},
                                                    double* __restrict__ tout = nullptr) {
@@ -2637,7 +2660,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
   // overlaps the stencil loads
   int p = -1, cnt = 0, hslot = 0, qq = 0;
   uint4 pkv[NCH];
-  uint4 bwv = make_uint4(~0u, ~0u, ~0u, ~0u);
+  BondRec bwv = bond_rec_none();
 #ifndef CHEM_NT_PRE
 #define CHEM_NT_PRE 1
 #endif
@@ -2654,7 +2677,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
     const int hr = (sgi / HY + 1) * SY + (sgi % HY + 1);
     hslot = T.rowoff[hr] + T.celloff[hr][1] + inrun;      // the home particle's own slot in the staged tile
     cnt = row_word_count(cw);
-    if (bslots) bwv = bslots[2 * (size_t)p];   // (inline bonds: first quad, issued with the list chunks, consumed after the pair loop)
+    if (bslots) bwv = bslots.rec0[p];   // (inline bonds: first word, issued with the list chunks, consumed after the pair loop)
 #pragma unroll
     for (int c = 0; c < NCH; ++c)                           // the tile's region is always allocated: safe before cnt is known
       pkv[c] = (sub + c * TPP) * 8 < S16 ? (CHEM_NT_PRE ? nt_load_u4(&reg[(size_t)(sub + c * TPP) * nhome + q]) : reg[(size_t)(sub + c * TPP) * nhome + q]) : make_uint4(0, 0, 0, 0);
@@ -2806,11 +2829,12 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
         //   slots instead, dev_bond_slots_tile) -- the partners' pair term is in the sums above: take it out again, then add the bonds.  An excluded
         //   pair within the cutoff now was within the list radius at the build, i.e. it IS in the list if its type pair is active.
         const R m2K = (R)(-2.0 * bond_K), r0b = (R)bond_r0;              // (one parameter set: kernel arguments, no table)
-        auto bond_quad = [&](const uint4 bq) {
-          const unsigned int bws[4] = {bq.x, bq.y, bq.z, bq.w};
+        auto bond_quad = [&](const BondRec bq) {
+          unsigned int bws[4];
+          bond_rec_unpack(bq, bws);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            if (bws[k] == ~0u) continue;
+            if (bws[k] == kBondRecNone) continue;
             const unsigned int sl = bws[k];
             Vec4<R> xj;
             if constexpr (D3) { xj = lds_gather3d(sx, sl); xj.w = (R)d3_types<R>(sx, CAP)[sl]; } else xj = sx[sl];
@@ -2839,7 +2863,7 @@ __device__ __forceinline__ void pair_tiles_body(int ntiles, int CAP, const Vec4<
           }
         };
         bond_quad(bwv);
-        if (bwv.w != ~0u) bond_quad(bslots[2 * (size_t)p + 1]);   // five to eight bonds: the second quad (rare)
+        if (bond_rec_full(bwv)) bond_quad(bslots.rec1[p]);   // five to eight bonds: the second word (rare)
       }
     }
     if (TPP > 1) {
@@ -2883,7 +2907,7 @@ __global__ __launch_bounds__(BS, sizeof(R) == 8 ? 4 : (BS == 1024 ? 2048 : 1536)
                                                    const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
                                                    int ntypes, const Vec4<R>* __restrict__ tab, UniLJ uni, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, int ablate, long long* __restrict__ dbg, TileSub sub_,
-                                                   DecideArgs da = DecideArgs{}, uint4* __restrict__ bslots = nullptr,
+                                                   DecideArgs da = DecideArgs{}, BondRecs bslots = BondRecs{},
                                                    double bond_K = 0.0, double bond_r0 = 0.0, int bond_mode = 0, ActMask bact = ActMask{}) {
   static_assert(MODE < 4, "MODE 4 is k_pair_tiles_q, MODE 5 k_pair_tiles_res, MODE 6 k_pair_tiles_cap, MODE 7 k_pair_tiles_rescap");
   pair_tiles_body<R, TPP, ENERGY, BS, MODE, DIAG>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, uni, eout, half_skin, ctl, guard, ablate, dbg,
@@ -2898,7 +2922,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CoulArgs<R> ca) {
   pair_tiles_body<R, 1, ENERGY, 512, 4, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, ca, ResArgs<R>{});
+                                               sub_, da, BondRecs{}, 0.0, 0.0, 0, ActMask{}, ca, ResArgs<R>{});
 }
 // MODE 5: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2909,7 +2933,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra) {
   pair_tiles_body<R, 1, ENERGY, 512, 5, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra);
+                                               sub_, da, BondRecs{}, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra);
 }
 // MODE 6: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2920,7 +2944,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, CapArgs<R> cp) {
   pair_tiles_body<R, 1, ENERGY, 512, 6, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ResArgs<R>{}, cp);
+                                               sub_, da, BondRecs{}, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ResArgs<R>{}, cp);
 }
 // MODE 7: one lane per particle, 512 threads; no inline bonds
 template <typename R, bool ENERGY>
@@ -2931,7 +2955,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                    int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
                                                    double half_skin, DevCtl* ctl, int guard, TileSub sub_, DecideArgs da, ResArgs<R> ra, CapArgs<R> cp) {
   pair_tiles_body<R, 1, ENERGY, 512, 7, false>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, guard, 0, nullptr,
-                                               sub_, da, nullptr, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra, cp);
+                                               sub_, da, BondRecs{}, 0.0, 0.0, 0, ActMask{}, CoulArgs<R>{}, ra, cp);
 }
 
 // =======================================================================================
@@ -3460,7 +3484,7 @@ template <typename R> struct FusedArgs {
   unsigned short* stage16; int* stage_cnt; int stage_cap, row_P;
   unsigned long long* blockmax; DevCtl* ctl; GridBar* gb;
   const int* bstart; const BondedEntry* bent; int4 *bwork, *bj; int nbent;
-  uint4* bslots;         // inline bonds (non-null: the bonded partners' LDS slots are recorded, eight words per particle)
+  BondRecs bslots;       // inline bonds (rec0 non-null: the bonded partners' LDS slots are recorded, one BondRec per particle in each array)
   int bond_pass;         // 1: the list build ignores the exclusions (= bonds); workgroups that have run out of tiles record the partner
                          //    slots (dev_bond_slots_tile) and every force launch takes the partners' pair term out again (k_pair_tiles bond_mode 2);
                          //    2: as 1, but k_bond_slots behind this launch records the slots (option bond_slots_kernel);
@@ -3681,7 +3705,7 @@ __global__ __launch_bounds__(BS, CHEM_FUSED_WAVES) void k_rebuild_fused(const Fu
         else
         dev_nlist_tile_f32<R, BS>(T, chem_dyn_lds, L, a.tago, (float)a.rl2, a.excl_start, a.excl_list, a.bond_pass ? 0 : a.has_excl, ordered ? a.stage16 : a.nl16, a.S,
                                ordered ? a.stage_cnt : a.nnh, (DIAG && a.want32) ? a.nlist : (int*)nullptr, a.S, a.nn, ctl, &a.box, a.rtag, a.x4o, ablate, (float)a.rl2_rows,
-                               a.bond_pass ? (uint4*)nullptr : a.bslots, nullptr, 0, 0x7fffffff, a.coop, sbase);
+                               a.bond_pass ? BondRecs{} : a.bslots, nullptr, 0, 0x7fffffff, a.coop, sbase);
       } else {
         tile_fill<R, BS, true>(T, sx, a.CAP, a.x4o, 1);
         __syncthreads();
@@ -4059,7 +4083,7 @@ __global__ __launch_bounds__(512, sizeof(R) == 8 ? 4 : 1536 / 256) void k_pair_t
                                                            const int* __restrict__ nnh, int S16,
                                                            const PairCore<R>* __restrict__ pcore, const PairExt<R>* __restrict__ pext,
                                                            int ntypes, const Vec4<R>* __restrict__ tab, double* __restrict__ eout,
-                                                           double half_skin, DevCtl* ctl, TileSub sub_, uint4* __restrict__ bslots, int bond_mode, ActMask bact,
+                                                           double half_skin, DevCtl* ctl, TileSub sub_, BondRecs bslots, int bond_mode, ActMask bact,
                                                            CoulArgs<R> ca, ResArgs<R> ra, CapArgs<R> cp, double* __restrict__ tout) {
   static_assert(MODE >= 3 && MODE <= 7, "tile tensor kernels: MODE 3..7");
   pair_tiles_body<R, 1, true, 512, MODE, false, true>(ntiles, CAP, x4, f4, desc, nl16, nnh, S16, pcore, pext, ntypes, tab, UniLJ{}, eout, half_skin, ctl, 0, 0, nullptr,
