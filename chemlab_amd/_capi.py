@@ -22,6 +22,8 @@ CHEM_MAX_FIX_SETS = 8
 CHEM_MAX_REGIONS = 16
 CHEM_RDF_MAX_PAIRS = 8
 CHEM_RDF_MAX_BINS = 1024
+CHEM_SQ_MAX_N = 16
+CHEM_SQ_MAX_PAIRS = 4
 
 # error codes
 OK, EINVAL, ENOSPC, EDEVICE, ESTATE, ENOTIMPL, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -142,6 +144,11 @@ class BarostatState(C.Structure):
 class RdfResult(C.Structure):
     _fields_ = [("r_max", C.c_double), ("nbins", C.c_int32), ("npairs", C.c_int32), ("split", C.c_int32),
                 ("frames", C.c_int64), ("pairs", C.c_uint64 * CHEM_RDF_MAX_PAIRS), ("density", C.c_double * CHEM_RDF_MAX_PAIRS)]
+
+
+class SqResult(C.Structure):
+    _fields_ = [("nmax", C.c_int32), ("npairs", C.c_int32), ("nvec", C.c_int64), ("frames", C.c_int64),
+                ("na", C.c_double * CHEM_SQ_MAX_PAIRS), ("nb", C.c_double * CHEM_SQ_MAX_PAIRS), ("box_sum", C.c_double * 3)]
 
 
 class Timers(C.Structure):
@@ -267,6 +274,12 @@ PRODUCT_ONLY = {
     "rdf_sample_every": (_i, [_P, _i]),
     "rdf_get": (_i, [_P, C.POINTER(RdfResult), C.POINTER(C.c_uint64), _i64]),
     "rdf_reset": (_i, [_P]),
+    # static structure factor accumulated on the device (the CPU checker has no structure factor)
+    "sq_init": (_i, [_P, _i, _i, _pi32]),
+    "sq_sample": (_i, [_P]),
+    "sq_sample_every": (_i, [_P, _i]),
+    "sq_get": (_i, [_P, C.POINTER(SqResult), _pd, _i64]),
+    "sq_reset": (_i, [_P]),
     # counters of option skip_idle (neighbour launch only on steps that can need a rebuild)
     "debug_idle_skipped": (_i64, [_P]),
     "debug_idle_wrong_skips": (_i64, [_P]),

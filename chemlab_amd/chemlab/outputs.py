@@ -200,3 +200,15 @@ def write_rdf(file_name, rdf, labels=None):
         out.append("%.6f " % rdf["r"][k] + " ".join("%.8e" % rdf["g"][s, p, k] for s in range(nsel) for p in range(parts)))
     with wopen(_prepare_path(file_name), "w") as f:
         f.write("\n".join(out) + "\n")
+
+
+def write_sq(file_name, sq, labels=None):
+    """The result of Engine.sq() as text: a header line, then one row per shell of width 2 pi / max(L): the mean |q| of the shell's
+    vectors, their number, one S column per selector.  labels: one name per selector (default sel0, sel1, ..)."""
+    nsel, nshell = sq["shell_S"].shape
+    labels = ["sel%d" % s for s in range(nsel)] if labels is None else list(labels)
+    out = ["# q count " + " ".join("S_" + c for c in labels) + "   (frames %d, nmax %d, %d vectors)" % (sq["frames"], sq["nmax"], sq["nvec"])]
+    for k in range(nshell):
+        out.append("%.6f %d " % (sq["shell_q"][k], sq["shell_count"][k]) + " ".join("%.8e" % sq["shell_S"][s, k] for s in range(nsel)))
+    with wopen(_prepare_path(file_name), "w") as f:
+        f.write("\n".join(out) + "\n")

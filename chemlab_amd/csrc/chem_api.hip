@@ -30,6 +30,7 @@
 #include "chem_fix_host.hpp"
 #include "chem_region_host.hpp"
 #include "chem_rdf_host.hpp"
+#include "chem_sq_host.hpp"
 #include "chem_ckpt_host.hpp"
 #include "chem_tab_host.hpp"
 #include "md_kernels.hpp"
@@ -310,6 +311,14 @@ struct Ctx {
   virtual void rdf_sample() = 0;
   virtual void rdf_get(chem_rdf_result* out, uint64_t* counts, int64_t cap) = 0;
   virtual void rdf_reset() = 0;
+  // Static structure factor (chem_sq_*; rule set: include/chem_mi355.h, host rules: chem_sq_host.hpp): as above, configuration here,
+  // accumulators and scratch on the device (allocated by sq_configure and the first plan only), neither in a checkpoint.
+  struct SqConf { bool on = false; int nmax = 0, npairs = 0, every = 0; int32_t tp[2 * CHEM_SQ_MAX_PAIRS] = {}; } sq;
+  virtual void sq_configure() = 0;
+  virtual void sq_sample() = 0;
+  virtual void sq_get(chem_sq_result* out, double* sums, int64_t cap) = 0;
+  virtual void sq_reset() = 0;
+  virtual double sq_time_frames(int frames) = 0;      // chem_debug_sq_frame_ms
   virtual int64_t verlet_pairs(int64_t* out, int64_t cap) = 0;
   virtual void modify_particle(int tag, int what, double value) = 0;
   virtual int res_apply_completions() = 0;
@@ -2073,6 +2082,104 @@ template <typename R> struct CtxT : Ctx {
     if (counts) for (size_t k = 0; k < nw; ++k) counts[k] = h[kRdfHead + k];
   }
 
+  // ---- static structure factor (chem_sq_*; the rules and the launch plan: chem_sq_host.hpp, the kernels: md_kernels.hpp) ----
+  static_assert(kSqTypes == kRdfTypes, "k_rdf_count leaves the type counts where k_sq_accum reads them");
+  DBuf<double> sq_acc, sq_part, sq_rho;      // frames, na, nb, box_sum, type counts of the frame in flight, then the sums from word kSqHead on; partials; rho
+  int sq_ncu = 0; size_t sq_lds_set = 0;
+  double sq_h_frames = 0, sq_h_na[CHEM_SQ_MAX_PAIRS] = {}, sq_h_nb[CHEM_SQ_MAX_PAIRS] = {}, sq_h_box[3] = {};      // the books of a decomposed context (host)
+  SqArgs sq_a{};
+  size_t sq_words() const { return (size_t)sq.npairs * (size_t)sq_nvec(sq.nmax); }
+  void sq_configure() override {
+    if (!sq.on) { if (sq_acc.p) { HIPCHK(hipStreamSynchronize(stream)); sq_acc.free(); sq_part.free(); sq_rho.free(); } return; }
+    sq_fill_classes(sq.nmax, sq.npairs, sq.tp, sq_a);
+    if (sq_acc.p) HIPCHK(hipStreamSynchronize(stream));      // (a smaller configuration before: its frames may still be running)
+    sq_acc.free(); sq_part.free(); sq_rho.free();
+    sq_acc.alloc((size_t)kSqHead + sq_words());
+    sq_rho.alloc((size_t)sq_a.ncls * sq_a.nvec * 2);
+    sq_reset();
+  }
+  void sq_reset() override {
+    HIPCHK(hipMemsetAsync(sq_acc.p, 0, sizeof(double) * ((size_t)kSqHead + sq_words()), stream));
+    sq_h_frames = 0;
+    for (int s = 0; s < CHEM_SQ_MAX_PAIRS; ++s) { sq_h_na[s] = 0.0; sq_h_nb[s] = 0.0; }
+    for (int d = 0; d < 3; ++d) sq_h_box[d] = 0.0;
+  }
+  // the plan of a frame of n home particles (asked where chem_run starts and at every frame); the scratch is allocated for the most
+  // super-chunks any n gets and the kernel is told its LDS here, so that a frame inside a run is launches and nothing else
+  SqPlan sq_plan_now() {
+    if (!sq_ncu) { hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, device)); sq_ncu = prop.multiProcessorCount; }
+    SqPlan pl{}; std::string why;
+    if (!sq_plan(n > 0 ? n : 1, sq.nmax, sq_a.ncls, kTileLdsBudget, sq_ncu, pl, why)) throw ChemError(CHEM_EINVAL, why);
+    sq_part.alloc((size_t)sq_super_cap(sq.nmax, sq_a.ncls, sq_ncu) * sq_partial_bytes(sq.nmax, sq_a.ncls) / sizeof(double));
+    if (sq_lds_set < pl.lds_bytes) {
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sq_walk<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+      sq_lds_set = pl.lds_bytes;
+    }
+    return pl;
+  }
+  // one frame of the positions as they are, behind whatever the stream holds (the forces of the step): the home slots x4[G .. G + n)
+  // on every path.  (Slabs: as for rdf_launch, dd_step_sync has returned; the all-reduce is the transport's, on this stream.)
+  void sq_launch() {
+    const SqPlan pl = sq_plan_now();
+    const SqArgs& a = sq_a;
+    const size_t rw = (size_t)a.ncls * a.nvec;
+    if (n > 0) {
+      hipLaunchKernelGGL(k_sq_walk<R>, dim3(pl.nqb, pl.nsuper), dim3(pl.block), pl.lds_bytes, stream, G, n, x4.p, boxd, a, pl.per, sq_part.p, (const DevCtl*)ctl.p);
+      hipLaunchKernelGGL(k_sq_reduce, dim3(cdiv((long long)rw, 256)), dim3(256), 0, stream, a, pl.nsuper, (const double*)sq_part.p, sq_rho.p, (const DevCtl*)ctl.p);
+    } else {
+      HIPCHK(hipMemsetAsync(sq_rho.p, 0, sizeof(double) * 2 * rw, stream));
+    }
+    if (dd_on) {
+      if (P > 1) tr->allreduce_sum_f64(sq_rho.p, 2 * rw, stream);
+      sync_type_mirrors();
+      long long c[CHEM_MAX_TYPES] = {};
+      for (int64_t t = 0; t < top.n; ++t) ++c[top.type[(size_t)t] & (CHEM_MAX_TYPES - 1)];
+      sq_h_frames += 1.0;
+      for (int s = 0; s < sq.npairs; ++s) { sq_h_na[s] += (double)sq_class_count(a, a.sel_a[s], c); sq_h_nb[s] += (double)sq_class_count(a, a.sel_b[s], c); }
+      for (int d = 0; d < 3; ++d) sq_h_box[d] += L[d];
+    } else if (n > 0) {
+      hipLaunchKernelGGL(k_rdf_count<R>, dim3(std::min(cdiv(n, 256), 4 * sq_ncu)), dim3(256), 0, stream, G, n, x4.p, reinterpret_cast<unsigned long long*>(sq_acc.p), (const DevCtl*)ctl.p);
+    }
+    hipLaunchKernelGGL(k_sq_accum, dim3(cdiv(a.nvec, 256)), dim3(256), 0, stream, a, boxd, dd_on ? 0 : 1, (const double*)sq_rho.p, sq_acc.p, (const DevCtl*)ctl.p);
+    HIPCHK(hipGetLastError());
+  }
+  void sq_sample() override {      // chem_observe's preconditions
+    flush_host_state();
+    if (resort) { rebuild_now(); compute_forces(); }
+    sq_launch();
+  }
+  // `frames` frames of the current state back to back between two events on the context's stream: milliseconds per frame
+  // (tools/sq_workload.py; the frames are accumulated like any other)
+  double sq_time_frames(int frames) override {
+    flush_host_state();
+    if (resort) { rebuild_now(); compute_forces(); }
+    (void)sq_plan_now();
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, stream));
+    for (int k = 0; k < frames; ++k) sq_launch();
+    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return (double)ms / (double)(frames > 0 ? frames : 1);
+  }
+  void sq_get(chem_sq_result* out, double* sums, int64_t cap) override {
+    const size_t nw = sq_words();
+    if (sums && cap < (int64_t)nw) throw ChemError(CHEM_ENOSPC, "sq_get: capacity " + std::to_string(cap) + " below npairs * nvec = " + std::to_string(nw));
+    std::vector<double> h;
+    sq_acc.download(h, sums ? (size_t)kSqHead + nw : (size_t)kSqHead, stream);
+    std::memset(out, 0, sizeof(*out));
+    out->nmax = sq.nmax; out->npairs = sq.npairs; out->nvec = sq_nvec(sq.nmax);
+    const double* const fr = dd_on ? &sq_h_frames : &h[kSqFrames];
+    const double* const na = dd_on ? sq_h_na : &h[kSqNa]; const double* const nb = dd_on ? sq_h_nb : &h[kSqNb]; const double* const bx = dd_on ? sq_h_box : &h[kSqBox];
+    out->frames = (int64_t)*fr;
+    for (int s = 0; s < sq.npairs; ++s) { out->na[s] = na[s]; out->nb[s] = nb[s]; }
+    for (int d = 0; d < 3; ++d) out->box_sum[d] = bx[d];
+    if (sums) for (size_t k = 0; k < nw; ++k) sums[k] = h[kSqHead + k];
+  }
+
   // ---- pressure tensor (chem_get_pressure_tensor; the rules: include/chem_mi355.h, the kernel: chem_tensor_host.hpp) ----
   // Everything below is allocated and launched by the call alone.
   DBuf<double> tpart, tredbuf;      // per-list sums, kinetic and pair block partials (one buffer, one download); the ranks' sums
@@ -2283,6 +2390,8 @@ template <typename R> struct CtxT : Ctx {
     flush_host_state();
     const bool rdf_due = rdf.on && rdf.every > 0;
     if (rdf_due) (void)rdf_plan_now();      // (refusals before the first step, not in the middle of the run)
+    const bool sq_due = sq.on && sq.every > 0;
+    if (sq_due) (void)sq_plan_now();        // (scratch and the LDS attribute before the first step)
     hint_invalidate();      // (whatever the last call's launches published: the first step of a call gets its neighbour launch)
     const double t0 = now_s();
     if (opt_time_pair) {
@@ -2383,6 +2492,7 @@ template <typename R> struct CtxT : Ctx {
       force_step_off = 0;
       resort = false;   // a rebuild requested by the last reaction step (force_rebuild on the device) has happened by now
       if (rdf_due && (step + 1) % rdf.every == 0) rdf_launch();      // a frame of x(step + 1): behind its forces, in front of the kick (reads only)
+      if (sq_due && (step + 1) % sq.every == 0) sq_launch();         // likewise
 
       if (last || react_due || atrp_due || reg_due || !opt_fuse || resc_kind || baro_on()) {
         launch_integrate<1>(lang, lang, step, 1);
@@ -4446,6 +4556,39 @@ int chem_rdf_get(chem_ctx* ctx, chem_rdf_result* out, uint64_t* counts, int64_t 
 }
 int chem_rdf_reset(chem_ctx* ctx) { API_BEGIN REQUIRE(CTX.rdf.on, CHEM_ESTATE, "rdf_reset before chem_rdf_init"); CTX.rdf_reset(); return 0; API_END(ctx) }
 
+int chem_sq_init(chem_ctx* ctx, int nmax, int npairs, const int32_t* type_pairs) {
+  API_BEGIN
+  Ctx& c = CTX;
+  std::string why;
+  if (sq_validate(nmax, npairs, type_pairs, why) != 0) throw ChemError(CHEM_EINVAL, why);
+  Ctx::SqConf q;
+  if (npairs > 0) {
+    q.on = true; q.nmax = nmax; q.npairs = npairs;
+    for (int k = 0; k < 2 * npairs; ++k) q.tp[k] = type_pairs[k];
+  }
+  c.sq = q;      // (in-run sampling is off again: the accumulators start from nothing)
+  c.sq_configure();
+  return 0;
+  API_END(ctx)
+}
+int chem_sq_sample(chem_ctx* ctx) { API_BEGIN REQUIRE(CTX.sq.on, CHEM_ESTATE, "sq_sample before chem_sq_init"); CTX.sq_sample(); return 0; API_END(ctx) }
+int chem_sq_sample_every(chem_ctx* ctx, int every) {
+  API_BEGIN
+  REQUIRE(CTX.sq.on, CHEM_ESTATE, "sq_sample_every before chem_sq_init");
+  CTX.sq.every = every > 0 ? every : 0;
+  return 0;
+  API_END(ctx)
+}
+int chem_sq_get(chem_ctx* ctx, chem_sq_result* out, double* sums, int64_t cap) {
+  API_BEGIN
+  REQUIRE(CTX.sq.on, CHEM_ESTATE, "sq_get before chem_sq_init");
+  REQUIRE(out, CHEM_EINVAL, "null output");
+  CTX.sq_get(out, sums, cap);
+  return 0;
+  API_END(ctx)
+}
+int chem_sq_reset(chem_ctx* ctx) { API_BEGIN REQUIRE(CTX.sq.on, CHEM_ESTATE, "sq_reset before chem_sq_init"); CTX.sq_reset(); return 0; API_END(ctx) }
+
 int chem_run(chem_ctx* ctx, int64_t nsteps) {
   API_BEGIN_NOJOIN   // a pending label merge keeps running beside the MD steps; react_step joins it
   REQUIRE(nsteps >= 0, CHEM_EINVAL, "nsteps");
@@ -4613,6 +4756,15 @@ int64_t chem_debug_dump_rebuild(chem_ctx* ctx, long long* out, int64_t cap) { re
 // diagnostic / tests: partner tags of the force list of particle `tag`, in list order; -1 without tiles
 // diagnostics / tests (unlisted, like chem_debug_force_list): how many times a run stopped by the device was resumed
 // ... and the tile geometry in use: out[0..5] = tiles, cells along x, wide tiles per row, width of the narrow ones, tile rows, LDS slots per tile
+// diagnostics of tools/sq_workload.py (not in the header): `frames` frames back to back, device milliseconds per frame between two events
+int chem_debug_sq_frame_ms(chem_ctx* ctx, int frames, double* ms) {
+  API_BEGIN
+  REQUIRE(CTX.sq.on, CHEM_ESTATE, "sq frame timing before chem_sq_init");
+  REQUIRE(frames > 0 && ms, CHEM_EINVAL, "frames");
+  *ms = CTX.sq_time_frames(frames);
+  return 0;
+  API_END(ctx)
+}
 int64_t chem_debug_tiles(chem_ctx* ctx, int32_t* out) { try { ctx->c->debug_tiles(out); return 0; } catch (...) { return -2; } }
 int64_t chem_debug_halts(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->halts_recovered : -1; }
 int64_t chem_debug_idle_skipped(chem_ctx* ctx) { return ctx && ctx->c ? ctx->c->idle_skipped : -1; }

@@ -20,6 +20,7 @@
 #include "chem_baro_host.hpp"
 #include "chem_region_host.hpp"
 #include "chem_rdf_host.hpp"
+#include "chem_sq_host.hpp"
 
 namespace chem {
 
@@ -5117,6 +5118,128 @@ __global__ __launch_bounds__(64) void k_rdf_frame(RdfArgs a, double V, unsigned 
       acc[kRdfPairs + s] += M;
       acc[kRdfDensity + s] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)acc[kRdfDensity + s]) + (double)M / V);
     }
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------------
+// Static structure factor (chem_sq_*; rule set: include/chem_mi355.h, enumeration, classes and launch plan: chem_sq_host.hpp).
+// All fp64 in both builds, no floating-point atomics: every sum has one owner and a fixed order.
+//
+// k_sq_walk: workgroup (blockIdx.x, blockIdx.y) owns the kSqQBlock wave vectors from blockIdx.x * kSqQBlock (kSqVpl per lane, in
+// registers for the whole launch) and the particle slots [blockIdx.y * per, min(n, (blockIdx.y + 1) * per)) of the range x4[i0 ..
+// i0 + n).  It stages kSqChunk particles at a time: thread (axis, j) decodes particle j, takes one sincospi of 2 f_a and writes
+// e_a(m) = exp(-i 2 pi m f_a), m = 0..nmax, by the recurrence e(m) = e(m - 1) e(1); negative m is the conjugate.  Then every lane
+// walks the staged particles in slot order: the product of its three table entries, added to the sums of the classes the particle
+// belongs to (the class mask is the same for the whole wave, so that is a scalar branch).  A lane's vectors are consecutive in k,
+// i.e. mostly the same (nx, ny) and consecutive nz: two of the three LDS reads are broadcasts.  part[((super * ncls + c) * nvec +
+// k) * 2 ..] = the partial of (class c, vector k) over the super-chunk.
+template <typename R>
+__global__ __launch_bounds__(kSqBlock) void k_sq_walk(int i0, int n, const Vec4<R>* __restrict__ x4, BoxD box, SqArgs a, int per, double* __restrict__ part,
+                                                      const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char chem_dyn_lds[];
+  __shared__ int smask[kSqChunk];
+  double2* const tab = reinterpret_cast<double2*>(chem_dyn_lds);      // [axis][particle][m]
+  const int t = threadIdx.x, M1 = a.nmax + 1;
+  const int lo = blockIdx.y * per, hi = n - lo < per ? n : lo + per;
+  int ox[kSqVpl], oy[kSqVpl], oz[kSqVpl]; double sy[kSqVpl], sz[kSqVpl];
+  double re[kSqVpl][kSqMaxClasses], im[kSqVpl][kSqMaxClasses];
+#pragma unroll
+  for (int v = 0; v < kSqVpl; ++v) {
+    const long long k = (long long)blockIdx.x * kSqQBlock + v * kSqBlock + t;
+    int nx = 0, ny = 0, nz = 0;
+    if (k < a.nvec) sq_vec(k, a.nmax, nx, ny, nz);
+    ox[v] = nx; oy[v] = kSqChunk * M1 + (ny < 0 ? -ny : ny); oz[v] = 2 * kSqChunk * M1 + (nz < 0 ? -nz : nz);
+    sy[v] = ny < 0 ? -1.0 : 1.0; sz[v] = nz < 0 ? -1.0 : 1.0;
+#pragma unroll
+    for (int c = 0; c < kSqMaxClasses; ++c) { re[v][c] = 0.0; im[v][c] = 0.0; }
+  }
+  for (int s0 = lo; s0 < hi; s0 += kSqChunk) {
+    __syncthreads();
+    if (t < 3 * kSqChunk) {
+      const int axis = t / kSqChunk, j = t % kSqChunk;
+      if (s0 + j < hi) {
+        const Vec4<R> xq = x4[i0 + s0 + j];
+        const D3 p = posD<R>(xq, box);
+        const double f = (axis == 0 ? p.x : axis == 1 ? p.y : p.z) * box.invL[axis];
+        double sn, cs;
+        ::sincospi(2.0 * f, &sn, &cs);
+        double2* const e = tab + (axis * kSqChunk + j) * M1;
+        double2 w = {1.0, 0.0};
+        e[0] = w;
+        for (int m = 1; m <= a.nmax; ++m) {
+          const double wr = w.x * cs + w.y * sn, wi = w.y * cs - w.x * sn;      // w * (cs - i sn)
+          w.x = wr; w.y = wi;
+          e[m] = w;
+        }
+        if (axis == 0) smask[j] = a.tmask[(int)xq.w & (kMaxTypes - 1)];
+      }
+    }
+    __syncthreads();
+    const int nj = hi - s0 < kSqChunk ? hi - s0 : kSqChunk;
+    for (int j = 0; j < nj; ++j) {
+      const int cm = __builtin_amdgcn_readfirstlane(smask[j]);
+      const double2* const e = tab + j * M1;
+#pragma unroll
+      for (int v = 0; v < kSqVpl; ++v) {
+        const double2 ex = e[ox[v]], ey = e[oy[v]], ez = e[oz[v]];
+        const double eyi = ey.y * sy[v], ezi = ez.y * sz[v];
+        const double qr = ex.x * ey.x - ex.y * eyi, qi = ex.x * eyi + ex.y * ey.x;
+        const double pr = qr * ez.x - qi * ezi, pi = qr * ezi + qi * ez.x;
+#pragma unroll
+        for (int c = 0; c < kSqMaxClasses; ++c)
+          if ((cm >> c) & 1) { re[v][c] += pr; im[v][c] += pi; }
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < kSqVpl; ++v) {
+    const long long k = (long long)blockIdx.x * kSqQBlock + v * kSqBlock + t;
+    if (k >= a.nvec) continue;
+#pragma unroll
+    for (int c = 0; c < kSqMaxClasses; ++c)
+      if (c < a.ncls) {
+        double2* const o = reinterpret_cast<double2*>(part) + ((size_t)blockIdx.y * a.ncls + c) * a.nvec + k;
+        *o = double2{re[v][c], im[v][c]};
+      }
+  }
+}
+
+// rho[(c * nvec + k) * 2 ..] = the partials of (class c, vector k) summed over the super-chunks in index order
+__global__ __launch_bounds__(256) void k_sq_reduce(SqArgs a, int nsuper, const double* __restrict__ part, double* __restrict__ rho, const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  const size_t w = (size_t)a.ncls * a.nvec, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= w) return;
+  const double2* const p = reinterpret_cast<const double2*>(part);
+  double2 s = {0.0, 0.0};
+  for (int u = 0; u < nsuper; ++u) { const double2 q = p[(size_t)u * w + i]; s.x += q.x; s.y += q.y; }
+  reinterpret_cast<double2*>(rho)[i] = s;
+}
+
+// sums[s][k] += Re(rho_A(k) conj rho_B(k)) from the (global) rho.  books != 0 (single domain): thread 0 of workgroup 0 also keeps
+// the books of the frame -- frames, na, nb from the type counts k_rdf_count left at kSqTypes (cleared again), box_sum; on slabs the
+// host keeps them (CtxT::sq_launch).
+__global__ __launch_bounds__(256) void k_sq_accum(SqArgs a, BoxD box, int books, const double* __restrict__ rho, double* __restrict__ acc,
+                                                  const DevCtl* __restrict__ ctl) {
+  if (ctl->halt) return;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k < a.nvec) {
+    const double2* const r = reinterpret_cast<const double2*>(rho);
+    for (int s = 0; s < a.nsel; ++s) {
+      const double2 ra = r[(size_t)a.sel_a[s] * a.nvec + k], rb = r[(size_t)a.sel_b[s] * a.nvec + k];
+      acc[kSqHead + (size_t)s * a.nvec + k] += ra.x * rb.x + ra.y * rb.y;
+    }
+  }
+  if (books && blockIdx.x == 0 && threadIdx.x == 0) {
+    unsigned long long* const tc = reinterpret_cast<unsigned long long*>(acc) + kSqTypes;
+    long long cnt[kMaxTypes];
+    for (int u = 0; u < kMaxTypes; ++u) { cnt[u] = (long long)tc[u]; tc[u] = 0ull; }
+    acc[kSqFrames] += 1.0;
+    for (int s = 0; s < a.nsel; ++s) {
+      acc[kSqNa + s] += (double)sq_class_count(a, a.sel_a[s], cnt);
+      acc[kSqNb + s] += (double)sq_class_count(a, a.sel_b[s], cnt);
+    }
+    for (int d = 0; d < 3; ++d) acc[kSqBox + d] += box.L[d];
   }
 }
 

@@ -50,6 +50,51 @@ def rdf_result(r_max, counts, frames, pairs, density):
                 density=np.asarray(density), r_max=float(r_max), nbins=nbins, split=parts == 2)
 
 
+def sq_nvec(nmax):
+    """The number of kept wave vectors: the canonical half of |n_a| <= nmax without n = 0."""
+    return ((2 * int(nmax) + 1) ** 3 - 1) // 2
+
+
+def sq_vectors(nmax):
+    """The integer triples n of the rule set in index order, (nvec, 3) int64: |n_a| <= nmax, the half with nx > 0, or nx = 0 and
+    ny > 0, or nx = ny = 0 and nz > 0, lexicographic in (nx, ny, nz) -- sq_vec of chem_sq_host.hpp."""
+    nmax = int(nmax)
+    r = np.arange(-nmax, nmax + 1)
+    n = np.stack(np.meshgrid(r, r, r, indexing="ij"), -1).reshape(-1, 3)      # lexicographic in (nx, ny, nz)
+    keep = (n[:, 0] > 0) | ((n[:, 0] == 0) & (n[:, 1] > 0)) | ((n[:, 0] == 0) & (n[:, 1] == 0) & (n[:, 2] > 0))
+    return n[keep].astype(np.int64)
+
+
+def sq_result(nmax, sums, frames, na, nb, box_sum):
+    """The dict Engine.sq() returns, from the raw sums and books of chem_sq_get (the division is done here): n (nvec, 3), sums
+    [npairs][nvec], S = sums / sqrt(na nb) (zeros before the first frame or for an empty set), q = |q(n)| at the mean box,
+    the shell average over bins of width 2 pi / max(mean box) -- shell_q (mean |q| of the shell's vectors), shell_count,
+    shell_S [npairs][shells], empty shells left out --, frames, na, nb, box_sum, box (the mean box), nmax, nvec."""
+    sums = np.asarray(sums, dtype=np.float64)
+    nsel, nvec = sums.shape
+    n = sq_vectors(nmax)
+    assert n.shape[0] == nvec == sq_nvec(nmax)
+    na, nb, box_sum = np.asarray(na, dtype=np.float64), np.asarray(nb, dtype=np.float64), np.asarray(box_sum, dtype=np.float64)
+    S = np.zeros(sums.shape, dtype=np.float64)
+    for s in range(nsel):
+        if na[s] > 0 and nb[s] > 0:
+            S[s] = sums[s] / np.sqrt(na[s] * nb[s])
+    frames = int(frames)
+    box = box_sum / frames if frames > 0 else np.zeros(3)
+    if frames > 0:
+        q = 2.0 * np.pi * np.sqrt(((n / box) ** 2).sum(axis=1))
+        dq = 2.0 * np.pi / box.max()
+        sh = np.floor(q / dq + 0.5).astype(np.int64)
+        ids = np.unique(sh)
+        shell_count = np.array([(sh == i).sum() for i in ids], dtype=np.int64)
+        shell_q = np.array([q[sh == i].mean() for i in ids])
+        shell_S = np.array([[S[s][sh == i].mean() for i in ids] for s in range(nsel)]).reshape(nsel, len(ids))
+    else:
+        q, shell_count, shell_q, shell_S = np.zeros(nvec), np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros((nsel, 0))
+    return dict(n=n, sums=sums, S=S, q=q, shell_q=shell_q, shell_count=shell_count, shell_S=shell_S, frames=frames, na=na, nb=nb,
+                box_sum=box_sum, box=box, nmax=int(nmax), nvec=nvec)
+
+
 class Engine:
     def __init__(self, device=0, precision=32, api=None, ctx=None):
         """precision: 32 (fp32 arrays, fp64 bonded/reaction distance) or 64 (all fp64)."""
@@ -259,6 +304,8 @@ class Engine:
             name = "region_add"
         if name == "rdf":
             name = "rdf_init"
+        if name == "sq":
+            name = "sq_init"
         return getattr(self.api, name, None) is not None
 
     # ---- region rules: FreezeRegion, ChangeParticleType (include/chem_mi355.h, chem_region_add ff.) ----
@@ -352,6 +399,43 @@ class Engine:
         self._ck(fn(self.ctx, C.byref(res), _ptr(counts, C.c_uint64), counts.size))
         return rdf_result(float(res.r_max), counts, int(res.frames), np.array(res.pairs[:nsel], dtype=np.uint64),
                           np.array(res.density[:nsel], dtype=np.float64))
+
+    # ---- static structure factor accumulated on the device (include/chem_mi355.h, chem_sq_init ff.) ----
+    def _sq_entry(self, name):
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise NotImplementedError("sq: the CPU checker has no structure factor")
+        return fn
+
+    def sq_init(self, nmax, type_pairs=((-1, -1),)):
+        """Configure (and reset) the structure-factor sums: the wave vectors 2 pi n / L with |n_a| <= nmax <= 16 (canonical half,
+        sq_vectors(nmax)), one set of sums per unordered type pair of `type_pairs` (-1 = any type; at most 4).  No pairs
+        switches it off."""
+        fn = self._sq_entry("sq_init")
+        tp = np.ascontiguousarray(type_pairs, dtype=np.int32).reshape(-1, 2)
+        self._ck(fn(self.ctx, int(nmax), tp.shape[0], _ptr(tp, C.c_int32) if tp.shape[0] else None))
+
+    def sq_sample(self):
+        """One frame of the current positions (the preconditions of observe())."""
+        self._ck(self._sq_entry("sq_sample")(self.ctx))
+
+    def sq_sample_every(self, every):
+        """A frame inside run() at every step s with s % every == 0, without a host round trip; every <= 0: off."""
+        self._ck(self._sq_entry("sq_sample_every")(self.ctx, int(every)))
+
+    def sq_reset(self):
+        """Zero the accumulators, keep the configuration."""
+        self._ck(self._sq_entry("sq_reset")(self.ctx))
+
+    def sq(self):
+        """The accumulated structure factor: the dict of sq_result()."""
+        fn = self._sq_entry("sq_get")
+        res = _capi.SqResult()
+        self._ck(fn(self.ctx, C.byref(res), None, 0))
+        nsel, nvec = int(res.npairs), int(res.nvec)
+        sums = np.zeros((nsel, nvec), dtype=np.float64)
+        self._ck(fn(self.ctx, C.byref(res), _ptr(sums, C.c_double), sums.size))
+        return sq_result(int(res.nmax), sums, int(res.frames), np.array(res.na[:nsel]), np.array(res.nb[:nsel]), np.array(res.box_sum[:3]))
 
     # ---- checkpoint and exact restart (include/chem_mi355.h, chem_checkpoint_save / chem_checkpoint_load) ----
     def _ckpt_entry(self, name):

@@ -1890,6 +1890,38 @@ class _RadialDistrF(_Observable):
         return self.system.engine.rdf()
 
 
+class _StaticStructF(_Observable):
+    """analysis.StaticStructF(system): partial structure factors on the reciprocal lattice of the box, accumulated on the device
+    (include/chem_mi355.h chem_sq_*).
+
+    start(nmax, types=None, every=1) once, behind the set-up: a frame inside integrator.run at every step s with s % every == 0,
+    the wave vectors 2 pi n / L with |n_a| <= nmax, one S per (t1, t2) of `types` (-1 = any type; default the total); result()
+    is the dict of Engine.sq() when the run is over.  compute(nmax, types=None) takes one frame of the current configuration and
+    returns the shell-averaged S of the first selector as a list.  (Upstream's class takes (nqx, nqy, nqz, bin_factor) and works
+    on the host; this rule set is this build's own.)"""
+
+    def __init__(self, system):
+        _Observable.__init__(self, system)
+
+    def _init(self, nmax, types):
+        e = self.system.engine
+        if not e.supports("sq"):
+            raise NotImplementedError("sq: the CPU checker has no structure factor")
+        e.sq_init(int(nmax), [(-1, -1)] if types is None else [tuple(t) for t in types])
+        return e
+
+    def compute(self, nmax, types=None):
+        e = self._init(nmax, types)
+        e.sq_sample()
+        return [float(v) for v in e.sq()["shell_S"][0]]
+
+    def start(self, nmax, types=None, every=1):
+        self._init(nmax, types).sq_sample_every(int(every))
+
+    def result(self):
+        return self.system.engine.sq()
+
+
 class _BoxSize(_Observable):
     """The `L` column that goes with `P` (start_simulation.py:466-469): the x edge of the current box.  The reference's
     class is in the external fork; what it reports for a box that is not cubic is unpinned."""
@@ -2048,7 +2080,7 @@ analysis = _ns(
     ChemicalConversionTypeState=_ChemicalConversionTypeState, SystemMonitor=_SystemMonitor,
     SystemMonitorOutputCSV=_SystemMonitorOutputCSV, ResolutionFixedPairList=_ResolutionFixedPairList,
     ResolutionFixedTripleList=_ResolutionFixedTripleList, ResolutionFixedQuadrupleList=_ResolutionFixedQuadrupleList,
-    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor, RadialDistrF=_RadialDistrF,
+    Pressure=_Pressure, BoxSize=_BoxSize, PressureTensor=_PressureTensor, RadialDistrF=_RadialDistrF, StaticStructF=_StaticStructF,
 )
 
 esutil = _ns(RNG=_RNG)

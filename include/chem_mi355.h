@@ -1034,6 +1034,60 @@ typedef struct chem_rdf_result { double r_max; int32_t nbins, npairs, split; int
 int chem_rdf_get(chem_ctx* ctx, chem_rdf_result* out, uint64_t* counts /* [npairs][1+split][nbins] */, int64_t cap);
 int chem_rdf_reset(chem_ctx* ctx);   /* zero the accumulators, keep the configuration */
 
+/* ---- static structure factor --------------------------------------------------------------- */
+/* Time-averaged partial structure factors on the reciprocal lattice of the box, accumulated on the device in fp64: the structure
+ * beyond max_cutoff that g(r) cannot show.  A frame can be taken inside chem_run without a host round trip.  (Upstream has
+ * analysis.StaticStructF; this rule set is this build's own.)
+ *   Vectors.   q(n) = 2 pi (nx / Lx, ny / Ly, nz / Lz) of the frame's box, n integer, |n_a| <= nmax, 1 <= nmax <= CHEM_SQ_MAX_N.
+ *              Only the canonical half is kept (S(-q) = S(q)): n != 0 with nx > 0, or nx = 0 and ny > 0, or nx = ny = 0 and
+ *              nz > 0.  nvec = ((2 nmax + 1)^3 - 1) / 2: 13 for nmax = 1, 171 for 3, 2456 for 8, 17968 for 16.  The index k runs
+ *              over the kept vectors in lexicographic order of (nx, ny, nz); the map k <-> n is sq_vec / sq_index of
+ *              chemlab_amd/csrc/chem_sq_host.hpp (Python: chemlab_amd.engine.sq_vectors), used by the kernels too.
+ *   Phases.    f_a = x_a * invL_a in fp64, x the decoded position the reaction scan and chem_rdf_* use (the fp32 build decodes
+ *              its fixed-point positions to double first), invL of the box the sampled step's forces were evaluated in;
+ *              theta_j(n) = 2 pi (nx f_x + ny f_y + nz f_z).  All arithmetic of this feature is fp64 in both precisions.
+ *   Selectors. Up to CHEM_SQ_MAX_PAIRS unordered type pairs (t1, t2), -1 = any type; types are those at the sampled step.  With
+ *              the type sets A (of t1) and B (of t2): rho_A(n) = sum over j with type_j in A of exp(-i theta_j(n)); dummies of
+ *              fixed-distance sets are included, as for g(r).
+ *   Accumulated, per selector s and vector k, over the frames: sums[s][k] += Re(rho_A(n_k) conj rho_B(n_k)); na[s] += N_A and
+ *              nb[s] += N_B, the particle counts of the two sets in the frame, as doubles; frames += 1; box_sum[a] += L_a.
+ *   Result.    S_s(n) = sums / sqrt(na nb), the Ashcroft-Langreth partial; (-1, -1) gives the total <|rho|^2> / N.  The
+ *              division, |q| at the mean box box_sum / frames and any shell average are the caller's.
+ *   Frames.    As for chem_rdf_*: chem_sq_sample takes one now, with chem_observe's preconditions and side effects and no
+ *              others.  chem_sq_sample_every(every) takes one inside chem_run at every step s with s % every == 0: of the
+ *              positions the forces of step s were evaluated at, enqueued behind that step's force launch and in front of the
+ *              next integrate launch, without a host wait; every <= 0 switches it off.  A run is not sampled at its starting step.
+ *   Read-only. With sampling on, positions, velocities, forces, events and rebuild counters are bit for bit those of the same
+ *              run without it.  A context that never calls chem_sq_* allocates nothing and launches what it launched before.
+ *   Determinism. No floating-point atomics.  A workgroup sums its particle slots in slot order, the partial sums of the
+ *              super-chunks are added in index order: the order is a function of (slot order, n, nvec, the launch plan) alone.
+ *              Two frames of the same context state give the same bits, and on a single domain run(a); run(b) accumulates bit
+ *              for bit what run(a + b) does.
+ *   Not state. Accumulators and configuration are no part of a checkpoint; save and load leave them alone.
+ * chem_sq_init: npairs = 0 switches everything off and frees the buffers; a second call reconfigures and resets (in-run sampling
+ * is off again).  chem_sq_get returns the configuration and the books in *out and the sums as [npairs][nvec] (sums may be NULL
+ * with cap 0 to read the books alone).
+ *   CHEM_EINVAL    nmax outside 1..CHEM_SQ_MAX_N, npairs outside 0..CHEM_SQ_MAX_PAIRS, a type outside -1..CHEM_MAX_TYPES-1, null
+ *                  type_pairs with npairs > 0.
+ *   CHEM_ENOSPC    chem_sq_get with a cap below npairs * nvec.
+ *   CHEM_ESTATE    chem_sq_sample, chem_sq_sample_every, chem_sq_get or chem_sq_reset before chem_sq_init (or after npairs = 0).
+ * Slabs.  Every rank sums rho over its home particles (never ghosts); the rho array (classes x nvec x 2 doubles) goes through the
+ * transport's all-reduce on the run's stream, as the velocity-rescale thermostat's kinetic energy does, and every rank squares and
+ * accumulates the global rho.  na, nb, frames and box_sum are kept on the host from the type table, which is replicated by tag.
+ * Every transport of this build hands every rank the same bits from its all-reduce (the in-process and the shared-memory
+ * transports add the ranks' words in rank order on every rank, RCCL delivers one reduced buffer), so every rank holds the same
+ * accumulators and chem_sq_get is NOT collective.  Slab sums differ from single-domain sums in the last bits (another order).
+ * The shared-memory transport (chem_comm_init_ipc) reduces at most 64 values per call and answers a frame with CHEM_ECOMM. */
+#define CHEM_SQ_MAX_N     16
+#define CHEM_SQ_MAX_PAIRS 4
+typedef struct chem_sq_result { int32_t nmax, npairs; int64_t nvec, frames;
+  double na[CHEM_SQ_MAX_PAIRS], nb[CHEM_SQ_MAX_PAIRS], box_sum[3]; } chem_sq_result;
+int chem_sq_init(chem_ctx* ctx, int nmax, int npairs, const int32_t* type_pairs /* 2*npairs, -1 = any */);
+int chem_sq_sample(chem_ctx* ctx);
+int chem_sq_sample_every(chem_ctx* ctx, int every);
+int chem_sq_get(chem_ctx* ctx, chem_sq_result* out, double* sums /* [npairs][nvec], may be NULL with cap 0 */, int64_t cap);
+int chem_sq_reset(chem_ctx* ctx);   /* zero the accumulators, keep the configuration */
+
 /* ---- the hot call -------------------------------------------------------------------- */
 /* integrator.run(n)  start_simulation.py:780.  No host round trip per step. */
 int chem_run(chem_ctx* ctx, int64_t nsteps);
